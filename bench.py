@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — one measurement update per step on BASELINE.json's headline configuration.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-         bench.py --gpus N --steps K --warmup W
+         bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the keys that describe the
+run. Everything else below (per-kernel times, `roofline`, `update_8d`, `cpu_baseline` and the parity check, the extra keys,
+the other scaling mode, the in-process group) needs --full; there the likelihood kernel is also timed with hipEvents inside
+the timed region. --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32): weights,
+likelihood, match_ratio, beam (workloads with beam points), stats (entropy, match ratio min / max, restored); a rank of a
+multi-rank run adds _rank<r> to the names. The inputs are generated from fixed seeds: the same arguments give the same inputs.
 
 A step = one pass of the hot path over one batch of synthetic input: likelihood-field kernel over
 N_p particles x N_s scan points (+ beam kernel when the workload has beam points), pf::measure
@@ -18,7 +25,7 @@ Particles shard across ranks; map and scan are replicated.  `--scaling weak` (de
 workload's full particle count.  `--scaling strong`: the workload's particles are split over the ranks.  With
 N > 1 both are measured (the one not asked for under `other_scaling`).
 
-Prints ONE JSON line on rank 0 with the driver's contract keys plus `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 with the driver's contract keys plus `roofline` and `cpu_baseline` (null without --full).
 
 `roofline` (dominant kernel = the likelihood kernel): every fraction is <= 1 and tied to a resource. Resources whose peak is
 a DOCUMENTED figure of /opt/skills/guides/MI355X_MICROARCH.md (`peak_kind` "documented"):
@@ -117,15 +124,15 @@ def parse():
     ap.add_argument("--map-jitter", type=float, default=0.0,
                     help="displace every map point uniformly by +-this (m): voxel-filter centroids instead of a lattice")
     ap.add_argument("--jitter-check", type=float, default=0.045,
-                    help="also time the likelihood kernel on the same map with every point displaced by +-this "
+                    help="with --full: also time the likelihood kernel on the same map with every point displaced by +-this "
                          "(extra key `map_jitter`; 0 = skip; C2/C3 only)")
     ap.add_argument("--lik-small", type=int, default=1)
     ap.add_argument("--overlap-models", type=int, default=1)
     ap.add_argument("--prewarm-ms", type=float, default=300.0,
                     help="wall time of untimed updates before the W warm-up steps (GPU clock ramp), 0 = none")
     ap.add_argument("--timing-mask", type=int, default=1,
-                    help="kernel groups timed with hipEvents INSIDE the timed region (bit 0 likelihood = the roofline "
-                         "kernel, 1 beam, 2 pf); the others are timed in a second pass of the same steps")
+                    help="with --full: kernel groups timed with hipEvents INSIDE the timed region (bit 0 likelihood = the "
+                         "roofline kernel, 1 beam, 2 pf); the others are timed in a second pass of the same steps")
     ap.add_argument("--scan-points", type=int, default=0, help="override the number of likelihood scan points")
     ap.add_argument("--lik-group", type=int, default=0, help="0 = the library's choice (16 / 8 / 4 by launch size)")
     ap.add_argument("--strict-order", type=int, default=-1,
@@ -143,12 +150,21 @@ def parse():
                          "reference's single process would use — instead of one process per GPU; prints the same JSON line")
     ap.add_argument("--sort-poses", choices=("none", "yaw", "xy", "cluster"), default="none",
                     help="A/B: re-order the synthetic particles by pose before the run (what pose-ordered particle groups would buy)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline, too: the likelihood kernel timed inside the timed region and every "
+                         "kernel group in a second pass of the steps, the roofline block, the host-buffer update (update_8d), "
+                         "the CPU baseline and parity check, the extra keys, the other scaling mode with N > 1 and the "
+                         "in-process group. Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed (weights, likelihoods, match ratios, beam "
+                         "scores when the workload has beam points, and the four stats) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra keys (post-update reductions, resampling, fused update, route A, jitter check)")
+                    help="with --full: skip the extra keys (post-update reductions, resampling, fused update, route A, "
+                         "jitter check)")
     ap.add_argument("--route-a-reps", type=int, default=40,
                     help="timed repetitions of the node's call site through the drop-in C++ classes "
-                         "(tests/cpp/adapter_demo.bin), 0 = skip")
+                         "(oracle/_ref/adapter_demo.bin), 0 = skip")
     ap.add_argument("--cpu-particles", type=int, default=0,
                     help="particles in the CPU-baseline sample (0 = as many as ~12 s of one core buys, at most all)")
     return ap.parse_args()
@@ -383,6 +399,30 @@ def _identity_noise(n):
     return a
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, per_particle, fixed, suffix=""):
+    """--dump-outputs: what the last timed step handed its caller, as <out_dir>/<name><suffix>.npy in float32. per_particle =
+    {name: array over the particles}, fixed = {name: small array}. Above DUMP_LIMIT_BYTES in all, the per-particle arrays
+    are cut to a sample of particles drawn with a fixed seed (the same one in every run of the same shape), written next to
+    them as particle_index (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(per_particle.values())))
+    fixed_bytes = sum(4 * np.asarray(a).size for a in fixed.values())
+    row_bytes = sum(4 * np.asarray(a)[0].size for a in per_particle.values())
+    idx = None
+    if fixed_bytes + n * row_bytes > DUMP_LIMIT_BYTES:
+        k = (DUMP_LIMIT_BYTES - fixed_bytes) // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(20251015).choice(n, k, replace=False))
+        np.save(os.path.join(out_dir, "particle_index%s.npy" % suffix), idx.astype(np.float64))
+    for name, a in per_particle.items():
+        a = np.asarray(a, np.float32)
+        np.save(os.path.join(out_dir, "%s%s.npy" % (name, suffix)), a if idx is None else a[idx])
+    for name, a in fixed.items():
+        np.save(os.path.join(out_dir, "%s%s.npy" % (name, suffix)), np.asarray(a, np.float32))
+
+
 @contextlib.contextmanager
 def no_gc(collect=False):
     """Timed host loops run with Python's cyclic garbage collector off (a generation-2 pass over a process that has torch
@@ -424,8 +464,8 @@ def _flush_c_stdio():
 def route_a(sc, dist_weight, n_b, reps):
     """The node's call site (src/mcl_3dl.cpp:377-426) through the drop-in C++ classes over the C ABI: per-particle
     measure() virtuals answered from one batched launch per model, weights normalised by the reference's pf.h on the
-    CPU. tests/cpp/adapter_demo.bin is built where the reference headers exist and travels as a file."""
-    exe = os.path.join(ROOT, "tests", "cpp", "adapter_demo.bin")
+    CPU. oracle/_ref/adapter_demo.bin is built where the reference headers exist and travels as a file."""
+    exe = os.path.join(ROOT, "oracle", "_ref", "adapter_demo.bin")
     if not os.path.exists(exe) or reps <= 0:
         return None
     with tempfile.TemporaryDirectory() as tmp:
@@ -467,10 +507,11 @@ def route_a(sc, dist_weight, n_b, reps):
                         "normalised by the reference's pf.h on the CPU)"}
 
 
-def in_process_group_run(workload, n_cfg, extra_cfg, dist_weight, devices, steps, warmup, collective=None):
+def in_process_group_run(workload, n_cfg, extra_cfg, dist_weight, devices, steps, warmup, collective=None, keep_last=False):
     """One process, len(devices) GPUs: the update through mcl3dl_hip_group_measure_update (host arrays in, host arrays out;
     particles sharded inside the library, scan ordered once and pushed to every device, one all-reduce per update). Weak
-    scaling like the main line: n_cfg particles per GPU. Returns a dict for the bench line."""
+    scaling like the main line: n_cfg particles per GPU. Returns a dict for the bench line (keep_last: plus what the last
+    timed call returned, under "last")."""
     from mcl_3dl_amd import capi
     from mcl_3dl_amd.synthetic import make_config
     n_dev = len(devices)
@@ -491,17 +532,21 @@ def in_process_group_run(workload, n_cfg, extra_cfg, dist_weight, devices, steps
         for _ in range(max(warmup, 3)):
             g.measure_update(*args_u)
         keep_gpu_warm(lambda: g.measure_update(*args_u), 0.15)   # clock ramp on every GPU of the group (set-up, not timed)
+        last = None
         with no_gc():
             t0 = time.perf_counter()
             for _ in range(steps):
-                g.measure_update(*args_u)
+                last = g.measure_update(*args_u)
             el = time.perf_counter() - t0
         st = g.collective_stats()
-        return {"n_gpus": n_dev, "particles_total": n_total, "ms_per_update": el / steps * 1e3,
-                "value": float(n_total) * len(sc.scan_lik) * steps / el, "unit": "particle·point evals/s",
-                "collective": "rccl" if st["rccl"] else "host", "collectives": st,
-                "what": "mcl3dl_hip_group_measure_update from ONE process over %d GPU(s): host arrays in / out (PCIe included, "
-                        "like update_8d), particles sharded inside the library, one all-reduce per update" % n_dev}
+        r = {"n_gpus": n_dev, "particles_total": n_total, "ms_per_update": el / steps * 1e3,
+             "value": float(n_total) * len(sc.scan_lik) * steps / el, "unit": "particle·point evals/s",
+             "collective": "rccl" if st["rccl"] else "host", "collectives": st,
+             "what": "mcl3dl_hip_group_measure_update from ONE process over %d GPU(s): host arrays in / out (PCIe included, "
+                     "like update_8d), particles sharded inside the library, one all-reduce per update" % n_dev}
+        if keep_last:
+            r["last"] = last
+        return r
     finally:
         g.close()
 
@@ -643,7 +688,14 @@ def main():
         if args.beam_points:
             extra_cfg["n_b"] = args.beam_points
         r = in_process_group_run(args.workload, n_cfg, extra_cfg, (1.0, 1.0, args.dist_weight_z), list(range(args.gpus)),
-                                 args.steps, args.warmup)
+                                 args.steps, args.warmup, keep_last=bool(args.dump_outputs))
+        if args.dump_outputs:
+            last = r.pop("last")
+            arrays = dict(weights=last["weights"], likelihood=last["lik"], match_ratio=last["quality"])
+            if extra_cfg.get("n_b", cfg["n_b"]):
+                arrays["beam"] = last["beam"]
+            dump_outputs(args.dump_outputs, arrays,
+                         dict(stats=[last["entropy"], last["match_ratio_min"], last["match_ratio_max"], last["restored"]]))
         _flush_c_stdio()   # RCCL announces itself through C stdio: out before the line, which must be the last one
         print(json.dumps({
             "metric": "particle·point evals/sec; filter-update Hz @ 4096 particles × 16k-pt scan", "value": r["value"],
@@ -855,16 +907,17 @@ def main():
     torch.cuda.synchronize(dev)
     setup_s = time.time() - t0
 
-    # exact workload counts for the algorithmic-bytes accounting (counting kernels, not timed)
-    ws = eng.workload_stats(main_sh.d_pose, n_p)
-    k_bar = ws["sum_k"] / max(ws["evals"], 1.0)
-    # B_lik = 16 (scan point) + 27*4 (cell-range entries) + 16*K (candidate points) per evaluation,
-    # + 28 B pose + 8 B result per particle
-    bytes_lik_launch = ws["evals"] * (16.0 + 27 * 4.0 + 16.0 * k_bar) + n_p * 36.0
-    bytes_beam_launch = 0.0
-    if n_b:
-        # B_beam per ray = 16 + S*1 + O*8 + T*16
-        bytes_beam_launch = ws["rays"] * 16.0 + ws["dda_steps"] + ws["dda_occupied"] * 8.0 + ws["dda_tested"] * 16.0
+    if args.full:
+        # exact workload counts for the algorithmic-bytes accounting (counting kernels, not timed)
+        ws = eng.workload_stats(main_sh.d_pose, n_p)
+        k_bar = ws["sum_k"] / max(ws["evals"], 1.0)
+        # B_lik = 16 (scan point) + 27*4 (cell-range entries) + 16*K (candidate points) per evaluation,
+        # + 28 B pose + 8 B result per particle
+        bytes_lik_launch = ws["evals"] * (16.0 + 27 * 4.0 + 16.0 * k_bar) + n_p * 36.0
+        bytes_beam_launch = 0.0
+        if n_b:
+            # B_beam per ray = 16 + S*1 + O*8 + T*16
+            bytes_beam_launch = ws["rays"] * 16.0 + ws["dda_steps"] + ws["dda_occupied"] * 8.0 + ws["dda_tested"] * 16.0
 
     # Clock ramp: a GPU coming out of idle needs tens of milliseconds of load before it holds its sustained clocks, far
     # more than W steps of a sub-millisecond update. Run the update for --prewarm-ms of wall time first (set-up, like the
@@ -911,63 +964,72 @@ def main():
         prewarm["ms"] = (time.perf_counter() - t_pre) * 1e3
     for _ in range(args.warmup):
         step(main_sh)
-    # (bit 3 = the whole update as one launch, which stands in for the likelihood kernel up to update_small_max particles)
-    eng.set_option("timing_mask", args.timing_mask | (8 if args.timing_mask & 1 else 0))
-    eng.set_kernel_timing(True)
-    eng.reset_kernel_time()
+    if args.full:
+        # (bit 3 = the whole update as one launch, which stands in for the likelihood kernel up to update_small_max particles)
+        eng.set_option("timing_mask", args.timing_mask | (8 if args.timing_mask & 1 else 0))
+        eng.set_kernel_timing(True)
+        eng.reset_kernel_time()
     elapsed = timed(main_sh, args.steps)
-    lik_ms, lik_n = eng.kernel_time(capi.KERNEL_LIKELIHOOD)
-    one_launch = False
-    if lik_n == 0:
-        lik_ms, lik_n = eng.kernel_time(capi.KERNEL_UPDATE)
-        one_launch = lik_n > 0
-    # Second pass of the same K steps, outside `elapsed`, every kernel group timed and the two models one after the other:
-    # the beam / pf durations (each timed group costs two event records per launch, so only the roofline kernel is
-    # timed inside the timed region), and the likelihood duration too when it ran concurrently with the beam kernels
-    # above (overlapping event intervals say nothing about either kernel).
-    overlapped = bool(n_b and n_s and args.overlap_models)
-    eng.set_option("timing_mask", 31)
-    eng.set_option("overlap_models", 0)
-    eng.reset_kernel_time()
-    coll_ms = 0.0
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(args.steps):
-        sh = main_sh
-        sh.d_w.copy_(sh.d_w0)
-        if not use_dist:
-            eng.update_device(sh.d_pose, sh.n, sh.d_w, sh.d_stats, d_lik=sh.d_lik, d_ratio=sh.d_ratio,
-                              d_beam=sh.d_beam if n_b else None)
-            continue
-        eng.measure_device(sh.d_pose, sh.n, sh.d_lik, sh.d_ratio, sh.d_beam if n_b else None)
-        eng.pf_partial_device(sh.d_w, sh.d_lik, sh.d_beam if n_b else None, None, sh.d_ratio, sh.n, sh.d_pack, rank, world)
-        if use_dist:
-            ev0.record(stream)
-            dist.all_reduce(sh.d_pack, op=dist.ReduceOp.SUM)
-            ev1.record(stream)
-        eng.pf_apply_device(sh.d_w, sh.n, sh.d_pack, sh.d_stats, world)
-        if use_dist:
-            torch.cuda.synchronize(dev)
-            coll_ms += ev0.elapsed_time(ev1)
-    torch.cuda.synchronize(dev)
-    lik2_ms, lik2_n = eng.kernel_time(capi.KERNEL_LIKELIHOOD)
-    if lik2_n == 0:
-        lik2_ms, lik2_n = eng.kernel_time(capi.KERNEL_UPDATE)
-    beam_ms, beam_n = eng.kernel_time(capi.KERNEL_BEAM)
-    pf_ms, pf_n = eng.kernel_time(capi.KERNEL_PF)
-    upd_ms, upd_n = eng.kernel_time(capi.KERNEL_UPDATE)
-    eng.set_option("overlap_models", args.overlap_models)
-    if overlapped or not (args.timing_mask & 1):
-        lik_ms, lik_n = lik2_ms, lik2_n
-        kernel_timing_pass = "second pass of the same steps (overlap_models=0, all kernel groups timed)"
-    else:
-        kernel_timing_pass = "likelihood: hipEvents inside the timed region; beam, pf: second pass of the same steps"
-    if one_launch:
-        kernel_timing_pass += "; `likelihood` = the one-launch update (likelihood + beam + pf::measure in one kernel)"
-    eng.set_kernel_timing(False)
+    if args.dump_outputs:
+        # what the last timed step handed its caller (a rank of a multi-rank run writes its own shard)
+        arrays = dict(weights=main_sh.d_w, likelihood=main_sh.d_lik, match_ratio=main_sh.d_ratio)
+        if n_b:
+            arrays["beam"] = main_sh.d_beam
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in arrays.items()},
+                     dict(stats=main_sh.d_stats.cpu().numpy()), "" if world == 1 else "_rank%d" % rank)
+    if args.full:
+        lik_ms, lik_n = eng.kernel_time(capi.KERNEL_LIKELIHOOD)
+        one_launch = False
+        if lik_n == 0:
+            lik_ms, lik_n = eng.kernel_time(capi.KERNEL_UPDATE)
+            one_launch = lik_n > 0
+        # Second pass of the same K steps, outside `elapsed`, every kernel group timed and the two models one after the other:
+        # the beam / pf durations (each timed group costs two event records per launch, so only the roofline kernel is
+        # timed inside the timed region), and the likelihood duration too when it ran concurrently with the beam kernels
+        # above (overlapping event intervals say nothing about either kernel).
+        overlapped = bool(n_b and n_s and args.overlap_models)
+        eng.set_option("timing_mask", 31)
+        eng.set_option("overlap_models", 0)
+        eng.reset_kernel_time()
+        coll_ms = 0.0
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(args.steps):
+            sh = main_sh
+            sh.d_w.copy_(sh.d_w0)
+            if not use_dist:
+                eng.update_device(sh.d_pose, sh.n, sh.d_w, sh.d_stats, d_lik=sh.d_lik, d_ratio=sh.d_ratio,
+                                  d_beam=sh.d_beam if n_b else None)
+                continue
+            eng.measure_device(sh.d_pose, sh.n, sh.d_lik, sh.d_ratio, sh.d_beam if n_b else None)
+            eng.pf_partial_device(sh.d_w, sh.d_lik, sh.d_beam if n_b else None, None, sh.d_ratio, sh.n, sh.d_pack, rank, world)
+            if use_dist:
+                ev0.record(stream)
+                dist.all_reduce(sh.d_pack, op=dist.ReduceOp.SUM)
+                ev1.record(stream)
+            eng.pf_apply_device(sh.d_w, sh.n, sh.d_pack, sh.d_stats, world)
+            if use_dist:
+                torch.cuda.synchronize(dev)
+                coll_ms += ev0.elapsed_time(ev1)
+        torch.cuda.synchronize(dev)
+        lik2_ms, lik2_n = eng.kernel_time(capi.KERNEL_LIKELIHOOD)
+        if lik2_n == 0:
+            lik2_ms, lik2_n = eng.kernel_time(capi.KERNEL_UPDATE)
+        beam_ms, beam_n = eng.kernel_time(capi.KERNEL_BEAM)
+        pf_ms, pf_n = eng.kernel_time(capi.KERNEL_PF)
+        upd_ms, upd_n = eng.kernel_time(capi.KERNEL_UPDATE)
+        eng.set_option("overlap_models", args.overlap_models)
+        if overlapped or not (args.timing_mask & 1):
+            lik_ms, lik_n = lik2_ms, lik2_n
+            kernel_timing_pass = "second pass of the same steps (overlap_models=0, all kernel groups timed)"
+        else:
+            kernel_timing_pass = "likelihood: hipEvents inside the timed region; beam, pf: second pass of the same steps"
+        if one_launch:
+            kernel_timing_pass += "; `likelihood` = the one-launch update (likelihood + beam + pf::measure in one kernel)"
+        eng.set_kernel_timing(False)
 
-    # the other scaling mode, same K steps, same bracketing (only when there is more than one rank to tell them apart)
+    # the other scaling mode, same K steps, same bracketing (with --full, when there is more than one rank to tell them apart)
     other = None
-    if world > 1 or args.also_other_scaling:
+    if (world > 1 and args.full) or args.also_other_scaling:
         other_sh = Shard("strong" if args.scaling == "weak" else "weak")
         for _ in range(max(args.warmup, 3)):
             step(other_sh)
@@ -981,101 +1043,103 @@ def main():
         evals_per_step = float(n_total) * n_s
         ms_per_step = elapsed / args.steps * 1e3
         value = evals_per_step * args.steps / elapsed
-        lik_avg_ms = lik_ms / max(lik_n, 1)
-        stats = main_sh.d_stats.cpu().numpy()
-        tiled = lik_mode["tiled"]
-        group = _tiled_group(n_s, n_p, args.lik_group)
-        if strict_mode == 3:
-            group = min(group, 16)
-        small = (not tiled) and n_s <= 32 and n_p >= 256 and args.lik_small
-        if tiled:
-            coop = bool(lik_coop and args.lik_index == 2)
-            defer = bool(coop and int(eng.get_option("lik_defer_active")))
-            kernel_name = "likelihood_tiled_kernel<%d, %d, %d, %s, %s, %s>" % (group, args.lik_index, 4 if group == 32 else 8,
-                                                                               "true" if coop else "false",
-                                                                               "true" if defer else "false",
-                                                                               "true" if strict_mode == 3 else "false")
-        elif small:
-            kernel_name = "likelihood_small_kernel<"
-        else:
-            wide = args.lik_index == 2 and n_s > 512 and n_p <= 512
-            kernel_name = "likelihood_kernel<%d, %d, false>" % (64 if n_s <= 128 else 1024 if wide else 256, args.lik_index)
-            if one_launch:
-                # the whole update as ONE launch (update_kernels.h): that kernel is what was timed, and what the counters are of
-                kernel_name = "update_small_kernel<%d, %d, true>" % (64 if n_s <= 128 else 1024 if wide else 256,
-                                                                     args.lik_index)
-        # counters of the same map kind: profiles/*_C2j_* = C2 with displaced map points (--map-jitter)
-        # (... and *_C2c_* / *_C5c_* = the same workload with the float sums inside the kernel, strict_order = 3)
-        pmc_tag = args.workload + ("j" if args.map_jitter else "") + ("c" if strict_mode == 3 else "")
-        pmc, pmc_src, pmc_refused = pmc_counters("void mcl3dl::" + kernel_name, pmc_tag)
-        # the committed counters are per launch of ONE shape: use them only for a launch of that many wavefronts
-        if tiled:
-            expected_waves = 4 * ((n_s + 255) // 256) * ((n_p + group - 1) // group)
-        elif small:
-            expected_waves = None
-        else:
-            expected_waves = n_p * (1 if n_s <= 128 else 16 if "<1024" in kernel_name else 4)
-        counters_note = pmc_refused
-        if pmc and (expected_waves is None or abs(pmc.get("SQ_WAVES", 0.0) - expected_waves) > 0.01 * expected_waves):
-            counters_note = ("committed counters (%s) are for a launch of %.0f wavefronts, this one has %s: not used"
-                             % (pmc_src, pmc.get("SQ_WAVES", 0.0), expected_waves))
-            pmc, pmc_src = None, None
-        cost, cost_src = valu_costs()
-        kernel_s = lik_avg_ms * 1e-3
-        res, traffic = kernel_resources(pmc, kernel_s if lik_n else 0.0, cost, cost_src)
-        # `bound` / `frac` are taken over the resources whose peak is a DOCUMENTED figure of the guide; fractions against
-        # peaks this repository measured itself are listed next to them (`frac_vs_measured_peaks`), never as `frac`
-        documented = {k: r for k, r in res.items() if r.get("peak_kind") == "documented"}
-        if documented:
-            bound = max(documented, key=lambda k: documented[k]["frac"])
-            top = documented[bound]
-        else:
-            bound, top = "hbm", {"achieved": None, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": None}
-        hbm_frac = res["hbm"]["frac"] if "hbm" in res else None
-        roofline = {
-            "bound": bound,
-            "kernel": kernel_name,
-            "achieved": top["achieved"], "peak": top["peak"], "unit": top["unit"], "frac": top["frac"],
-            "frac_definition": ("largest fraction among the resources with a documented peak (hbm 8 TB/s, l2 34.5 TB/s, "
-                                "valu_issue = wave64 VALU instructions/s against 1024 SIMDs x 2.4 GHz / 2 cycles per "
-                                "instruction); the same launch against peaks measured here: frac_vs_measured_peaks"),
-            "frac_vs_measured_peaks": {k: r["frac"] for k, r in res.items() if r.get("peak_kind") == "measured"},
-            # north_star: ">= 40 % of HBM-read roofline" — answered, not dropped
-            "hbm_target": {"frac": hbm_frac, "target": HBM_TARGET_FRAC,
-                           "status": "not applicable: the index is built so that a scan tile's working set is L2-resident "
-                                     "(TCC hit %s); HBM traffic is %s of the algorithmic bytes of SURVEY.md 8d, i.e. nothing is "
-                                     "re-read from HBM — the kernel is bound by VALU issue and L2 request rate, not by HBM"
-                                     % ("%.1f %%" % (100.0 * pmc["TCC_HIT_sum"] / max(pmc["TCC_HIT_sum"] + pmc.get("TCC_MISS_sum", 0.0), 1.0))
-                                        if pmc and "TCC_HIT_sum" in pmc else "n/a",
-                                        "%.2g" % (traffic / bytes_lik_launch) if traffic else "n/a")},
-            "traffic": traffic,
-            "counters_source": pmc_src,
-            "counters_note": counters_note,
-            "counters_box": "counters = mean per launch of the committed --pmc passes (another MI355X box than this run's: "
-                            "instruction and request counts are properties of the launch, identical from box to box; the "
-                            "kernel time they are divided by is this run's)",
-            "avg_launch_ms": lik_avg_ms, "launches": lik_n,
-            "resources": res,
-            # the canonical structure of SURVEY.md §8d, for the record; NOT priced against the HBM peak (the shipped index
-            # reads 68 B per evaluation — brick-table entry + one 64-byte voxel record — and reads them from L2)
-            "algorithmic_bytes_per_launch": bytes_lik_launch,
-            "algorithmic_bytes_per_eval": bytes_lik_launch / max(ws["evals"], 1.0),
-            "algorithmic_rate_GBps": bytes_lik_launch / kernel_s / 1e9 if lik_n else None,
-            # SURVEY.md 8d's own fraction, spelled out so that nobody has to recompute it: algorithmic bytes of the canonical
-            # 27-cell structure / kernel time / 8 TB/s. It EXCEEDS 1 (20 at C2) because those bytes are never read: the
-            # kernel fetches one pre-pruned 64-byte record per evaluation (index_bytes_per_eval) out of L2, so the HBM
-            # roofline of 8d does not bind this design — `frac` above is the resource that does
-            "frac_algorithmic_hbm": (bytes_lik_launch / kernel_s / 1e9 / HBM_PEAK_GBPS) if lik_n else None,
-            "frac_algorithmic_hbm_note": "SURVEY 8d: (16 + 27*4 + 16*K) B per evaluation / kernel time / 8 TB/s; > 1 means the "
-                                         "canonical bytes are not read at all (pre-pruned voxel records from L2), not that "
-                                         "the part was exceeded",
-            "k_bar": k_bar,
-            "index_bytes_per_eval": 68.0 if args.lik_index == 2 else None,
-            # L1 (TCP) cache-line accesses per cycle and CU: the resource that bound the kernel before the cooperative
-            # fetch — kept as an observation, the counter has no documented peak
-            "l1_accesses_per_cycle_per_cu": (pmc["TCP_TOTAL_CACHE_ACCESSES_sum"] / 256.0 / (kernel_s * CLOCK_HZ)
-                                             if pmc and "TCP_TOTAL_CACHE_ACCESSES_sum" in pmc and lik_n else None),
-        }
+        roofline = None
+        if args.full:
+            lik_avg_ms = lik_ms / max(lik_n, 1)
+            stats = main_sh.d_stats.cpu().numpy()
+            tiled = lik_mode["tiled"]
+            group = _tiled_group(n_s, n_p, args.lik_group)
+            if strict_mode == 3:
+                group = min(group, 16)
+            small = (not tiled) and n_s <= 32 and n_p >= 256 and args.lik_small
+            if tiled:
+                coop = bool(lik_coop and args.lik_index == 2)
+                defer = bool(coop and int(eng.get_option("lik_defer_active")))
+                kernel_name = "likelihood_tiled_kernel<%d, %d, %d, %s, %s, %s>" % (group, args.lik_index, 4 if group == 32 else 8,
+                                                                                   "true" if coop else "false",
+                                                                                   "true" if defer else "false",
+                                                                                   "true" if strict_mode == 3 else "false")
+            elif small:
+                kernel_name = "likelihood_small_kernel<"
+            else:
+                wide = args.lik_index == 2 and n_s > 512 and n_p <= 512
+                kernel_name = "likelihood_kernel<%d, %d, false>" % (64 if n_s <= 128 else 1024 if wide else 256, args.lik_index)
+                if one_launch:
+                    # the whole update as ONE launch (update_kernels.h): that kernel is what was timed, and what the counters are of
+                    kernel_name = "update_small_kernel<%d, %d, true>" % (64 if n_s <= 128 else 1024 if wide else 256,
+                                                                         args.lik_index)
+            # counters of the same map kind: profiles/*_C2j_* = C2 with displaced map points (--map-jitter)
+            # (... and *_C2c_* / *_C5c_* = the same workload with the float sums inside the kernel, strict_order = 3)
+            pmc_tag = args.workload + ("j" if args.map_jitter else "") + ("c" if strict_mode == 3 else "")
+            pmc, pmc_src, pmc_refused = pmc_counters("void mcl3dl::" + kernel_name, pmc_tag)
+            # the committed counters are per launch of ONE shape: use them only for a launch of that many wavefronts
+            if tiled:
+                expected_waves = 4 * ((n_s + 255) // 256) * ((n_p + group - 1) // group)
+            elif small:
+                expected_waves = None
+            else:
+                expected_waves = n_p * (1 if n_s <= 128 else 16 if "<1024" in kernel_name else 4)
+            counters_note = pmc_refused
+            if pmc and (expected_waves is None or abs(pmc.get("SQ_WAVES", 0.0) - expected_waves) > 0.01 * expected_waves):
+                counters_note = ("committed counters (%s) are for a launch of %.0f wavefronts, this one has %s: not used"
+                                 % (pmc_src, pmc.get("SQ_WAVES", 0.0), expected_waves))
+                pmc, pmc_src = None, None
+            cost, cost_src = valu_costs()
+            kernel_s = lik_avg_ms * 1e-3
+            res, traffic = kernel_resources(pmc, kernel_s if lik_n else 0.0, cost, cost_src)
+            # `bound` / `frac` are taken over the resources whose peak is a DOCUMENTED figure of the guide; fractions against
+            # peaks this repository measured itself are listed next to them (`frac_vs_measured_peaks`), never as `frac`
+            documented = {k: r for k, r in res.items() if r.get("peak_kind") == "documented"}
+            if documented:
+                bound = max(documented, key=lambda k: documented[k]["frac"])
+                top = documented[bound]
+            else:
+                bound, top = "hbm", {"achieved": None, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": None}
+            hbm_frac = res["hbm"]["frac"] if "hbm" in res else None
+            roofline = {
+                "bound": bound,
+                "kernel": kernel_name,
+                "achieved": top["achieved"], "peak": top["peak"], "unit": top["unit"], "frac": top["frac"],
+                "frac_definition": ("largest fraction among the resources with a documented peak (hbm 8 TB/s, l2 34.5 TB/s, "
+                                    "valu_issue = wave64 VALU instructions/s against 1024 SIMDs x 2.4 GHz / 2 cycles per "
+                                    "instruction); the same launch against peaks measured here: frac_vs_measured_peaks"),
+                "frac_vs_measured_peaks": {k: r["frac"] for k, r in res.items() if r.get("peak_kind") == "measured"},
+                # north_star: ">= 40 % of HBM-read roofline" — answered, not dropped
+                "hbm_target": {"frac": hbm_frac, "target": HBM_TARGET_FRAC,
+                               "status": "not applicable: the index is built so that a scan tile's working set is L2-resident "
+                                         "(TCC hit %s); HBM traffic is %s of the algorithmic bytes of SURVEY.md 8d, i.e. nothing is "
+                                         "re-read from HBM — the kernel is bound by VALU issue and L2 request rate, not by HBM"
+                                         % ("%.1f %%" % (100.0 * pmc["TCC_HIT_sum"] / max(pmc["TCC_HIT_sum"] + pmc.get("TCC_MISS_sum", 0.0), 1.0))
+                                            if pmc and "TCC_HIT_sum" in pmc else "n/a",
+                                            "%.2g" % (traffic / bytes_lik_launch) if traffic else "n/a")},
+                "traffic": traffic,
+                "counters_source": pmc_src,
+                "counters_note": counters_note,
+                "counters_box": "counters = mean per launch of the committed --pmc passes (another MI355X box than this run's: "
+                                "instruction and request counts are properties of the launch, identical from box to box; the "
+                                "kernel time they are divided by is this run's)",
+                "avg_launch_ms": lik_avg_ms, "launches": lik_n,
+                "resources": res,
+                # the canonical structure of SURVEY.md §8d, for the record; NOT priced against the HBM peak (the shipped index
+                # reads 68 B per evaluation — brick-table entry + one 64-byte voxel record — and reads them from L2)
+                "algorithmic_bytes_per_launch": bytes_lik_launch,
+                "algorithmic_bytes_per_eval": bytes_lik_launch / max(ws["evals"], 1.0),
+                "algorithmic_rate_GBps": bytes_lik_launch / kernel_s / 1e9 if lik_n else None,
+                # SURVEY.md 8d's own fraction, spelled out so that nobody has to recompute it: algorithmic bytes of the canonical
+                # 27-cell structure / kernel time / 8 TB/s. It EXCEEDS 1 (20 at C2) because those bytes are never read: the
+                # kernel fetches one pre-pruned 64-byte record per evaluation (index_bytes_per_eval) out of L2, so the HBM
+                # roofline of 8d does not bind this design — `frac` above is the resource that does
+                "frac_algorithmic_hbm": (bytes_lik_launch / kernel_s / 1e9 / HBM_PEAK_GBPS) if lik_n else None,
+                "frac_algorithmic_hbm_note": "SURVEY 8d: (16 + 27*4 + 16*K) B per evaluation / kernel time / 8 TB/s; > 1 means the "
+                                             "canonical bytes are not read at all (pre-pruned voxel records from L2), not that "
+                                             "the part was exceeded",
+                "k_bar": k_bar,
+                "index_bytes_per_eval": 68.0 if args.lik_index == 2 else None,
+                # L1 (TCP) cache-line accesses per cycle and CU: the resource that bound the kernel before the cooperative
+                # fetch — kept as an observation, the counter has no documented peak
+                "l1_accesses_per_cycle_per_cu": (pmc["TCP_TOTAL_CACHE_ACCESSES_sum"] / 256.0 / (kernel_s * CLOCK_HZ)
+                                                 if pmc and "TCP_TOTAL_CACHE_ACCESSES_sum" in pmc and lik_n else None),
+            }
         out = {
             "metric": "particle·point evals/sec; filter-update Hz @ 4096 particles × 16k-pt scan",  # BASELINE.json
             "value": value,
@@ -1120,7 +1184,7 @@ def main():
                                 "region that is the same code path at N = 1 and N > 1, so that the driver's scaling efficiency "
                                 "compares like with like. The METRIC's own region (SURVEY.md section 8d: scan upload + pose / weight "
                                 "H2D + kernels + weight D2H from / to host buffers) is `value_8d` / `ms_per_step_8d` right below "
-                                "(and `headline`), timed in the same run from C; it is the lower of the two and the one DESIGN.md "
+                                "(and `headline`), timed in the same run from C with --full; it is the lower of the two and the one DESIGN.md "
                                 "quotes as the update rate. (VERDICT round 5 asked for `value` := the 8d region; the bench contract "
                                 "forbids a PCIe-inclusive `value`, so both stand side by side at the top level.)",
             "value_device_resident": value,
@@ -1128,391 +1192,394 @@ def main():
             "ms_per_step_8d": None,
             "roofline": roofline,
             "prewarm": prewarm,
-            "kernel_timing_pass": kernel_timing_pass,
-            "kernels_ms_per_step": {"likelihood": lik_avg_ms, "beam": beam_ms / max(beam_n, 1) if n_b else 0.0,
-                                    "pf": pf_ms / max(args.steps, 1),
-                                    # the whole update as ONE launch (<= update_small_max particles): then the three above are 0
-                                    "update_one_launch": upd_ms / max(args.steps, 1),
-                                    "collective": coll_ms / args.steps if use_dist else 0.0},
+            "cpu_baseline": None,
             "setup_seconds": setup_s,
-            "index": dict(eng.index_stats(), lik_index=args.lik_index, voxel_ratio=args.cand_voxel_ratio,
-                          footprint_bytes=eng.memory_footprint()),
-            "result_check": {"entropy": float(stats[0]), "match_ratio_min": float(stats[1]),
-                             "match_ratio_max": float(stats[2]), "restored": bool(stats[3])},
+            "full": args.full,
         }
         if other:
             out["other_scaling"] = other
-        # self-consistency of the numbers that were timed: normalised weights sum to 1 and reproduce the entropy
-        # (one rank's share of the sum when particles are sharded)
-        wf = main_sh.d_w.cpu().numpy().astype(np.float64)
-        out["result_check"]["weight_sum_this_rank"] = float(wf.sum())
-        if world == 1:
-            out["result_check"]["entropy_from_weights"] = float(-(wf[wf > 0] * np.log(wf[wf > 0])).sum())
-        if n_b:
-            beam_avg = beam_ms / max(beam_n, 1)
-            out["beam"] = {"rays_per_s": ws["rays"] / (beam_avg * 1e-3), "dda_steps_per_s": ws["dda_steps"] / (beam_avg * 1e-3),
-                           "algorithmic_GBps": bytes_beam_launch / (beam_avg * 1e-3) / 1e9, "avg_launch_ms": beam_avg,
-                           "avg_launch_ms_includes": "penalty memset + beam_origin_kernel + beam_kernel + beam_finalize_kernel "
-                                                     "(one timed group, run alone: overlap_models = 0)"}
-            # the beam kernel's own counter-derived fractions (same pricing as `roofline`), against the kernel's share of the
-            # timed group: its rocprofv3 share of beam_kernel in the group is > 95 % at these sizes
-            bpmc, bsrc, bnote = pmc_counters("void mcl3dl::beam_kernel<false", pmc_tag)
-            if bnote:
-                out["beam"]["counters_note"] = bnote
-            beam_waves = 4 * ((n_p * n_b + 255) // 256)
-            if bpmc and abs(bpmc.get("SQ_WAVES", 0.0) - beam_waves) > 0.01 * beam_waves:
-                bpmc = None   # counters of another launch shape
-            if bpmc:
-                bres, btraffic = kernel_resources(bpmc, beam_avg * 1e-3, cost, cost_src)
-                for r in bres.values():
-                    r.pop("note", None)
-                bdoc = {k: r for k, r in bres.items() if r.get("peak_kind") == "documented"}
-                if bdoc:
-                    bb = max(bdoc, key=lambda k: bdoc[k]["frac"])
-                    out["beam"]["roofline"] = {"bound": bb, "frac": bdoc[bb]["frac"], "traffic": btraffic,
-                                               "frac_vs_measured_peaks": {k: r["frac"] for k, r in bres.items()
-                                                                          if r.get("peak_kind") == "measured"},
-                                               "counters_source": bsrc, "resources": bres,
-                                               "algorithmic_bytes_per_launch": bytes_beam_launch}
-        d_pose, d_w, d_w0, d_lik, d_ratio, d_beam, d_stats = (main_sh.d_pose, main_sh.d_w, main_sh.d_w0, main_sh.d_lik,
-                                                              main_sh.d_ratio, main_sh.d_beam, main_sh.d_stats)
-        if world == 1:
-            # SURVEY.md section 8d's definition of one update: host buffers in, host buffers out (scan ordering + upload,
-            # pose and prior-weight H2D, kernels, reduction, weight D2H) through the synchronous host entry point
-            eng.set_stream(None)
-            # timed from C (tools/benchloop.c: the reference's caller is C++; ctypes spends ~15 us per call converting the 19
-            # arguments) on pageable arrays — every array staged through the library's page-locked block — and on arrays the
-            # caller allocated with mcl3dl_hip_host_alloc (read and written in place); the Python-call figure next to them
-            h_pose = np.ascontiguousarray(sc.poses, np.float32)
-            h_w0 = np.ascontiguousarray(sc.weights, np.float32)
-            h_lik = np.ascontiguousarray(sc.scan_lik, np.float32)
-            h_beam = np.ascontiguousarray(sc.scan_beam, np.float32) if n_b else None
-            h_lab = np.ascontiguousarray(sc.scan_beam_label, np.uint32) if n_b else None
-            h_org = np.ascontiguousarray(sc.origins, np.float32)
-            o_lik, o_ratio, o_beam = (np.zeros(n_p, np.float32) for _ in range(3))
-            with no_gc():
-                host_ms, per = eng.time_measure_update(h_pose, h_w0, h_w0.copy(), h_lik, h_beam, h_lab, h_org, o_lik, o_ratio,
-                                                       o_beam, args.steps, warm_ms=150.0)
-            pin = dict(pose=eng.host_array((n_p, 7)), w=eng.host_array(n_p), lik=eng.host_array((n_s, 3)),
-                       beam=eng.host_array((n_b, 3)) if n_b else None, lab=eng.host_array(n_b, np.uint32) if n_b else None,
-                       org=eng.host_array((len(h_org), 3)), o_lik=eng.host_array(n_p), o_ratio=eng.host_array(n_p),
-                       o_beam=eng.host_array(n_p))
-            pin["pose"][:] = h_pose
-            pin["lik"][:] = h_lik
-            pin["org"][:] = h_org
+        if args.full:
+            out["kernel_timing_pass"] = kernel_timing_pass
+            out["kernels_ms_per_step"] = {"likelihood": lik_avg_ms, "beam": beam_ms / max(beam_n, 1) if n_b else 0.0,
+                                          "pf": pf_ms / max(args.steps, 1),
+                                          # the whole update as ONE launch (<= update_small_max particles): then the three above are 0
+                                          "update_one_launch": upd_ms / max(args.steps, 1),
+                                          "collective": coll_ms / args.steps if use_dist else 0.0}
+            out["index"] = dict(eng.index_stats(), lik_index=args.lik_index, voxel_ratio=args.cand_voxel_ratio,
+                                footprint_bytes=eng.memory_footprint())
+            out["result_check"] = {"entropy": float(stats[0]), "match_ratio_min": float(stats[1]),
+                                   "match_ratio_max": float(stats[2]), "restored": bool(stats[3])}
+            # self-consistency of the numbers that were timed: normalised weights sum to 1 and reproduce the entropy
+            # (one rank's share of the sum when particles are sharded)
+            wf = main_sh.d_w.cpu().numpy().astype(np.float64)
+            out["result_check"]["weight_sum_this_rank"] = float(wf.sum())
+            if world == 1:
+                out["result_check"]["entropy_from_weights"] = float(-(wf[wf > 0] * np.log(wf[wf > 0])).sum())
             if n_b:
-                pin["beam"][:] = h_beam
-                pin["lab"][:] = h_lab
-            with no_gc():
-                pinned_ms, _per = eng.time_measure_update(pin["pose"], h_w0, pin["w"], pin["lik"], pin["beam"], pin["lab"],
-                                                          pin["org"], pin["o_lik"], pin["o_ratio"], pin["o_beam"], args.steps,
-                                                          warm_ms=100.0)
-            same_results = bool(np.array_equal(pin["o_lik"], o_lik) and np.array_equal(pin["o_ratio"], o_ratio))
-            keep_gpu_warm(lambda: eng.measure_update(sc.poses, sc.weights, sc.scan_lik, sc.scan_beam, sc.scan_beam_label,
-                                                     sc.origins), 0.1)
-            with no_gc():
-                t2 = time.perf_counter()
+                beam_avg = beam_ms / max(beam_n, 1)
+                out["beam"] = {"rays_per_s": ws["rays"] / (beam_avg * 1e-3), "dda_steps_per_s": ws["dda_steps"] / (beam_avg * 1e-3),
+                               "algorithmic_GBps": bytes_beam_launch / (beam_avg * 1e-3) / 1e9, "avg_launch_ms": beam_avg,
+                               "avg_launch_ms_includes": "penalty memset + beam_origin_kernel + beam_kernel + beam_finalize_kernel "
+                                                         "(one timed group, run alone: overlap_models = 0)"}
+                # the beam kernel's own counter-derived fractions (same pricing as `roofline`), against the kernel's share of the
+                # timed group: its rocprofv3 share of beam_kernel in the group is > 95 % at these sizes
+                bpmc, bsrc, bnote = pmc_counters("void mcl3dl::beam_kernel<false", pmc_tag)
+                if bnote:
+                    out["beam"]["counters_note"] = bnote
+                beam_waves = 4 * ((n_p * n_b + 255) // 256)
+                if bpmc and abs(bpmc.get("SQ_WAVES", 0.0) - beam_waves) > 0.01 * beam_waves:
+                    bpmc = None   # counters of another launch shape
+                if bpmc:
+                    bres, btraffic = kernel_resources(bpmc, beam_avg * 1e-3, cost, cost_src)
+                    for r in bres.values():
+                        r.pop("note", None)
+                    bdoc = {k: r for k, r in bres.items() if r.get("peak_kind") == "documented"}
+                    if bdoc:
+                        bb = max(bdoc, key=lambda k: bdoc[k]["frac"])
+                        out["beam"]["roofline"] = {"bound": bb, "frac": bdoc[bb]["frac"], "traffic": btraffic,
+                                                   "frac_vs_measured_peaks": {k: r["frac"] for k, r in bres.items()
+                                                                              if r.get("peak_kind") == "measured"},
+                                                   "counters_source": bsrc, "resources": bres,
+                                                   "algorithmic_bytes_per_launch": bytes_beam_launch}
+            d_pose, d_w, d_w0, d_lik, d_ratio, d_beam, d_stats = (main_sh.d_pose, main_sh.d_w, main_sh.d_w0, main_sh.d_lik,
+                                                                  main_sh.d_ratio, main_sh.d_beam, main_sh.d_stats)
+            if world == 1:
+                # SURVEY.md section 8d's definition of one update: host buffers in, host buffers out (scan ordering + upload,
+                # pose and prior-weight H2D, kernels, reduction, weight D2H) through the synchronous host entry point
+                eng.set_stream(None)
+                # timed from C (tools/benchloop.c: the reference's caller is C++; ctypes spends ~15 us per call converting the 19
+                # arguments) on pageable arrays — every array staged through the library's page-locked block — and on arrays the
+                # caller allocated with mcl3dl_hip_host_alloc (read and written in place); the Python-call figure next to them
+                h_pose = np.ascontiguousarray(sc.poses, np.float32)
+                h_w0 = np.ascontiguousarray(sc.weights, np.float32)
+                h_lik = np.ascontiguousarray(sc.scan_lik, np.float32)
+                h_beam = np.ascontiguousarray(sc.scan_beam, np.float32) if n_b else None
+                h_lab = np.ascontiguousarray(sc.scan_beam_label, np.uint32) if n_b else None
+                h_org = np.ascontiguousarray(sc.origins, np.float32)
+                o_lik, o_ratio, o_beam = (np.zeros(n_p, np.float32) for _ in range(3))
+                with no_gc():
+                    host_ms, per = eng.time_measure_update(h_pose, h_w0, h_w0.copy(), h_lik, h_beam, h_lab, h_org, o_lik, o_ratio,
+                                                           o_beam, args.steps, warm_ms=150.0)
+                pin = dict(pose=eng.host_array((n_p, 7)), w=eng.host_array(n_p), lik=eng.host_array((n_s, 3)),
+                           beam=eng.host_array((n_b, 3)) if n_b else None, lab=eng.host_array(n_b, np.uint32) if n_b else None,
+                           org=eng.host_array((len(h_org), 3)), o_lik=eng.host_array(n_p), o_ratio=eng.host_array(n_p),
+                           o_beam=eng.host_array(n_p))
+                pin["pose"][:] = h_pose
+                pin["lik"][:] = h_lik
+                pin["org"][:] = h_org
+                if n_b:
+                    pin["beam"][:] = h_beam
+                    pin["lab"][:] = h_lab
+                with no_gc():
+                    pinned_ms, _per = eng.time_measure_update(pin["pose"], h_w0, pin["w"], pin["lik"], pin["beam"], pin["lab"],
+                                                              pin["org"], pin["o_lik"], pin["o_ratio"], pin["o_beam"], args.steps,
+                                                              warm_ms=100.0)
+                same_results = bool(np.array_equal(pin["o_lik"], o_lik) and np.array_equal(pin["o_ratio"], o_ratio))
+                keep_gpu_warm(lambda: eng.measure_update(sc.poses, sc.weights, sc.scan_lik, sc.scan_beam, sc.scan_beam_label,
+                                                         sc.origins), 0.1)
+                with no_gc():
+                    t2 = time.perf_counter()
+                    for _ in range(args.steps):
+                        eng.measure_update(sc.poses, sc.weights, sc.scan_lik, sc.scan_beam, sc.scan_beam_label, sc.origins)
+                    python_ms = (time.perf_counter() - t2) / args.steps * 1e3
+                for a in pin.values():
+                    if a is not None:
+                        eng.host_free(a)
+                out["value_8d"] = n_p * n_s / (host_ms * 1e-3)
+                out["ms_per_step_8d"] = host_ms
+                fp = out["index"]["footprint_bytes"]
+                index_bytes = int(fp["cand_table"] + fp["cand_start"] + fp["cand_points"])
+                map_bytes = 16 * int(len(sc.map_xyz))
+                out["headline"] = {
+                    "value_8d": out["value_8d"], "ms_per_update_8d": host_ms, "update_hz_8d": 1e3 / host_ms,
+                    "value_device_resident": value, "ms_per_step_device_resident": ms_per_step,
+                    "region_8d": "SURVEY.md section 8d: host buffers in (scan, poses, prior weights), host buffers out (weights, "
+                                 "likelihoods), PCIe and scan ordering included — mcl3dl_hip_measure_update timed from C",
+                    "likelihood_sum": out["config"]["accumulate"],
+                    "index_bytes": index_bytes, "map_bytes": map_bytes, "index_bytes_per_map_byte": index_bytes / max(map_bytes, 1),
+                }
+                roofline["frac_of_update"] = {"device_resident": lik_avg_ms / ms_per_step if lik_n else None,
+                                              "update_8d": lik_avg_ms / host_ms if lik_n else None,
+                                              "what": "dominant kernel's average launch time / time of one whole update"}
+                out["update_8d"] = {"ms_per_update": host_ms, "value": n_p * n_s / (host_ms * 1e-3),
+                                    "unit": "particle·point evals/s", "update_hz": 1e3 / host_ms, "steps": args.steps,
+                                    "median_ms": float(np.median(per)), "min_ms": float(per.min()),
+                                    "overhead_over_device_resident_ms": host_ms - ms_per_step,
+                                    "ms_per_update_page_locked_arrays": pinned_ms,
+                                    "value_page_locked_arrays": n_p * n_s / (pinned_ms * 1e-3),
+                                    "page_locked_results_equal": same_results,
+                                    "ms_per_update_called_from_python": python_ms,
+                                    "what": "mcl3dl_hip_measure_update on host buffers, timed from C (tools/benchloop.c): scan upload + "
+                                            "ordering + pose/weight H2D + kernels + weight/likelihood D2H, PCIe included (SURVEY.md "
+                                            "section 8d's timed region); pageable caller arrays (ms_per_update) and arrays from "
+                                            "mcl3dl_hip_host_alloc (ms_per_update_page_locked_arrays)"}
+                if not args.no_extras and args.workload in ("C1", "C2", "C3") and strict_mode in (0, 2):
+                    # The same region for a caller that HOLDS its scan in the engine's order (mcl3dl_hip_scan_order_host; the drop-in
+                    # classes with MCL3DL_HIP_ENGINE_ORDER=1): no ordering launches (scan_presorted) and the reference's float
+                    # recurrence inside the likelihood kernel (strict_order = 3) — likelihoods bit-identical to the reference on the
+                    # caller's own array — next to the caller-order replay (strict_order = 1). Checked against the CPU reference below.
+                    held = np.ascontiguousarray(h_lik[capi.scan_order_host(h_lik)])
+                    eo = {}
+                    e_lik, e_ratio, e_beam = (np.zeros(n_p, np.float32) for _ in range(3))
+                    try:
+                        for tag, scan_arr, so, pre in (("caller_order_replay", h_lik, 1, 0), ("engine_order_in_kernel", h_lik, 3, 0),
+                                                       ("held_in_engine_order_presorted_fp64", held, 0, 1),
+                                                       ("held_in_engine_order_presorted_in_kernel", held, 3, 1)):
+                            eng.set_option("strict_order", so)
+                            eng.set_option("scan_presorted", pre)
+                            with no_gc():
+                                ms_e, _ = eng.time_measure_update(h_pose, h_w0, h_w0.copy(), scan_arr, h_beam, h_lab, h_org, e_lik, e_ratio,
+                                                                  e_beam, args.steps, warm_ms=100.0)
+                            eo[tag + "_ms"] = ms_e
+                    finally:
+                        eng.set_option("strict_order", strict_mode)
+                        eng.set_option("scan_presorted", 0)
+                    eo["default_ms"] = host_ms
+                    eo["held_scan_likelihoods"] = e_lik.copy()   # (popped again below: compared with the CPU reference on `held`)
+                    eo["held_scan"] = held
+                    eo["what"] = ("mcl3dl_hip_measure_update on host buffers timed from C, as update_8d: the float sums replayed in the "
+                                  "caller's order behind the kernel (strict_order 1), run inside the kernel in the engine's order (3), "
+                                  "and for a caller that holds its scan in that order (option scan_presorted: no ordering launches) — "
+                                  "the last one is bit-identical to the reference on the caller's own array")
+                    out["engine_order"] = eo
+                eng.set_stream(stream.cuda_stream)
+            if not args.no_extras:
+                # the reductions that follow the update in the node (expectationBiased + max + covariance) on the
+                # device-resident particles; each call ends with a D2H of a dozen scalars
+                rewarm()
+                t3 = time.perf_counter()
+                for _ in range(10):
+                    mean7, _tot, _im, _ib = eng.expectation_device(d_pose, d_w, None, n_p)
+                    eng.covariance_device(d_pose, d_w, n_p, mean7)
+                out["post_update_reductions"] = {"ms": (time.perf_counter() - t3) / 10 * 1e3,
+                                                 "what": "expectationBiased + max + covariance over this rank's particles"}
+                # resampling of this rank's particles with the weights the update just produced: host bookkeeping
+                # (prefix sums, tie sort, it/it_prev walk) + device lower_bound / gather; noise = identity (timing only)
+                w_host = d_w.cpu().numpy()
+                st13 = np.zeros((n_p, 13), np.float32)
+                st13[:, :7] = main_sh.host_poses
+                t4 = time.perf_counter()
+                for _ in range(5):
+                    pstep = eng.resample_begin(w_host)
+                    _src, _dup, n_dup = eng.resample_plan(0, 0.37 * pstep)
+                    ident = _identity_noise(n_dup)
+                    eng.resample_apply(st13, ident)
+                out["resample"] = {"ms": (time.perf_counter() - t4) / 5 * 1e3, "duplicates": int(n_dup),
+                                   "what": "mcl3dl_hip_resample_begin + plan + apply, host buffers, %d particles" % n_p}
+                # the same with weights and 13-float states resident on the device (what a multi-GPU host runs per rank after
+                # the all-gather, mcl_3dl_amd/distributed.py:sharded_resample)
+                d_st_in = torch.from_numpy(st13).to(dev)
+                d_st_out = torch.empty_like(d_st_in)
+                torch.cuda.synchronize(dev)
+                t6 = time.perf_counter()
+                for _ in range(5):
+                    pstep = eng.resample_begin_device(d_w, n_p)
+                    _src, _dup, n_dup2 = eng.resample_plan(0, 0.37 * pstep, want_plan=False)
+                    eng.resample_apply_device(d_st_in, ident[:n_dup2], d_st_out)
+                out["resample"]["ms_device_resident"] = (time.perf_counter() - t6) / 5 * 1e3
+            if world == 1 and not args.no_extras:
+                # the fused device-resident call (measure + pf::measure in one C call), host wall per call back to back. Not `value`.
+                # (its hipGraph-replay form measured slower for two rounds and was removed in round 5)
+                fused = {}
+                rewarm()
+                for use_graph in (0,):
+                    for _ in range(3):
+                        d_w.copy_(d_w0)
+                        eng.update_device(d_pose, n_p, d_w, d_stats, d_lik=d_lik, d_ratio=d_ratio, d_beam=d_beam if n_b else None)
+                    torch.cuda.synchronize(dev)
+                    t5 = time.perf_counter()
+                    for _ in range(args.steps):
+                        d_w.copy_(d_w0)
+                        eng.update_device(d_pose, n_p, d_w, d_stats, d_lik=d_lik, d_ratio=d_ratio, d_beam=d_beam if n_b else None)
+                    torch.cuda.synchronize(dev)
+                    fused["graph" if use_graph else "eager"] = (time.perf_counter() - t5) / args.steps * 1e3
+                # one whole filter iteration with everything resident on the device: measurement update -> expectation + max
+                # (the node publishes the pose from it) -> resampling of the 13-float states; noise = identity
+                rewarm()
+                t7 = time.perf_counter()
                 for _ in range(args.steps):
-                    eng.measure_update(sc.poses, sc.weights, sc.scan_lik, sc.scan_beam, sc.scan_beam_label, sc.origins)
-                python_ms = (time.perf_counter() - t2) / args.steps * 1e3
-            for a in pin.values():
-                if a is not None:
-                    eng.host_free(a)
-            out["value_8d"] = n_p * n_s / (host_ms * 1e-3)
-            out["ms_per_step_8d"] = host_ms
-            fp = out["index"]["footprint_bytes"]
-            index_bytes = int(fp["cand_table"] + fp["cand_start"] + fp["cand_points"])
-            map_bytes = 16 * int(len(sc.map_xyz))
-            out["headline"] = {
-                "value_8d": out["value_8d"], "ms_per_update_8d": host_ms, "update_hz_8d": 1e3 / host_ms,
-                "value_device_resident": value, "ms_per_step_device_resident": ms_per_step,
-                "region_8d": "SURVEY.md section 8d: host buffers in (scan, poses, prior weights), host buffers out (weights, "
-                             "likelihoods), PCIe and scan ordering included — mcl3dl_hip_measure_update timed from C",
-                "likelihood_sum": out["config"]["accumulate"],
-                "index_bytes": index_bytes, "map_bytes": map_bytes, "index_bytes_per_map_byte": index_bytes / max(map_bytes, 1),
-            }
-            roofline["frac_of_update"] = {"device_resident": lik_avg_ms / ms_per_step if lik_n else None,
-                                          "update_8d": lik_avg_ms / host_ms if lik_n else None,
-                                          "what": "dominant kernel's average launch time / time of one whole update"}
-            out["update_8d"] = {"ms_per_update": host_ms, "value": n_p * n_s / (host_ms * 1e-3),
-                                "unit": "particle·point evals/s", "update_hz": 1e3 / host_ms, "steps": args.steps,
-                                "median_ms": float(np.median(per)), "min_ms": float(per.min()),
-                                "overhead_over_device_resident_ms": host_ms - ms_per_step,
-                                "ms_per_update_page_locked_arrays": pinned_ms,
-                                "value_page_locked_arrays": n_p * n_s / (pinned_ms * 1e-3),
-                                "page_locked_results_equal": same_results,
-                                "ms_per_update_called_from_python": python_ms,
-                                "what": "mcl3dl_hip_measure_update on host buffers, timed from C (tools/benchloop.c): scan upload + "
-                                        "ordering + pose/weight H2D + kernels + weight/likelihood D2H, PCIe included (SURVEY.md "
-                                        "section 8d's timed region); pageable caller arrays (ms_per_update) and arrays from "
-                                        "mcl3dl_hip_host_alloc (ms_per_update_page_locked_arrays)"}
-            if not args.no_extras and args.workload in ("C1", "C2", "C3") and strict_mode in (0, 2):
-                # The same region for a caller that HOLDS its scan in the engine's order (mcl3dl_hip_scan_order_host; the drop-in
-                # classes with MCL3DL_HIP_ENGINE_ORDER=1): no ordering launches (scan_presorted) and the reference's float
-                # recurrence inside the likelihood kernel (strict_order = 3) — likelihoods bit-identical to the reference on the
-                # caller's own array — next to the caller-order replay (strict_order = 1). Checked against the CPU reference below.
-                held = np.ascontiguousarray(h_lik[capi.scan_order_host(h_lik)])
-                eo = {}
-                e_lik, e_ratio, e_beam = (np.zeros(n_p, np.float32) for _ in range(3))
-                try:
-                    for tag, scan_arr, so, pre in (("caller_order_replay", h_lik, 1, 0), ("engine_order_in_kernel", h_lik, 3, 0),
-                                                   ("held_in_engine_order_presorted_fp64", held, 0, 1),
-                                                   ("held_in_engine_order_presorted_in_kernel", held, 3, 1)):
-                        eng.set_option("strict_order", so)
-                        eng.set_option("scan_presorted", pre)
-                        with no_gc():
-                            ms_e, _ = eng.time_measure_update(h_pose, h_w0, h_w0.copy(), scan_arr, h_beam, h_lab, h_org, e_lik, e_ratio,
-                                                              e_beam, args.steps, warm_ms=100.0)
-                        eo[tag + "_ms"] = ms_e
-                finally:
-                    eng.set_option("strict_order", strict_mode)
-                    eng.set_option("scan_presorted", 0)
-                eo["default_ms"] = host_ms
-                eo["held_scan_likelihoods"] = e_lik.copy()   # (popped again below: compared with the CPU reference on `held`)
-                eo["held_scan"] = held
-                eo["what"] = ("mcl3dl_hip_measure_update on host buffers timed from C, as update_8d: the float sums replayed in the "
-                              "caller's order behind the kernel (strict_order 1), run inside the kernel in the engine's order (3), "
-                              "and for a caller that holds its scan in that order (option scan_presorted: no ordering launches) — "
-                              "the last one is bit-identical to the reference on the caller's own array")
-                out["engine_order"] = eo
-            eng.set_stream(stream.cuda_stream)
-        if not args.no_extras:
-            # the reductions that follow the update in the node (expectationBiased + max + covariance) on the
-            # device-resident particles; each call ends with a D2H of a dozen scalars
-            rewarm()
-            t3 = time.perf_counter()
-            for _ in range(10):
-                mean7, _tot, _im, _ib = eng.expectation_device(d_pose, d_w, None, n_p)
-                eng.covariance_device(d_pose, d_w, n_p, mean7)
-            out["post_update_reductions"] = {"ms": (time.perf_counter() - t3) / 10 * 1e3,
-                                             "what": "expectationBiased + max + covariance over this rank's particles"}
-            # resampling of this rank's particles with the weights the update just produced: host bookkeeping
-            # (prefix sums, tie sort, it/it_prev walk) + device lower_bound / gather; noise = identity (timing only)
-            w_host = d_w.cpu().numpy()
-            st13 = np.zeros((n_p, 13), np.float32)
-            st13[:, :7] = main_sh.host_poses
-            t4 = time.perf_counter()
-            for _ in range(5):
-                pstep = eng.resample_begin(w_host)
-                _src, _dup, n_dup = eng.resample_plan(0, 0.37 * pstep)
-                ident = _identity_noise(n_dup)
-                eng.resample_apply(st13, ident)
-            out["resample"] = {"ms": (time.perf_counter() - t4) / 5 * 1e3, "duplicates": int(n_dup),
-                               "what": "mcl3dl_hip_resample_begin + plan + apply, host buffers, %d particles" % n_p}
-            # the same with weights and 13-float states resident on the device (what a multi-GPU host runs per rank after
-            # the all-gather, mcl_3dl_amd/distributed.py:sharded_resample)
-            d_st_in = torch.from_numpy(st13).to(dev)
-            d_st_out = torch.empty_like(d_st_in)
-            torch.cuda.synchronize(dev)
-            t6 = time.perf_counter()
-            for _ in range(5):
-                pstep = eng.resample_begin_device(d_w, n_p)
-                _src, _dup, n_dup2 = eng.resample_plan(0, 0.37 * pstep, want_plan=False)
-                eng.resample_apply_device(d_st_in, ident[:n_dup2], d_st_out)
-            out["resample"]["ms_device_resident"] = (time.perf_counter() - t6) / 5 * 1e3
-        if world == 1 and not args.no_extras:
-            # the fused device-resident call (measure + pf::measure in one C call), host wall per call back to back. Not `value`.
-            # (its hipGraph-replay form measured slower for two rounds and was removed in round 5)
-            fused = {}
-            rewarm()
-            for use_graph in (0,):
-                for _ in range(3):
                     d_w.copy_(d_w0)
                     eng.update_device(d_pose, n_p, d_w, d_stats, d_lik=d_lik, d_ratio=d_ratio, d_beam=d_beam if n_b else None)
+                    eng.expectation_device(d_pose, d_w, None, n_p)
+                    pstep = eng.resample_begin_device(d_w, n_p)
+                    _s, _d, nd = eng.resample_plan(0, 0.37 * pstep, want_plan=False)
+                    eng.resample_apply_device(d_st_in, _identity_noise(nd), d_st_out)
                 torch.cuda.synchronize(dev)
-                t5 = time.perf_counter()
-                for _ in range(args.steps):
-                    d_w.copy_(d_w0)
-                    eng.update_device(d_pose, n_p, d_w, d_stats, d_lik=d_lik, d_ratio=d_ratio, d_beam=d_beam if n_b else None)
-                torch.cuda.synchronize(dev)
-                fused["graph" if use_graph else "eager"] = (time.perf_counter() - t5) / args.steps * 1e3
-            # one whole filter iteration with everything resident on the device: measurement update -> expectation + max
-            # (the node publishes the pose from it) -> resampling of the 13-float states; noise = identity
-            rewarm()
-            t7 = time.perf_counter()
-            for _ in range(args.steps):
-                d_w.copy_(d_w0)
-                eng.update_device(d_pose, n_p, d_w, d_stats, d_lik=d_lik, d_ratio=d_ratio, d_beam=d_beam if n_b else None)
-                eng.expectation_device(d_pose, d_w, None, n_p)
-                pstep = eng.resample_begin_device(d_w, n_p)
-                _s, _d, nd = eng.resample_plan(0, 0.37 * pstep, want_plan=False)
-                eng.resample_apply_device(d_st_in, _identity_noise(nd), d_st_out)
-            torch.cuda.synchronize(dev)
-            out["filter_iteration"] = {"ms": (time.perf_counter() - t7) / args.steps * 1e3,
-                                       "what": "update + expectationBiased/max + resample, device-resident, one GPU"}
-            out["fused_update"] = {"ms_per_update_eager": fused["eager"],
-                                   "what": "mcl3dl_hip_update_device, device-resident, plain launches"}
-        if world == 1 and not args.no_cpu_baseline:
-            order = None
-            if strict_mode == 3:
-                eng.upload_scan(sc.scan_lik, sc.scan_beam, sc.scan_beam_label, sc.origins)
-                order = eng.scan_order(len(sc.scan_lik))
-                out["result_check"]["sum_order"] = ("engine (mcl3dl_hip_scan_order): the CPU reference below was given the scan "
-                                                    "in that order, the order the timed kernel summed it in")
-            cb, cpu_lik, cpu_q = cpu_baseline(sc, dist_weight, args.cpu_particles, n_b, scan_order=order)
-            out["cpu_baseline"] = cb
-            # parity spot check of the very numbers that were timed
-            n = len(cpu_lik)
-            gl = d_lik[:n].cpu().numpy()
-            gq = d_ratio[:n].cpu().numpy()
-            out["result_check"]["max_rel_err_vs_cpu"] = float(np.max(np.abs(gl - cpu_lik) / np.maximum(np.abs(cpu_lik), 1e-30)))
-            out["result_check"]["match_ratio_equal"] = bool(np.array_equal(gq, cpu_q))
-            out["result_check"]["tolerance"] = ("default mode: every float term bit-identical to the reference's, summed in fp64; "
-                                                "the reference sums sequentially in float, so max_rel_err_vs_cpu is the "
-                                                "reference's own rounding (random walk: ~5e-6 at 16 384 points, ~1e-5 at "
-                                                "65 536); --strict-order 1 reproduces the reference's float bit for bit")
-            out["result_check"]["cpu_sample_particles"] = n
-            eo = out.get("engine_order")
-            if eo and "held_scan" in eo:
-                from oracle import pyoracle as _po
-                o2 = _po.Oracle("ref" if _po.available("ref") else "port")
-                o2.set_map(sc.map_xyz, sc.map_label, dist_weight=dist_weight)
-                o2.set_likelihood_params(_po.LikelihoodParams())
-                m = min(n, 64)
-                ref_lik, _q = o2.likelihood_measure(sc.poses[:m], eo["held_scan"])
-                eo["bit_identical_to_cpu_reference_on_the_held_scan"] = bool(np.array_equal(eo["held_scan_likelihoods"][:m], ref_lik))
-                eo["checked_particles"] = m
-        else:
-            out["cpu_baseline"] = None
-        if "engine_order" in out:
-            out["engine_order"].pop("held_scan", None)
-            out["engine_order"].pop("held_scan_likelihoods", None)
-        if world == 1 and not args.no_extras:
-            ra = route_a(sc, dist_weight, n_b, args.route_a_reps if args.workload in ("C1", "C2", "C3") else 0)
-            if ra:
-                out["route_a"] = ra
-        if world == 1 and not args.no_extras and args.workload in ("C1", "C2", "C3") and args.lik_index == 2:
-            # a mapcloud_update of ~1 % of the map (a new surface 0.12 m in front of the walls around the
-            # robot) — only the touched bricks of the candidate-voxel index are re-compiled; next to it the whole-map build
-            full_ms = eng.index_stats()["build_ms"]
-            tp = sc.true_pose[:3]
-            range_to_pose = np.linalg.norm(sc.map_xyz - tp, axis=1)
-            near = sc.map_xyz[np.argsort(range_to_pose)[:max(len(sc.map_xyz) // 100, 16)]]
-            inward = (tp - near) / np.maximum(np.linalg.norm(tp - near, axis=1, keepdims=True), 1e-6)
-            upd = (near + 0.12 * inward).astype(np.float32)
-            t8 = time.perf_counter()
-            n_map, ust = eng.map_update(upd, None, leaf=(0.1, 0.1, 0.1), stamp=77)
-            first_ms = (time.perf_counter() - t8) * 1e3
-            # the node replaces its update cloud every few seconds (src/mcl_3dl.cpp:141-153): the steady state is an update
-            # that REPLACES the previous one — the same surface moved by a centimetre each time (the first call also pays for
-            # the scratch blocks every later one recycles)
-            walls, outcomes, after, steady, split_after, split_steady = [], [], [], [], [], []
-            split_cloud = np.ascontiguousarray(sc.scan_lik)
-            m_out, u_out = (eng.host_array((len(split_cloud), 3)) for _ in range(2))
-
-            def small_split():
-                # matched / unmatched of the scan (src/mcl_3dl.cpp:761-805): the consumer of the cell grid, which a map update
-                # now merges into instead of rebuilding (host_grid_builders.h)
-                t9 = time.perf_counter()
-                eng.match_split_into(sc.true_pose, m_out, u_out, xyz=split_cloud)
-                return (time.perf_counter() - t9) * 1e3
-
-            small_split()
-
-            def small_measure():
-                # 64 particles against the whole scan, both models: whatever the update left to rebuild is paid here
-                t9 = time.perf_counter()
-                eng.measure_batch(sc.poses[:64], sc.scan_lik, sc.scan_beam if n_b else None,
-                                  sc.scan_beam_label if n_b else None, sc.origins)
-                return (time.perf_counter() - t9) * 1e3
-
-            small_measure()
-            for rep in range(6):
-                upd_k = (near + (0.13 + 0.01 * rep) * inward).astype(np.float32)
+                out["filter_iteration"] = {"ms": (time.perf_counter() - t7) / args.steps * 1e3,
+                                           "what": "update + expectationBiased/max + resample, device-resident, one GPU"}
+                out["fused_update"] = {"ms_per_update_eager": fused["eager"],
+                                       "what": "mcl3dl_hip_update_device, device-resident, plain launches"}
+            if world == 1 and not args.no_cpu_baseline:
+                order = None
+                if strict_mode == 3:
+                    eng.upload_scan(sc.scan_lik, sc.scan_beam, sc.scan_beam_label, sc.origins)
+                    order = eng.scan_order(len(sc.scan_lik))
+                    out["result_check"]["sum_order"] = ("engine (mcl3dl_hip_scan_order): the CPU reference below was given the scan "
+                                                        "in that order, the order the timed kernel summed it in")
+                cb, cpu_lik, cpu_q = cpu_baseline(sc, dist_weight, args.cpu_particles, n_b, scan_order=order)
+                out["cpu_baseline"] = cb
+                # parity spot check of the very numbers that were timed
+                n = len(cpu_lik)
+                gl = d_lik[:n].cpu().numpy()
+                gq = d_ratio[:n].cpu().numpy()
+                out["result_check"]["max_rel_err_vs_cpu"] = float(np.max(np.abs(gl - cpu_lik) / np.maximum(np.abs(cpu_lik), 1e-30)))
+                out["result_check"]["match_ratio_equal"] = bool(np.array_equal(gq, cpu_q))
+                out["result_check"]["tolerance"] = ("default mode: every float term bit-identical to the reference's, summed in fp64; "
+                                                    "the reference sums sequentially in float, so max_rel_err_vs_cpu is the "
+                                                    "reference's own rounding (random walk: ~5e-6 at 16 384 points, ~1e-5 at "
+                                                    "65 536); --strict-order 1 reproduces the reference's float bit for bit")
+                out["result_check"]["cpu_sample_particles"] = n
+                eo = out.get("engine_order")
+                if eo and "held_scan" in eo:
+                    from oracle import pyoracle as _po
+                    o2 = _po.Oracle("ref" if _po.available("ref") else "port")
+                    o2.set_map(sc.map_xyz, sc.map_label, dist_weight=dist_weight)
+                    o2.set_likelihood_params(_po.LikelihoodParams())
+                    m = min(n, 64)
+                    ref_lik, _q = o2.likelihood_measure(sc.poses[:m], eo["held_scan"])
+                    eo["bit_identical_to_cpu_reference_on_the_held_scan"] = bool(np.array_equal(eo["held_scan_likelihoods"][:m], ref_lik))
+                    eo["checked_particles"] = m
+            else:
+                out["cpu_baseline"] = None
+            if "engine_order" in out:
+                out["engine_order"].pop("held_scan", None)
+                out["engine_order"].pop("held_scan_likelihoods", None)
+            if world == 1 and not args.no_extras:
+                ra = route_a(sc, dist_weight, n_b, args.route_a_reps if args.workload in ("C1", "C2", "C3") else 0)
+                if ra:
+                    out["route_a"] = ra
+            if world == 1 and not args.no_extras and args.workload in ("C1", "C2", "C3") and args.lik_index == 2:
+                # a mapcloud_update of ~1 % of the map (a new surface 0.12 m in front of the walls around the
+                # robot) — only the touched bricks of the candidate-voxel index are re-compiled; next to it the whole-map build
+                full_ms = eng.index_stats()["build_ms"]
+                tp = sc.true_pose[:3]
+                range_to_pose = np.linalg.norm(sc.map_xyz - tp, axis=1)
+                near = sc.map_xyz[np.argsort(range_to_pose)[:max(len(sc.map_xyz) // 100, 16)]]
+                inward = (tp - near) / np.maximum(np.linalg.norm(tp - near, axis=1, keepdims=True), 1e-6)
+                upd = (near + 0.12 * inward).astype(np.float32)
                 t8 = time.perf_counter()
-                n_map, ust = eng.map_update(upd_k, None, leaf=(0.1, 0.1, 0.1), stamp=177 + rep)
-                walls.append((time.perf_counter() - t8) * 1e3)
-                outcomes.append(int(ust["outcome"]))
-                after.append(small_measure())
-                steady.append(small_measure())
-                split_after.append(small_split())
-                split_steady.append(small_split())
-            wall_ms = float(np.median(walls))
-            out["map_update"] = dict(ust, update_points=int(n_map - len(sc.map_xyz)), map_points=int(len(sc.map_xyz)),
-                                     wall_ms=wall_ms, wall_ms_first=first_ms, wall_ms_each=walls, outcomes=outcomes,
-                                     overflow_compactions=int(eng.get_option("cand_ovf_compactions")),
-                                     first_measure_after_update_ms=float(np.median(after)),
-                                     same_measure_steady_ms=float(np.median(steady)),
-                                     first_match_split_after_update_ms=float(np.median(split_after)),
-                                     same_match_split_steady_ms=float(np.median(split_steady)),
-                                     cell_grid_merges=int(eng.get_option("lik_grid_merges")),
-                                     cell_grid_rebuilds=int(eng.get_option("lik_grid_rebuilds")),
-                                     dda_overlay_updates=int(eng.get_option("dda_overlay_updates")),
-                                     full_build_ms=full_ms,
-                                     what="mcl3dl_hip_map_update: VoxelGrid of the update + incremental index update "
-                                          "(device_ms = the index part), median wall time of six updates that each replace the "
-                                          "previous one; wall_ms_first = the first update (allocates the scratch blocks the "
-                                          "others recycle); includes the host copy of the map; outcome 0 = incremental; "
-                                          "first_measure_after_update_ms = a 64-particle measure_batch of both models right "
-                                          "behind each update (it pays for whatever the update left to rebuild: nothing, when "
-                                          "the DDA grid took the update as an overlay) next to the same call once more")
-            eng.map_update(None, None, stamp=78)  # withdraw it again
-            eng.host_free(m_out)
-            eng.host_free(u_out)
-        if world == 1 and not args.no_extras and args.jitter_check > 0 and args.workload in ("C2", "C3") and not args.map_jitter:
-            # standing robustness figure: the same workload on a map whose points are voxel-filter centroids, not a lattice
-            scj = make_config(args.workload, n_p=n_cfg, seed=12345, map_jitter=args.jitter_check, **extra_cfg)
-            eng.set_map(scj.map_xyz, scj.map_label, stamp=2, dist_weight=dist_weight)
-            eng.upload_scan(scj.scan_lik, scj.scan_beam, scj.scan_beam_label, scj.origins)
-            dj = torch.from_numpy(scj.poses).to(dev).contiguous()
-            t_warm = time.perf_counter()   # the GPU has been idle through the CPU baseline: ramp the clock up again
-            while time.perf_counter() - t_warm < 0.3:
-                for _ in range(20):
-                    eng.measure_device(dj, n_p, d_lik, d_ratio, None)
-                eng.synchronize()
-            eng.set_option("timing_mask", 1)
-            eng.set_kernel_timing(True)
-            eng.reset_kernel_time()
-            for _ in range(args.steps):
-                eng.measure_device(dj, n_p, d_lik, d_ratio, None)
-            jm, jn = eng.kernel_time(capi.KERNEL_LIKELIHOOD)
-            eng.set_kernel_timing(False)
-            out["map_jitter"] = {"jitter_m": args.jitter_check, "likelihood_ms": jm / max(jn, 1),
-                                 "vs_lattice": (jm / max(jn, 1)) / lik_avg_ms if lik_avg_ms else None,
-                                 "index": eng.index_stats()}
-        if world == 1 and not args.no_extras and args.workload in ("C2", "C3") and not args.map_jitter and args.dist_weight_z == 1.0:
-            # standing figure at the metric the reference SHIPS (dist_weight_z = 5, src/parameters.cpp:108-110; the demo's 2.0,
-            # config/test_localization.yaml:5): the rescaled z axis stretches the index (3.7 x the records at z x 5). Parity at
-            # these weights and sizes: tests/test_gpu_dist_weight_fullsize.py
-            shipped = {}
-            for wz in (5.0, 2.0):
-                eng.set_map(sc.map_xyz, sc.map_label, stamp=40 + int(wz), dist_weight=(1.0, 1.0, wz))
-                eng.upload_scan(sc.scan_lik, sc.scan_beam, sc.scan_beam_label, sc.origins)
-                dw_pose = torch.from_numpy(sc.poses).to(dev).contiguous()
-                t_warm = time.perf_counter()
-                while time.perf_counter() - t_warm < 0.2:
+                n_map, ust = eng.map_update(upd, None, leaf=(0.1, 0.1, 0.1), stamp=77)
+                first_ms = (time.perf_counter() - t8) * 1e3
+                # the node replaces its update cloud every few seconds (src/mcl_3dl.cpp:141-153): the steady state is an update
+                # that REPLACES the previous one — the same surface moved by a centimetre each time (the first call also pays for
+                # the scratch blocks every later one recycles)
+                walls, outcomes, after, steady, split_after, split_steady = [], [], [], [], [], []
+                split_cloud = np.ascontiguousarray(sc.scan_lik)
+                m_out, u_out = (eng.host_array((len(split_cloud), 3)) for _ in range(2))
+
+                def small_split():
+                    # matched / unmatched of the scan (src/mcl_3dl.cpp:761-805): the consumer of the cell grid, which a map update
+                    # now merges into instead of rebuilding (host_grid_builders.h)
+                    t9 = time.perf_counter()
+                    eng.match_split_into(sc.true_pose, m_out, u_out, xyz=split_cloud)
+                    return (time.perf_counter() - t9) * 1e3
+
+                small_split()
+
+                def small_measure():
+                    # 64 particles against the whole scan, both models: whatever the update left to rebuild is paid here
+                    t9 = time.perf_counter()
+                    eng.measure_batch(sc.poses[:64], sc.scan_lik, sc.scan_beam if n_b else None,
+                                      sc.scan_beam_label if n_b else None, sc.origins)
+                    return (time.perf_counter() - t9) * 1e3
+
+                small_measure()
+                for rep in range(6):
+                    upd_k = (near + (0.13 + 0.01 * rep) * inward).astype(np.float32)
+                    t8 = time.perf_counter()
+                    n_map, ust = eng.map_update(upd_k, None, leaf=(0.1, 0.1, 0.1), stamp=177 + rep)
+                    walls.append((time.perf_counter() - t8) * 1e3)
+                    outcomes.append(int(ust["outcome"]))
+                    after.append(small_measure())
+                    steady.append(small_measure())
+                    split_after.append(small_split())
+                    split_steady.append(small_split())
+                wall_ms = float(np.median(walls))
+                out["map_update"] = dict(ust, update_points=int(n_map - len(sc.map_xyz)), map_points=int(len(sc.map_xyz)),
+                                         wall_ms=wall_ms, wall_ms_first=first_ms, wall_ms_each=walls, outcomes=outcomes,
+                                         overflow_compactions=int(eng.get_option("cand_ovf_compactions")),
+                                         first_measure_after_update_ms=float(np.median(after)),
+                                         same_measure_steady_ms=float(np.median(steady)),
+                                         first_match_split_after_update_ms=float(np.median(split_after)),
+                                         same_match_split_steady_ms=float(np.median(split_steady)),
+                                         cell_grid_merges=int(eng.get_option("lik_grid_merges")),
+                                         cell_grid_rebuilds=int(eng.get_option("lik_grid_rebuilds")),
+                                         dda_overlay_updates=int(eng.get_option("dda_overlay_updates")),
+                                         full_build_ms=full_ms,
+                                         what="mcl3dl_hip_map_update: VoxelGrid of the update + incremental index update "
+                                              "(device_ms = the index part), median wall time of six updates that each replace the "
+                                              "previous one; wall_ms_first = the first update (allocates the scratch blocks the "
+                                              "others recycle); includes the host copy of the map; outcome 0 = incremental; "
+                                              "first_measure_after_update_ms = a 64-particle measure_batch of both models right "
+                                              "behind each update (it pays for whatever the update left to rebuild: nothing, when "
+                                              "the DDA grid took the update as an overlay) next to the same call once more")
+                eng.map_update(None, None, stamp=78)  # withdraw it again
+                eng.host_free(m_out)
+                eng.host_free(u_out)
+            if world == 1 and not args.no_extras and args.jitter_check > 0 and args.workload in ("C2", "C3") and not args.map_jitter:
+                # standing robustness figure: the same workload on a map whose points are voxel-filter centroids, not a lattice
+                scj = make_config(args.workload, n_p=n_cfg, seed=12345, map_jitter=args.jitter_check, **extra_cfg)
+                eng.set_map(scj.map_xyz, scj.map_label, stamp=2, dist_weight=dist_weight)
+                eng.upload_scan(scj.scan_lik, scj.scan_beam, scj.scan_beam_label, scj.origins)
+                dj = torch.from_numpy(scj.poses).to(dev).contiguous()
+                t_warm = time.perf_counter()   # the GPU has been idle through the CPU baseline: ramp the clock up again
+                while time.perf_counter() - t_warm < 0.3:
                     for _ in range(20):
-                        eng.measure_device(dw_pose, n_p, d_lik, d_ratio, None)
+                        eng.measure_device(dj, n_p, d_lik, d_ratio, None)
                     eng.synchronize()
                 eng.set_option("timing_mask", 1)
                 eng.set_kernel_timing(True)
                 eng.reset_kernel_time()
                 for _ in range(args.steps):
-                    eng.measure_device(dw_pose, n_p, d_lik, d_ratio, None)
-                wm, wn = eng.kernel_time(capi.KERNEL_LIKELIHOOD)
+                    eng.measure_device(dj, n_p, d_lik, d_ratio, None)
+                jm, jn = eng.kernel_time(capi.KERNEL_LIKELIHOOD)
                 eng.set_kernel_timing(False)
-                st = eng.index_stats()
-                shipped["z%g" % wz] = {"dist_weight": [1.0, 1.0, wz], "likelihood_ms": wm / max(wn, 1),
-                                       "vs_unit_weight": (wm / max(wn, 1)) / lik_avg_ms if lik_avg_ms else None,
-                                       "evals_per_s": n_p * n_s / (wm / max(wn, 1) * 1e-3) if wm else None,
-                                       "records_bytes": eng.memory_footprint()["cand_start"], "build_ms": st["build_ms"],
-                                       "voxels_with_overflow": st["voxels_with_overflow"]}
-            out["dist_weight_shipped"] = shipped
-            eng.set_map(sc.map_xyz, sc.map_label, stamp=49, dist_weight=dist_weight)
-            eng.upload_scan(sc.scan_lik, sc.scan_beam, sc.scan_beam_label, sc.origins)
-        if world == 1 and not args.no_extras:
-            out.update(cloud_path_extras(eng, sc, n_s, n_b, with_cpu=not args.no_cpu_baseline))
-        # the in-process route (the one the reference's single process would use) on the same GPUs, next to the
-        # one-process-per-GPU figures above: a group of 1 with the RCCL call in the loop on one GPU, of all N on a node
-        if not args.no_extras or world > 1:
-            try:
-                if world == 1:
-                    out["in_process_group"] = in_process_group_run(args.workload, n_cfg, extra_cfg, dist_weight,
-                                                                   [0], args.steps, args.warmup)
-                else:
-                    out["in_process_group"] = in_process_group_child(args, world)
-            except Exception as e:  # never lose the line over the side measurement
-                out["in_process_group"] = {"error": str(e)[-300:]}
+                out["map_jitter"] = {"jitter_m": args.jitter_check, "likelihood_ms": jm / max(jn, 1),
+                                     "vs_lattice": (jm / max(jn, 1)) / lik_avg_ms if lik_avg_ms else None,
+                                     "index": eng.index_stats()}
+            if world == 1 and not args.no_extras and args.workload in ("C2", "C3") and not args.map_jitter and args.dist_weight_z == 1.0:
+                # standing figure at the metric the reference SHIPS (dist_weight_z = 5, src/parameters.cpp:108-110; the demo's 2.0,
+                # config/test_localization.yaml:5): the rescaled z axis stretches the index (3.7 x the records at z x 5). Parity at
+                # these weights and sizes: tests/test_gpu_dist_weight_fullsize.py
+                shipped = {}
+                for wz in (5.0, 2.0):
+                    eng.set_map(sc.map_xyz, sc.map_label, stamp=40 + int(wz), dist_weight=(1.0, 1.0, wz))
+                    eng.upload_scan(sc.scan_lik, sc.scan_beam, sc.scan_beam_label, sc.origins)
+                    dw_pose = torch.from_numpy(sc.poses).to(dev).contiguous()
+                    t_warm = time.perf_counter()
+                    while time.perf_counter() - t_warm < 0.2:
+                        for _ in range(20):
+                            eng.measure_device(dw_pose, n_p, d_lik, d_ratio, None)
+                        eng.synchronize()
+                    eng.set_option("timing_mask", 1)
+                    eng.set_kernel_timing(True)
+                    eng.reset_kernel_time()
+                    for _ in range(args.steps):
+                        eng.measure_device(dw_pose, n_p, d_lik, d_ratio, None)
+                    wm, wn = eng.kernel_time(capi.KERNEL_LIKELIHOOD)
+                    eng.set_kernel_timing(False)
+                    st = eng.index_stats()
+                    shipped["z%g" % wz] = {"dist_weight": [1.0, 1.0, wz], "likelihood_ms": wm / max(wn, 1),
+                                           "vs_unit_weight": (wm / max(wn, 1)) / lik_avg_ms if lik_avg_ms else None,
+                                           "evals_per_s": n_p * n_s / (wm / max(wn, 1) * 1e-3) if wm else None,
+                                           "records_bytes": eng.memory_footprint()["cand_start"], "build_ms": st["build_ms"],
+                                           "voxels_with_overflow": st["voxels_with_overflow"]}
+                out["dist_weight_shipped"] = shipped
+                eng.set_map(sc.map_xyz, sc.map_label, stamp=49, dist_weight=dist_weight)
+                eng.upload_scan(sc.scan_lik, sc.scan_beam, sc.scan_beam_label, sc.origins)
+            if world == 1 and not args.no_extras:
+                out.update(cloud_path_extras(eng, sc, n_s, n_b, with_cpu=not args.no_cpu_baseline))
+            # the in-process route (the one the reference's single process would use) on the same GPUs, next to the
+            # one-process-per-GPU figures above: a group of 1 with the RCCL call in the loop on one GPU, of all N on a node
+            if not args.no_extras or world > 1:
+                try:
+                    if world == 1:
+                        out["in_process_group"] = in_process_group_run(args.workload, n_cfg, extra_cfg, dist_weight,
+                                                                       [0], args.steps, args.warmup)
+                    else:
+                        out["in_process_group"] = in_process_group_child(args, world)
+                except Exception as e:  # never lose the line over the side measurement
+                    out["in_process_group"] = {"error": str(e)[-300:]}
         line = json.dumps(out)
     if use_dist and world > 1:
         dist.barrier(group=cpu_pg)   # ranks 1.. waited on the CPU while rank 0 ran the in-process group

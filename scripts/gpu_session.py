@@ -42,7 +42,7 @@ def sh(cmd, log, timeout, env=None):
 
 
 def bench(name, bargs, timeout=600):
-    sh("python bench.py %s 2>%s/%s.err | tail -1 > %s/%s.json" % (bargs, OUT, name, OUT, name), name + ".log", timeout)
+    sh("python bench.py --full %s 2>%s/%s.err | tail -1 > %s/%s.json" % (bargs, OUT, name, OUT, name), name + ".log", timeout)
     try:
         d = json.load(open("%s/%s.json" % (OUT, name)))
         k = d["kernels_ms_per_step"]

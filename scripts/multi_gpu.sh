@@ -25,10 +25,10 @@ timeout 1500 python -m pytest tests/test_gpu_group.py tests/test_gpu_group_state
 line() { # tag, n, extra bench args
   local port=$((29500 + RANDOM % 2000))
   if [ "$2" -eq 1 ] || [[ "$1" == inproc_* ]]; then   # (the in-process group is ONE process with a worker thread per GPU)
-    timeout 1200 python bench.py --gpus $2 --steps 20 --warmup 3 $3 2>$O/$1.err | tail -1 > $O/$1.json
+    timeout 1200 python bench.py --gpus $2 --steps 20 --warmup 3 --full $3 2>$O/$1.err | tail -1 > $O/$1.json
   else
     timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node $2 --master-addr 127.0.0.1 --master-port $port \
-      bench.py --gpus $2 --steps 20 --warmup 3 $3 2>$O/$1.err | tail -1 > $O/$1.json
+      bench.py --gpus $2 --steps 20 --warmup 3 --full $3 2>$O/$1.err | tail -1 > $O/$1.json
   fi
   python - "$O/$1.json" "$1" <<'PY'
 import json, sys

@@ -11,7 +11,7 @@ prof() { # tag, bench args
   echo "profile $1: $(tail -1 $O/prof_$1.log)"
 }
 line() { # name, bench args
-  timeout 1500 python bench.py $2 2>$O/bench_$1.err | tail -1 > $O/bench_$1.json
+  timeout 1500 python bench.py --full $2 2>$O/bench_$1.err | tail -1 > $O/bench_$1.json
   python - "$O/bench_$1.json" "$1" <<'PY'
 import json,sys
 try:

@@ -5,7 +5,7 @@ O=gpurun_out/r06p; mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -q -x 2>&1 | grep -vE "RCCL|HIP version|ROCm version|Hostname|Librccl" | tail -8
 MCL3DL_TAIL_AB=2 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fuzz.py tests/test_gpu_fullsize.py tests/test_gpu_update_staged.py tests/test_gpu_group.py tests/test_gpu_c4c5.py -m gpu -q -x 2>&1 | grep -vE "RCCL|HIP version|ROCm version|Hostname|Librccl" | tail -4
 run() { # name, AB, bench args
-  MCL3DL_TAIL_AB="$2" timeout 900 python bench.py $3 2>$O/$1.err | tail -1 > $O/$1.json
+  MCL3DL_TAIL_AB="$2" timeout 900 python bench.py --full $3 2>$O/$1.err | tail -1 > $O/$1.json
   python - "$O/$1.json" "$1" <<'PY'
 import json,sys
 try:

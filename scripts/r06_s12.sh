@@ -3,7 +3,7 @@
 O=gpurun_out/r06q; mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -q -x 2>&1 | grep -vE "RCCL|HIP version|ROCm version|Hostname|Librccl" | tail -5
 run() { # name, switch, bench args
-  MCL3DL_BEAM_TAIL="$2" timeout 900 python bench.py $3 2>$O/$1.err | tail -1 > $O/$1.json
+  MCL3DL_BEAM_TAIL="$2" timeout 900 python bench.py --full $3 2>$O/$1.err | tail -1 > $O/$1.json
   python - "$O/$1.json" "$1" <<'PY'
 import json,sys
 try:

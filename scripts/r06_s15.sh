@@ -3,7 +3,7 @@
 # library, same box, C2), the merged launch at G = 8 / 4 shapes, then the whole suite
 O=gpurun_out/r06t; mkdir -p $O
 run() { # name, lib, env, bench args
-  MCL3DL_HIP_LIB="$2" MCL3DL_HIP_OPTIONS="$3" timeout 900 python bench.py $4 2>$O/$1.err | tail -1 > $O/$1.json
+  MCL3DL_HIP_LIB="$2" MCL3DL_HIP_OPTIONS="$3" timeout 900 python bench.py --full $4 2>$O/$1.err | tail -1 > $O/$1.json
   python - "$O/$1.json" "$1" <<'PY'
 import json,sys
 try:

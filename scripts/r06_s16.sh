@@ -8,7 +8,7 @@ for r in 1 2 3; do
 for v in prev new; do
   LIB=""; [ $v = prev ] && LIB=$PREV
   for w in C2 C3; do
-  MCL3DL_HIP_LIB="$LIB" timeout 900 python bench.py --workload $w --steps 20 --warmup 3 --no-cpu-baseline 2>$O/${w}_$v$r.err | tail -1 > $O/${w}_$v$r.json
+  MCL3DL_HIP_LIB="$LIB" timeout 900 python bench.py --full --workload $w --steps 20 --warmup 3 --no-cpu-baseline 2>$O/${w}_$v$r.err | tail -1 > $O/${w}_$v$r.json
   python - "$O/${w}_$v$r.json" "${w}_$v$r" <<'PY'
 import json,sys
 try:

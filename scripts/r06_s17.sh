@@ -4,7 +4,7 @@
 O=gpurun_out/r06v; mkdir -p $O
 timeout 2400 python -m pytest tests/test_gpu_fullsize.py tests/test_gpu_c4c5.py tests/test_gpu_strict_chunks.py tests/test_gpu_fuzz.py -m gpu -q 2>&1 | grep -vE "RCCL|HIP version|ROCm version|Hostname|Librccl" | tail -3
 run() { # name, switch, bench args
-  MCL3DL_REPLAY_AB="$2" timeout 900 python bench.py $3 2>$O/$1.err | tail -1 > $O/$1.json
+  MCL3DL_REPLAY_AB="$2" timeout 900 python bench.py --full $3 2>$O/$1.err | tail -1 > $O/$1.json
   python - "$O/$1.json" "$1" <<'PY'
 import json,sys
 try:

@@ -2,7 +2,7 @@
 # round 6 session 18: the merged launch in front of the caller-order replay where no second stream would be used (below 262 144 rays)
 O=gpurun_out/r06x; mkdir -p $O
 run() { # name, overlap, bench args
-  timeout 900 python bench.py $3 --overlap-models $2 2>$O/$1.err | tail -1 > $O/$1.json
+  timeout 900 python bench.py --full $3 --overlap-models $2 2>$O/$1.err | tail -1 > $O/$1.json
   python - "$O/$1.json" "$1" <<'PY'
 import json,sys
 try:

@@ -3,7 +3,7 @@
 O=gpurun_out/r06y; mkdir -p $O
 timeout 1500 python -m pytest tests/test_gpu_launch_paths.py tests/test_gpu_pf_fused.py tests/test_gpu_fuzz.py tests/test_gpu_parity.py tests/test_gpu_rows.py tests/test_gpu_api_fuzz.py tests/test_gpu_update_staged.py tests/test_gpu_group.py -m gpu -q 2>&1 | grep -vE "RCCL|HIP version|ROCm version|Hostname|Librccl" | tail -6
 run() { # name, overlap, bench args
-  timeout 900 python bench.py $3 --overlap-models $2 2>$O/$1.err | tail -1 > $O/$1.json
+  timeout 900 python bench.py --full $3 --overlap-models $2 2>$O/$1.err | tail -1 > $O/$1.json
   python - "$O/$1.json" "$1" <<'PY'
 import json,sys
 try:

@@ -3,7 +3,7 @@
 O=gpurun_out/r06zz; mkdir -p $O
 timeout 1500 python -m pytest tests/test_gpu_chain.py tests/test_gpu_launch_paths.py tests/test_gpu_c4c5.py tests/test_gpu_fullsize.py tests/test_gpu_adapter.py tests/test_gpu_api_fuzz.py -m gpu -q 2>&1 | grep -vE "RCCL|HIP version|ROCm version|Hostname|Librccl" | tail -5
 run() { # name, overlap, bench args
-  timeout 900 python bench.py $3 --overlap-models $2 2>$O/$1.err | tail -1 > $O/$1.json
+  timeout 900 python bench.py --full $3 --overlap-models $2 2>$O/$1.err | tail -1 > $O/$1.json
   python - "$O/$1.json" "$1" <<'PY'
 import json,sys
 try:

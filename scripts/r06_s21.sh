@@ -4,7 +4,7 @@
 O=gpurun_out/r06zy; mkdir -p $O
 timeout 1500 python -m pytest tests/test_gpu_c4c5.py tests/test_gpu_fullsize.py tests/test_gpu_launch_paths.py tests/test_gpu_strict_chunks.py -m gpu -q 2>&1 | grep -vE "RCCL|HIP version|ROCm version|Hostname|Librccl" | tail -4
 run() { # name, switch, bench args
-  MCL3DL_BEAM_LATE="$2" timeout 900 python bench.py $3 2>$O/$1.err | tail -1 > $O/$1.json
+  MCL3DL_BEAM_LATE="$2" timeout 900 python bench.py --full $3 2>$O/$1.err | tail -1 > $O/$1.json
   python - "$O/$1.json" "$1" <<'PY'
 import json,sys
 try:

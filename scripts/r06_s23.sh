@@ -2,7 +2,7 @@
 # round 6 session 23: in front of the caller-order replay, up to how many rays is the merged launch better than two streams?
 O=gpurun_out/r06zw; mkdir -p $O
 run() { # name, max rays, bench args
-  MCL3DL_MERGE_STRICT_MAX_RAYS="$2" timeout 900 python bench.py $3 2>$O/$1.err | tail -1 > $O/$1.json
+  MCL3DL_MERGE_STRICT_MAX_RAYS="$2" timeout 900 python bench.py --full $3 2>$O/$1.err | tail -1 > $O/$1.json
   python - "$O/$1.json" "$1" <<'PY'
 import json,sys
 try:

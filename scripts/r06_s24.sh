@@ -3,7 +3,7 @@
 # on (sixteen half-tiles per XCD instead of eight tiles); this tree against the previous commit's library
 O=gpurun_out/r06zv; mkdir -p $O
 run() { # name, lib, bench args
-  MCL3DL_HIP_LIB="$2" timeout 900 python bench.py $3 2>$O/$1.err | tail -1 > $O/$1.json
+  MCL3DL_HIP_LIB="$2" timeout 900 python bench.py --full $3 2>$O/$1.err | tail -1 > $O/$1.json
   python - "$O/$1.json" "$1" <<'PY'
 import json,sys
 try:

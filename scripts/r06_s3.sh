@@ -5,7 +5,7 @@ O=gpurun_out/r06d; mkdir -p $O
 PYTHONPATH=. timeout 600 python scripts/r06_rows_check.py > $O/rows_check.txt 2>&1; tail -22 $O/rows_check.txt
 Q="--steps 20 --warmup 3 --no-extras --no-cpu-baseline"
 run() { # name, options, bench args
-  MCL3DL_HIP_OPTIONS="$2" timeout 600 python bench.py $3 2>$O/$1.err | tail -1 > $O/$1.json
+  MCL3DL_HIP_OPTIONS="$2" timeout 600 python bench.py --full $3 2>$O/$1.err | tail -1 > $O/$1.json
   python - "$O/$1.json" "$1" <<'PY'
 import json,sys
 try:

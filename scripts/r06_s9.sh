@@ -5,7 +5,7 @@ O=gpurun_out/r06k; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fullsize.py tests/test_gpu_defer.py tests/test_gpu_bound.py tests/test_gpu_chain.py tests/test_gpu_fuzz.py -m gpu -q -x 2>&1 | tail -3
 Q="--steps 20 --warmup 3 --no-extras --no-cpu-baseline"
 run() { # name, options, bench args
-  MCL3DL_HIP_OPTIONS="$2" timeout 900 python bench.py $3 2>$O/$1.err | tail -1 > $O/$1.json
+  MCL3DL_HIP_OPTIONS="$2" timeout 900 python bench.py --full $3 2>$O/$1.err | tail -1 > $O/$1.json
   python - "$O/$1.json" "$1" <<'PY'
 import json,sys
 try:

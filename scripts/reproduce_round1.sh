@@ -1,10 +1,11 @@
 #!/bin/bash
 # The commands behind DESIGN.md section 6 (run from the repo root on a box with one MI355X; through gpurun here:
 #   /usr/local/graft/bin/gpurun --timeout 1500 -- 'bash scripts/reproduce_round1.sh').
-# Output: gpurun_out/r01g_bench_*.json (one bench.py line each); profiles via profiles/run_profiles.sh.
+# Output: <dir>/r01g_bench_*.json (one `bench.py --full` line each; <dir> = the first argument, a new temporary directory
+# without one); profiles via profiles/run_profiles.sh.
 set -u
-mkdir -p gpurun_out
-run() { name=$1; shift; timeout 600 python bench.py "$@" 2>/dev/null | tail -1 > gpurun_out/r01g_bench_$name.json; echo "$name done"; }
+O=${1:-$(mktemp -d)}; mkdir -p "$O"; echo "bench lines in $O"
+run() { name=$1; shift; timeout 600 python bench.py --full "$@" 2>/dev/null | tail -1 > "$O/r01g_bench_$name.json"; echo "$name done"; }
 run C2                                   # headline: 4096 particles x 16 384 points, 1 M-pt map (includes the CPU baseline)
 run C1 --workload C1
 run C3 --workload C3

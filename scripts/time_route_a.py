@@ -1,4 +1,4 @@
-"""Route A (the node's pf_->measure(measure_func) through the drop-in C++ classes, tests/cpp/adapter_demo.bin) for several
+"""Route A (the node's pf_->measure(measure_func) through the drop-in C++ classes, oracle/_ref/adapter_demo.bin) for several
 slice sizes of the progressive batch (MCL3DL_HIP_BATCH_SLICE; 0 = automatic, a value above the particle count = one slice).
 Run on the GPU box:   python scripts/time_route_a.py C2 [reps] [slice ...]"""
 import json

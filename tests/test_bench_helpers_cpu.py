@@ -151,3 +151,32 @@ def test_counters_are_tied_to_the_sources_they_profiled(tmp_path, monkeypatch):
         w.writerow(["void mcl3dl::beam_kernel<false, false>(args)", "SQ_WAVES", "32768", 5])
     vals, src, note = bench.pmc_counters("void mcl3dl::beam_kernel<false", "C3")
     assert vals == {"SQ_WAVES": 32768.0} and note is None
+
+
+def test_plain_run_is_the_default_and_dump_outputs_is_opt_in(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float32_and_samples_above_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    w = np.arange(1000, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "all"), dict(weights=w, likelihood=2 * w), dict(stats=[1.5, 0.25, 0.75, 0]))
+    assert np.array_equal(np.load(str(tmp_path / "all" / "weights.npy")), w)
+    assert np.load(str(tmp_path / "all" / "stats.npy")).dtype == np.float32
+    assert not (tmp_path / "all" / "particle_index.npy").exists()
+    # above the limit: the same fixed sample of particles from every run, its indices written next to it
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 16 + 100 * 16)
+    for name in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / name), dict(weights=w, likelihood=2 * w), dict(stats=[1.5, 0.25, 0.75, 0]), "_rank1")
+    idx = np.load(str(tmp_path / "s1" / "particle_index_rank1.npy"))
+    got = np.load(str(tmp_path / "s1" / "weights_rank1.npy"))
+    assert idx.dtype == np.float64 and len(idx) == 100 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got, w[idx.astype(np.int64)])
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "likelihood_rank1.npy")), 2 * got)
+    assert np.array_equal(idx, np.load(str(tmp_path / "s2" / "particle_index_rank1.npy")))
+    assert sum(f.stat().st_size for f in (tmp_path / "s1").iterdir()) <= 16 + 100 * 16 + 4 * 128   # (+ the .npy headers)

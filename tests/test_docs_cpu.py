@@ -32,7 +32,7 @@ def test_cited_files_exist():
                     import glob
                     ok = bool(glob.glob(full))
                 else:
-                    ok = os.path.exists(full) or p.endswith(".so") or "/_ref/" in p or p.endswith(".bin")   # built artefacts
+                    ok = os.path.exists(full) or p.endswith(".so") or "/_ref/" in p + "/" or p.endswith(".bin")   # built artefacts
                 if not ok:
                     missing.append((doc, cite))
         for cite in BARE.findall(text):

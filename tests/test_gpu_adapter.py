@@ -1,4 +1,4 @@
-"""GPU test of the drop-in boundary: tests/cpp/adapter_demo.bin is a miniature of the reference node's call
+"""GPU test of the drop-in boundary: oracle/_ref/adapter_demo.bin (from tests/cpp/adapter_demo.cpp) is a miniature of the reference node's call
 site compiled against the DROP-IN C++ headers (same class names as the reference: LidarMeasurementModelLikelihood,
 LidarMeasurementModelBeam, pf::ParticleFilter) — code written for the reference's plugin surface, running on the HIP
 engine through the C ABI.  Its output is compared with the CPU oracle's measure_update on the same scene."""
@@ -14,13 +14,14 @@ from oracle import pyoracle
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEMO = os.path.join(ROOT, "tests", "cpp", "adapter_demo.bin")
+DEMO = os.path.join(ROOT, "oracle", "_ref", "adapter_demo.bin")
 
 
 def need_binary(path):
     """The adapter programs compile against the reference's own headers (pf.h, chunked_kdtree.h, ...), so they are built
-    where /root/reference exists (__graft_entry__.build()) and travel to the GPU box as files. Missing on a box that has
-    no reference tree: nothing to run. Missing where the reference IS present: the build is broken."""
+    where the reference exists (__graft_entry__.build(): oracle/Makefile puts them under oracle/_ref/) and travel to the GPU
+    box as files. Missing on a box that has no reference tree: nothing to run. Missing where the reference IS present: the
+    build is broken."""
     if os.path.exists(path):
         return
     if os.path.exists("/root/reference/include/mcl_3dl/pf.h"):
@@ -112,7 +113,7 @@ def test_rest_of_the_plugin_surface(tmp_path):
     """getMaxSearchRange, refreshParameters, setGlobalLocalizationStatus, filter, getSinTotalRef, getFilterLabelMax of the
     drop-in classes against the reference's own classes: tests/cpp/surface_check.cpp is built against both, the two
     record streams must be byte-identical."""
-    exe = os.path.join(ROOT, "tests", "cpp", "surface_gpu.bin")
+    exe = os.path.join(ROOT, "oracle", "_ref", "surface_gpu.bin")
     need_binary(exe)
     got_path = str(tmp_path / "surface_gpu.out")
     proc = subprocess.run([exe, got_path], capture_output=True, text=True, timeout=300)

@@ -1,10 +1,12 @@
 """bench.py's output contract, on the GPU box: the LAST stdout line is one JSON object with the driver's keys plus the
-`roofline` and `cpu_baseline` objects; the torch.distributed (RCCL) path runs with one rank; figures are sane."""
+`roofline` and `cpu_baseline` objects (filled with --full); the torch.distributed (RCCL) path runs with one rank; figures are
+sane; a plain run times the steps alone and --dump-outputs writes what the last of them computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -20,14 +22,14 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def run_bench(*extra):
+def run_bench(*extra, full=True):
     # a fresh rendezvous port per run (a fixed one can still sit in TIME_WAIT from the previous test's process group), and
     # one retry: a communicator that fails to come up is the box's business, not bench.py's contract
     for attempt in (0, 1):
         env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
         proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "C1", "--steps", "3",
-                               "--warmup", "1", "--prewarm-ms", "20", *extra], capture_output=True, text=True, timeout=600,
-                              cwd=ROOT, env=env)
+                               "--warmup", "1", "--prewarm-ms", "20", *(("--full",) if full else ()), *extra],
+                              capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
         if proc.returncode == 0 or "--force-dist" not in extra:
             break
         # an intermittent communicator bring-up is information: say so where the test log shows it
@@ -102,7 +104,7 @@ def test_headline_workload_gates():
         reference's own per-particle loop on the host, i.e. the box's CPU: the gate is 0.90 since a box of round 6 measured 0.61)."""
     env = dict(os.environ)
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "C2", "--steps", "10", "--warmup", "3",
-                           "--cpu-particles", "4"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                           "--full", "--cpu-particles", "4"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-2000:]
     d = json.loads([ln for ln in proc.stdout.splitlines() if ln.strip()][-1])
     for k in KEYS:
@@ -193,7 +195,7 @@ def test_two_ranks_through_the_launcher_on_one_gpu():
     proc = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
                            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "C1", "--steps", "3", "--warmup", "1",
-                           "--prewarm-ms", "20"], capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
+                           "--prewarm-ms", "20", "--full"], capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
     assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-3000:]
     lines = [ln for ln in proc.stdout.splitlines() if ln.strip()]
     d = json.loads(lines[-1])
@@ -206,3 +208,55 @@ def test_two_ranks_through_the_launcher_on_one_gpu():
     assert d["kernels_ms_per_step"]["collective"] > 0
     # the child that would drive both GPUs from one process reports why it could not: the line survives
     assert "error" in d["in_process_group"] and "--gpus 2" in d["in_process_group"]["error"]
+
+
+DUMPED = ("weights", "likelihood", "match_ratio", "stats")
+
+
+def test_plain_run_times_the_steps_and_dumps_what_they_computed(tmp_path):
+    """Without --full the line carries the headline alone (no side measurement, no check), and --dump-outputs writes what the
+    last timed step computed: the same arrays, bit for bit, from a second run with the same arguments."""
+    runs = []
+    for name in ("a", "b"):
+        d = run_bench("--steps", "5", "--dump-outputs", str(tmp_path / name), full=False)
+        runs.append(d)
+        for k in KEYS:
+            assert k in d, k
+        assert d["full"] is False and d["steps"] == 5 and d["warmup"] == 1 and d["n_gpus"] == 1
+        assert d["metric"].startswith("particle·point evals/sec") and d["unit"] == "particle·point evals/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["value"] > 1e8 and d["ms_per_step"] > 0
+        assert abs(d["value"] - d["config"]["particles_total"] * d["config"]["scan_points"] / (d["ms_per_step"] * 1e-3)) \
+            < 1e-6 * d["value"]
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["value_8d"] is None
+        for k in ("update_8d", "kernels_ms_per_step", "result_check", "in_process_group", "scan_preparation", "other_scaling"):
+            assert k not in d, k
+    n = runs[0]["config"]["particles_total"]
+    for name in DUMPED:
+        a, b = (np.load(str(tmp_path / r / (name + ".npy"))) for r in ("a", "b"))
+        assert a.dtype == np.float32 and a.shape == ((4,) if name == "stats" else (n,)), (name, a.shape)
+        np.testing.assert_array_equal(a, b)
+    assert not (tmp_path / "a" / "beam.npy").exists()   # C1 has no beam points
+    w = np.load(str(tmp_path / "a" / "weights.npy")).astype(np.float64)
+    stats = np.load(str(tmp_path / "a" / "stats.npy"))
+    assert abs(w.sum() - 1.0) < 1e-5
+    assert abs(stats[0] - float(-(w[w > 0] * np.log(w[w > 0])).sum())) < 1e-4
+
+
+def test_dumped_outputs_are_the_engine_update_of_the_same_inputs(tmp_path):
+    """The dumped arrays are what the single-GPU update computes from the run's inputs: weights, likelihoods and match ratios
+    of C3 (likelihood + beam model) against the engine's host-buffer update of the same synthetic scene."""
+    from mcl_3dl_amd import capi
+    from mcl_3dl_amd.synthetic import make_config
+    run_bench("--workload", "C3", "--particles", "256", "--dump-outputs", str(tmp_path), full=False)
+    sc = make_config("C3", n_p=256, seed=12345)
+    eng = capi.Engine(0)
+    try:
+        eng.set_map(sc.map_xyz, sc.map_label, stamp=1, dist_weight=(1.0, 1.0, 1.0))
+        eng.set_likelihood_params()
+        eng.set_beam_params(num_points=len(sc.scan_beam), dda_grid_size=0.2)
+        got = eng.measure_update(sc.poses, sc.weights, sc.scan_lik, sc.scan_beam, sc.scan_beam_label, sc.origins)
+    finally:
+        eng.close()
+    for name, key in (("likelihood", "lik"), ("match_ratio", "quality"), ("beam", "beam"), ("weights", "weights")):
+        np.testing.assert_allclose(np.load(str(tmp_path / (name + ".npy"))), got[key], rtol=1e-5, atol=0, err_msg=name)

@@ -196,7 +196,7 @@ def test_rccl_refuses_repeated_devices_with_a_clear_error(scene):
 
 
 def test_node_call_site_on_a_device_group(tmp_path, oracle_kind):
-    """tests/cpp/adapter_demo.bin (the reference's plugin surface, src/mcl_3dl.cpp untouched) with the particles sharded
+    """oracle/_ref/adapter_demo.bin (the reference's plugin surface, src/mcl_3dl.cpp untouched) with the particles sharded
     over three contexts: MCL3DL_HIP_DEVICES=0,0,0."""
     from test_gpu_adapter import DEMO, need_binary, write_scene
     need_binary(DEMO)
