@@ -432,8 +432,8 @@ int mcl3dl_hip_group_measure_update(mcl3dl_hip_group* g, const float* pose, cons
  *   upload_state      the particle vector (include/mcl_3dl/pf.h:457) as 13 floats per particle {pos 3, rot 4 (x,y,z,w),
  *                     odom_err_integ lin 3, ang 3} (State6DOF, state_6dof.h:56-66) + probabilities (NULL: 1 / n_p each),
  *                     scattered into contiguous shards (mcl3dl_hip_group_shard); they stay on the devices until the next
- *                     upload. The motion model (prediction) is the caller's: download, predict, upload — or keep the states
- *                     where they are when nothing moved.
+ *                     upload. What the node does to the particles between two scans (motion prediction, IMU measurement,
+ *                     odometry noise, the odometry-error reset) runs on the resident particles too: see the calls below.
  *   update_resident   pf::measure (pf.h:252-279 with the lambda of src/mcl_3dl.cpp:402-425) over the resident particles:
  *                     only the scan (and the odometry factor `extra`, n_p floats or NULL) goes up, one all-reduce of
  *                     2 + 2N doubles, four scalars come back; out_weight / out_lik / out_match_ratio / out_beam (each may be
@@ -468,6 +468,38 @@ int mcl3dl_hip_group_resample_begin(mcl3dl_hip_group* g, size_t n_out /*0 = as m
 int mcl3dl_hip_group_resample_plan(mcl3dl_hip_group* g, int mode, float initial_p, uint32_t* out_source /*n_out or NULL*/,
                                    uint8_t* out_duplicate /*n_out or NULL*/, size_t* out_n_duplicates);
 int mcl3dl_hip_group_resample_apply(mcl3dl_hip_group* g, const float* noise13 /*n_dup*13, host*/, size_t n_noise);
+/* ---- between two scans, on the resident particles (no state download) --------------------------------------------------
+ * The rest of what src/mcl_3dl.cpp does to every particle. All but measure_imu are shard-local: one launch per device, no
+ * collective. The caller keeps drawing the random numbers (the reference draws them from one sequential engine), as for
+ * resample_apply's noise13.
+ *   set_odom_noise       State6DOF's odometry noise {noise_ll_, noise_la_, noise_al_, noise_aa_} per resident particle, already
+ *                        scaled by the caller (src/mcl_3dl.cpp:817-825 draws N(0, 1) * odom_err_*). upload_state installs zeros
+ *                        (State6DOF's constructors); resample_apply keeps a copied particle's noise and gives a duplicated one
+ *                        zeros (pf.h:211-222: operator+ returns a fresh State6DOF); add_noise zeroes it. download_odom_noise
+ *                        reads it back.
+ *   predict              cbOdom (src/mcl_3dl.cpp:227-232): MotionPredictionModelDifferentialDrive(lin_tc, ang_tc)
+ *                        (motion_prediction_model_differential_drive.h:46-67): setOdoms(prev, cur, time_diff) on the host, predict()
+ *                        on every particle. Poses are 7 floats {pos 3, rot x, y, z, w}.
+ *   reset_odom_integ     integ_reset_func (src/mcl_3dl.cpp:190-195, 652-658): odom_err_integ_lin_ = odom_err_integ_ang_ = 0.
+ *   add_noise            pf::noise / addNoiseUsingNoiseGenerator (pf.h:226-237, the expansion reset of src/mcl_3dl.cpp:850-860):
+ *                        state = state + noise13[i] (State6DOF::operator+, state_6dof.h:249-260), noise caller-drawn.
+ *   measure_imu          cbImu (src/mcl_3dl.cpp:997-1002): pf::measure (pf.h:252-279) with ImuMeasurementModelGravity(acc_var)
+ *                        after setAccMeasure(acc3) (imu_measurement_model_gravity.h:41-56); the same partial sums, all-reduce
+ *                        and restore rule as update_resident. out_weight / out_lik may be NULL.
+ *   set_odom_error_sigma measure()'s odometry factor (src/mcl_3dl.cpp:420-423): sigma > 0 makes update_resident with extra == NULL
+ *                        apply NormalLikelihood(sigma)(|odom_err_integ_lin_|) formed on the devices from the resident states;
+ *                        0 (the default) keeps NULL's meaning, no factor.
+ * sinf / cosf / acosf / expf of the reference are evaluated in double and rounded to float on the device (within 1 ulp of a
+ * faithful libm; DESIGN.md, "Numerics"); everything else is the reference's float arithmetic in its order. */
+int mcl3dl_hip_group_set_odom_noise(mcl3dl_hip_group* g, const float* noise4 /*n_p*4*/, size_t n_p);
+int mcl3dl_hip_group_download_odom_noise(mcl3dl_hip_group* g, float* noise4 /*n_p*4*/, size_t n_p);
+int mcl3dl_hip_group_predict(mcl3dl_hip_group* g, const float* odom_prev7, const float* odom_cur7, float time_diff,
+                             float odom_err_integ_lin_tc, float odom_err_integ_ang_tc);
+int mcl3dl_hip_group_reset_odom_integ(mcl3dl_hip_group* g);
+int mcl3dl_hip_group_add_noise(mcl3dl_hip_group* g, const float* noise13 /*n_p*13*/, size_t n_p);
+int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float acc_var, float* out_weight /*n_p or NULL*/,
+                                 float* out_lik /*n_p or NULL*/, float* entropy, int* restored);
+int mcl3dl_hip_group_set_odom_error_sigma(mcl3dl_hip_group* g, float sigma);
 /* How many updates went through each kind of collective so far. */
 int mcl3dl_hip_group_collective_stats(const mcl3dl_hip_group* g, uint64_t* rccl_all_reduces, uint64_t* host_combines);
 

@@ -109,6 +109,13 @@ SIGNATURES = {
     "mcl3dl_hip_group_resample_begin": (_i, [_p, _sz, _p]),
     "mcl3dl_hip_group_resample_plan": (_i, [_p, _i, _f, _p, _p, _p]),
     "mcl3dl_hip_group_resample_apply": (_i, [_p, _p, _sz]),
+    "mcl3dl_hip_group_set_odom_noise": (_i, [_p, _p, _sz]),
+    "mcl3dl_hip_group_download_odom_noise": (_i, [_p, _p, _sz]),
+    "mcl3dl_hip_group_predict": (_i, [_p, _p, _p, _f, _f, _f]),
+    "mcl3dl_hip_group_reset_odom_integ": (_i, [_p]),
+    "mcl3dl_hip_group_add_noise": (_i, [_p, _p, _sz]),
+    "mcl3dl_hip_group_measure_imu": (_i, [_p, _p, _f, _p, _p, _p, _p]),
+    "mcl3dl_hip_group_set_odom_error_sigma": (_i, [_p, _f]),
     "mcl3dl_hip_get_option": (_i, [_p, C.c_char_p, C.POINTER(_d)]),
     "mcl3dl_hip_index_stats": (_i, [_p, _p]),
 }
@@ -366,6 +373,45 @@ class Group:
     def resample_apply(self, noise13=None):
         nz = None if noise13 is None or len(noise13) == 0 else _np_f32(noise13, 13)
         self._check(self.lib.mcl3dl_hip_group_resample_apply(self.h, _ptr(nz), 0 if nz is None else len(nz)))
+
+    # ---- between two scans, on the resident particles (include/mcl3dl_hip.h) -----------------------------------------------
+    def set_odom_noise(self, noise4):
+        """State6DOF's {noise_ll_, noise_la_, noise_al_, noise_aa_} per resident particle (already scaled)."""
+        nz = _np_f32(noise4, 4)
+        self._check(self.lib.mcl3dl_hip_group_set_odom_noise(self.h, _ptr(nz), len(nz)))
+
+    def download_odom_noise(self):
+        n = self.resident()
+        nz = np.zeros((n, 4), np.float32)
+        self._check(self.lib.mcl3dl_hip_group_download_odom_noise(self.h, _ptr(nz), n))
+        return nz
+
+    def predict(self, odom_prev7, odom_cur7, time_diff, lin_tc=10.0, ang_tc=10.0):
+        """cbOdom's pf_->predict with MotionPredictionModelDifferentialDrive(lin_tc, ang_tc) (odom_err_integ_*_tc)."""
+        a, b = _np_f32(odom_prev7), _np_f32(odom_cur7)
+        self._check(self.lib.mcl3dl_hip_group_predict(self.h, _ptr(a), _ptr(b), float(time_diff), float(lin_tc), float(ang_tc)))
+
+    def reset_odom_integ(self):
+        self._check(self.lib.mcl3dl_hip_group_reset_odom_integ(self.h))
+
+    def add_noise(self, noise13):
+        """pf::noise with caller-drawn noise states (State6DOF::operator+)."""
+        nz = _np_f32(noise13, 13)
+        self._check(self.lib.mcl3dl_hip_group_add_noise(self.h, _ptr(nz), len(nz)))
+
+    def measure_imu(self, acc, acc_var, fetch=True):
+        """cbImu's pf_->measure with ImuMeasurementModelGravity(acc_var) after setAccMeasure(acc)."""
+        n_p = self.resident()
+        a = _np_f32(acc)
+        w, lik = (np.zeros(n_p, np.float32), np.zeros(n_p, np.float32)) if fetch else (None, None)
+        ent, rest = C.c_float(0), C.c_int(0)
+        self._check(self.lib.mcl3dl_hip_group_measure_imu(self.h, _ptr(a), float(acc_var), _ptr(w), _ptr(lik), C.byref(ent),
+                                                          C.byref(rest)))
+        return dict(weights=w, lik=lik, entropy=float(ent.value), restored=bool(rest.value))
+
+    def set_odom_error_sigma(self, sigma):
+        """sigma > 0: update_resident without `extra` applies the node's odometry factor formed on the devices."""
+        self._check(self.lib.mcl3dl_hip_group_set_odom_error_sigma(self.h, float(sigma)))
 
 
 class Engine:

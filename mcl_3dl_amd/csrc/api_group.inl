@@ -458,6 +458,14 @@ namespace
 {
 int resident_poses(mcl3dl_hip_ctx* ctx);  // api_group_state.inl
 
+// NormalLikelihood<float>(sigma)'s constants as nd.h:46-48 forms them: a_ from a double expression; sq2_ = (sigma * sigma) in
+// float, * 2.0 in double, narrowed to float
+void normal_likelihood_constants(float sigma, float* a, float* sq2)
+{
+  *a = static_cast<float>(1.0 / std::sqrt(2.0 * M_PI * sigma * sigma));
+  *sq2 = static_cast<float>(sigma * sigma * 2.0);
+}
+
 // One update over the group's shards. resident = false: mcl3dl_hip_group_measure_update (poses and prior weights come from the
 // host, the weights go back). resident = true: the particles mcl3dl_hip_group_upload_state / _resample_apply left on the
 // devices (pose = first 7 floats of each 13-float state, kept as ctx->pose; weights in ctx->gs_weight, updated in place);
@@ -502,6 +510,11 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
   const bool host_combine = g->collective == 1 && !no_collective;
   std::vector<float> stats(4 * static_cast<size_t>(N), 0.f);
   std::vector<float*> rank_weights(static_cast<size_t>(N), nullptr);  // where each rank's prior weights are on its device
+  // the node's odometry factor formed on the devices from the resident states (mcl3dl_hip_group_set_odom_error_sigma)
+  const bool device_extra = resident && !extra && g->odom_sigma > 0.f;
+  float nd_a = 0.f, nd_sq2 = 0.f;
+  if (device_extra)
+    normal_likelihood_constants(g->odom_sigma, &nd_a, &nd_sq2);
   if (!resident)
     g->n_pose_uploaded = 0;
 
@@ -633,6 +646,12 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
             rank_weights[r] = d_w;
             if (extra && !staged)
               TRY(h2d(ctx, ctx->extra.p, extra + lo, fb));
+            if (device_extra)
+            {
+              hipLaunchKernelGGL(odom_factor_kernel, dim3((static_cast<int>(n) + 255) / 256), dim3(256), 0, ctx->stream,
+                                 ctx->gs_state[ctx->gs_cur].as<float>(), static_cast<int>(n), nd_a, nd_sq2, ctx->extra.as<float>());
+              HIP_TRY(hipGetLastError());
+            }
             // (the sum over the tiled kernel's per-tile partials and the beam model's last step ride in the first pf::measure kernel,
             // as on one GPU: one launch less per model and rank)
             LikTail tail;
@@ -641,7 +660,7 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
             TRY(launch_measure(ctx, ctx->pose.as<float>(), n, ctx->lik.as<float>(), ctx->ratio.as<float>(),
                                ctx->beam.as<float>(), false, nullptr, &tail));
             TRY(pf_partial_behind_measure(ctx, d_w, ctx->lik.as<float>(), ctx->beam.as<float>(),
-                                          extra ? ctx->extra.as<float>() : nullptr, ctx->ratio.as<float>(), n, r, N,
+                                          (extra || device_extra) ? ctx->extra.as<float>() : nullptr, ctx->ratio.as<float>(), n, r, N,
                                           ctx->packed.as<double>(), tail));
           }
           else

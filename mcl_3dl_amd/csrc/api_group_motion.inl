@@ -1,0 +1,423 @@
+// api_group_motion.inl — included inside the extern "C" block of mcl3dl_hip.hip after api_group_state.inl: what the node does to
+// every particle between two scans, on the particles RESIDENT on the group's devices (motion_kernels.h):
+//
+//   mcl3dl_hip_group_set_odom_noise / _download_odom_noise   State6DOF's noise_ll_ / la_ / al_ / aa_ (src/mcl_3dl.cpp:817-825)
+//   mcl3dl_hip_group_predict                                 cbOdom's pf_->predict (:227-232), differential-drive model
+//   mcl3dl_hip_group_reset_odom_integ                        integ_reset_func (:190-195, :652-658)
+//   mcl3dl_hip_group_add_noise                               pf_->noise (:850-860; pf.h:226-237) with caller-drawn noise
+//   mcl3dl_hip_group_measure_imu                             cbImu's pf_->measure (:997-1002), gravity model
+//   mcl3dl_hip_group_set_odom_error_sigma                    measure()'s odometry factor (:420-423) formed on the devices
+//
+// Everything but the IMU update is shard-local (one launch per rank, no collective). The IMU update is pf::measure: the same
+// partial sums / one all-reduce / apply as mcl3dl_hip_group_update_resident, with the likelihood formed in the partial-sum pass.
+namespace
+{
+// MotionPredictionModelDifferentialDrive::setOdoms (motion_prediction_model_differential_drive.h:46-54) in float, once per
+// call, + the two decay factors of predict (:66-67)
+MotionStep motion_step(const float* prev7, const float* cur7, float time_diff, float lin_tc, float ang_tc)
+{
+  const Quat prev_rot = { prev7[3], prev7[4], prev7[5], prev7[6] };
+  const Quat cur_rot = { cur7[3], cur7[4], cur7[5], cur7[6] };
+  const Quat pinv = qinv(prev_rot);
+  MotionStep m;
+  m.t = qrot(pinv, vsub(Vec3f{ cur7[0], cur7[1], cur7[2] }, Vec3f{ prev7[0], prev7[1], prev7[2] }));
+  m.rq = qmul(pinv, cur_rot);
+  // Quat::getAxisAng (quat.h:226-238): the angle only; std::acos of a float is the host libm's acosf
+  if (std::fabs(m.rq.w) >= 1.0 - 0.000001)
+    m.ang = 0.0f;
+  else
+  {
+    m.ang = static_cast<float>(std::acos(m.rq.w) * 2.0);
+    if (m.ang > M_PI)
+      m.ang = static_cast<float>(m.ang - 2.0 * M_PI);
+  }
+  m.t_norm = std::sqrt(vdot(m.t, m.t));
+  m.decay_lin = static_cast<float>(1.0 - static_cast<double>(time_diff / lin_tc));
+  m.decay_ang = static_cast<float>(1.0 - static_cast<double>(time_diff / ang_tc));
+  return m;
+}
+
+// the shard-local calls: f(ctx, n) on every rank whose shard holds particles
+int group_each_shard(mcl3dl_hip_group* g, const std::function<int(mcl3dl_hip_ctx*, int, size_t, size_t)>& f)
+{
+  const size_t n_p = g->n_resident;
+  if (n_p == 0)
+    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  const int N = g->n();
+  int bad = 0;
+  const int rc = g->pool.run_all(
+      [&](int r) -> int
+      {
+        mcl3dl_hip_ctx* ctx = g->ctx[r];
+        size_t lo, hi;
+        shard_bounds(n_p, N, r, &lo, &hi);
+        const size_t n = hi - lo;
+        if (n == 0)
+          return 0;
+        HIP_TRY(hipSetDevice(ctx->device));
+        if (ctx->gs_n != n)
+          return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, n);
+        return f(ctx, r, lo, n);
+      },
+      &bad);
+  return rc ? g->fail_rank(rc, bad) : 0;
+}
+
+inline dim3 grid_of(size_t n)
+{
+  return dim3(static_cast<unsigned>((n + 255) / 256));
+}
+}  // namespace
+
+int mcl3dl_hip_group_set_odom_noise(mcl3dl_hip_group* g, const float* noise4, size_t n_p)
+{
+  if (!g)
+    return -1;
+  if (!noise4)
+    return g->fail(-3, "null noise array");
+  if (g->n_resident == 0 || g->n_resident != n_p)
+    return g->fail(-5, "%zu particles are resident, %zu noise records given", g->n_resident, n_p);
+  const int N = g->n();
+  int bad = 0;
+  const int rc = g->pool.run_all(
+      [&](int r) -> int
+      {
+        mcl3dl_hip_ctx* ctx = g->ctx[r];
+        size_t lo, hi;
+        shard_bounds(n_p, N, r, &lo, &hi);
+        HIP_TRY(hipSetDevice(ctx->device));
+        // (room for the LARGEST shard on every rank, an empty one included: the resampling step's all-gather sends that many)
+        TRY(ensure(ctx, ctx->gs_noise[ctx->gs_cur], sizeof(float) * 4 * ((n_p + N - 1) / N)));
+        if (hi == lo)
+          return 0;
+        TRY(h2d(ctx, ctx->gs_noise[ctx->gs_cur].p, noise4 + 4 * lo, sizeof(float) * 4 * (hi - lo)));
+        return sync_stream(ctx);
+      },
+      &bad);
+  if (rc)
+  {
+    g->noise_on = false;  // (some shards may hold the new noise, others none: the caller sets it again)
+    return g->fail_rank(rc, bad);
+  }
+  g->noise_on = true;
+  return 0;
+}
+
+int mcl3dl_hip_group_download_odom_noise(mcl3dl_hip_group* g, float* noise4, size_t n_p)
+{
+  if (!g)
+    return -1;
+  if (!noise4)
+    return g->fail(-3, "null noise array");
+  if (g->n_resident == 0 || g->n_resident != n_p)
+    return g->fail(-5, "%zu particles are resident, %zu asked for", g->n_resident, n_p);
+  if (!g->noise_on)
+  {
+    std::fill(noise4, noise4 + 4 * n_p, 0.0f);
+    return 0;
+  }
+  return group_each_shard(g,
+                          [&](mcl3dl_hip_ctx* ctx, int, size_t lo, size_t n) -> int
+                          {
+                            TRY(d2h(ctx, noise4 + 4 * lo, ctx->gs_noise[ctx->gs_cur].p, sizeof(float) * 4 * n));
+                            return sync_stream(ctx);
+                          });
+}
+
+int mcl3dl_hip_group_predict(mcl3dl_hip_group* g, const float* odom_prev7, const float* odom_cur7, float time_diff,
+                             float odom_err_integ_lin_tc, float odom_err_integ_ang_tc)
+{
+  if (!g)
+    return -1;
+  if (!odom_prev7 || !odom_cur7)
+    return g->fail(-3, "null odometry pose");
+  const MotionStep m = motion_step(odom_prev7, odom_cur7, time_diff, odom_err_integ_lin_tc, odom_err_integ_ang_tc);
+  const bool noise = g->noise_on;
+  return group_each_shard(g,
+                          [&](mcl3dl_hip_ctx* ctx, int, size_t, size_t n) -> int
+                          {
+                            // the pose mirror is written by the same launch (resident_poses() then finds it current)
+                            TRY(ensure(ctx, ctx->pose, sizeof(float) * 7 * n));
+                            hipLaunchKernelGGL(predict_kernel, grid_of(n), dim3(256), 0, ctx->stream,
+                                               ctx->gs_state[ctx->gs_cur].as<float>(),
+                                               noise ? ctx->gs_noise[ctx->gs_cur].as<float>() : static_cast<float*>(nullptr),
+                                               static_cast<int>(n), m, ctx->pose.as<float>());
+                            HIP_TRY(hipGetLastError());
+                            ctx->poses_set(n);
+                            ctx->pose_resident = true;
+                            return sync_stream(ctx);
+                          });
+}
+
+int mcl3dl_hip_group_reset_odom_integ(mcl3dl_hip_group* g)
+{
+  if (!g)
+    return -1;
+  return group_each_shard(g,
+                          [&](mcl3dl_hip_ctx* ctx, int, size_t, size_t n) -> int
+                          {
+                            hipLaunchKernelGGL(reset_odom_integ_kernel, grid_of(n), dim3(256), 0, ctx->stream,
+                                               ctx->gs_state[ctx->gs_cur].as<float>(), static_cast<int>(n));
+                            HIP_TRY(hipGetLastError());
+                            return sync_stream(ctx);
+                          });
+}
+
+int mcl3dl_hip_group_add_noise(mcl3dl_hip_group* g, const float* noise13, size_t n_p)
+{
+  if (!g)
+    return -1;
+  if (!noise13)
+    return g->fail(-3, "null noise array");
+  if (g->n_resident == 0 || g->n_resident != n_p)
+    return g->fail(-5, "%zu particles are resident, %zu noise states given", g->n_resident, n_p);
+  const int rc = group_each_shard(g,
+                                  [&](mcl3dl_hip_ctx* ctx, int, size_t lo, size_t n) -> int
+                                  {
+                                    TRY(ensure(ctx, ctx->rs_d_noise, sizeof(float) * 13 * n));
+                                    TRY(h2d(ctx, ctx->rs_d_noise.p, noise13 + 13 * lo, sizeof(float) * 13 * n));
+                                    TRY(ensure(ctx, ctx->pose, sizeof(float) * 7 * n));
+                                    hipLaunchKernelGGL(add_noise_kernel, grid_of(n), dim3(256), 0, ctx->stream,
+                                                       ctx->gs_state[ctx->gs_cur].as<float>(), ctx->rs_d_noise.as<float>(),
+                                                       static_cast<int>(n), ctx->pose.as<float>());
+                                    HIP_TRY(hipGetLastError());
+                                    ctx->poses_set(n);
+                                    ctx->pose_resident = true;
+                                    return sync_stream(ctx);
+                                  });
+  // operator+ returns a fresh State6DOF: every particle's odometry noise is 0 now (the node redraws it after the next scan)
+  g->noise_on = false;
+  return rc;
+}
+
+int mcl3dl_hip_group_set_odom_error_sigma(mcl3dl_hip_group* g, float sigma)
+{
+  if (!g)
+    return -1;
+  if (!(sigma >= 0.f) || std::isinf(sigma))
+    return g->fail(-3, "odometry error sigma must be finite and >= 0 (0 = no factor)");
+  g->odom_sigma = sigma;
+  return 0;
+}
+
+int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float acc_var, float* out_weight, float* out_lik,
+                                 float* entropy, int* restored)
+{
+  if (!g)
+    return -1;
+  if (!acc3)
+    return g->fail(-3, "null acceleration");
+  const size_t n_p = g->n_resident;
+  if (n_p == 0)
+    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  // ImuMeasurementModelGravity(acc_var) + setAccMeasure(acc) (imu_measurement_model_gravity.h:41-48)
+  ImuGravity imu{};
+  imu.acc = Vec3f{ acc3[0], acc3[1], acc3[2] };
+  imu.acc_norm = std::sqrt(vdot(imu.acc, imu.acc));
+  normal_likelihood_constants(acc_var, &imu.a, &imu.sq2);
+  const int N = g->n();
+  const bool no_collective = N == 1 && g->direct_single;
+  const bool host_combine = g->collective == 1 && !no_collective;
+  if (!no_collective)
+    TRY(group_comms(g));
+  const size_t n_pack = 2 + 2 * static_cast<size_t>(N);
+  std::vector<float> stats(4 * static_cast<size_t>(N), 0.f);
+  const auto imu_of = [&](mcl3dl_hip_ctx* ctx) -> ImuGravity
+  {
+    ImuGravity m = imu;
+    m.state13 = ctx->gs_state[ctx->gs_cur].as<float>();
+    m.lik_out = ctx->lik.as<float>();
+    return m;
+  };
+  // the results of a rank home
+  const auto fetch = [&](mcl3dl_hip_ctx* ctx, int r, size_t lo, size_t n) -> int
+  {
+    TRY(d2h(ctx, &stats[4 * r], ctx->stats4.p, sizeof(float) * 4));
+    if (out_weight)
+      TRY(d2h(ctx, out_weight + lo, ctx->gs_weight.p, sizeof(float) * n));
+    if (out_lik)
+      TRY(d2h(ctx, out_lik + lo, ctx->lik.p, sizeof(float) * n));
+    return sync_stream(ctx);
+  };
+  int bad = 0;
+  if (no_collective)
+  {
+    // one device: pf::measure as mcl3dl_hip_group_update_resident's single-GPU form runs it (pf_measure_single: the fused
+    // work-group up to pf_fused_max particles, else partial + apply), the likelihood formed inside — one or two launches
+    mcl3dl_hip_ctx* ctx = g->ctx[0];
+    const int rc = [&]() -> int
+    {
+      HIP_TRY(hipSetDevice(ctx->device));
+      const size_t n = ctx->gs_n;
+      if (n != n_p)
+        return ctx->fail(-5, "this device holds %zu resident particles, not %zu", n, n_p);
+      const int nb = pf_blocks(n);
+      TRY(ensure(ctx, ctx->lik, sizeof(float) * n));
+      TRY(ensure(ctx, ctx->wnew, sizeof(float) * n));
+      TRY(ensure(ctx, ctx->block_partials, sizeof(double) * 4 * nb));
+      TRY(ensure(ctx, ctx->partial4, sizeof(double) * 4));
+      TRY(ensure(ctx, ctx->stats4, sizeof(float) * 4));
+      const ImuGravity m = imu_of(ctx);
+      float* d_w = ctx->gs_weight.as<float>();
+      const bool float_w = pf_float_order(ctx, n);
+      const int ni = static_cast<int>(n);
+      const float* none = nullptr;
+      EventPair ep{};
+      TRY(timing_begin(ctx, MCL3DL_KERNEL_PF, &ep));
+      if (n <= static_cast<size_t>(std::min(ctx->pf_fused_max, PF_FUSED_MAX)) && ctx->pf_fused)
+        hipLaunchKernelGGL(pf_fused_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_w, none, none, none, none, ni,
+                           ctx->wnew.as<float>(), ctx->partial4.as<double>(), ctx->stats4.as<float>(), PfEmit{}, float_w ? 1 : 0,
+                           BeamCounts{}, m);
+      else
+      {
+        hipLaunchKernelGGL(pf_partial_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_w, none, none, none, none, ni,
+                           ctx->wnew.as<float>(), ctx->block_partials.as<double>(), BeamCounts{}, m);
+        if (!float_w)
+          hipLaunchKernelGGL(pf_apply_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_w, ctx->wnew.as<float>(), ni, 1,
+                             static_cast<const double*>(nullptr), ctx->stats4.as<float>(), PfEmit{}, none, none, none,
+                             ctx->block_partials.as<double>(), nb, 0, ctx->partial4.as<double>());
+        else
+        {
+          // the reference's float recurrence over the weights (strict_order 1 beyond pf_fused_max) between the two
+          hipLaunchKernelGGL(pf_reduce_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->block_partials.as<double>(), nb, 0, 1,
+                             ctx->partial4.as<double>());
+          hipLaunchKernelGGL(pf_strict_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->wnew.as<float>(), ni,
+                             ctx->partial4.as<double>());
+          hipLaunchKernelGGL(pf_apply_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_w, ctx->wnew.as<float>(), ni, 1,
+                             ctx->partial4.as<double>(), ctx->stats4.as<float>());
+        }
+      }
+      TRY(timing_end(ctx, ep));
+      HIP_TRY(hipGetLastError());
+      return fetch(ctx, 0, 0, n);
+    }();
+    if (rc)
+      return g->fail_rank(rc, 0);
+  }
+  else
+  {
+    // N shards: partial sums, the record all-reduced (RCCL, or through the host), apply — the steps and the 2 + 2N-double
+    // record of mcl3dl_hip_group_update_resident
+    std::vector<int> rcs(N, 0);
+    constexpr int RC_ABANDONED = -8;
+    const auto phase_b = [&](mcl3dl_hip_ctx* ctx, int r, size_t lo, size_t n) -> int
+    {
+      if (n == 0)
+        return sync_stream(ctx);
+      hipLaunchKernelGGL(pf_apply_kernel, dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, ctx->stream, ctx->gs_weight.as<float>(),
+                         ctx->wnew.as<float>(), static_cast<int>(n), N, ctx->packed.as<double>(), ctx->stats4.as<float>());
+      HIP_TRY(hipGetLastError());
+      return fetch(ctx, r, lo, n);
+    };
+    int rc = g->pool.run_all(
+        [&](int r) -> int
+        {
+          mcl3dl_hip_ctx* ctx = g->ctx[r];
+          size_t lo, hi;
+          shard_bounds(n_p, N, r, &lo, &hi);
+          const size_t n = hi - lo;
+          const auto phase_a = [&]() -> int
+          {
+            HIP_TRY(hipSetDevice(ctx->device));
+            TRY(ensure(ctx, ctx->packed, sizeof(double) * n_pack));
+            TRY(ensure(ctx, ctx->stats4, sizeof(float) * 4));
+            if (n == 0)
+              return pack_empty(ctx, r, N, ctx->packed.as<double>());
+            if (ctx->gs_n != n)
+              return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, n);
+            const int nb = pf_blocks(n);
+            TRY(ensure(ctx, ctx->lik, sizeof(float) * n));
+            TRY(ensure(ctx, ctx->wnew, sizeof(float) * n));
+            TRY(ensure(ctx, ctx->block_partials, sizeof(double) * 4 * nb));
+            const float* none = nullptr;
+            hipLaunchKernelGGL(pf_partial_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, ctx->gs_weight.as<float>(), none, none,
+                               none, none, static_cast<int>(n), ctx->wnew.as<float>(), ctx->block_partials.as<double>(),
+                               BeamCounts{}, imu_of(ctx));
+            hipLaunchKernelGGL(pf_reduce_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->block_partials.as<double>(), nb, r, N,
+                               ctx->packed.as<double>());
+            if (N == 1 && pf_float_order(ctx, n))
+              hipLaunchKernelGGL(pf_strict_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->wnew.as<float>(),
+                                 static_cast<int>(n), ctx->packed.as<double>());
+            HIP_TRY(hipGetLastError());
+            return 0;
+          };
+          int rc_a = phase_a();
+          const bool all_ok = g->vote.vote(rc_a == 0);
+          if (rc_a == 0 && !all_ok)
+            rc_a = ctx->fail(RC_ABANDONED, "IMU update abandoned: another rank failed ahead of the collective");
+          if (rc_a != 0)
+          {
+            (void)hipStreamSynchronize(ctx->stream);
+            return rcs[r] = rc_a;
+          }
+          if (host_combine)
+          {
+            g->host_packed[r].resize(n_pack);
+            TRY(d2h(ctx, g->host_packed[r].data(), ctx->packed.p, sizeof(double) * n_pack));
+            return rcs[r] = sync_stream(ctx);
+          }
+          const ncclResult_t nrc = g->rccl.AllReduce(ctx->packed.p, ctx->packed.p, n_pack, ncclDouble, ncclSum, g->comms[r],
+                                                     ctx->stream);
+          const bool enqueued = g->vote.vote(nrc == ncclSuccess);
+          if (nrc != ncclSuccess)
+            return rcs[r] = ctx->fail(-7, "ncclAllReduce failed: %s", g->rccl.GetErrorString(nrc));
+          if (!enqueued)
+            return rcs[r] = ctx->fail(RC_ABANDONED, "IMU update abandoned: another rank could not enqueue the all-reduce");
+          return rcs[r] = phase_b(ctx, r, lo, n);
+        },
+        &bad);
+    if (rc)
+    {
+      for (int r = 0; r < N; ++r)
+        if (rcs[r] != 0 && rcs[r] != RC_ABANDONED)
+        {
+          rc = rcs[r];
+          bad = r;
+          break;
+        }
+      if (!host_combine && !g->comms.empty())
+        g->drop_comms();
+      return g->fail_rank(rc, bad);
+    }
+    if (host_combine)
+    {
+      std::vector<double> total(n_pack, 0.0);
+      for (int r = 0; r < N; ++r)  // rank order: deterministic
+        for (size_t i = 0; i < n_pack; ++i)
+          total[i] += g->host_packed[r][i];
+      rc = g->pool.run_all(
+          [&](int r) -> int
+          {
+            mcl3dl_hip_ctx* ctx = g->ctx[r];
+            size_t lo, hi;
+            shard_bounds(n_p, N, r, &lo, &hi);
+            HIP_TRY(hipSetDevice(ctx->device));
+            TRY(h2d(ctx, ctx->packed.p, total.data(), sizeof(double) * n_pack));
+            return phase_b(ctx, r, lo, hi - lo);
+          },
+          &bad);
+      if (rc)
+        return g->fail_rank(rc, bad);
+      ++g->collectives_host;
+    }
+    else
+      ++g->collectives_rccl;
+  }
+  // every rank computed the same scalars from the same record: the first non-empty shard's
+  int src = 0;
+  for (int r = 0; r < N; ++r)
+  {
+    size_t lo, hi;
+    shard_bounds(n_p, N, r, &lo, &hi);
+    if (hi > lo)
+    {
+      src = r;
+      break;
+    }
+  }
+  if (entropy)
+    *entropy = stats[4 * src + 0];
+  if (restored)
+    *restored = stats[4 * src + 3] != 0.0f;
+  return 0;
+}

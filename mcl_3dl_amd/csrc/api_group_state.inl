@@ -22,19 +22,20 @@ __global__ void state13_to_pose7_kernel(const float* __restrict__ state13, int n
     pose7[7 * static_cast<size_t>(i) + k] = state13[13 * static_cast<size_t>(i) + k];
 }
 
-// padded all-gather layout [rank][max_count][13] -> flat particle order (shards differ in size by at most one)
+// padded all-gather layout [rank][max_count][width] -> flat particle order (shards differ in size by at most one); width 13 for
+// the states, 4 for the odometry noise
 __global__ void unpad_states_kernel(const float* __restrict__ padded, size_t max_count, size_t base, size_t rem, size_t n,
-                                    float* __restrict__ flat)
+                                    float* __restrict__ flat, size_t width = 13)
 {
   const size_t t = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= 13 * n)
+  if (t >= width * n)
     return;
-  const size_t i = t / 13, k = t % 13;
+  const size_t i = t / width, k = t % width;
   // owner of particle i under shard_bounds: the first `rem` shards hold base + 1 particles
   const size_t split = rem * (base + 1);
   const size_t r = i < split ? i / (base + 1) : rem + (base ? (i - split) / base : 0);
   const size_t lo = r * base + (r < rem ? r : rem);
-  flat[t] = padded[(r * max_count + (i - lo)) * 13 + k];
+  flat[t] = padded[(r * max_count + (i - lo)) * width + k];
 }
 
 int rebuild_pose(mcl3dl_hip_ctx* ctx, size_t n)
@@ -70,6 +71,7 @@ int mcl3dl_hip_group_upload_state(mcl3dl_hip_group* g, const float* state13, con
     return g->fail(-3, "bad state array");
   g->n_resident = 0;
   g->rs_begun = g->rs_planned = false;
+  g->noise_on = false;  // State6DOF's constructors: no odometry noise until set_odom_noise
   int bad = 0;
   const int N = g->n();
   const int rc = g->pool.run_all(
@@ -313,10 +315,18 @@ int mcl3dl_hip_group_resample_apply(mcl3dl_hip_group* g, const float* noise13, s
   const bool host_gather = g->collective == 1 && !single;
   if (!single && !host_gather)
     TRY(group_comms(g));
+  // the odometry noise travels with the states once it has been installed (api_group_motion.inl); without it this call issues
+  // the same collectives and launches as it always did
+  const bool with_noise = g->noise_on;
   if (host_gather)
   {
     g->h_state.resize(13 * n_p);
     TRY(mcl3dl_hip_group_download_state(g, g->h_state.data(), nullptr, n_p));
+    if (with_noise)
+    {
+      g->h_noise.resize(4 * n_p);
+      TRY(mcl3dl_hip_group_download_odom_noise(g, g->h_noise.data(), n_p));
+    }
   }
   const size_t base = n_p / N, rem = n_p % N, max_count = base + (rem ? 1 : 0);
   int bad = 0;
@@ -332,6 +342,7 @@ int mcl3dl_hip_group_resample_apply(mcl3dl_hip_group* g, const float* noise13, s
         const size_t n = hi - lo, n_new = ohi - olo;
         const int other = ctx->gs_cur ^ 1;
         const float* d_all = nullptr;
+        const float* d_noise_all = nullptr;
         // everything ahead of the collective; the all-gather is entered by all ranks or by none
         const auto prepare = [&]() -> int
         {
@@ -339,14 +350,28 @@ int mcl3dl_hip_group_resample_apply(mcl3dl_hip_group* g, const float* noise13, s
           const size_t cap_new = std::max<size_t>((n_out + N - 1) / N, 1);
           TRY(ensure(ctx, ctx->gs_state[other], sizeof(float) * 13 * cap_new));
           TRY(ensure(ctx, ctx->gs_weight, sizeof(float) * cap_new));
+          if (with_noise)
+            TRY(ensure(ctx, ctx->gs_noise[other], sizeof(float) * 4 * cap_new));
           if (single)
             return 0;
           TRY(ensure(ctx, ctx->gs_all, sizeof(float) * 13 * n_p));
+          if (with_noise)
+            TRY(ensure(ctx, ctx->gs_noise_all, sizeof(float) * 4 * n_p));
           if (host_gather)
+          {
+            if (with_noise)
+              TRY(h2d(ctx, ctx->gs_noise_all.p, g->h_noise.data(), sizeof(float) * 4 * n_p));
             return h2d(ctx, ctx->gs_all.p, g->h_state.data(), sizeof(float) * 13 * n_p);
+          }
           TRY(ensure(ctx, ctx->gs_pad, sizeof(float) * 13 * max_count * static_cast<size_t>(N)));
           if (ctx->gs_state[ctx->gs_cur].cap < sizeof(float) * 13 * max_count)  // (every shard buffer holds the largest shard)
             return ctx->fail(-4, "internal: shard buffer smaller than the all-gather's send count");
+          if (with_noise)
+          {
+            TRY(ensure(ctx, ctx->gs_noise_pad, sizeof(float) * 4 * max_count * static_cast<size_t>(N)));
+            if (ctx->gs_noise[ctx->gs_cur].cap < sizeof(float) * 4 * max_count)
+              return ctx->fail(-4, "internal: noise buffer smaller than the all-gather's send count");
+          }
           return 0;
         };
         int rc_p = prepare();
@@ -363,9 +388,15 @@ int mcl3dl_hip_group_resample_apply(mcl3dl_hip_group* g, const float* noise13, s
           return rcs[r] = rc_p;
         }
         if (single)
+        {
           d_all = ctx->gs_state[ctx->gs_cur].as<float>();
+          d_noise_all = ctx->gs_noise[ctx->gs_cur].as<float>();
+        }
         else if (host_gather)
+        {
           d_all = ctx->gs_all.as<float>();
+          d_noise_all = ctx->gs_noise_all.as<float>();
+        }
         else
         {
           // 13 floats x max_count per rank over xGMI into the padded layout, then into particle order
@@ -381,11 +412,34 @@ int mcl3dl_hip_group_resample_apply(mcl3dl_hip_group* g, const float* noise13, s
                              ctx->gs_pad.as<float>(), max_count, base, rem, n_p, ctx->gs_all.as<float>());
           HIP_TRY(hipGetLastError());
           d_all = ctx->gs_all.as<float>();
+          if (with_noise)
+          {
+            // the four noise floats of every particle the same way: a second all-gather, only while noise is installed
+            const ncclResult_t nrc2 = g->rccl.AllGather(ctx->gs_noise[ctx->gs_cur].p, ctx->gs_noise_pad.p, 4 * max_count,
+                                                        ncclFloat, g->comms[r], ctx->stream);
+            const bool enqueued2 = g->vote.vote(nrc2 == ncclSuccess);
+            if (nrc2 != ncclSuccess)
+              return rcs[r] = ctx->fail(-7, "ncclAllGather (odometry noise) failed: %s", g->rccl.GetErrorString(nrc2));
+            if (!enqueued2)
+              return rcs[r] = ctx->fail(RC_ABANDONED, "resampling abandoned: another rank could not enqueue the all-gather");
+            hipLaunchKernelGGL(unpad_states_kernel, dim3(static_cast<unsigned>((4 * n_p + 255) / 256)), dim3(256), 0, ctx->stream,
+                               ctx->gs_noise_pad.as<float>(), max_count, base, rem, n_p, ctx->gs_noise_all.as<float>(),
+                               static_cast<size_t>(4));
+            HIP_TRY(hipGetLastError());
+            d_noise_all = ctx->gs_noise_all.as<float>();
+          }
         }
         (void)n;
         if (n_new)
         {
           TRY(mcl3dl_hip_resample_apply_slice_device(ctx, d_all, noise13, n_noise, olo, n_new, ctx->gs_state[other].as<float>()));
+          if (with_noise)
+          {
+            hipLaunchKernelGGL(resample_noise_kernel, dim3((static_cast<int>(n_new) + 255) / 256), dim3(256), 0, ctx->stream,
+                               d_noise_all, ctx->rs_d_source.as<uint32_t>() + olo, ctx->rs_d_slot.as<uint32_t>() + olo,
+                               static_cast<int>(n_new), ctx->gs_noise[other].as<float>());
+            HIP_TRY(hipGetLastError());
+          }
           // pf.h:207 / 417: every particle of the new generation weighs 1 / n
           hipLaunchKernelGGL(fill_kernel, dim3((static_cast<int>(n_new) + 255) / 256), dim3(256), 0, ctx->stream,
                              ctx->gs_weight.as<float>(), 1.0f / static_cast<float>(n_out), static_cast<float*>(nullptr), 0.0f,
@@ -411,6 +465,7 @@ int mcl3dl_hip_group_resample_apply(mcl3dl_hip_group* g, const float* noise13, s
     if (!single && !host_gather && !g->comms.empty())
       g->drop_comms();
     g->n_resident = 0;  // the shards may be half way into the new generation
+    g->noise_on = false;
     return g->fail_rank(rc, bad);
   }
   if (!single && !host_gather)

@@ -314,6 +314,7 @@ struct mcl3dl_hip_ctx
   // this rank's shard of a device group's resident particles (api_group_state.inl): 13-float states (ping-pong), weights;
   // the 7-float poses the measurement kernels read are kept in `pose`
   DevBuf gs_state[2], gs_weight, gs_all, gs_pad, gs_rec;
+  DevBuf gs_noise[2], gs_noise_all, gs_noise_pad;  // odometry noise {ll, la, al, aa} beside gs_state (api_group_motion.inl)
   int gs_cur = 0;
   size_t gs_n = 0;
 

@@ -254,6 +254,11 @@ struct mcl3dl_hip_group
   size_t rs_n_out = 0;                   // set by group_resample_begin
   bool rs_begun = false, rs_planned = false;
   size_t rs_n_dup = 0;
+  // api_group_motion.inl: State6DOF's odometry noise is on the devices (gs_noise) once set_odom_noise installed it; until then, and
+  // again after an upload or add_noise, it is zero everywhere and nothing holds or moves it
+  bool noise_on = false;
+  float odom_sigma = 0.f;        // > 0: update_resident without `extra` forms the odometry factor on the devices
+  std::vector<float> h_noise;    // host gather buffer of the resampling step
 
   // a communicator that saw a failed or abandoned collective: aborted where RCCL can (a pending collective would block a
   // plain destroy), rebuilt by group_comms on next use

@@ -45,4 +45,5 @@ extern "C"
 #include "api_cloud.inl"
 #include "api_group.inl"
 #include "api_group_state.inl"
+#include "api_group_motion.inl"
 }  // extern "C"

@@ -5,6 +5,7 @@
 
 #include "device_math.h"
 #include "float_chain.h"
+#include "motion_kernels.h"
 
 #pragma clang fp contract(off)
 
@@ -54,7 +55,8 @@ __global__ __launch_bounds__(PF_BLOCK) void pf_partial_kernel(const float* __res
                                                               const float* __restrict__ extra,
                                                               const float* __restrict__ ratio, int n,
                                                               float* __restrict__ w_new,
-                                                              double* __restrict__ block_partials, BeamCounts bc = BeamCounts{})
+                                                              double* __restrict__ block_partials, BeamCounts bc = BeamCounts{},
+                                                              ImuGravity imu = ImuGravity{})
 {
   double s = 0.0, t = 0.0, rmax = 0.0, rneg = -1.0;  // match_ratio_max = 0, match_ratio_min = 1 (mcl_3dl.cpp:398-399)
   for (int i = blockIdx.x * PF_BLOCK + threadIdx.x; i < n; i += gridDim.x * PF_BLOCK)
@@ -64,7 +66,7 @@ __global__ __launch_bounds__(PF_BLOCK) void pf_partial_kernel(const float* __res
       l *= beam_score_from_count(bc, i);
     else if (beam)
       l *= beam[i];
-    l *= lik[i];
+    l *= imu.state13 ? imu_gravity_likelihood(imu, i) : lik[i];  // (the IMU update: the likelihood formed here, lik == null)
     if (extra)
       l = l * extra[i];
     const float wn = w[i] * l;  // pf.h:258
@@ -393,7 +395,8 @@ __global__ __launch_bounds__(1024) void pf_fused_kernel(float* __restrict__ w, c
                                                         const float* __restrict__ beam, const float* __restrict__ extra,
                                                         const float* __restrict__ ratio, int n, float* __restrict__ w_new,
                                                         double* __restrict__ packed, float* __restrict__ stats4,
-                                                        PfEmit emit = PfEmit{}, int float_order = 0, BeamCounts bc = BeamCounts{})
+                                                        PfEmit emit = PfEmit{}, int float_order = 0, BeamCounts bc = BeamCounts{},
+                                                        ImuGravity imu = ImuGravity{})
 {
   // float_order: pf::measure's `sum += p.probability_` (pf.h:255-260) as the reference runs it — float, sequentially, in
   // particle order (float_chain.h) — instead of the fp64 tree: the weights are divided by exactly the reference's float
@@ -415,7 +418,7 @@ __global__ __launch_bounds__(1024) void pf_fused_kernel(float* __restrict__ w, c
         l *= beam_score_from_count(bc, i);
       else if (beam)
         l *= beam[i];
-      l *= lik[i];
+      l *= imu.state13 ? imu_gravity_likelihood(imu, i) : lik[i];  // (as in pf_partial_kernel; no emit.lik then)
       if (extra)
         l = l * extra[i];
       const float wn = w[i] * l;
@@ -866,14 +869,7 @@ __global__ void resample_apply_kernel(const float* __restrict__ state_in, const 
       o[k] = s[k];
     return;
   }
-  const float* a = noise13 + 13 * static_cast<size_t>(slot);
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-    o[k] = s[k] + a[k];
-#pragma unroll
-  for (int k = 7; k < 13; ++k)
-    o[k] = s[k] + a[k];
-  const Quat r = qnormalized(qmul(Quat{ a[3], a[4], a[5], a[6] }, Quat{ s[3], s[4], s[5], s[6] }));
+  const Quat r = qnormalized(state6dof_plus(s, noise13 + 13 * static_cast<size_t>(slot), o));
   o[3] = r.x;
   o[4] = r.y;
   o[5] = r.z;
