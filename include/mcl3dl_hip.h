@@ -500,6 +500,43 @@ int mcl3dl_hip_group_add_noise(mcl3dl_hip_group* g, const float* noise13 /*n_p*1
 int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float acc_var, float* out_weight /*n_p or NULL*/,
                                  float* out_lik /*n_p or NULL*/, float* entropy, int* restored);
 int mcl3dl_hip_group_set_odom_error_sigma(mcl3dl_hip_group* g, float sigma);
+/* ---- global localisation: the particle set seeded from the map, on the devices ---------------------------------------------
+ * The reference's `global_localization` service (cbGlobalLocalization, src/mcl_3dl.cpp:1039-1099), step by step:
+ *   1. pcl::VoxelGrid(leaf = (float)grid) over pc_map_: the BASE map only, a map update overlay is ignored;
+ *   2. a KdTreeFLANN over the centroids with the map's dist_weight; centroid p is dropped when
+ *      radiusSearch(p2, grid, ..., 1) finds anything, p2 = p with p2.z = (float)((double)p.z + (0.01 + grid)): some centroid c
+ *      (p itself included) has d2(c, p2) < (float)(grid * grid) in the rescaled metric, flann::L2_Simple float arithmetic;
+ *   3. remove_if / erase: the survivors ("standable" points) keep their VoxelGrid order;
+ *   4. resizeParticle(points * div_yaw); particle i = point i / div_yaw with rotation i % div_yaw,
+ *      (Quat(Vec3(0, 0, 2 pi cnt / div_yaw)) * imu_quat).normalized(), probability (float)(1.0 / (float)points) — one over the
+ *      number of POINTS —, both odom_err_integ_* and the odometry noise zero.
+ * Points, rotations and weights are the reference's bit for bit: the div_yaw rotations are formed on the host (the host's
+ * cosf / sinf, as the reference forms them) and handed to the seeding kernel as a table.
+ *   _rotations    pure host function, no context: out_quat4 = div_yaw x {x, y, z, w}; imu_quat4 NULL = identity. -3 for
+ *                 div_yaw < 1, a NULL output or a non-finite quaternion.
+ *   _points       steps 1-3 on one context. The surviving points stay on the device for _seed_device — until the next map
+ *                 call — and are returned when out_xyz != NULL (capacity in points; -3 when too small, *n_points still set).
+ *                 *n_centroids = leaves of step 1. The context's map index is neither used nor rebuilt: the centroids are
+ *                 searched through a cell grid of their own ("Global localisation"), which is refused with -3 when
+ *                 a large dist_weight stretches the centroid cloud over more than 2^28 cells of edge 1.01 grid.
+ *   _seed_device  step 4 for particles [first, first + count) of the global order into caller-owned device arrays (any may be
+ *                 NULL), each starting at particle `first`: 13-float states, 7-float poses, weights.
+ *   group form    the service: every rank runs steps 1-3 on its replica of the map (deterministic, no collective) and seeds its
+ *                 own shard (mcl3dl_hip_group_shard). Afterwards *n_particles = *n_points * div_yaw particles are RESIDENT,
+ *                 exactly as after mcl3dl_hip_group_upload_state with the same states and weights (no odometry noise, no
+ *                 resampling in progress). With one device and "direct_single" 1 no thread and no RCCL is touched.
+ * Errors, all of which leave previously resident particles untouched: -5 no map; -3 grid <= 0, div_yaw < 1, non-finite
+ * imu_quat4; -5 "no standable point" when nothing survives step 2 (every centroid finds ITSELF when
+ * dist_weight_z * (0.01 + grid) < grid; the reference would resizeParticle(0)); -3 when the particles needed exceed
+ * max_particles (0 = no cap) or what upload_state accepts — the message names the count, *n_points / *n_particles are set. */
+int mcl3dl_hip_global_localization_rotations(int div_yaw, const float* imu_quat4 /*NULL = identity*/,
+                                             float* out_quat4 /*div_yaw*4*/);
+int mcl3dl_hip_global_localization_points(mcl3dl_hip_ctx* ctx, double grid, float* out_xyz /*capacity*3 or NULL*/,
+                                          size_t capacity, size_t* n_points, size_t* n_centroids);
+int mcl3dl_hip_global_localization_seed_device(mcl3dl_hip_ctx* ctx, int div_yaw, const float* imu_quat4, size_t first,
+                                               size_t count, float* d_state13, float* d_pose7, float* d_weight);
+int mcl3dl_hip_group_global_localization(mcl3dl_hip_group* g, double grid, int div_yaw, const float* imu_quat4,
+                                         size_t max_particles /*0 = no cap*/, size_t* n_points, size_t* n_particles);
 /* How many updates went through each kind of collective so far. */
 int mcl3dl_hip_group_collective_stats(const mcl3dl_hip_group* g, uint64_t* rccl_all_reduces, uint64_t* host_combines);
 

@@ -116,6 +116,10 @@ SIGNATURES = {
     "mcl3dl_hip_group_add_noise": (_i, [_p, _p, _sz]),
     "mcl3dl_hip_group_measure_imu": (_i, [_p, _p, _f, _p, _p, _p, _p]),
     "mcl3dl_hip_group_set_odom_error_sigma": (_i, [_p, _f]),
+    "mcl3dl_hip_global_localization_rotations": (_i, [_i, _p, _p]),
+    "mcl3dl_hip_global_localization_points": (_i, [_p, _d, _p, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
+    "mcl3dl_hip_global_localization_seed_device": (_i, [_p, _i, _p, _sz, _sz, _p, _p, _p]),
+    "mcl3dl_hip_group_global_localization": (_i, [_p, _d, _i, _p, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
     "mcl3dl_hip_get_option": (_i, [_p, C.c_char_p, C.POINTER(_d)]),
     "mcl3dl_hip_index_stats": (_i, [_p, _p]),
 }
@@ -198,6 +202,16 @@ def group_shard(n_p, n_devices, rank):
     if lib.mcl3dl_hip_group_shard(n_p, n_devices, rank, C.byref(b), C.byref(c)) != 0:
         raise EngineError("group_shard: bad arguments")
     return int(b.value), int(c.value)
+
+
+def global_localization_rotations(div_yaw, imu_quat=None):
+    """The div_yaw rotations cbGlobalLocalization gives its particles, (div_yaw, 4) float32 {x, y, z, w} (no GPU needed)."""
+    lib = load_library()
+    q = None if imu_quat is None else _np_f32(imu_quat)
+    out = np.zeros((max(int(div_yaw), 0), 4), np.float32)
+    if (q is not None and q.size != 4) or lib.mcl3dl_hip_global_localization_rotations(int(div_yaw), _ptr(q), _ptr(out)) != 0:
+        raise ValueError("global_localization_rotations: div_yaw must be >= 1 and imu_quat four finite floats")
+    return out
 
 
 class Group:
@@ -412,6 +426,15 @@ class Group:
     def set_odom_error_sigma(self, sigma):
         """sigma > 0: update_resident without `extra` applies the node's odometry factor formed on the devices."""
         self._check(self.lib.mcl3dl_hip_group_set_odom_error_sigma(self.h, float(sigma)))
+
+    def global_localization(self, grid, div_yaw, imu_quat=None, max_particles=0):
+        """cbGlobalLocalization on the group: afterwards n_points * div_yaw particles are resident. Returns
+        (n_points, n_particles)."""
+        q = None if imu_quat is None else _np_f32(imu_quat).reshape(4)
+        a, b = C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_group_global_localization(self.h, float(grid), int(div_yaw), _ptr(q),
+                                                                  int(max_particles), C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
 
 class Engine:
@@ -727,6 +750,23 @@ class Engine:
         sq = np.zeros(len(q), np.float32)
         self._check(self.lib.mcl3dl_hip_radius_search(self.h, _ptr(q), len(q), float(radius), _ptr(idx), _ptr(sq)))
         return idx, sq
+
+    def global_localization_points(self, grid):
+        """Steps 1-3 of cbGlobalLocalization on the base map: the standable points (n, 3) in VoxelGrid order and the number
+        of VoxelGrid centroids they were chosen from. The points stay on the device for global_localization_seed_device."""
+        n, c = C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_global_localization_points(self.h, float(grid), None, 0, C.byref(n), C.byref(c)))
+        xyz = np.zeros((n.value, 3), np.float32)
+        self._check(self.lib.mcl3dl_hip_global_localization_points(self.h, float(grid), _ptr(xyz), len(xyz), C.byref(n),
+                                                                   C.byref(c)))
+        return xyz[:n.value], int(c.value)
+
+    def global_localization_seed_device(self, div_yaw, first, count, d_state13=None, d_pose7=None, d_weight=None,
+                                        imu_quat=None):
+        """Step 4 for particles [first, first + count) into device arrays (torch tensors or raw addresses; any may be None)."""
+        q = None if imu_quat is None else _np_f32(imu_quat).reshape(4)
+        self._check(self.lib.mcl3dl_hip_global_localization_seed_device(self.h, int(div_yaw), _ptr(q), int(first), int(count),
+                                                                        _ptr(d_state13), _ptr(d_pose7), _ptr(d_weight)))
 
     def dda_trace(self, begin, end, max_out=4096):
         b = _np_f32(begin)

@@ -310,6 +310,13 @@ struct mcl3dl_hip_ctx
   int scan_order_device = 4096;  // scans of at least this many points (both models together) are ordered on the device; 0 = never
   size_t n_base = 0;  // points of the base map; anything behind them in map_xyz is the current map update
   DevBuf ms_xyz, ms_out, ms_flag[2];
+  // global localisation (api_global_loc.inl): VoxelGrid centroids of the base map, their private cell grid (rescaled points
+  // sorted by cell + run delimiters), keep flags / scan, the surviving points in VoxelGrid order, the div_yaw rotations.
+  // gl_valid: gl_pts holds gl_n_points points made from the map that (gl_stamp, gl_n_base, gl_n_map) name
+  DevBuf gl_centroids, gl_sorted, gl_cells, gl_flag, gl_pts, gl_rot;
+  size_t gl_n_points = 0, gl_n_centroids = 0, gl_n_base = 0, gl_n_map = 0;
+  uint64_t gl_stamp = 0;
+  bool gl_valid = false;
 
   // this rank's shard of a device group's resident particles (api_group_state.inl): 13-float states (ping-pong), weights;
   // the 7-float poses the measurement kernels read are kept in `pose`

@@ -15,6 +15,8 @@
 //                         matched / unmatched output (each with the min / max or the count the next step needs fused in)
 //   sort_kernels.h        stable radix sort of the cloud path: keys made in the first pass, points written by the last
 //   cloud_keys.h          the sort keys (VoxelGrid leaf index, Morton key, range key)
+//   global_loc_kernels.h  global localisation: the blocked-above test over the VoxelGrid centroids of the base map, and the seeding
+//                         of points x div_yaw particles into a shard of resident particles
 //   stage_kernels.h       head and tail of a host-buffer update as one launch each: scan ordering + pose / weight take-over
 //                         from page-locked host memory; lik_finalize + pf::measure with the results written back there
 //
@@ -32,3 +34,4 @@
 #include "sort_kernels.h"
 #include "stage_kernels.h"
 #include "grid_kernels.h"
+#include "global_loc_kernels.h"

@@ -46,4 +46,5 @@ extern "C"
 #include "api_group.inl"
 #include "api_group_state.inl"
 #include "api_group_motion.inl"
+#include "api_global_loc.inl"
 }  // extern "C"
