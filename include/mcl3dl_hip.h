@@ -84,6 +84,20 @@ int mcl3dl_hip_set_beam_params(mcl3dl_hip_ctx* ctx, float map_grid_x, float map_
                                float dda_grid_size, float ray_angle_half, float hit_range, float beam_likelihood_min,
                                uint32_t num_points, float ang_total_ref, uint32_t filter_label_max,
                                int add_penalty_short_only_mode);
+/* Replaces: the choice of raycaster in LidarMeasurementModelBeam::refreshParameters (src/lidar_measurement_model_beam.cpp:69-79)
+ * by beam/use_raycast_using_dda (include/mcl_3dl/parameters.h:109, src/parameters.cpp:289 — false by default there).
+ * mode 0 = RaycastUsingDDA (include/mcl_3dl/raycasts/raycast_using_dda.h; this library's default and its fast path),
+ * mode 1 = RaycastUsingKDTree (include/mcl_3dl/raycasts/raycast_using_kdtree.h:58-109): steps of the smallest map_grid edge,
+ * at each a ChunkedKdtree::radiusSearch (mcl3dl_hip_radius_search's definition, exact) and the surface's inclination from
+ * a second search — the only caster that reports TOTAL_REFLECTION. Mode 1 uses map_grid_x/y/z, hit_range (the caster's
+ * hit_tolerance_), beam_likelihood_min, num_points, ang_total_ref, filter_label_max and add_penalty_short_only_mode of
+ * mcl3dl_hip_set_beam_params and ignores dda_grid_size and ray_angle_half. Any other mode: -3. May be changed at any time;
+ * the next call that casts rays (measure_batch, measure_update, measure_device, update_device, beam_status, the group
+ * forms) uses it. mcl3dl_hip_dda_trace stays on the DDA caster. */
+int mcl3dl_hip_set_beam_raycast(mcl3dl_hip_ctx* ctx, int mode);
+/* Replaces: reading LidarMeasurementModelBeamParameters::use_raycast_using_dda_ back (include/mcl_3dl/parameters.h:109):
+ * *mode = 0 (DDA) or 1 (kd-tree). */
+int mcl3dl_hip_get_beam_raycast(mcl3dl_hip_ctx* ctx, int* mode);
 
 /* ---- host entry points (synchronous) ------------------------------------------------------------- */
 /* Replaces: the N_p calls of LidarMeasurementModelLikelihood::measure
@@ -406,6 +420,9 @@ int mcl3dl_hip_group_set_beam_params(mcl3dl_hip_group* g, float map_grid_x, floa
                                      float dda_grid_size, float ray_angle_half, float hit_range,
                                      float beam_likelihood_min, uint32_t num_points, float ang_total_ref,
                                      uint32_t filter_label_max, int add_penalty_short_only_mode);
+/* Replaces: beam/use_raycast_using_dda (src/parameters.cpp:289) for every rank's model at once: mcl3dl_hip_set_beam_raycast
+ * on every context of the group. */
+int mcl3dl_hip_group_set_beam_raycast(mcl3dl_hip_group* g, int mode);
 int mcl3dl_hip_group_set_option(mcl3dl_hip_group* g, const char* name, double value);
 /* Sharded forms of mcl3dl_hip_upload_poses / _measure_batch / _measure_update: same arguments, same results; host arrays
  * are scattered to / gathered from the shards. measure_batch needs no collective; measure_update runs the one all-reduce. */

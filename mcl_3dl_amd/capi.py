@@ -30,6 +30,8 @@ SIGNATURES = {
     "mcl3dl_hip_set_map": (_i, [_p, _p, _p, _sz, _u64, _p]),
     "mcl3dl_hip_set_likelihood_params": (_i, [_p, _f, _f, _f]),
     "mcl3dl_hip_set_beam_params": (_i, [_p, _f, _f, _f, _f, _f, _f, _f, _u32, _f, _u32, _i]),
+    "mcl3dl_hip_set_beam_raycast": (_i, [_p, _i]),
+    "mcl3dl_hip_get_beam_raycast": (_i, [_p, C.POINTER(_i)]),
     "mcl3dl_hip_upload_poses": (_i, [_p, _p, _sz]),
     "mcl3dl_hip_scan_order": (_i, [_p, _p, _sz]),
     "mcl3dl_hip_scan_order_host": (_i, [_p, _sz, _p]),
@@ -91,6 +93,7 @@ SIGNATURES = {
     "mcl3dl_hip_group_set_map": (_i, [_p, _p, _p, _sz, _u64, _p]),
     "mcl3dl_hip_group_set_likelihood_params": (_i, [_p, _f, _f, _f]),
     "mcl3dl_hip_group_set_beam_params": (_i, [_p, _f, _f, _f, _f, _f, _f, _f, _u32, _f, _u32, _i]),
+    "mcl3dl_hip_group_set_beam_raycast": (_i, [_p, _i]),
     "mcl3dl_hip_group_set_option": (_i, [_p, C.c_char_p, _d]),
     "mcl3dl_hip_group_upload_poses": (_i, [_p, _p, _sz]),
     "mcl3dl_hip_group_measure_batch": (_i, [_p, _p, _sz, _p, _sz, _p, _p, _sz, _p, _sz, _p, _p, _p]),
@@ -260,6 +263,18 @@ class Group:
             self.h, map_grid[0], map_grid[1], map_grid[2], dda_grid_size, ray_angle_half, hit_range,
             beam_likelihood_min, int(num_points), ang_total_ref, int(filter_label_max),
             int(bool(add_penalty_short_only_mode))))
+
+    def set_beam_raycast(self, mode):
+        """0 = RaycastUsingDDA (default), 1 = RaycastUsingKDTree (the reference's default), on every rank."""
+        self._check(self.lib.mcl3dl_hip_group_set_beam_raycast(self.h, int(mode)))
+
+    def get_beam_raycast(self):
+        """The caster of rank 0 (set_beam_raycast gives every rank the same)."""
+        mode = C.c_int(-1)
+        ctx = self.lib.mcl3dl_hip_group_context(self.h, 0)
+        if self.lib.mcl3dl_hip_get_beam_raycast(ctx, C.byref(mode)) != 0:
+            raise EngineError("mcl3dl_hip_get_beam_raycast failed on the group's rank 0")
+        return int(mode.value)
 
     def set_option(self, name, value):
         self._check(self.lib.mcl3dl_hip_group_set_option(self.h, name.encode(), float(value)))
@@ -492,6 +507,15 @@ class Engine:
             self.h, map_grid[0], map_grid[1], map_grid[2], dda_grid_size, ray_angle_half, hit_range,
             beam_likelihood_min, int(num_points), ang_total_ref, int(filter_label_max),
             int(bool(add_penalty_short_only_mode))))
+
+    def set_beam_raycast(self, mode):
+        """0 = RaycastUsingDDA (default, the fast path), 1 = RaycastUsingKDTree (the reference's default caster)."""
+        self._check(self.lib.mcl3dl_hip_set_beam_raycast(self.h, int(mode)))
+
+    def get_beam_raycast(self):
+        mode = C.c_int(-1)
+        self._check(self.lib.mcl3dl_hip_get_beam_raycast(self.h, C.byref(mode)))
+        return int(mode.value)
 
     # ---- host entry points -------------------------------------------------------------------------------------
     @staticmethod

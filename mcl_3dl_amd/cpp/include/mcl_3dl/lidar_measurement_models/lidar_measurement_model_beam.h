@@ -1,6 +1,7 @@
 // Drop-in for the reference header of the same path: class mcl_3dl::LidarMeasurementModelBeam with the reference's public
 // surface — enum BeamStatus, getBeamStatus, getSinTotalRef, getFilterLabelMax are what the node's debug markers use
-// (src/mcl_3dl.cpp:471-478). The raycaster is the DDA one, resident on the GPU; use_raycast_using_dda_ = false is refused.
+// (src/mcl_3dl.cpp:471-478). Both raycasters are resident on the GPU: use_raycast_using_dda_ selects RaycastUsingDDA (true; the
+// fast one) or RaycastUsingKDTree (false, the reference's default) through mcl3dl_hip_set_beam_raycast.
 #ifndef MCL_3DL_HIP_LIDAR_MEASUREMENT_MODEL_BEAM_H
 #define MCL_3DL_HIP_LIDAR_MEASUREMENT_MODEL_BEAM_H
 

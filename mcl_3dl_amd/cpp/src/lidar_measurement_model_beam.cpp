@@ -1,7 +1,6 @@
-// GPU-backed mcl_3dl::LidarMeasurementModelBeam (drop-in for src/lidar_measurement_model_beam.cpp, DDA raycaster).
+// GPU-backed mcl_3dl::LidarMeasurementModelBeam (drop-in for src/lidar_measurement_model_beam.cpp, either raycaster).
 #include <algorithm>
 #include <cmath>
-#include <stdexcept>
 
 #include <mcl_3dl/lidar_measurement_models/lidar_measurement_model_beam.h>
 
@@ -14,13 +13,11 @@ LidarMeasurementModelBeam::LidarMeasurementModelBeam(const std::shared_ptr<Param
 }
 
 // reference: src/lidar_measurement_model_beam.cpp:58-80. The derived constants that decide results (hit_range^2,
-// beam_likelihood_, the DDA caster) are re-derived inside the engine by mcl3dl_hip_set_beam_params with the reference's
-// expressions; only what the public getters expose is kept here.
+// beam_likelihood_, the caster's constants) are re-derived inside the engine by mcl3dl_hip_set_beam_params with the
+// reference's expressions, and the caster itself (:69-79: RaycastUsingDDA or RaycastUsingKDTree by use_raycast_using_dda_) is
+// selected there by mcl3dl_hip_set_beam_raycast; only what the public getters expose is kept here.
 void LidarMeasurementModelBeam::refreshParameters()
 {
-  if (!params_->use_raycast_using_dda_)
-    throw std::runtime_error("mcl3dl_hip: the GPU beam model implements RaycastUsingDDA only; set "
-                             "beam/use_raycast_using_dda to true");
   search_range_ = std::max({ params_->map_grid_x_, params_->map_grid_y_, params_->map_grid_z_ }) * 4;
   sin_total_ref_ = sinf(params_->ang_total_ref_);
   const std::shared_ptr<Params> params = params_;
@@ -36,6 +33,7 @@ void LidarMeasurementModelBeam::pushBeamParameters(const Params& p)
                                            p.ray_angle_half_, p.hit_range_, p.beam_likelihood_min_,
                                            static_cast<std::uint32_t>(p.num_points_default_), p.ang_total_ref_,
                                            p.filter_label_max_, p.add_penalty_short_only_mode_ ? 1 : 0));
+  e.check(mcl3dl_hip_group_set_beam_raycast(e.group(), p.use_raycast_using_dda_ ? 0 : 1));
 }
 
 void LidarMeasurementModelBeam::pushParameters() const
@@ -63,6 +61,9 @@ LidarMeasurementResult LidarMeasurementModelBeam::measure(ChunkedKdtree<PointTyp
 // fromIndex(current_index_), :219-223 — the node draws the collision marker there, src/mcl_3dl.cpp:489-491). The collided
 // voxel is the collided point's voxel: toIndex (:205-217: float difference, double division, truncation), then the
 // centre in double, rounded to float by Vec3's constructor.
+// With RaycastUsingKDTree the reference reports the marching position of the colliding step and the measured sin_angle_
+// (raycast_using_kdtree.h:104); the engine returns the status and the collided point, so result.pos_ is that point (within
+// the first search radius of the marching position) and sin_angle_ only says which side of getSinTotalRef() it fell on.
 LidarMeasurementModelBeam::BeamStatus LidarMeasurementModelBeam::getBeamStatus(ChunkedKdtree<PointType>::Ptr& kdtree,
                                                                                const Vec3& lidar_pos,
                                                                                const Vec3& scan_pos,
@@ -78,6 +79,11 @@ LidarMeasurementModelBeam::BeamStatus LidarMeasurementModelBeam::getBeamStatus(C
   if (hit >= 0)
   {
     const PointType* p = &kdtree->getInputCloud()->points[hit];
+    if (!params_->use_raycast_using_dda_)
+    {
+      result = CastResult(Vec3(p->x, p->y, p->z), true, status == 3 ? 0.0f : 1.0f, p);
+      return static_cast<BeamStatus>(status);
+    }
     const double grid = params_->dda_grid_size_;
     const float c[3] = { p->x, p->y, p->z };
     float centre[3];

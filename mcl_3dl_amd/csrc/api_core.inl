@@ -197,6 +197,9 @@ int mcl3dl_hip_set_likelihood_params(mcl3dl_hip_ctx* ctx, float match_dist_min, 
     return ctx->fail(-3, "match_dist_min must be > 0");
   if (match_dist_min != ctx->match_dist_min)
     ctx->lik_dirty = ctx->cand_dirty = ctx->lik_base_dirty = true;  // cell / voxel edges follow the search radius
+  if (ctx->lik_cell_from_beam)
+    ctx->lik_dirty = ctx->lik_base_dirty = true;  // (a cell grid laid out for the kd-tree caster alone: lik_cell_edge)
+  ctx->lik_params_set = true;
   ctx->match_dist_min = match_dist_min;
   ctx->match_dist_flat = match_dist_flat;
   ctx->match_weight = match_weight;
@@ -241,6 +244,29 @@ int mcl3dl_hip_set_beam_params(mcl3dl_hip_ctx* ctx, float map_grid_x, float map_
     ctx->dda_dirty = true;
   if (derived_changed)
     beam_refresh(ctx);
+  return 0;
+}
+
+int mcl3dl_hip_set_beam_raycast(mcl3dl_hip_ctx* ctx, int mode)
+{
+  if (!ctx)
+    return -1;
+  if (mode != 0 && mode != 1)
+    return ctx->fail(-3, "beam raycast mode must be 0 (RaycastUsingDDA) or 1 (RaycastUsingKDTree), not %d", mode);
+  if (mode == ctx->beam_raycast)
+    return 0;
+  ++ctx->generation;
+  ctx->beam_raycast = mode;  // (nothing is built or dropped here: each caster's structures are built when it first casts)
+  return 0;
+}
+
+int mcl3dl_hip_get_beam_raycast(mcl3dl_hip_ctx* ctx, int* mode)
+{
+  if (!ctx)
+    return -1;
+  if (!mode)
+    return ctx->fail(-3, "null mode");
+  *mode = ctx->beam_raycast;
   return 0;
 }
 
@@ -995,7 +1021,7 @@ int measure_update_staged(mcl3dl_hip_ctx* ctx, const float* pose, const float* e
   // one commit did — the hazard tests/test_gpu_api_fuzz.py is asked to find again)
   if (!ctx->test_late_structures)
   {
-    TRY(ensure_structures(ctx, n_s > 0, n_b > 0));
+    TRY(ensure_caster_structures(ctx, n_s > 0, n_b > 0));
     if (n_b > 0)
       TRY(ensure_pow_table(ctx, n_b));
   }
@@ -1349,7 +1375,7 @@ int mcl3dl_hip_beam_status(mcl3dl_hip_ctx* ctx, const float* begin_xyz, const fl
   if (n > 0x7fffffffu)
     return ctx->fail(-3, "too many rays");
   HIP_TRY(hipSetDevice(ctx->device));
-  TRY(ensure_structures(ctx, false, true));
+  TRY(ensure_caster_structures(ctx, false, true));
   TRY(ensure(ctx, ctx->ray_begin, sizeof(float) * 3 * n));
   TRY(ensure(ctx, ctx->ray_end, sizeof(float) * 3 * n));
   TRY(ensure(ctx, ctx->ray_status, sizeof(int) * n));
@@ -1357,9 +1383,14 @@ int mcl3dl_hip_beam_status(mcl3dl_hip_ctx* ctx, const float* begin_xyz, const fl
   TRY(h2d(ctx, ctx->ray_begin.p, begin_xyz, sizeof(float) * 3 * n));
   TRY(h2d(ctx, ctx->ray_end.p, end_xyz, sizeof(float) * 3 * n));
   const int ni = static_cast<int>(n);
-  hipLaunchKernelGGL(beam_status_kernel, dim3((ni + 63) / 64), dim3(64), 0, ctx->stream, ctx->ray_begin.as<float>(),
-                     ctx->ray_end.as<float>(), ni, ctx->dg, beam_params(ctx), ctx->ray_status.as<int>(),
-                     ctx->ray_hit.as<int>());
+  if (ctx->beam_raycast == 1)
+    hipLaunchKernelGGL(beam_kd_status_kernel, dim3((ni + 63) / 64), dim3(64), 0, ctx->stream, ctx->ray_begin.as<float>(),
+                       ctx->ray_end.as<float>(), ni, ctx->lg, kd_ray_params(ctx), beam_params(ctx), ctx->ray_status.as<int>(),
+                       ctx->ray_hit.as<int>());
+  else
+    hipLaunchKernelGGL(beam_status_kernel, dim3((ni + 63) / 64), dim3(64), 0, ctx->stream, ctx->ray_begin.as<float>(),
+                       ctx->ray_end.as<float>(), ni, ctx->dg, beam_params(ctx), ctx->ray_status.as<int>(),
+                       ctx->ray_hit.as<int>());
   HIP_TRY(hipGetLastError());
   TRY(d2h(ctx, status, ctx->ray_status.p, sizeof(int) * n));
   if (hit_index)

@@ -155,6 +155,19 @@ int mcl3dl_hip_group_set_beam_params(mcl3dl_hip_group* g, float map_grid_x, floa
   return 0;
 }
 
+int mcl3dl_hip_group_set_beam_raycast(mcl3dl_hip_group* g, int mode)
+{
+  if (!g)
+    return -1;
+  for (int r = 0; r < g->n(); ++r)
+  {
+    const int rc = mcl3dl_hip_set_beam_raycast(g->ctx[r], mode);
+    if (rc)
+      return g->fail_rank(rc, r);
+  }
+  return 0;
+}
+
 int mcl3dl_hip_group_set_option(mcl3dl_hip_group* g, const char* name, double value)
 {
   if (!g || !name)

@@ -81,6 +81,17 @@ struct mcl3dl_hip_ctx
   // derived, src/lidar_measurement_model_beam.cpp:65-67
   float hit_range_sq = 0, beam_likelihood = 0, sin_total_ref = 0;
 
+  // which raycaster the beam model casts with (mcl3dl_hip_set_beam_raycast): 0 = RaycastUsingDDA, 1 = RaycastUsingKDTree — the
+  // fixed-step march over the cell-sorted map (beam_kd_kernels.h). Read by every call that casts rays, when it casts them.
+  int beam_raycast = 0;
+  // the cell grid's edge follows match_dist_min — unless no likelihood parameters were ever set and the grid is first wanted by
+  // the kd-tree caster: then it follows that caster's first search radius (lik_cell_edge, host_map_compilers.h).
+  // lik_cell_from_beam: the grid in place was built with that edge
+  bool lik_params_set = false, lik_cell_from_beam = false;
+  // the kd-tree caster's dilated occupancy bitmap of the cell grid in place (beam_kd_kernels.h:kd_occupancy_kernel), and the reach
+  // it was dilated by; 0 = not built for this grid (the grid builders reset it)
+  DevBuf kd_occ;
+  int kd_occ_reach = 0;
   bool lik_dirty = true, dda_dirty = true, cand_dirty = true;
   DevBuf lik_pts, lik_cells;
   // the cell grid of the BASE map alone (host_grid_builders.h): after a map update the grid in use (lik_pts / lik_cells) is the

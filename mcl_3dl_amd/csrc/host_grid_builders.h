@@ -51,7 +51,7 @@ int build_lik_grid_device(mcl3dl_hip_ctx* ctx)
   const size_t n_base = (ctx->n_base && ctx->n_base <= n) ? ctx->n_base : n;
   const size_t n_upd = n - n_base;
   const long long nn = static_cast<long long>(n);
-  const float cell = ctx->match_dist_min * 1.01f;
+  const float cell = lik_cell_edge(ctx);
   if (!(cell > 0.f) || !std::isfinite(cell))
     return ctx->fail(-3, "match_dist_min must be positive and finite");
   if (n == 0 || n > 0x7fffffffu)
@@ -184,6 +184,8 @@ int build_lik_grid_device(mcl3dl_hip_ctx* ctx)
   ctx->footprint[0] = sizeof(float4) * n;
   ctx->footprint[1] = sizeof(uint32_t) * (ncell + 1);
   ctx->lik_dirty = false;
+  ctx->lik_cell_from_beam = lik_cell_is_beams(ctx);
+  ctx->kd_occ_reach = 0;  // (the kd-tree caster's bitmap is of the previous grid)
   return 0;
 }
 

@@ -10,6 +10,35 @@ int build_dda_grid(mcl3dl_hip_ctx* ctx);
 int ensure_map_dev(mcl3dl_hip_ctx* ctx);  // host_grid_builders.h: the map as a device cloud {x, y, z, label}
 int cloud_minmax(mcl3dl_hip_ctx* ctx, const float4* pts, long long n, float* host6, unsigned long long* host_cnt);  // host_cloud.h
 
+// The two search radii of RaycastUsingKDTree (raycast_using_kdtree.h:83, :94): double expressions narrowed to the float
+// parameter of ChunkedKdtree::radiusSearch.
+void kd_ray_radii(const mcl3dl_hip_ctx* ctx, float* grid_min, float* r1, float* r2)
+{
+  const float mn = std::min({ ctx->map_grid[0], ctx->map_grid[1], ctx->map_grid[2] });
+  const float mx = std::max({ ctx->map_grid[0], ctx->map_grid[1], ctx->map_grid[2] });
+  *grid_min = mn;
+  *r1 = static_cast<float>(std::sqrt(2.0) * mx / 2.0);
+  *r2 = static_cast<float>(mn * 2 + std::sqrt(2.0) * mx / 2.0);
+}
+
+// Edge of the cell grid's cubes. A context whose likelihood parameters were never set and that casts with the kd-tree caster
+// lays the grid out for that caster's first radius (one cell each way per step of a ray); everybody else for match_dist_min.
+bool lik_cell_is_beams(const mcl3dl_hip_ctx* ctx)
+{
+  return !ctx->lik_params_set && ctx->beam_raycast == 1;
+}
+
+float lik_cell_edge(const mcl3dl_hip_ctx* ctx)
+{
+  if (lik_cell_is_beams(ctx))
+  {
+    float mn, r1, r2;
+    kd_ray_radii(ctx, &mn, &r1, &r2);
+    return r1 * 1.01f;
+  }
+  return ctx->match_dist_min * 1.01f;
+}
+
 // ---- map compiler: exact-NN grid -----------------------------------------------------------------------
 // Replaces ChunkedKdtree::setInputCloud + pcl::KdTreeFLANN::setInputCloud.  The reference's chunking is a memory
 // device (20 m chunks with duplicated margins, chunked_kdtree.h:124-216) whose query result equals the global
@@ -19,7 +48,7 @@ int cloud_minmax(mcl3dl_hip_ctx* ctx, const float4* pts, long long n, float* hos
 int build_lik_grid_host(mcl3dl_hip_ctx* ctx)
 {
   const size_t n = ctx->map_xyz.size() / 3;
-  const float cell = ctx->match_dist_min * 1.01f;
+  const float cell = lik_cell_edge(ctx);
   if (!(cell > 0.f) || !std::isfinite(cell))
     return ctx->fail(-3, "match_dist_min must be positive and finite");
   const float inv = 1.0f / cell;
@@ -89,6 +118,8 @@ int build_lik_grid_host(mcl3dl_hip_ctx* ctx)
   ctx->footprint[0] = sizeof(float4) * n;
   ctx->footprint[1] = sizeof(uint32_t) * (ncell + 1);
   ctx->lik_dirty = false;
+  ctx->lik_cell_from_beam = lik_cell_is_beams(ctx);
+  ctx->kd_occ_reach = 0;  // (the kd-tree caster's bitmap is of the previous grid)
   return 0;
 }
 

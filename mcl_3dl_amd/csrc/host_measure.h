@@ -9,6 +9,14 @@ int ensure_structures(mcl3dl_hip_ctx* ctx, bool need_lik, bool need_dda, bool ne
   if (!ctx->has_map)
     return ctx->fail(-5, "no map: call mcl3dl_hip_set_map first");
   bool built = false;
+  // a cell grid laid out for the kd-tree caster's radius (lik_cell_edge) does not serve the likelihood model's 27-cell
+  // search: that model running on its default parameters counts as having set them
+  if (need_lik && ctx->lik_index == 0 && !need_cells && !ctx->lik_params_set && (ctx->lik_cell_from_beam || lik_cell_is_beams(ctx)))
+  {
+    ctx->lik_params_set = true;
+    if (ctx->lik_cell_from_beam)
+      ctx->lik_dirty = ctx->lik_base_dirty = true;
+  }
   if (need_lik && (ctx->lik_index == 0 || need_cells) && ctx->lik_dirty)
   {
     TRY(build_lik_grid(ctx));
@@ -26,6 +34,68 @@ int ensure_structures(mcl3dl_hip_ctx* ctx, bool need_lik, bool need_dda, bool ne
   }
   if (built)
     scratch_trim(ctx, 64u << 20);  // the temporaries of a whole-map build do not stay parked (map updates keep their small ones)
+  return 0;
+}
+
+// RaycastUsingKDTree's constants for the cell grid in place (ensure_caster_structures has run).
+KdRayParams kd_ray_params(const mcl3dl_hip_ctx* ctx)
+{
+  KdRayParams k;
+  float r1, r2;
+  kd_ray_radii(ctx, &k.grid_min, &r1, &r2);
+  k.hit_tolerance = ctx->hit_range;
+  k.two_grid_min = k.grid_min * 2.0;
+  // pcl::KdTreeFLANN::radiusSearch: (float)(radius * radius) with radius widened to double
+  k.r1_sq = static_cast<float>(static_cast<double>(r1) * static_cast<double>(r1));
+  k.r2_sq = static_cast<float>(static_cast<double>(r2) * static_cast<double>(r2));
+  // cells each way that hold every point within the radius: ceil(r / cell), with half a percent of a cell for the float
+  // rounding of the binning expression (the grid's own edge is 1 % over the radius it is laid out for)
+  const double cell = 1.0 / static_cast<double>(ctx->lg.inv_cell);
+  const auto reach = [&](float r) { return static_cast<int>(std::min(std::ceil(static_cast<double>(r) / cell + 0.005), 1.0e6)); };
+  k.reach1 = reach(r1);
+  k.reach2 = reach(r2);
+  k.wx = ctx->weight[0];
+  k.wy = ctx->weight[1];
+  k.wz = ctx->weight[2];
+  k.has_weight = ctx->has_weight ? 1 : 0;
+  k.map = ctx->map_dev.as<float4>();
+  k.occ = ctx->kd_occ.as<uint32_t>();
+  return k;
+}
+
+// What the beam model's caster needs before it casts (need_beam: there are rays): the DDA grid for RaycastUsingDDA; for
+// RaycastUsingKDTree the cell-sorted map — whatever the likelihood model's index is, and also when that model never runs —
+// and the map itself on the device (labels, unscaled points). A context on the kd-tree caster never builds the DDA grid here.
+int ensure_caster_structures(mcl3dl_hip_ctx* ctx, bool need_lik, bool need_beam, bool need_cells = false)
+{
+  if (ctx->beam_raycast != 1)
+    return ensure_structures(ctx, need_lik, need_beam, need_cells);
+  TRY(ensure_structures(ctx, need_lik, false, need_cells));
+  if (need_beam)
+  {
+    if (ctx->lik_dirty)
+    {
+      TRY(build_lik_grid(ctx));
+      scratch_trim(ctx, 64u << 20);
+    }
+    TRY(ensure_map_dev(ctx));
+    // the dilated occupancy bitmap of this grid, for this reach of the first search (a map update's merge, a new cell edge,
+    // other map_grid sizes: built again — one pass over the run delimiters)
+    const KdRayParams k = kd_ray_params(ctx);
+    if (ctx->kd_occ_reach != k.reach1)
+    {
+      const unsigned long long n_cells = static_cast<unsigned long long>(ctx->lg.nx) * ctx->lg.ny * ctx->lg.nz;
+      const unsigned long long blocks = (n_cells + 255) / 256;
+      if (blocks > 0x7fffffffull)
+        return ctx->fail(-4, "the cell grid has too many cells for the kd-tree caster's occupancy bitmap");
+      TRY(ensure(ctx, ctx->kd_occ, sizeof(unsigned long long) * ((n_cells + 63) / 64)));
+      hipLaunchKernelGGL(kd_occupancy_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, ctx->stream, ctx->lg, k.reach1,
+                         n_cells, ctx->kd_occ.as<unsigned long long>());
+      HIP_TRY(hipGetLastError());
+      ctx->kd_occ_reach = k.reach1;
+      ++ctx->generation;
+    }
+  }
   return 0;
 }
 
@@ -443,7 +513,12 @@ int launch_measure(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, float* 
     return ctx->fail(-3, "too many particles");
   const bool want_lik = (d_lik || d_ratio || stats);
   const bool want_beam = (d_beam || stats);
-  TRY(ensure_structures(ctx, want_lik && ctx->n_s > 0, want_beam && ctx->n_b > 0, stats));
+  // (the ray statistics are the DDA walk's: that launch stays on the DDA caster)
+  const bool kd = ctx->beam_raycast == 1 && !stats;
+  if (kd)
+    TRY(ensure_caster_structures(ctx, want_lik && ctx->n_s > 0, want_beam && ctx->n_b > 0, stats));
+  else
+    TRY(ensure_structures(ctx, want_lik && ctx->n_s > 0, want_beam && ctx->n_b > 0, stats));
   const int np = static_cast<int>(n_p);
   bool beam_forked = false, beam_ones_by_finalize = false;
   bool merged = false;  // the beam kernel's work-groups ride in the tiled likelihood kernel's launch (lik_beam_kernel)
@@ -501,7 +576,9 @@ int launch_measure(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, float* 
         if (ctx->penalty.cap != cap0)
           ctx->penalty_clean_n = 0;  // (a new allocation: nothing is known about its content)
       }
-      const bool beam_prepared = !stats && ctx->beam_prepare && n_rays >= ctx->beam_prepare_min_rays &&
+      // (the prepared origins and the launches of both models below are the DDA walk's: the kd-tree caster runs as a launch of
+      // its own, behind or — from overlap_min_rays rays — beside the likelihood kernel on the second stream)
+      const bool beam_prepared = !kd && !stats && ctx->beam_prepare && n_rays >= ctx->beam_prepare_min_rays &&
                                  static_cast<long long>(n_p) * static_cast<long long>(ctx->n_o) < 0x7fffffffLL;
       if (beam_prepared)
         TRY(ensure(ctx, ctx->beam_origin, sizeof(BeamOrigin) * n_p * ctx->n_o));
@@ -515,11 +592,11 @@ int launch_measure(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, float* 
       // Measured, C3: 0.3446 (two streams) -> 0.3313 ms; 4096 rays per particle: 1.0855 -> 1.0070 (profiles/r06s_lik_beam_one_launch.txt).
       // (the per-particle likelihood kernel's 256-thread form takes the beam kernel's work-groups along the same way:
       // lik_particle_beam_kernel)
-      merged_particle = ctx->overlap_models && !stats && want_lik && ctx->n_s > 0 && !plan.tiled && !plan.small && !plan.chain &&
+      merged_particle = !kd && ctx->overlap_models && !stats && want_lik && ctx->n_s > 0 && !plan.tiled && !plan.small && !plan.chain &&
                         ctx->lik_index == 2 && !(np <= ctx->lik_wide_max_particles && ctx->n_s > 512) && blocks >= 16 &&
                         blocks < 0x0fffffffLL && ctx->dg.ov_n == 0;
       // (the in-kernel chain's single-tile form, strict_order 3, rides the same way: a consumer's producer keeps its lower block index)
-      merged_chain = ctx->overlap_models && !stats && want_lik && ctx->n_s > 0 && plan.tiled && plan.chain && plan.chain_ppl != 4 &&
+      merged_chain = !kd && ctx->overlap_models && !stats && want_lik && ctx->n_s > 0 && plan.tiled && plan.chain && plan.chain_ppl != 4 &&
                      plan.group_size <= 16 && ctx->lik_coop && ctx->lik_index == 2 && ctx->match_dist_min > 1e-5f && blocks >= 64 &&
                      blocks < 0x3fffffffLL && plan.blocks < 0x3fffffffLL && ctx->dg.ov_n == 0;
       // (in front of the caller-order replay: two streams only where they would be used — from overlap_min_rays rays — AND the replay
@@ -528,7 +605,7 @@ int launch_measure(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, float* 
       // profiles/r06s_lik_beam_one_launch.txt)
       const bool replay_is_long = plan.strict_terms != nullptr && n_rays >= ctx->overlap_min_rays &&
                                   strict_terms_bytes(n_p, static_cast<int>(ctx->n_s), plan.group_size) >= (static_cast<size_t>(512) << 20);
-      merged = ctx->overlap_models && !stats && want_lik && ctx->n_s > 0 && plan.tiled && !plan.chain && !plan.chunk &&
+      merged = !kd && ctx->overlap_models && !stats && want_lik && ctx->n_s > 0 && plan.tiled && !plan.chain && !plan.chunk &&
                !replay_is_long && plan.group_size <= 16 && ctx->lik_coop && ctx->lik_index == 2 && ctx->match_dist_min > 1e-5f &&
                blocks >= 64 && blocks < 0x3fffffffLL && plan.blocks < 0x3fffffffLL &&
                ctx->dg.ov_n == 0;  // (the beam kernel's map-update-overlay form needs 66 VGPRs: it would spill inside the 64 of the merged launch)
@@ -586,12 +663,21 @@ int launch_measure(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, float* 
         }
         else
         {
+        if (kd)
+        {
+          hipLaunchKernelGGL(beam_kd_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, bs, d_pose,
+                             ctx->scan_beam.as<float4>(), static_cast<int>(ctx->n_b), ctx->origins.as<float4>(), n_rays, ctx->lg,
+                             kd_ray_params(ctx), bp, ctx->penalty.as<unsigned>());
+        }
+        else
+        {
         // (a map update rides on the DDA grid as an overlay: the kernel that looks it up is chosen only then)
         const auto kernel = ctx->dg.ov_n > 0 ? beam_kernel<false, true> : beam_kernel<false, false>;
         hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, bs, d_pose,
                            ctx->scan_beam.as<float4>(), static_cast<int>(ctx->n_b), ctx->origins.as<float4>(), n_rays,
                            ctx->dg, bp, ctx->penalty.as<unsigned>(), static_cast<RayStats*>(nullptr), prepared,
                            static_cast<int>(ctx->n_o));
+        }
         if (tail && tail->want_beam)
           tail->beam_pending = true;
         else
@@ -1099,6 +1185,8 @@ int launch_update_small(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, fl
     return 0;
   if (n_p > static_cast<size_t>(ctx->update_small_max))
     return 0;
+  if (ctx->beam_raycast == 1 && ctx->n_b > 0)
+    return 0;  // the one-launch kernel casts with the DDA walk: the kd-tree caster runs through the separate kernels
   const int ns = static_cast<int>(ctx->n_s);
   if (ns > 0)
   {

@@ -4,6 +4,8 @@
 //                         candidate-voxel index (map_compiler.h) or the cell-sorted map; strict-order sums; radius search
 //   likelihood_chain_multi.h  strict_order = 3 for few particles on long scans: several tiles per work-group, a quarter of the hand-offs
 //   beam_kernels.h        beam model: one lane per ray, DDA walk through 4x4x4 occupancy bricks, point tests, penalty count
+//   beam_kd_kernels.h     beam model with the reference's default caster (RaycastUsingKDTree): fixed-step march, exact nearest-
+//                         within-radius over the cell-sorted map at every step
 //   pf_kernels.h          pf::measure (weights, deterministic fp64 reductions, normalisation, entropy) and the "next" rows
 //                         (expectation / max / covariance, resampling)
 //   motion_kernels.h      between two scans, on resident particles: motion prediction, odometry-error reset, pf::noise, the
@@ -27,6 +29,7 @@
 #include "likelihood_kernels.h"
 #include "likelihood_chain_multi.h"
 #include "beam_kernels.h"
+#include "beam_kd_kernels.h"
 #include "motion_kernels.h"
 #include "pf_kernels.h"
 #include "update_kernels.h"
