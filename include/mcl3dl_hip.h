@@ -321,7 +321,9 @@ int mcl3dl_hip_update_device(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_
  * inside a leaf unspecified; PCL is not vendored by the reference: parity at this boundary is against the restatement
  * in oracle/). Non-finite points are dropped by the filter. Intensity is not carried.
  * download: which = 0 pc_local_full, 1 / 2 clipped likelihood / beam cloud, 3 / 4 sampled clouds in the caller's index
- * order (xyz NULL: only *n). */
+ * order (xyz NULL: only *n); 5 / 6 the likelihood / beam scan AS INSTALLED, in the engine's order (n_s points, label 0 /
+ * n_b points, label = origin id) — available whenever a scan is installed, by mcl3dl_hip_upload_scan (ordered on the host
+ * or on the device), _scan_finish or a host-buffer update call; 0..4 need a mcl3dl_hip_scan_begin. */
 int mcl3dl_hip_scan_begin(mcl3dl_hip_ctx* ctx, const float* xyz /*n*3*/, const uint32_t* label /*n or NULL*/, size_t n,
                           const float* leaf3, const float* clip_lik4, const float* clip_beam4, size_t* n_full,
                           size_t* n_lik_clipped, size_t* n_beam_clipped);
@@ -351,7 +353,7 @@ int mcl3dl_hip_scan_finish(mcl3dl_hip_ctx* ctx, const uint32_t* idx_lik /*n_s*/,
 int mcl3dl_hip_scan_download(mcl3dl_hip_ctx* ctx, int which, float* xyz, uint32_t* label, size_t capacity, size_t* n);
 /* Introspection: the stable radix sort the cloud path runs on the device (VoxelGrid leaf order, scan ordering; replaces the
  * std::sort of pcl::VoxelGrid and nothing else of the reference), exposed so that it can be checked on its own:
- * (keys, vals) sorted ascending by key bits [0, end_bit), equal keys in input order. One launch up to 16 384 pairs. */
+ * (keys, vals) sorted ascending by key bits [0, end_bit), equal keys in input order. One launch up to 2048 pairs. */
 int mcl3dl_hip_sort_pairs(mcl3dl_hip_ctx* ctx, const uint32_t* keys, const uint32_t* vals /*NULL: 0..n-1*/, size_t n,
                           int end_bit, uint32_t* out_keys, uint32_t* out_vals);
 

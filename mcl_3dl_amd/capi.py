@@ -841,6 +841,9 @@ class Engine:
         return ok, ov
 
     def scan_download(self, which):
+        """(xyz, label) of a cloud the scan path holds on the device: which = 0 pc_local_full, 1 / 2 the clipped likelihood /
+        beam cloud, 3 / 4 the sampled clouds in the caller's index order (all after scan_begin); 5 / 6 the likelihood / beam
+        scan as installed, in the engine's order (label = 0 / the origin id), after upload_scan, scan_finish or an update."""
         n = C.c_size_t(0)
         self._check(self.lib.mcl3dl_hip_scan_download(self.h, which, None, None, 0, C.byref(n)))
         xyz = np.zeros((n.value, 3), np.float32)

@@ -118,7 +118,14 @@ int mcl3dl_hip_scan_download(mcl3dl_hip_ctx* ctx, int which, float* xyz, uint32_
 {
   if (!ctx)
     return -1;
-  if (!ctx->sp_ready)
+  // 5 / 6: the scans as installed, by whichever route (upload_scan ordered on the host or on the device, scan_finish, an
+  // update call); 0..4: the stages of mcl3dl_hip_scan_begin / _finish
+  if (which < 0 || which > 6)
+    return ctx->fail(-3, "which must be 0..6");
+  const bool installed = which >= 5;
+  if (installed && !ctx->has_scan)
+    return ctx->fail(-5, "no scan installed");
+  if (!installed && !ctx->sp_ready)
     return ctx->fail(-5, "no prepared scan");
   HIP_TRY(hipSetDevice(ctx->device));
   const float4* src = nullptr;
@@ -130,7 +137,8 @@ int mcl3dl_hip_scan_download(mcl3dl_hip_ctx* ctx, int which, float* xyz, uint32_
     case 2: src = ctx->sp_clip[1].as<float4>(); cnt = ctx->sp_n_clip[1]; break;
     case 3: src = ctx->sp_samp[0].as<float4>(); cnt = ctx->sp_n_samp[0]; break;
     case 4: src = ctx->sp_samp[1].as<float4>(); cnt = ctx->sp_n_samp[1]; break;
-    default: return ctx->fail(-3, "which must be 0..4");
+    case 5: src = ctx->scan_lik.as<float4>(); cnt = ctx->n_s; break;
+    default: src = ctx->scan_beam.as<float4>(); cnt = ctx->n_b; break;
   }
   if (n)
     *n = cnt;

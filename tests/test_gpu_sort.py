@@ -2,7 +2,9 @@
 — one launch of one work-group (<= 2048 pairs), one launch per pass over n / 1024 or n / 4096 work-groups (<= 524 288),
 rocprim beyond — against numpy's
 stable argsort. The sort stands where pcl::VoxelGrid calls std::sort (src/mcl_3dl.cpp:363-367) and where
-mcl3dl_hip_upload_scan orders the scans; its users are compared with the reference in test_gpu_scan_prep.py / test_gpu_map_path.py."""
+mcl3dl_hip_upload_scan orders the scans; its users are compared with the reference in test_gpu_scan_prep.py / test_gpu_map_path.py,
+and at every size class of the instances they really run (keys made inside the sort, points written by its last pass) in
+test_gpu_cloud_edges.py."""
 import numpy as np
 import pytest
 
