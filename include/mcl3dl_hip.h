@@ -556,6 +556,40 @@ int mcl3dl_hip_global_localization_seed_device(mcl3dl_hip_ctx* ctx, int div_yaw,
                                                size_t count, float* d_state13, float* d_pose7, float* d_weight);
 int mcl3dl_hip_group_global_localization(mcl3dl_hip_group* g, double grid, int div_yaw, const float* imu_quat4,
                                          size_t max_particles /*0 = no cap*/, size_t* n_points, size_t* n_particles);
+/* ---- normal-weighted scan sampling: point normals and sampling weights on the device -----------------------------------------
+ * The reference's second sampler, PointCloudSamplerWithNormal (point_cloud_sampler_with_normal.h; the node's
+ * use_random_sampler_with_normal), up to its first random draw:
+ *   _direction       pure host function, no context: setParticleStatistics (:75-89), the max_weight ladder (:110-127) and
+ *                    fpc_local (:128-129). pos_cov(i, j) = |cov36[6 i + j]| for i, j < 3 as doubles (lower triangle read, as Eigen's
+ *                    SelfAdjointEigenSolver reads it), symmetric eigen-decomposition in double, eigenvalues ascending,
+ *                    ratio = sqrt(l2 / l1), the three-way branch as written there (a NaN ratio fails both comparisons),
+ *                    fpc_global = the eigenvector of l2 narrowed to float (its sign is arbitrary, the weights use |.|),
+ *                    fpc_local = rot.inv() * fpc_global in the reference's float Quat arithmetic. -3 for a NULL mean7 / cov36 /
+ *                    out_fpc_local3 / out_max_weight or a non-finite input.
+ *   _normal_weights  :130-158 on a cloud mcl3dl_hip_scan_begin left on the device (which = 0 pc_local_full, 1 / 2 the clipped
+ *                    likelihood / beam cloud), in the cloud's order. pcl::NormalEstimation is not pinned by the reference, so
+ *                    the normal is defined here: neighbours of point i = every j, i included, with
+ *                    d2 = ((dx dx) + dy dy) + dz dz < (float)(r r) in float, plain metric (mcl3dl_hip_radius_search's expression; a
+ *                    non-finite point is nobody's neighbour); fewer than 3: normal NaN, weight 1; else moments in double about
+ *                    the query, normal = unit eigenvector of the smallest eigenvalue of the covariance (fp64 cyclic Jacobi),
+ *                    c = min(1, |n . fpc_local|), weight = 1 + (max_weight - 1) ((pi/2 - acos c) / (pi/2)), all in double.
+ *                    out_cumulative[i] = weight[i] + out_cumulative[i - 1]: the reference's sequential double recurrence, run on
+ *                    the host over the downloaded weights. out_normal_xyz: the normals narrowed to float, sign arbitrary.
+ *                    capacity in points. *n = points of the cloud, *n_without_normal = points with fewer than 3 neighbours.
+ * The caller runs the draw (:159-177: uniform_real_distribution over [0, out_cumulative[n - 1]), lower_bound, unordered_set) with
+ * its own std::default_random_engine and hands the indices to mcl3dl_hip_scan_finish; when the cloud has no more points than
+ * asked for (:104-108) no weights are needed at all. The prepared clouds, the installed scans, the map's indices and a current
+ * global-localisation point set are left as they are.
+ * Errors of _normal_weights: -5 without a preceding mcl3dl_hip_scan_begin; -3 for which outside 0..2, a normal_search_range
+ * that is not positive and finite, non-finite fpc_local3 / max_weight, capacity < *n with an output array given (*n is still
+ * set), or a cloud whose cell grid (edge 1.01 normal_search_range) would need more than 2^28 cells — the message names the count.
+ * An empty cloud returns 0 with nothing written. */
+int mcl3dl_hip_sampler_normal_direction(const float* mean7 /*px,py,pz,qx,qy,qz,qw*/, const float* cov36 /*row-major 6x6*/,
+                                        double perform_weighting_ratio, double max_weight_ratio, double max_weight,
+                                        float* out_fpc_local3, double* out_max_weight, double* out_eigen_value_ratio /*or NULL*/);
+int mcl3dl_hip_scan_normal_weights(mcl3dl_hip_ctx* ctx, int which, double normal_search_range, const float* fpc_local3,
+                                   double max_weight, double* out_cumulative /*n or NULL*/, float* out_normal_xyz /*n*3 or NULL*/,
+                                   size_t capacity, size_t* n, size_t* n_without_normal /*or NULL*/);
 /* How many updates went through each kind of collective so far. */
 int mcl3dl_hip_group_collective_stats(const mcl3dl_hip_group* g, uint64_t* rccl_all_reduces, uint64_t* host_combines);
 

@@ -123,6 +123,8 @@ SIGNATURES = {
     "mcl3dl_hip_global_localization_points": (_i, [_p, _d, _p, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
     "mcl3dl_hip_global_localization_seed_device": (_i, [_p, _i, _p, _sz, _sz, _p, _p, _p]),
     "mcl3dl_hip_group_global_localization": (_i, [_p, _d, _i, _p, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
+    "mcl3dl_hip_sampler_normal_direction": (_i, [_p, _p, _d, _d, _d, _p, C.POINTER(_d), C.POINTER(_d)]),
+    "mcl3dl_hip_scan_normal_weights": (_i, [_p, _i, _d, _p, _d, _p, _p, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
     "mcl3dl_hip_get_option": (_i, [_p, C.c_char_p, C.POINTER(_d)]),
     "mcl3dl_hip_index_stats": (_i, [_p, _p]),
 }
@@ -215,6 +217,23 @@ def global_localization_rotations(div_yaw, imu_quat=None):
     if (q is not None and q.size != 4) or lib.mcl3dl_hip_global_localization_rotations(int(div_yaw), _ptr(q), _ptr(out)) != 0:
         raise ValueError("global_localization_rotations: div_yaw must be >= 1 and imu_quat four finite floats")
     return out
+
+
+def sampler_normal_direction(mean, cov, perform_weighting_ratio=2.0, max_weight_ratio=5.0, max_weight=5.0):
+    """PointCloudSamplerWithNormal's setParticleStatistics, max_weight ladder and fpc_local (no GPU needed): mean = the seven
+    floats {px, py, pz, qx, qy, qz, qw} of the particles' mean, cov = their 6x6 covariance. Returns (fpc_local float32[3],
+    max_weight, eigen_value_ratio); the defaults are the reference's parameter defaults."""
+    lib = load_library()
+    m = _np_f32(mean).reshape(-1)
+    c = _np_f32(cov).reshape(-1)
+    if m.size != 7 or c.size != 36:
+        raise ValueError("sampler_normal_direction: mean must hold 7 floats and cov 36")
+    fpc = np.zeros(3, np.float32)
+    mw, ratio = C.c_double(0.0), C.c_double(0.0)
+    if lib.mcl3dl_hip_sampler_normal_direction(_ptr(m), _ptr(c), float(perform_weighting_ratio), float(max_weight_ratio),
+                                               float(max_weight), _ptr(fpc), C.byref(mw), C.byref(ratio)) != 0:
+        raise ValueError("sampler_normal_direction: the mean, the covariance and the parameters must be finite")
+    return fpc, float(mw.value), float(ratio.value)
 
 
 class Group:
@@ -851,6 +870,25 @@ class Engine:
         if n.value:
             self._check(self.lib.mcl3dl_hip_scan_download(self.h, which, _ptr(xyz), _ptr(lab), n.value, C.byref(n)))
         return xyz, lab
+
+    def scan_normal_weights(self, which, normal_search_range, fpc_local, max_weight, normals=False):
+        """PointCloudSamplerWithNormal::sample up to its first draw on a cloud scan_begin left on the device (which = 0
+        pc_local_full, 1 / 2 the clipped likelihood / beam cloud): returns (cumulative float64[n], normals float32[n, 3] or
+        None, n_without_normal). Draw from [0, cumulative[-1]) with np.searchsorted(cumulative, u, "left") — the reference's
+        lower_bound — and hand the indices to scan_finish."""
+        f = _np_f32(fpc_local).reshape(-1)
+        if f.size != 3:
+            raise ValueError("scan_normal_weights: fpc_local must hold 3 floats")
+        n, nw = C.c_size_t(0), C.c_size_t(0)
+        args = (self.h, int(which), float(normal_search_range), _ptr(f), float(max_weight))
+        if 0 <= int(which) <= 2:  # the size of the cloud, without running anything (a bad `which` is refused below)
+            self._check(self.lib.mcl3dl_hip_scan_download(self.h, int(which), None, None, 0, C.byref(n)))
+        else:
+            self._check(self.lib.mcl3dl_hip_scan_normal_weights(*args, None, None, 0, C.byref(n), C.byref(nw)))
+        cum = np.zeros(n.value, np.float64)
+        nrm = np.zeros((n.value, 3), np.float32) if normals else None
+        self._check(self.lib.mcl3dl_hip_scan_normal_weights(*args, _ptr(cum), _ptr(nrm), n.value, C.byref(n), C.byref(nw)))
+        return cum, nrm, int(nw.value)
 
     def set_map_downsampled(self, xyz, label=None, leaf=(0.1, 0.1, 0.1), stamp=1, dist_weight=(1.0, 1.0, 1.0)):
         pts = _np_f32(xyz, 3)

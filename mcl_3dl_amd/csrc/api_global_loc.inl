@@ -8,11 +8,10 @@
 //
 // The centroid search does not go through the context's map index (that one covers the map, not the centroid cloud, and
 // must come out of this untouched): the centroids get a cell grid of their own, cell edge 1.01 x radius in the dist_weight
-// metric, built with the kernels that build the map's cell grid (grid_kernels.h) into buffers of this file's own.
+// metric, built by host_grid_builders.h:build_transient_cell_grid (the kernels that build the map's cell grid, grid_kernels.h) into
+// buffers of this file's own.
 namespace
 {
-constexpr size_t GL_MAX_CELLS = 1u << 28;  // 1 GiB of run delimiters
-
 // Quat(Vec3(0, 0, yaw)) — setRPY, include/mcl_3dl/quat.h:202-215, every product kept (they decide the signs of the zeros)
 Quat gl_quat_from_yaw(float yaw)
 {
@@ -42,69 +41,8 @@ bool gl_points_current(const mcl3dl_hip_ctx* ctx)
 // cell grid over the n_c centroids in ctx->gl_centroids, rescaled by the dist_weight: ctx->gl_sorted / ctx->gl_cells
 int gl_build_centroid_grid(mcl3dl_hip_ctx* ctx, size_t n_c, float radius, LikGrid* out, int* reach)
 {
-  const long long nc = static_cast<long long>(n_c);
-  TempBuf sp;
-  TRY(scratch_alloc(ctx, sp, sizeof(float4) * n_c));
-  hipLaunchKernelGGL(grid_rescale_kernel, dim3(blocks_for(nc)), dim3(256), 0, ctx->stream, ctx->gl_centroids.as<float4>(), nc,
-                     ctx->weight[0], ctx->weight[1], ctx->weight[2], ctx->has_weight ? 1 : 0, static_cast<float4*>(sp.p));
-  float mm[6];
-  unsigned long long n_finite = 0;
-  TRY(cloud_minmax(ctx, static_cast<const float4*>(sp.p), nc, mm, &n_finite));
-  if (n_finite != n_c)
-    return ctx->fail(-3, "%llu rescaled centroid(s) are not finite (dist_weight %g %g %g)",
-                     static_cast<unsigned long long>(n_c) - n_finite, ctx->weight[0], ctx->weight[1], ctx->weight[2]);
-  const float cell = radius * 1.01f;
-  const float inv = 1.0f / cell;
-  if (!(cell > 0.f) || !std::isfinite(cell) || !std::isfinite(inv))
-    return ctx->fail(-3, "global localisation grid %g cannot be a cell edge", radius);
-  float o[3];
-  int dim[3];
-  double total = 1;
-  for (int a = 0; a < 3; ++a)
-  {
-    o[a] = mm[a] - 2.0f * cell;
-    const double d = std::floor((static_cast<double>(mm[3 + a]) - o[a]) * inv) + 3;
-    if (!(d < 2.0e9))
-      return ctx->fail(-3, "the centroid cloud spans %.3g cells of %.3g along axis %d (dist_weight %g %g %g)", d, cell, a,
-                       ctx->weight[0], ctx->weight[1], ctx->weight[2]);
-    dim[a] = static_cast<int>(floorf((mm[3 + a] - o[a]) * inv)) + 3;
-    total *= dim[a];
-  }
-  if (total > static_cast<double>(GL_MAX_CELLS))
-    return ctx->fail(-3, "the centroid index would need %.3g cells of edge %.3g (%d x %d x %d with dist_weight %g %g %g); "
-                         "at most %zu are supported", total, cell, dim[0], dim[1], dim[2], ctx->weight[0], ctx->weight[1],
-                     ctx->weight[2], GL_MAX_CELLS);
-  const size_t ncell = static_cast<size_t>(dim[0]) * dim[1] * dim[2];
-  TRY(ensure(ctx, ctx->gl_sorted, sizeof(float4) * n_c));
-  TRY(ensure(ctx, ctx->gl_cells, sizeof(uint32_t) * (ncell + 1)));
-  for (int k = 0; k < 2; ++k)
-  {
-    TRY(ensure(ctx, ctx->cl_key[k], sizeof(uint32_t) * (n_c + 1)));
-    TRY(ensure(ctx, ctx->cl_val[k], sizeof(uint32_t) * (n_c + 1)));
-  }
-  HIP_TRY(hipMemsetAsync(ctx->gl_cells.p, 0, sizeof(uint32_t) * (ncell + 1), ctx->stream));
-  const CellGeom geom{ o[0], o[1], o[2], inv, dim[0], dim[1], dim[2] };
-  hipLaunchKernelGGL(lik_cell_key_kernel, dim3(blocks_for(nc)), dim3(256), 0, ctx->stream, static_cast<const float4*>(sp.p), nc,
-                     geom, ctx->cl_key[0].as<uint32_t>(), ctx->cl_val[0].as<uint32_t>(), ctx->gl_cells.as<uint32_t>());
-  TRY(sort_pairs(ctx, nc, sort_bits(ncell)));
-  hipLaunchKernelGGL(grid_gather_kernel, dim3(blocks_for(nc)), dim3(256), 0, ctx->stream, static_cast<const float4*>(sp.p),
-                     ctx->cl_val[1].as<uint32_t>(), nc, ctx->gl_sorted.as<float4>());
-  HIP_TRY(hipGetLastError());
-  TRY(device_exclusive_scan(ctx, ctx->gl_cells.as<uint32_t>(), static_cast<long long>(ncell) + 1));
-  out->cell_start = ctx->gl_cells.as<uint32_t>();
-  out->pts = ctx->gl_sorted.as<float4>();
-  out->ox = o[0];
-  out->oy = o[1];
-  out->oz = o[2];
-  out->inv_cell = inv;
-  out->nx = dim[0];
-  out->ny = dim[1];
-  out->nz = dim[2];
-  // A neighbour is within `radius` of the query along every axis, i.e. within 1 / 1.01 = 0.9901 cells; the two float cell
-  // coordinates floorf((s - o) * inv) are each off by at most 2^-23 of their magnitude: with up to 16 384 cells per axis that is
-  // 0.004 cells together, so the neighbour's cell is the query's or next to it. Longer axes get one more cell each way.
-  *reach = std::max(dim[0], std::max(dim[1], dim[2])) <= 16384 ? 1 : 2;
-  return 0;
+  return build_transient_cell_grid(ctx, ctx->gl_centroids.as<float4>(), n_c, ctx->has_weight ? ctx->weight : nullptr, radius, true,
+                                   "centroid", ctx->gl_sorted, ctx->gl_cells, out, reach, nullptr);
 }
 }  // namespace
 

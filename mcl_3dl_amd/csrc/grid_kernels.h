@@ -81,6 +81,22 @@ __device__ inline uint32_t lik_cell_of(const float4 p, const CellGeom& g)
   return static_cast<uint32_t>((static_cast<size_t>(cz) * g.ny + cy) * g.nx + cx);
 }
 
+// lik_cell_key_kernel for a cloud that may hold non-finite points (a scan, build_transient_cell_grid): those go to cell 0 by
+// decree instead of through a float-to-int conversion of NaN / infinity. Finite points: the same key.
+__global__ void lik_cell_key_any_kernel(const float4* __restrict__ sp, long long n, CellGeom g, uint32_t* __restrict__ key,
+                                        uint32_t* __restrict__ val, uint32_t* __restrict__ count)
+{
+  const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n)
+    return;
+  const float4 p = sp[i];
+  const bool finite = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
+  const uint32_t k = finite ? lik_cell_of(p, g) : 0u;
+  key[i] = k;
+  val[i] = static_cast<uint32_t>(i);
+  atomicAdd(&count[k], 1u);
+}
+
 __global__ void lik_update_key_kernel(const float4* __restrict__ sp_upd, int n_u, CellGeom g, uint32_t* __restrict__ key,
                                       uint32_t* __restrict__ val)
 {

@@ -328,6 +328,9 @@ struct mcl3dl_hip_ctx
   size_t gl_n_points = 0, gl_n_centroids = 0, gl_n_base = 0, gl_n_map = 0;
   uint64_t gl_stamp = 0;
   bool gl_valid = false;
+  // the normal-weighted sampler (api_sampler.inl): the scan's private cell grid (points sorted by cell + run delimiters), the
+  // per-point weights and normals in cloud order, the number of points without a normal
+  DevBuf sn_sorted, sn_cells, sn_weight, sn_normal, sn_count;
 
   // this rank's shard of a device group's resident particles (api_group_state.inl): 13-float states (ping-pong), weights;
   // the 7-float poses the measurement kernels read are kept in `pose`

@@ -354,4 +354,95 @@ int build_dda_grid(mcl3dl_hip_ctx* ctx)
   ctx->grid_build_wall_ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return rc;
 }
+
+// ---- a cell grid over a TRANSIENT cloud (global localisation's centroids, the normal sampler's scan) -----------------------
+// Not the context's map index: the sorted points and the run delimiters go into buffers the caller names, the map's grid and
+// its dirty flags are not touched. Same kernels and the same sequence as the map's grid above: rescale (w = index in the
+// cloud) -> min / max -> geometry on the host -> cell keys + histogram -> stable sort -> gather -> exclusive scan.
+constexpr size_t GL_MAX_CELLS = 1u << 28;  // 1 GiB of run delimiters
+
+// cloud: n points on the device. weight3: the dist_weight the search metric rescales by, nullptr = the plain metric.
+// radius: the search radius in that metric; the cell edge is 1.01 x radius. require_finite: a non-finite (rescaled) point is
+// an error (-3); otherwise such points are sorted into cell 0 of the grid, where no float distance to them passes a `<`,
+// and *n_finite says how many points are finite (0: no grid was built, *out is empty). `what` names the cloud in messages.
+int build_transient_cell_grid(mcl3dl_hip_ctx* ctx, const float4* cloud, size_t n, const float* weight3, float radius,
+                              bool require_finite, const char* what, DevBuf& sorted, DevBuf& cells, LikGrid* out, int* reach,
+                              unsigned long long* n_finite_out)
+{
+  const long long nc = static_cast<long long>(n);
+  const float w3[3] = { weight3 ? weight3[0] : 1.f, weight3 ? weight3[1] : 1.f, weight3 ? weight3[2] : 1.f };
+  TempBuf sp;
+  TRY(scratch_alloc(ctx, sp, sizeof(float4) * n));
+  hipLaunchKernelGGL(grid_rescale_kernel, dim3(blocks_for(nc)), dim3(256), 0, ctx->stream, cloud, nc, w3[0], w3[1], w3[2],
+                     weight3 ? 1 : 0, static_cast<float4*>(sp.p));
+  float mm[6];
+  unsigned long long n_finite = 0;
+  TRY(cloud_minmax(ctx, static_cast<const float4*>(sp.p), nc, mm, &n_finite));
+  if (n_finite_out)
+    *n_finite_out = n_finite;
+  if (require_finite && n_finite != n)
+    return ctx->fail(-3, "%llu rescaled %s(s) are not finite (dist_weight %g %g %g)", static_cast<unsigned long long>(n) - n_finite,
+                     what, w3[0], w3[1], w3[2]);
+  *out = LikGrid{};
+  *reach = 1;
+  if (n_finite == 0)
+    return 0;
+  const float cell = radius * 1.01f;
+  const float inv = 1.0f / cell;
+  if (!(cell > 0.f) || !std::isfinite(cell) || !std::isfinite(inv))
+    return ctx->fail(-3, "%s grid: %g cannot be a cell edge", what, radius);
+  float o[3];
+  int dim[3];
+  double total = 1;
+  for (int a = 0; a < 3; ++a)
+  {
+    o[a] = mm[a] - 2.0f * cell;
+    const double d = std::floor((static_cast<double>(mm[3 + a]) - o[a]) * inv) + 3;
+    if (!(d < 2.0e9))
+      return ctx->fail(-3, "the %s cloud spans %.3g cells of %.3g along axis %d (dist_weight %g %g %g)", what, d, cell, a, w3[0],
+                       w3[1], w3[2]);
+    dim[a] = static_cast<int>(floorf((mm[3 + a] - o[a]) * inv)) + 3;
+    total *= dim[a];
+  }
+  if (total > static_cast<double>(GL_MAX_CELLS))
+    return ctx->fail(-3, "the %s index would need %.3g cells of edge %.3g (%d x %d x %d with dist_weight %g %g %g); "
+                         "at most %zu are supported", what, total, cell, dim[0], dim[1], dim[2], w3[0], w3[1], w3[2],
+                     GL_MAX_CELLS);
+  const size_t ncell = static_cast<size_t>(dim[0]) * dim[1] * dim[2];
+  TRY(ensure(ctx, sorted, sizeof(float4) * n));
+  TRY(ensure(ctx, cells, sizeof(uint32_t) * (ncell + 1)));
+  for (int k = 0; k < 2; ++k)
+  {
+    TRY(ensure(ctx, ctx->cl_key[k], sizeof(uint32_t) * (n + 1)));
+    TRY(ensure(ctx, ctx->cl_val[k], sizeof(uint32_t) * (n + 1)));
+  }
+  HIP_TRY(hipMemsetAsync(cells.p, 0, sizeof(uint32_t) * (ncell + 1), ctx->stream));
+  const CellGeom geom{ o[0], o[1], o[2], inv, dim[0], dim[1], dim[2] };
+  if (require_finite)
+    hipLaunchKernelGGL(lik_cell_key_kernel, dim3(blocks_for(nc)), dim3(256), 0, ctx->stream, static_cast<const float4*>(sp.p), nc,
+                       geom, ctx->cl_key[0].as<uint32_t>(), ctx->cl_val[0].as<uint32_t>(), cells.as<uint32_t>());
+  else
+    hipLaunchKernelGGL(lik_cell_key_any_kernel, dim3(blocks_for(nc)), dim3(256), 0, ctx->stream,
+                       static_cast<const float4*>(sp.p), nc, geom, ctx->cl_key[0].as<uint32_t>(), ctx->cl_val[0].as<uint32_t>(),
+                       cells.as<uint32_t>());
+  TRY(sort_pairs(ctx, nc, sort_bits(ncell)));
+  hipLaunchKernelGGL(grid_gather_kernel, dim3(blocks_for(nc)), dim3(256), 0, ctx->stream, static_cast<const float4*>(sp.p),
+                     ctx->cl_val[1].as<uint32_t>(), nc, sorted.as<float4>());
+  HIP_TRY(hipGetLastError());
+  TRY(device_exclusive_scan(ctx, cells.as<uint32_t>(), static_cast<long long>(ncell) + 1));
+  out->cell_start = cells.as<uint32_t>();
+  out->pts = sorted.as<float4>();
+  out->ox = o[0];
+  out->oy = o[1];
+  out->oz = o[2];
+  out->inv_cell = inv;
+  out->nx = dim[0];
+  out->ny = dim[1];
+  out->nz = dim[2];
+  // A neighbour is within `radius` of the query along every axis, i.e. within 1 / 1.01 = 0.9901 cells; the two float cell
+  // coordinates floorf((s - o) * inv) are each off by at most 2^-23 of their magnitude: with up to 16 384 cells per axis that is
+  // 0.004 cells together, so the neighbour's cell is the query's or next to it. Longer axes get one more cell each way.
+  *reach = std::max(dim[0], std::max(dim[1], dim[2])) <= 16384 ? 1 : 2;
+  return 0;
+}
 }  // namespace

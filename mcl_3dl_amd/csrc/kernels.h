@@ -38,3 +38,4 @@
 #include "stage_kernels.h"
 #include "grid_kernels.h"
 #include "global_loc_kernels.h"
+#include "sampler_kernels.h"

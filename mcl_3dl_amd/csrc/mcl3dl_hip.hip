@@ -47,4 +47,5 @@ extern "C"
 #include "api_group_state.inl"
 #include "api_group_motion.inl"
 #include "api_global_loc.inl"
+#include "api_sampler.inl"
 }  // extern "C"
