@@ -483,12 +483,28 @@ int mcl3dl_hip_group_update_resident(mcl3dl_hip_group* g, const float* extra /*n
 int mcl3dl_hip_group_expectation(mcl3dl_hip_group* g, const float* bias /*n_p or NULL*/, float* out_mean7, float* out_total,
                                  int64_t* out_max_index, int64_t* out_max_biased_index);
 int mcl3dl_hip_group_covariance(mcl3dl_hip_group* g, const float* mean7, float* out_cov36);
+/* The pose-jump bias of every scan + the biased expectation, in one pass over the resident particles.
+ * Replaces pf_->bias(bias_func) + expectationBiased() + max() of src/mcl_3dl.cpp:436-452 (the branch for at most num_particles_
+ * particles; the uniform-bias branch :428-435 is mcl3dl_hip_group_expectation with bias == NULL):
+ *   probability_bias_ = nl_lin(|pos - prev.pos|) * nl_ang(ang) + 1e-6 with NormalLikelihood<float>(bias_var_dist / bias_var_ang)
+ *   (nd.h:41-58; the two values are used as sigmas, as the reference does) and ang = getAxisAng (quat.h:226-239) of
+ *   rot * prev.rot.inv(), formed from each RESIDENT pose inside the moments pass of mcl3dl_hip_group_expectation: no bias array
+ *   exists unless out_bias (n_p floats) asks for it. Mean, total, max and biased-max index are those of
+ *   mcl3dl_hip_group_expectation(g, <these biases>, ...), bit for bit. prev7 = state_prev_ {pos 3, rot x, y, z, w}.
+ * -3: a NULL or non-finite prev7, a sigma that is not finite and > 0. -5: no resident particles.
+ *   download_particle   pf_->max()'s STATE (src/mcl_3dl.cpp:452): the 13 floats and the weight of ONE resident particle, copied
+ *                       from the rank that owns it (mcl3dl_hip_group_shard), no collective. Either output may be NULL.
+ *                       -3: index out of range. */
+int mcl3dl_hip_group_expectation_jump_bias(mcl3dl_hip_group* g, const float* prev7, float bias_var_dist, float bias_var_ang,
+                                           float* out_bias /*n_p or NULL*/, float* out_mean7, float* out_total,
+                                           int64_t* out_max_index, int64_t* out_max_biased_index);
+int mcl3dl_hip_group_download_particle(mcl3dl_hip_group* g, int64_t index, float* out_state13, float* out_weight);
 int mcl3dl_hip_group_resample_begin(mcl3dl_hip_group* g, size_t n_out /*0 = as many as there are*/, float* out_pstep);
 int mcl3dl_hip_group_resample_plan(mcl3dl_hip_group* g, int mode, float initial_p, uint32_t* out_source /*n_out or NULL*/,
                                    uint8_t* out_duplicate /*n_out or NULL*/, size_t* out_n_duplicates);
 int mcl3dl_hip_group_resample_apply(mcl3dl_hip_group* g, const float* noise13 /*n_dup*13, host*/, size_t n_noise);
 /* ---- between two scans, on the resident particles (no state download) --------------------------------------------------
- * The rest of what src/mcl_3dl.cpp does to every particle. All but measure_imu are shard-local: one launch per device, no
+ * The rest of what src/mcl_3dl.cpp does to every particle. All but measure_imu / measure_landmark are shard-local: one launch per device, no
  * collective. The caller keeps drawing the random numbers (the reference draws them from one sequential engine), as for
  * resample_apply's noise13.
  *   set_odom_noise       State6DOF's odometry noise {noise_ll_, noise_la_, noise_al_, noise_aa_} per resident particle, already
@@ -508,8 +524,19 @@ int mcl3dl_hip_group_resample_apply(mcl3dl_hip_group* g, const float* noise13 /*
  *   set_odom_error_sigma measure()'s odometry factor (src/mcl_3dl.cpp:420-423): sigma > 0 makes update_resident with extra == NULL
  *                        apply NormalLikelihood(sigma)(|odom_err_integ_lin_|) formed on the devices from the resident states;
  *                        0 (the default) keeps NULL's meaning, no factor.
- * sinf / cosf / acosf / expf of the reference are evaluated in double and rounded to float on the device (within 1 ulp of a
- * faithful libm; DESIGN.md, "Numerics"); everything else is the reference's float arithmetic in its order. */
+ *   measure_landmark     cbLandmark (src/mcl_3dl.cpp:899-929): pf::measure with NormalLikelihoodNd<float, 6> (nd.h:60-80) over
+ *                        {pos, getRPY(rot)} of s - measured (state_6dof.h:262-274, quat.h:191-201); the odometry-error fields
+ *                        take no part. measured7 = {pos 3, rot x, y, z, w}. cov36 is the message's covariance array as the
+ *                        reference maps it: COLUMN-major, sigma(r, c) = (float)cov36[6 * c + r] (moot for a symmetric matrix).
+ *                        Determinant and inverse of the float matrix come from an LU with partial pivoting in double, each
+ *                        rounded to float once; x^T sigma^-1 x is summed sequentially in float (Eigen's own LU and reduction
+ *                        order are not pinned by the reference: DESIGN.md). A launch of its own forms the likelihoods, then the
+ *                        same partial sums, all-reduce and restore rule as measure_imu. -3: NULL or non-finite arguments, a
+ *                        singular covariance or one without a positive determinant (the reference would weigh with NaN and
+ *                        restore). A determinant beyond float range is no error: a_ = 0, every likelihood 0, the update
+ *                        restores, as in the reference. The caller resamples afterwards (resample_begin / _plan / _apply).
+ * sinf / cosf / acosf / expf / atan2f / asinf of the reference are evaluated in double and rounded to float on the device
+ * (within 1 ulp of a faithful libm; DESIGN.md, "Numerics"); everything else is the reference's float arithmetic in its order. */
 int mcl3dl_hip_group_set_odom_noise(mcl3dl_hip_group* g, const float* noise4 /*n_p*4*/, size_t n_p);
 int mcl3dl_hip_group_download_odom_noise(mcl3dl_hip_group* g, float* noise4 /*n_p*4*/, size_t n_p);
 int mcl3dl_hip_group_predict(mcl3dl_hip_group* g, const float* odom_prev7, const float* odom_cur7, float time_diff,
@@ -519,6 +546,9 @@ int mcl3dl_hip_group_add_noise(mcl3dl_hip_group* g, const float* noise13 /*n_p*1
 int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float acc_var, float* out_weight /*n_p or NULL*/,
                                  float* out_lik /*n_p or NULL*/, float* entropy, int* restored);
 int mcl3dl_hip_group_set_odom_error_sigma(mcl3dl_hip_group* g, float sigma);
+int mcl3dl_hip_group_measure_landmark(mcl3dl_hip_group* g, const float* measured7, const double* cov36,
+                                      float* out_weight /*n_p or NULL*/, float* out_lik /*n_p or NULL*/, float* entropy,
+                                      int* restored);
 /* ---- global localisation: the particle set seeded from the map, on the devices ---------------------------------------------
  * The reference's `global_localization` service (cbGlobalLocalization, src/mcl_3dl.cpp:1039-1099), step by step:
  *   1. pcl::VoxelGrid(leaf = (float)grid) over pc_map_: the BASE map only, a map update overlay is ignored;

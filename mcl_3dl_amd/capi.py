@@ -118,6 +118,9 @@ SIGNATURES = {
     "mcl3dl_hip_group_reset_odom_integ": (_i, [_p]),
     "mcl3dl_hip_group_add_noise": (_i, [_p, _p, _sz]),
     "mcl3dl_hip_group_measure_imu": (_i, [_p, _p, _f, _p, _p, _p, _p]),
+    "mcl3dl_hip_group_measure_landmark": (_i, [_p, _p, _p, _p, _p, _p, _p]),
+    "mcl3dl_hip_group_expectation_jump_bias": (_i, [_p, _p, _f, _f, _p, _p, _p, _p, _p]),
+    "mcl3dl_hip_group_download_particle": (_i, [_p, C.c_int64, _p, _p]),
     "mcl3dl_hip_group_set_odom_error_sigma": (_i, [_p, _f]),
     "mcl3dl_hip_global_localization_rotations": (_i, [_i, _p, _p]),
     "mcl3dl_hip_global_localization_points": (_i, [_p, _d, _p, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
@@ -397,6 +400,27 @@ class Group:
         self._check(self.lib.mcl3dl_hip_group_expectation(self.h, _ptr(b), _ptr(mean), C.byref(total), C.byref(im), C.byref(ib)))
         return mean, float(total.value), int(im.value), int(ib.value)
 
+    def expectation_jump_bias(self, prev7, var_dist, var_ang, fetch_bias=False):
+        """The node's pose-jump bias (bias_var_dist / bias_var_ang about state_prev_ = prev7) formed from the resident poses
+        inside the moments pass + expectationBiased / max / maxBiased. Returns (mean7, total, max index, biased max index), and
+        the biases as a fifth element with fetch_bias."""
+        n_p = self.resident()
+        pv = _np_f32(prev7)
+        b = np.zeros(n_p, np.float32) if fetch_bias else None
+        mean = np.zeros(7, np.float32)
+        total = C.c_float(0)
+        im, ib = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.mcl3dl_hip_group_expectation_jump_bias(self.h, _ptr(pv), float(var_dist), float(var_ang), _ptr(b),
+                                                                    _ptr(mean), C.byref(total), C.byref(im), C.byref(ib)))
+        out = (mean, float(total.value), int(im.value), int(ib.value))
+        return out + (b,) if fetch_bias else out
+
+    def download_particle(self, i):
+        """State (13 floats) and weight of one resident particle, from the rank that owns it."""
+        s, w = np.zeros(13, np.float32), C.c_float(0)
+        self._check(self.lib.mcl3dl_hip_group_download_particle(self.h, int(i), _ptr(s), C.byref(w)))
+        return s, np.float32(w.value)
+
     def covariance(self, mean7):
         m = _np_f32(mean7)
         cov = np.zeros((6, 6), np.float32)
@@ -455,6 +479,18 @@ class Group:
         ent, rest = C.c_float(0), C.c_int(0)
         self._check(self.lib.mcl3dl_hip_group_measure_imu(self.h, _ptr(a), float(acc_var), _ptr(w), _ptr(lik), C.byref(ent),
                                                           C.byref(rest)))
+        return dict(weights=w, lik=lik, entropy=float(ent.value), restored=bool(rest.value))
+
+    def measure_landmark(self, measured7, cov36, fetch=True):
+        """cbLandmark's pf_->measure: NormalLikelihoodNd<float, 6> over s - measured; cov36 is the message's covariance array
+        (column-major doubles, or a 6 x 6 array whose [c][r] is sigma(r, c): moot for a symmetric matrix)."""
+        n_p = self.resident()
+        m = _np_f32(measured7)
+        cov = np.ascontiguousarray(cov36, dtype=np.float64).reshape(36)
+        w, lik = (np.zeros(n_p, np.float32), np.zeros(n_p, np.float32)) if fetch else (None, None)
+        ent, rest = C.c_float(0), C.c_int(0)
+        self._check(self.lib.mcl3dl_hip_group_measure_landmark(self.h, _ptr(m), _ptr(cov), _ptr(w), _ptr(lik), C.byref(ent),
+                                                               C.byref(rest)))
         return dict(weights=w, lik=lik, entropy=float(ent.value), restored=bool(rest.value))
 
     def set_odom_error_sigma(self, sigma):

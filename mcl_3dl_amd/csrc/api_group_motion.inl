@@ -7,9 +7,11 @@
 //   mcl3dl_hip_group_add_noise                               pf_->noise (:850-860; pf.h:226-237) with caller-drawn noise
 //   mcl3dl_hip_group_measure_imu                             cbImu's pf_->measure (:997-1002), gravity model
 //   mcl3dl_hip_group_set_odom_error_sigma                    measure()'s odometry factor (:420-423) formed on the devices
+//   mcl3dl_hip_group_measure_landmark                        cbLandmark's pf_->measure (:899-929), NormalLikelihoodNd<float, 6>
 //
-// Everything but the IMU update is shard-local (one launch per rank, no collective). The IMU update is pf::measure: the same
-// partial sums / one all-reduce / apply as mcl3dl_hip_group_update_resident, with the likelihood formed in the partial-sum pass.
+// Everything but the IMU and the landmark update is shard-local (one launch per rank, no collective). Those two are pf::measure:
+// the same partial sums / one all-reduce / apply as mcl3dl_hip_group_update_resident (group_measure_resident), the IMU
+// likelihood formed in the partial-sum pass, the landmark likelihood by a launch of its own in front (landmark_kernels.h).
 namespace
 {
 // MotionPredictionModelDifferentialDrive::setOdoms (motion_prediction_model_differential_drive.h:46-54) in float, once per
@@ -200,21 +202,20 @@ int mcl3dl_hip_group_set_odom_error_sigma(mcl3dl_hip_group* g, float sigma)
   return 0;
 }
 
-int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float acc_var, float* out_weight, float* out_lik,
-                                 float* entropy, int* restored)
+namespace
 {
-  if (!g)
-    return -1;
-  if (!acc3)
-    return g->fail(-3, "null acceleration");
+// What a likelihood model does on one shard ahead of pf::measure, ctx->lik holding room for the shard's n likelihoods: either
+// it fills *imu (the likelihood is then formed inside the partial-sum pass) or it enqueues a launch of its own that writes
+// ctx->lik and points *lik there.
+using ShardModel = std::function<int(mcl3dl_hip_ctx*, size_t, const float**, ImuGravity*)>;
+
+// pf::measure (pf.h:252-279) over the resident particles with the likelihoods of `model`: one device — the fused work-group up
+// to pf_fused_max particles, else partial + apply; N shards — vote, partial sums, the 2 + 2N-double record all-reduced (RCCL, or
+// through the host), apply: the steps of mcl3dl_hip_group_update_resident. `what` names the update in error texts.
+int group_measure_resident(mcl3dl_hip_group* g, const char* what, const ShardModel& model, float* out_weight, float* out_lik,
+                           float* entropy, int* restored)
+{
   const size_t n_p = g->n_resident;
-  if (n_p == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
-  // ImuMeasurementModelGravity(acc_var) + setAccMeasure(acc) (imu_measurement_model_gravity.h:41-48)
-  ImuGravity imu{};
-  imu.acc = Vec3f{ acc3[0], acc3[1], acc3[2] };
-  imu.acc_norm = std::sqrt(vdot(imu.acc, imu.acc));
-  normal_likelihood_constants(acc_var, &imu.a, &imu.sq2);
   const int N = g->n();
   const bool no_collective = N == 1 && g->direct_single;
   const bool host_combine = g->collective == 1 && !no_collective;
@@ -222,13 +223,6 @@ int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float a
     TRY(group_comms(g));
   const size_t n_pack = 2 + 2 * static_cast<size_t>(N);
   std::vector<float> stats(4 * static_cast<size_t>(N), 0.f);
-  const auto imu_of = [&](mcl3dl_hip_ctx* ctx) -> ImuGravity
-  {
-    ImuGravity m = imu;
-    m.state13 = ctx->gs_state[ctx->gs_cur].as<float>();
-    m.lik_out = ctx->lik.as<float>();
-    return m;
-  };
   // the results of a rank home
   const auto fetch = [&](mcl3dl_hip_ctx* ctx, int r, size_t lo, size_t n) -> int
   {
@@ -257,7 +251,9 @@ int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float a
       TRY(ensure(ctx, ctx->block_partials, sizeof(double) * 4 * nb));
       TRY(ensure(ctx, ctx->partial4, sizeof(double) * 4));
       TRY(ensure(ctx, ctx->stats4, sizeof(float) * 4));
-      const ImuGravity m = imu_of(ctx);
+      ImuGravity m{};
+      const float* d_lik = nullptr;
+      TRY(model(ctx, n, &d_lik, &m));
       float* d_w = ctx->gs_weight.as<float>();
       const bool float_w = pf_float_order(ctx, n);
       const int ni = static_cast<int>(n);
@@ -265,12 +261,12 @@ int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float a
       EventPair ep{};
       TRY(timing_begin(ctx, MCL3DL_KERNEL_PF, &ep));
       if (n <= static_cast<size_t>(std::min(ctx->pf_fused_max, PF_FUSED_MAX)) && ctx->pf_fused)
-        hipLaunchKernelGGL(pf_fused_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_w, none, none, none, none, ni,
+        hipLaunchKernelGGL(pf_fused_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_w, d_lik, none, none, none, ni,
                            ctx->wnew.as<float>(), ctx->partial4.as<double>(), ctx->stats4.as<float>(), PfEmit{}, float_w ? 1 : 0,
                            BeamCounts{}, m);
       else
       {
-        hipLaunchKernelGGL(pf_partial_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_w, none, none, none, none, ni,
+        hipLaunchKernelGGL(pf_partial_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_w, d_lik, none, none, none, ni,
                            ctx->wnew.as<float>(), ctx->block_partials.as<double>(), BeamCounts{}, m);
         if (!float_w)
           hipLaunchKernelGGL(pf_apply_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_w, ctx->wnew.as<float>(), ni, 1,
@@ -330,9 +326,12 @@ int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float a
             TRY(ensure(ctx, ctx->wnew, sizeof(float) * n));
             TRY(ensure(ctx, ctx->block_partials, sizeof(double) * 4 * nb));
             const float* none = nullptr;
-            hipLaunchKernelGGL(pf_partial_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, ctx->gs_weight.as<float>(), none, none,
+            ImuGravity m{};
+            const float* d_lik = nullptr;
+            TRY(model(ctx, n, &d_lik, &m));
+            hipLaunchKernelGGL(pf_partial_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, ctx->gs_weight.as<float>(), d_lik, none,
                                none, none, static_cast<int>(n), ctx->wnew.as<float>(), ctx->block_partials.as<double>(),
-                               BeamCounts{}, imu_of(ctx));
+                               BeamCounts{}, m);
             hipLaunchKernelGGL(pf_reduce_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->block_partials.as<double>(), nb, r, N,
                                ctx->packed.as<double>());
             if (N == 1 && pf_float_order(ctx, n))
@@ -344,7 +343,7 @@ int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float a
           int rc_a = phase_a();
           const bool all_ok = g->vote.vote(rc_a == 0);
           if (rc_a == 0 && !all_ok)
-            rc_a = ctx->fail(RC_ABANDONED, "IMU update abandoned: another rank failed ahead of the collective");
+            rc_a = ctx->fail(RC_ABANDONED, "%s abandoned: another rank failed ahead of the collective", what);
           if (rc_a != 0)
           {
             (void)hipStreamSynchronize(ctx->stream);
@@ -362,7 +361,7 @@ int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float a
           if (nrc != ncclSuccess)
             return rcs[r] = ctx->fail(-7, "ncclAllReduce failed: %s", g->rccl.GetErrorString(nrc));
           if (!enqueued)
-            return rcs[r] = ctx->fail(RC_ABANDONED, "IMU update abandoned: another rank could not enqueue the all-reduce");
+            return rcs[r] = ctx->fail(RC_ABANDONED, "%s abandoned: another rank could not enqueue the all-reduce", what);
           return rcs[r] = phase_b(ctx, r, lo, n);
         },
         &bad);
@@ -420,4 +419,139 @@ int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float a
   if (restored)
     *restored = stats[4 * src + 3] != 0.0f;
   return 0;
+}
+}  // namespace
+
+int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float acc_var, float* out_weight, float* out_lik,
+                                 float* entropy, int* restored)
+{
+  if (!g)
+    return -1;
+  if (!acc3)
+    return g->fail(-3, "null acceleration");
+  if (g->n_resident == 0)
+    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  // ImuMeasurementModelGravity(acc_var) + setAccMeasure(acc) (imu_measurement_model_gravity.h:41-48)
+  ImuGravity imu{};
+  imu.acc = Vec3f{ acc3[0], acc3[1], acc3[2] };
+  imu.acc_norm = std::sqrt(vdot(imu.acc, imu.acc));
+  normal_likelihood_constants(acc_var, &imu.a, &imu.sq2);
+  return group_measure_resident(
+      g, "IMU update",
+      [&](mcl3dl_hip_ctx* ctx, size_t, const float**, ImuGravity* m) -> int
+      {
+        *m = imu;
+        m->state13 = ctx->gs_state[ctx->gs_cur].as<float>();
+        m->lik_out = ctx->lik.as<float>();
+        return 0;
+      },
+      out_weight, out_lik, entropy, restored);
+}
+
+namespace
+{
+// NormalLikelihoodNd<float, 6>'s constructor (nd.h:67-71) on sigma(r, c) = (float)cov36[6 * c + r]: determinant and inverse of
+// the FLOAT matrix by LU with partial pivoting in double (Doolittle, rows swapped for the largest |pivot|, the first of equals),
+// each rounded to float once — Eigen's own float LU is not pinned by the reference ("What is not reproduced").
+// false: a non-finite entry, a zero pivot, det <= 0 or NaN, or a non-finite inverse.
+bool landmark_normal_constants(const double* cov36, float* a, float* sinv36)
+{
+  double A[6][6];
+  for (int r = 0; r < 6; ++r)
+    for (int c = 0; c < 6; ++c)
+    {
+      if (!std::isfinite(cov36[6 * c + r]))
+        return false;
+      const float f = static_cast<float>(cov36[6 * c + r]);
+      if (!std::isfinite(f))
+        return false;
+      A[r][c] = static_cast<double>(f);
+    }
+  int perm[6] = { 0, 1, 2, 3, 4, 5 };
+  double det = 1.0;
+  for (int k = 0; k < 6; ++k)
+  {
+    int p = k;
+    for (int i = k + 1; i < 6; ++i)
+      if (std::fabs(A[i][k]) > std::fabs(A[p][k]))
+        p = i;
+    if (A[p][k] == 0.0)
+      return false;
+    if (p != k)
+    {
+      for (int j = 0; j < 6; ++j)
+        std::swap(A[k][j], A[p][j]);
+      std::swap(perm[k], perm[p]);
+      det = -det;
+    }
+    for (int i = k + 1; i < 6; ++i)
+    {
+      A[i][k] = A[i][k] / A[k][k];
+      for (int j = k + 1; j < 6; ++j)
+        A[i][j] = A[i][j] - A[i][k] * A[k][j];
+    }
+  }
+  for (int k = 0; k < 6; ++k)
+    det = det * A[k][k];
+  const float det_f = static_cast<float>(det);
+  if (!(det_f > 0.0f))
+    return false;
+  for (int c = 0; c < 6; ++c)
+  {
+    double y[6], x[6];
+    for (int i = 0; i < 6; ++i)
+    {
+      double s = perm[i] == c ? 1.0 : 0.0;
+      for (int j = 0; j < i; ++j)
+        s = s - A[i][j] * y[j];
+      y[i] = s;
+    }
+    for (int i = 5; i >= 0; --i)
+    {
+      double s = y[i];
+      for (int j = i + 1; j < 6; ++j)
+        s = s - A[i][j] * x[j];
+      x[i] = s / A[i][i];
+    }
+    for (int r = 0; r < 6; ++r)
+    {
+      sinv36[6 * r + c] = static_cast<float>(x[r]);
+      if (!std::isfinite(sinv36[6 * r + c]))
+        return false;
+    }
+  }
+  // a_ = 1.0 / (pow(2 pi, 0.5 * 6) * sqrt(det)) (nd.h:69): the square root of a float is a float; det_f = inf gives a_ = 0
+  *a = static_cast<float>(1.0 / (std::pow(2.0 * M_PI, 3.0) * static_cast<double>(std::sqrt(det_f))));
+  return true;
+}
+}  // namespace
+
+int mcl3dl_hip_group_measure_landmark(mcl3dl_hip_group* g, const float* measured7, const double* cov36, float* out_weight,
+                                      float* out_lik, float* entropy, int* restored)
+{
+  if (!g)
+    return -1;
+  if (!measured7 || !cov36)
+    return g->fail(-3, "null landmark pose / covariance");
+  for (int k = 0; k < 7; ++k)
+    if (!std::isfinite(measured7[k]))
+      return g->fail(-3, "non-finite landmark pose");
+  if (g->n_resident == 0)
+    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  LandmarkModel lm{};
+  if (!landmark_normal_constants(cov36, &lm.a, lm.sinv))
+    return g->fail(-3, "landmark covariance: non-finite, singular or without a positive determinant");
+  lm.pos = Vec3f{ measured7[0], measured7[1], measured7[2] };
+  lm.rot_inv = qinv(Quat{ measured7[3], measured7[4], measured7[5], measured7[6] });
+  return group_measure_resident(
+      g, "landmark update",
+      [&](mcl3dl_hip_ctx* ctx, size_t n, const float** lik, ImuGravity*) -> int
+      {
+        hipLaunchKernelGGL(landmark_likelihood_kernel, grid_of(n), dim3(256), 0, ctx->stream,
+                           ctx->gs_state[ctx->gs_cur].as<float>(), static_cast<int>(n), lm, ctx->lik.as<float>());
+        HIP_TRY(hipGetLastError());
+        *lik = ctx->lik.as<float>();
+        return 0;
+      },
+      out_weight, out_lik, entropy, restored);
 }

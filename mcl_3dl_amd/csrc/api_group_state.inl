@@ -155,11 +155,13 @@ int mcl3dl_hip_group_update_resident(mcl3dl_hip_group* g, const float* extra, co
                            restored);
 }
 
-int mcl3dl_hip_group_expectation(mcl3dl_hip_group* g, const float* bias, float* out_mean7, float* out_total,
-                                 int64_t* out_max_index, int64_t* out_max_biased_index)
+namespace
 {
-  if (!g)
-    return -1;
+// pf::expectationBiased + max + maxBiased over the shards. jump == null: probability_bias_ is the caller's array (or 1);
+// else it is formed from each resident pose inside the moments pass, and fetched into out_bias only when asked for.
+int group_expectation_impl(mcl3dl_hip_group* g, const float* bias, const JumpBias* jump, float* out_bias, float* out_mean7,
+                           float* out_total, int64_t* out_max_index, int64_t* out_max_biased_index)
+{
   const size_t n_p = g->n_resident;
   if (n_p == 0)
     return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
@@ -191,10 +193,24 @@ int mcl3dl_hip_group_expectation(mcl3dl_hip_group* g, const float* bias, float* 
           TRY(h2d(ctx, ctx->extra.p, bias + lo, sizeof(float) * n));
           d_bias = ctx->extra.as<float>();
         }
-        TRY(resident_poses(ctx));
-        TRY(mcl3dl_hip_moments_partial_device(ctx, ctx->pose.as<float>(), ctx->gs_weight.as<float>(), d_bias, n,
-                                              ctx->gs_rec.as<double>()));
+        JumpBias jb{};
+        if (jump)
+        {
+          if (ctx->gs_n != n)
+            return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, n);
+          jb = *jump;
+          if (out_bias)
+          {
+            TRY(ensure(ctx, ctx->extra, sizeof(float) * n));
+            jb.bias_out = ctx->extra.as<float>();
+          }
+        }
+        TRY(resident_poses(ctx));  // (the mirror of the RESIDENT states: re-derived when another call wrote the pose buffer)
+        TRY(moments_partial_launch(ctx, ctx->pose.as<float>(), ctx->gs_weight.as<float>(), d_bias, jump ? &jb : nullptr, n,
+                                   ctx->gs_rec.as<double>()));
         TRY(d2h(ctx, rec, ctx->gs_rec.p, sizeof(double) * 16));
+        if (jump && out_bias)
+          TRY(d2h(ctx, out_bias + lo, ctx->extra.p, sizeof(float) * n));
         return sync_stream(ctx);
       },
       &bad);
@@ -204,6 +220,72 @@ int mcl3dl_hip_group_expectation(mcl3dl_hip_group* g, const float* bias, float* 
                                 out_max_biased_index) != 0)
     return g->fail(-3, "moments_finish rejected the records");
   return 0;
+}
+}  // namespace
+
+int mcl3dl_hip_group_expectation(mcl3dl_hip_group* g, const float* bias, float* out_mean7, float* out_total,
+                                 int64_t* out_max_index, int64_t* out_max_biased_index)
+{
+  if (!g)
+    return -1;
+  return group_expectation_impl(g, bias, nullptr, nullptr, out_mean7, out_total, out_max_index, out_max_biased_index);
+}
+
+int mcl3dl_hip_group_expectation_jump_bias(mcl3dl_hip_group* g, const float* prev7, float bias_var_dist, float bias_var_ang,
+                                           float* out_bias, float* out_mean7, float* out_total, int64_t* out_max_index,
+                                           int64_t* out_max_biased_index)
+{
+  if (!g)
+    return -1;
+  if (!prev7)
+    return g->fail(-3, "null previous pose");
+  for (int k = 0; k < 7; ++k)
+    if (!std::isfinite(prev7[k]))
+      return g->fail(-3, "non-finite previous pose");
+  if (!(bias_var_dist > 0.f) || !(bias_var_ang > 0.f) || std::isinf(bias_var_dist) || std::isinf(bias_var_ang))
+    return g->fail(-3, "bias_var_dist / bias_var_ang must be finite and > 0");
+  // NormalLikelihood<float> nl_lin(bias_var_dist_), nl_ang(bias_var_ang_); state_prev_.rot_.inv() (src/mcl_3dl.cpp:438-445)
+  JumpBias jb{};
+  jb.prev_pos = Vec3f{ prev7[0], prev7[1], prev7[2] };
+  jb.prev_rot_inv = qinv(Quat{ prev7[3], prev7[4], prev7[5], prev7[6] });
+  normal_likelihood_constants(bias_var_dist, &jb.a_lin, &jb.sq2_lin);
+  normal_likelihood_constants(bias_var_ang, &jb.a_ang, &jb.sq2_ang);
+  return group_expectation_impl(g, nullptr, &jb, out_bias, out_mean7, out_total, out_max_index, out_max_biased_index);
+}
+
+int mcl3dl_hip_group_download_particle(mcl3dl_hip_group* g, int64_t index, float* out_state13, float* out_weight)
+{
+  if (!g)
+    return -1;
+  const size_t n_p = g->n_resident;
+  if (n_p == 0)
+    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  if (index < 0 || static_cast<uint64_t>(index) >= n_p)
+    return g->fail(-3, "particle %lld of %zu asked for", static_cast<long long>(index), n_p);
+  const int N = g->n();
+  const size_t i = static_cast<size_t>(index);
+  for (int r = 0; r < N; ++r)
+  {
+    size_t lo, hi;
+    shard_bounds(n_p, N, r, &lo, &hi);
+    if (i < lo || i >= hi)
+      continue;
+    // one rank, 52 + 4 bytes, no collective: on the calling thread
+    mcl3dl_hip_ctx* ctx = g->ctx[r];
+    const int rc = [&]() -> int
+    {
+      HIP_TRY(hipSetDevice(ctx->device));
+      if (ctx->gs_n != hi - lo)
+        return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, hi - lo);
+      if (out_state13)
+        TRY(d2h(ctx, out_state13, ctx->gs_state[ctx->gs_cur].as<float>() + 13 * (i - lo), sizeof(float) * 13));
+      if (out_weight)
+        TRY(d2h(ctx, out_weight, ctx->gs_weight.as<float>() + (i - lo), sizeof(float)));
+      return sync_stream(ctx);
+    }();
+    return rc ? g->fail_rank(rc, r) : 0;
+  }
+  return g->fail(-4, "internal: no shard holds particle %zu", i);
 }
 
 int mcl3dl_hip_group_covariance(mcl3dl_hip_group* g, const float* mean7, float* out_cov36)

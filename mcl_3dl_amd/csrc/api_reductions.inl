@@ -109,11 +109,12 @@ int mcl3dl_hip_covariance_device(mcl3dl_hip_ctx* ctx, const float* d_pose, const
 }
 
 // ---- the same reductions over particle shards (one record per GPU, combined after an all-gather / all-reduce) -------
-int mcl3dl_hip_moments_partial_device(mcl3dl_hip_ctx* ctx, const float* d_pose, const float* d_weight,
-                                      const float* d_bias, size_t n, double* d_out16)
+namespace
 {
-  if (!ctx)
-    return -1;
+// jump == null: the caller's bias array (or none); else the pose-jump bias formed inside the pass (landmark_kernels.h)
+int moments_partial_launch(mcl3dl_hip_ctx* ctx, const float* d_pose, const float* d_weight, const float* d_bias,
+                           const JumpBias* jump, size_t n, double* d_out16)
+{
   if (n == 0 || n > 0x7fffffffu || !d_pose || !d_weight || !d_out16)
     return ctx->fail(-3, "bad arguments to moments_partial");
   HIP_TRY(hipSetDevice(ctx->device));
@@ -122,12 +123,25 @@ int mcl3dl_hip_moments_partial_device(mcl3dl_hip_ctx* ctx, const float* d_pose, 
   TRY(ensure(ctx, ctx->mom_arg, sizeof(ArgMax) * 2 * nb));
   TRY(ensure(ctx, ctx->mom_out, sizeof(double) * COV_N));
   TRY(ensure(ctx, ctx->mom_idx, sizeof(int) * 2));
-  hipLaunchKernelGGL(pf_moments_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_pose, d_weight, d_bias,
-                     static_cast<int>(n), ctx->mom_blocks.as<double>(), ctx->mom_arg.as<ArgMax>());
+  if (jump)
+    hipLaunchKernelGGL(pf_moments_jump_bias_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_pose, d_weight, *jump,
+                       static_cast<int>(n), ctx->mom_blocks.as<double>(), ctx->mom_arg.as<ArgMax>());
+  else
+    hipLaunchKernelGGL(pf_moments_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_pose, d_weight, d_bias,
+                       static_cast<int>(n), ctx->mom_blocks.as<double>(), ctx->mom_arg.as<ArgMax>());
   hipLaunchKernelGGL(pf_moments_reduce_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->mom_blocks.as<double>(),
                      ctx->mom_arg.as<ArgMax>(), nb, ctx->mom_out.as<double>(), ctx->mom_idx.as<int>(), d_out16);
   HIP_TRY(hipGetLastError());
   return 0;
+}
+}  // namespace
+
+int mcl3dl_hip_moments_partial_device(mcl3dl_hip_ctx* ctx, const float* d_pose, const float* d_weight,
+                                      const float* d_bias, size_t n, double* d_out16)
+{
+  if (!ctx)
+    return -1;
+  return moments_partial_launch(ctx, d_pose, d_weight, d_bias, nullptr, n, d_out16);
 }
 
 int mcl3dl_hip_moments_finish(const double* parts16, int world, const uint64_t* index_offset, float* out_mean7,

@@ -10,6 +10,8 @@
 //                         (expectation / max / covariance, resampling)
 //   motion_kernels.h      between two scans, on resident particles: motion prediction, odometry-error reset, pf::noise, the
 //                         scan update's odometry factor, the IMU gravity likelihood (inside pf::measure's partial-sum pass)
+//   landmark_kernels.h    on resident particles: the pose-jump bias formed inside the moments pass, the landmark likelihood
+//                         (NormalLikelihoodNd<float, 6> over s - measured)
 //   update_kernels.h      likelihood + beam + pf::measure in ONE launch for the reference's operating range (launch-bound sizes)
 //   map_compiler.h        device-side compiler of the candidate-voxel index (whole map, or the bricks a map update touches)
 //   grid_kernels.h        the cell-sorted exact-NN grid and the DDA occupancy / voxel index, built on the device
@@ -32,6 +34,7 @@
 #include "beam_kd_kernels.h"
 #include "motion_kernels.h"
 #include "pf_kernels.h"
+#include "landmark_kernels.h"
 #include "update_kernels.h"
 #include "cloud_kernels.h"
 #include "sort_kernels.h"

@@ -585,11 +585,19 @@ __device__ inline ArgMax argmax_better(ArgMax a, ArgMax b)
   return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
 }
 
-__global__ __launch_bounds__(PF_BLOCK) void pf_moments_kernel(const float* __restrict__ pose7,
-                                                              const float* __restrict__ w,
-                                                              const float* __restrict__ bias, int n,
-                                                              double* __restrict__ block_mom /*[grid][MOM_N]*/,
-                                                              ArgMax* __restrict__ block_arg /*[grid][2]*/)
+// probability_bias_ as pf::bias left it (pf.h:238-244): the caller's array, or 1 for every particle
+struct BiasArray
+{
+  const float* bias;  // [n] or null
+  __device__ float operator()(const float*, int i) const { return bias ? bias[i] : 1.0f; }
+};
+
+// The moments pass over one shard; Bias(pose of particle i, i) = probability_bias_ of that particle (BiasArray, or formed from
+// the pose on the spot: landmark_kernels.h).
+template <class Bias>
+__device__ __forceinline__ void pf_moments_body(const float* __restrict__ pose7, const float* __restrict__ w, const Bias& bias,
+                                                int n, double* __restrict__ block_mom /*[grid][MOM_N]*/,
+                                                ArgMax* __restrict__ block_arg /*[grid][2]*/)
 {
   double m[MOM_N];
 #pragma unroll
@@ -600,7 +608,7 @@ __global__ __launch_bounds__(PF_BLOCK) void pf_moments_kernel(const float* __res
   for (int i = blockIdx.x * PF_BLOCK + threadIdx.x; i < n; i += gridDim.x * PF_BLOCK)
   {
     const float* ps = pose7 + 7 * static_cast<size_t>(i);
-    const float prob = w[i] * (bias ? bias[i] : 1.0f);  // pf.h:300
+    const float prob = w[i] * bias(ps, i);  // pf.h:300
     const Quat rot = { ps[3], ps[4], ps[5], ps[6] };
     const Vec3f front = vscale(qrot(rot, Vec3f{ 1.0f, 0.0f, 0.0f }), prob);  // state_6dof.h:337-338
     const Vec3f up = vscale(qrot(rot, Vec3f{ 0.0f, 0.0f, 1.0f }), prob);
@@ -663,6 +671,15 @@ __global__ __launch_bounds__(PF_BLOCK) void pf_moments_kernel(const float* __res
   }
 }
 
+__global__ __launch_bounds__(PF_BLOCK) void pf_moments_kernel(const float* __restrict__ pose7,
+                                                              const float* __restrict__ w,
+                                                              const float* __restrict__ bias, int n,
+                                                              double* __restrict__ block_mom /*[grid][MOM_N]*/,
+                                                              ArgMax* __restrict__ block_arg /*[grid][2]*/)
+{
+  pf_moments_body(pose7, w, BiasArray{ bias }, n, block_mom, block_arg);
+}
+
 __global__ __launch_bounds__(64) void pf_moments_reduce_kernel(const double* __restrict__ block_mom,
                                                                const ArgMax* __restrict__ block_arg, int n_blocks,
                                                                double* __restrict__ out_mom /*[MOM_N]*/,
@@ -696,16 +713,26 @@ __global__ __launch_bounds__(64) void pf_moments_reduce_kernel(const double* __r
 }
 
 // Quat::getRPY, include/mcl_3dl/quat.h:188-203 (float storage, double intermediates; device atan2f / asinf)
-__host__ __device__ inline Vec3f quat_get_rpy(Quat q)
+struct RpyTerms
+{
+  float t0, t1, t2, t3, t4;
+};
+__host__ __device__ inline RpyTerms quat_rpy_terms(Quat q)
 {
   const float ysq = q.y * q.y;
-  const float t0 = static_cast<float>(-2.0 * (ysq + q.z * q.z) + 1.0);
-  const float t1 = static_cast<float>(+2.0 * (q.x * q.y + q.w * q.z));
+  RpyTerms t;
+  t.t0 = static_cast<float>(-2.0 * (ysq + q.z * q.z) + 1.0);
+  t.t1 = static_cast<float>(+2.0 * (q.x * q.y + q.w * q.z));
   const double t2d = -2.0 * (q.x * q.z - q.w * q.y);
-  const float t2 = static_cast<float>(t2d > 1.0 ? 1.0 : (t2d < -1.0 ? -1.0 : t2d));
-  const float t3 = static_cast<float>(+2.0 * (q.y * q.z + q.w * q.x));
-  const float t4 = static_cast<float>(-2.0 * (q.x * q.x + ysq) + 1.0);
-  return { atan2f(t3, t4), asinf(t2), atan2f(t1, t0) };
+  t.t2 = static_cast<float>(t2d > 1.0 ? 1.0 : (t2d < -1.0 ? -1.0 : t2d));
+  t.t3 = static_cast<float>(+2.0 * (q.y * q.z + q.w * q.x));
+  t.t4 = static_cast<float>(-2.0 * (q.x * q.x + ysq) + 1.0);
+  return t;
+}
+__host__ __device__ inline Vec3f quat_get_rpy(Quat q)
+{
+  const RpyTerms t = quat_rpy_terms(q);
+  return { atan2f(t.t3, t.t4), asinf(t.t2), atan2f(t.t1, t.t0) };
 }
 
 constexpr int COV_N = 22;  // 21 upper-triangular sums + p_sum
