@@ -534,7 +534,7 @@ int mcl3dl_hip_measure_device(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n
   if (!ctx)
     return -1;
   HIP_TRY(hipSetDevice(ctx->device));
-  return launch_measure(ctx, d_pose, n_p, d_lik, d_match_ratio, d_beam, false, nullptr);
+  return launch_measure(ctx, d_pose, n_p, d_lik, d_match_ratio, d_beam);
 }
 
 int mcl3dl_hip_workload_stats(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, double* stats6)
@@ -542,7 +542,7 @@ int mcl3dl_hip_workload_stats(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n
   if (!ctx || !stats6)
     return -1;
   HIP_TRY(hipSetDevice(ctx->device));
-  return launch_measure(ctx, d_pose, n_p, nullptr, nullptr, nullptr, true, stats6);
+  return measure_stats(ctx, d_pose, n_p, stats6);
 }
 
 int mcl3dl_hip_pf_partial_device(mcl3dl_hip_ctx* ctx, const float* d_weight, const float* d_lik, const float* d_beam,
@@ -750,7 +750,7 @@ int enqueue_update(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, float* 
   LikTail tail;
   tail.want = pf_takes_tiles(ctx, n_p) && d_lik && d_ratio && d_beam;
   tail.want_beam = d_beam != nullptr;
-  TRY(launch_measure(ctx, d_pose, n_p, d_lik, d_ratio, d_beam, false, nullptr, &tail));
+  TRY(launch_measure(ctx, d_pose, n_p, d_lik, d_ratio, d_beam, &tail));
   TRY(pf_measure_single(ctx, d_weight, d_lik, d_beam, d_extra, d_ratio, n_p, d_stats4, ho, &tail));
   return 0;
 }
@@ -861,8 +861,7 @@ int mcl3dl_hip_measure_batch(mcl3dl_hip_ctx* ctx, const float* pose, size_t n_p,
   }
   const bool lik_wanted = out_lik || out_match_ratio;
   TRY(launch_measure(ctx, ctx->pose.as<float>(), n_p, lik_wanted ? ctx->lik.as<float>() : nullptr,
-                     lik_wanted ? ctx->ratio.as<float>() : nullptr, out_beam ? ctx->beam.as<float>() : nullptr, false,
-                     nullptr));
+                     lik_wanted ? ctx->ratio.as<float>() : nullptr, out_beam ? ctx->beam.as<float>() : nullptr));
   if (out_lik)
     TRY(d2h(ctx, out_lik, ctx->lik.p, sizeof(float) * n_p));
   if (out_match_ratio)
@@ -1203,7 +1202,7 @@ int measure_update_staged(mcl3dl_hip_ctx* ctx, const float* pose, const float* e
       {
         const size_t n = std::min(slice, n_p - lo);
         TRY(launch_measure(ctx, ctx->pose.as<float>() + 7 * lo, n, lik_wanted ? d_lik + lo : nullptr,
-                           lik_wanted ? d_ratio + lo : nullptr, out_beam ? d_beam + lo : nullptr, false, nullptr));
+                           lik_wanted ? d_ratio + lo : nullptr, out_beam ? d_beam + lo : nullptr));
         PfEmit es{};
         es.lik = e.lik ? e.lik + lo : nullptr;
         es.ratio = e.ratio ? e.ratio + lo : nullptr;
@@ -1218,7 +1217,7 @@ int measure_update_staged(mcl3dl_hip_ctx* ctx, const float* pose, const float* e
       return 2;
     }
     TRY(launch_measure(ctx, ctx->pose.as<float>(), n_p, lik_wanted ? d_lik : nullptr, lik_wanted ? d_ratio : nullptr,
-                       out_beam ? d_beam : nullptr, false, nullptr));
+                       out_beam ? d_beam : nullptr));
     if (blk3)
     {
       PfEmit e{};

@@ -295,8 +295,7 @@ int mcl3dl_hip_group_measure_batch(mcl3dl_hip_group* g, const float* pose, size_
         TRY(ensure(ctx, ctx->beam, sizeof(float) * n));
         const bool lik_wanted = out_lik || out_match_ratio;
         TRY(launch_measure(ctx, ctx->pose.as<float>(), n, lik_wanted ? ctx->lik.as<float>() : nullptr,
-                           lik_wanted ? ctx->ratio.as<float>() : nullptr, out_beam ? ctx->beam.as<float>() : nullptr,
-                           false, nullptr));
+                           lik_wanted ? ctx->ratio.as<float>() : nullptr, out_beam ? ctx->beam.as<float>() : nullptr));
         if (out_lik)
           TRY(d2h(ctx, out_lik + lo, ctx->lik.p, sizeof(float) * n));
         if (out_match_ratio)
@@ -671,7 +670,7 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
             tail.want = n <= static_cast<size_t>(1024) * PF_BLOCK;
             tail.want_beam = true;
             TRY(launch_measure(ctx, ctx->pose.as<float>(), n, ctx->lik.as<float>(), ctx->ratio.as<float>(),
-                               ctx->beam.as<float>(), false, nullptr, &tail));
+                               ctx->beam.as<float>(), &tail));
             TRY(pf_partial_behind_measure(ctx, d_w, ctx->lik.as<float>(), ctx->beam.as<float>(),
                                           (extra || device_extra) ? ctx->extra.as<float>() : nullptr, ctx->ratio.as<float>(), n, r, N,
                                           ctx->packed.as<double>(), tail));

@@ -1,6 +1,8 @@
-// host_measure.h — part of the single translation unit mcl3dl_hip.hip: parameter structs for the kernels and
-// launch_measure, the one place that enqueues the likelihood and beam kernels of an update.
+// host_measure.h — part of the single translation unit mcl3dl_hip.hip: parameter structs for the kernels, the rules that
+// choose among them (each written once), plan_measure — every decision, size check and buffer of a scan update, before anything
+// is enqueued — and launch_measure with one small launcher per route, the one place that enqueues the likelihood and beam kernels.
 #pragma once
+#include <type_traits>
 
 namespace
 {
@@ -178,23 +180,16 @@ int ensure_pow_table(mcl3dl_hip_ctx* ctx, size_t n_b_coming = 0)
   return 0;
 }
 
-// Which likelihood kernel an update of np particles x ns points runs, with every size check and every buffer the launch
-// needs done HERE — before launch_measure forks the beam kernels onto the second stream, so that no error path can
-// return with un-joined work in flight.
-struct LikPlan
+// ---- compile-time dispatch: a runtime value picks the template instance (each list names every instance there is) ------
+// f(std::integral_constant<int, V>) for the V that equals v; the LAST value listed also takes whatever matches none
+template <int V, int... Rest, class F>
+void dispatch_int(int v, F&& f)
 {
-  bool tiled = false, small = false;
-  int group_size = 16, W = 1, n_tiles = 0, n_groups = 0;
-  long long blocks = 0;
-  float* strict_terms = nullptr;
-  size_t chunk = 0;    // > 0: the scan is ordered in chunks of the caller's order and replayed chunk by chunk (two term buffers)
-  bool chain = false;  // the float sum in the scan array's order inside the tiled kernel (likelihood_kernels.h: LikChain)
-  uint32_t chain_tag0 = 0;
-  int chain_ppl = 1;   // > 1: likelihood_chain_multi_kernel, that many tiles per work-group (n_super super-tiles)
-  int n_super = 0;
-  bool rows = false;   // per-particle / small-scan kernel with the terms parked in LDS at their ORIGINAL scan indices and added up
-                       // as the reference adds them (float, sequentially, caller's order): bit-identical likelihoods
-};
+  if constexpr (sizeof...(Rest) > 0)
+    if (v != V)
+      return dispatch_int<Rest...>(v, f);
+  f(std::integral_constant<int, V>{});
+}
 
 // Scans up to this many points fit the caller-order term row of the per-particle kernels (48 KB of the 64 KB of LDS a
 // work-group gets without asking for more).
@@ -219,6 +214,8 @@ struct LikMode
 LikMode lik_mode(const mcl3dl_hip_ctx* ctx, int np, int ns)
 {
   LikMode m;
+  // tiled from lik_tiled_min points up (default 1024), and already from three quarters of that when there are enough particles
+  // to fill the GPU with (tile, group) pairs (4096 x 1000: 30.6 us tiled against 34.9 us; 64 x 1000 and 4096 x 512: no gain)
   const bool by_size = ctx->lik_tiled && np >= 4 &&
                        (ns >= ctx->lik_tiled_min || (np >= 256 && 4 * static_cast<long long>(ns) >= 3ll * ctx->lik_tiled_min));
   if (ctx->strict_order == 3)
@@ -244,7 +241,68 @@ LikMode lik_mode(const mcl3dl_hip_ctx* ctx, int np, int ns)
   return m;
 }
 
-// does an update over ns scan points replay the likelihood terms in the reference's float order?
+// the small-scan kernel (likelihood_small_kernel: W lanes per particle) takes what the tiled kernel leaves of short scans
+bool lik_small_applies(const mcl3dl_hip_ctx* ctx, const LikMode& m, int np, int ns)
+{
+  return !m.tiled && ns <= 32 && np >= 256 && ctx->lik_small;
+}
+
+// the likelihood kernels' cooperative form: its sqrt needs match_dist_min > 1.2e-7 m (likelihood_kernels.h:sqrt_in_radius)
+bool lik_coop_active(const mcl3dl_hip_ctx* ctx)
+{
+  return ctx->lik_coop && ctx->lik_index == 2 && ctx->match_dist_min > 1e-5f;
+}
+
+// Work-group size of the per-particle likelihood kernel — and of whatever carries it (lik_particle_beam_kernel, the one-launch
+// update): the same everywhere, so that the lanes add in the same order.
+int lik_particle_block(const mcl3dl_hip_ctx* ctx, int np, int ns)
+{
+  if (ns <= 128)
+    return 64;
+  // few particles: 16 wavefronts share a scan — a quarter of the dependent load chains per lane
+  if (ctx->lik_index == 2 && np <= ctx->lik_wide_max_particles && ns > 512)
+    return 1024;
+  return 256;
+}
+
+// (BLOCK, MODE) of the per-particle kernels: the 1024-thread form exists for MODE 2 only
+template <class F>
+void dispatch_particle(int block, int mode, F&& f)
+{
+  if (mode == 2)
+    dispatch_int<64, 1024, 256>(block, [&](auto b) { f(b, std::integral_constant<int, 2>{}); });
+  else
+    dispatch_int<64, 256>(block, [&](auto b) { f(b, std::integral_constant<int, 0>{}); });
+}
+
+// Work-groups of the tiled kernel over n_tiles tiles of 256 points — per XCD: the interleaved tiles of the largest multiple of
+// eight, then an eighth of the remaining (tile, group) pairs
+long long tiled_blocks(int n_tiles, int n_groups)
+{
+  const long long full_tiles = n_tiles & ~7, rem_items = static_cast<long long>(n_tiles - full_tiles) * n_groups;
+  return 8 * ((full_tiles / 8) * n_groups + (rem_items + 7) / 8);
+}
+
+// A launch of both models: rounds of beam8 x 8 beam work-groups + other8 x 8 of the likelihood kernel's, beam8 : other8 ~ the
+// two grids' ratio (each at most 8); grid = work-groups of the whole launch
+struct Interleave
+{
+  uint32_t beam8 = 1, other8 = 1;
+  long long grid = 0;
+};
+
+Interleave interleave(long long n_beam, long long n_other)
+{
+  Interleave il;
+  if (n_beam >= n_other)
+    il.beam8 = static_cast<uint32_t>(std::min<long long>(8, (n_beam + n_other / 2) / n_other));
+  else
+    il.other8 = static_cast<uint32_t>(std::min<long long>(8, (n_other + n_beam / 2) / n_beam));
+  const long long rounds = std::max((n_beam + 8 * il.beam8 - 1) / (8 * il.beam8), (n_other + 8 * il.other8 - 1) / (8 * il.other8));
+  il.grid = rounds * 8 * (il.beam8 + il.other8);
+  return il;
+}
+
 // the tiled kernel with its overflow rounds deferred (likelihood_kernels.h): needs packed 64-byte records; mode 2 = only
 // on maps where enough voxels overflow for a wavefront to meet one in nearly every round
 bool lik_defer_active(const mcl3dl_hip_ctx* ctx)
@@ -255,13 +313,6 @@ bool lik_defer_active(const mcl3dl_hip_ctx* ctx)
     return true;
   const double with_cand = ctx->cand_stats[4], over4 = ctx->cand_stats[5];
   return with_cand > 0 && over4 / with_cand > ctx->lik_defer_min_frac;
-}
-
-// strict_order = 3: the reference's float recurrence over the scan in the ENGINE's order (mcl3dl_hip_scan_order), inside the
-// tiled kernel — no term array, no replay (needs the page-locked error word of the hand-off: ensure_chain)
-bool lik_chain(const mcl3dl_hip_ctx* ctx)
-{
-  return ctx->strict_order == 3;
 }
 
 // hand-off words + error word of the in-kernel chain for n_p particles and n_tiles tiles; *tag0 = tag of tile 0
@@ -355,140 +406,257 @@ int plan_group_size(const mcl3dl_hip_ctx* ctx, int np, int ns)
   return group_size;
 }
 
-int plan_lik(mcl3dl_hip_ctx* ctx, size_t n_p, int ns, LikPlan* pl)
+// ---- the plan of one launch_measure call ------------------------------------------------------------------------------
+enum class LikRoute
+{
+  None,        // no likelihood output asked for
+  Ones,        // no scan points: (1, 0) for every particle by fill_kernel
+  Small,       // likelihood_small_kernel<W, MODE>
+  Tiled,       // likelihood_tiled_kernel<G, MODE, MINW, COOP, DEFER> + lik_finalize_kernel / the caller's tail kernel / the replay
+  Chain,       // likelihood_tiled_kernel<G, MODE, 8, COOP, DEFER, CHAIN>: the float sum in the scan array's order inside the kernel
+  ChainMulti,  // likelihood_chain_multi_kernel: four tiles per work-group (n_super super-tiles)
+  Particle     // likelihood_kernel<BLOCK, MODE>
+};
+
+enum class BeamRoute
+{
+  None,            // no beam output asked for
+  OnesByFill,      // no beam points: ones by fill_kernel
+  OnesByFinalize,  // ... by whatever finishes the tiled likelihood kernel's sums
+  Main,            // a launch of its own on the context's stream
+  Aux,             // ... on the second stream, forked and joined (mcl3dl_hip_ctx::aux_stream)
+  MergedTiled,     // its work-groups ride in the tiled likelihood kernel's launch (lik_beam_kernel)
+  MergedChain,     // ... in the tiled kernel's in-kernel-chain form (strict_order 3)
+  MergedParticle   // ... in the per-particle likelihood kernel's (lik_particle_beam_kernel)
+};
+
+// Every decision of one call — which kernels run, on which streams, with which template arguments — with every size check and
+// every buffer the launches need done by plan_measure: before launch_measure forks the beam kernels onto the second stream, so
+// that no error path can return with un-joined work in flight.
+struct MeasurePlan
+{
+  LikRoute lik = LikRoute::None;
+  // are the likelihoods of this launch the reference's floats bit for bit (caller-order rows, the float-order replay, the
+  // in-kernel chain, or no terms at all)? pf::measure then adds the weights as the reference does, too (pf_float_order)
+  bool lik_exact = false;
+  int mode = 0;                      // MODE: 2 = candidate records (lik_index 2), 0 = cell search
+  bool coop = false, defer = false;  // COOP, DEFER (the latter for the tiled routes only)
+  int group_size = 16;               // G (MINW follows from it: 4 for 32, else 8)
+  int W = 1, block = 256;            // lanes per particle of the small-scan kernel; the per-particle kernel's work-group size
+  int n_tiles = 0, n_groups = 0, n_super = 0;
+  long long blocks = 0;
+  float* strict_terms = nullptr;
+  size_t chunk = 0;    // > 0: the scan is ordered in chunks of the caller's order and replayed chunk by chunk (two term buffers)
+  uint32_t chain_tag0 = 0;
+  bool rows = false;   // per-particle / small-scan kernel with the terms parked in LDS at their ORIGINAL scan indices and added up
+                       // as the reference adds them (float, sequentially, caller's order): bit-identical likelihoods
+  BeamRoute beam = BeamRoute::None;
+  bool kd = false;        // RaycastUsingKDTree (beam_kd_kernel) instead of the DDA walk
+  bool prepared = false;  // beam_origin_kernel first: what depends only on (particle, origin), once per pair
+  long long n_rays = 0, beam_blocks = 0;
+  bool replay_is_long = false;
+
+  bool chain() const
+  {
+    return lik == LikRoute::Chain || lik == LikRoute::ChainMulti;
+  }
+  bool tiled() const
+  {
+    return lik == LikRoute::Tiled || chain();
+  }
+};
+
+// The AUTOMATIC replay (scans of at least strict_auto_min points) costs ns x n_p floats of device memory — 0.5 GB at
+// 32 768 x 4096, 26 GB at 65 536 x 100 000. It is a refinement (the fp64 sums are within ~1e-5 of the reference's
+// float at such sizes), so it must never make an update fail: when the buffer would take more than half of the free
+// device memory, or its allocation fails, this launch sums in fp64 like smaller scans do. (strict_order = 1 — asked for
+// explicitly — still fails loudly.)
+bool auto_replay_affordable(mcl3dl_hip_ctx* ctx, size_t need)
+{
+  const bool over_cap = ctx->strict_auto_max_bytes > 0.0 && static_cast<double>(need) > ctx->strict_auto_max_bytes;
+  if (!over_cap && need <= ctx->strict_terms.cap)
+    return true;
+  if (!over_cap)
+  {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess)
+    {
+      (void)hipGetLastError();
+      free_b = 0;
+    }
+    if (need + need / 4 <= (free_b + ctx->strict_terms.cap) / 2 && ensure(ctx, ctx->strict_terms, need) == 0)
+      return true;
+    (void)hipGetLastError();
+    ctx->err.clear();
+  }
+  ++ctx->strict_auto_skipped;
+  return false;
+}
+
+// strict_order = 3: the reference's float recurrence over the scan in the ENGINE's order (mcl3dl_hip_scan_order), inside the
+// tiled kernel — no term array, no replay: the chain forms' grids and hand-off words (ensure_chain: with a page-locked error word)
+int plan_chain(mcl3dl_hip_ctx* ctx, size_t n_p, MeasurePlan* pl)
 {
   const int np = static_cast<int>(n_p);
-  const bool chain = lik_chain(ctx);
-  const LikMode mode = lik_mode(ctx, np, ns);
-  pl->tiled = mode.tiled;
-  bool strict = mode.replay;
-  int group_size = plan_group_size(ctx, np, ns);
-  if (chain && group_size > 16)
-    group_size = 16;
-  if (strict && ctx->strict_order == 2)
+  // few particles on a long scan (default kernel family only): four tiles per work-group, a quarter of the hand-offs
+  // (likelihood_chain_multi.h). chain_ppl: 0 = by size, 1 = never, 4 = whenever the family allows.
+  const bool family = pl->coop && pl->defer && ctx->lik_group == 0;
+  int n_handoffs = pl->n_tiles;
+  if (family && (ctx->chain_ppl == 4 || (ctx->chain_ppl == 0 && pl->n_tiles >= 16 && np <= ctx->chain_multi_max)))
   {
-    // The AUTOMATIC replay (scans of at least strict_auto_min points) costs ns x n_p floats of device memory — 0.5 GB at
-    // 32 768 x 4096, 26 GB at 65 536 x 100 000. It is a refinement (the fp64 sums are within ~1e-5 of the reference's
-    // float at such sizes), so it must never make an update fail: when the buffer would take more than half of the free
-    // device memory, or its allocation fails, this launch sums in fp64 like smaller scans do. (strict_order = 1 — asked for
-    // explicitly — still fails loudly.)
-    const size_t need = strict_plan_bytes(ctx, n_p, ns, group_size);
-    if (ctx->strict_auto_max_bytes > 0.0 && static_cast<double>(need) > ctx->strict_auto_max_bytes)
-    {
-      strict = false;
-      ++ctx->strict_auto_skipped;
-    }
-    else if (need > ctx->strict_terms.cap)
-    {
-      size_t free_b = 0, total_b = 0;
-      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess)
-      {
-        (void)hipGetLastError();
-        free_b = 0;
-      }
-      const bool over_cap = ctx->strict_auto_max_bytes > 0.0 && static_cast<double>(need) > ctx->strict_auto_max_bytes;
-      if (over_cap || need + need / 4 > (free_b + ctx->strict_terms.cap) / 2 || ensure(ctx, ctx->strict_terms, need) != 0)
-      {
-        (void)hipGetLastError();
-        ctx->err.clear();
-        strict = false;
-        ++ctx->strict_auto_skipped;
-      }
-    }
+    pl->lik = LikRoute::ChainMulti;
+    pl->group_size = 4;
+    pl->n_groups = (np + 3) / 4;
+    n_handoffs = pl->n_super = (pl->n_tiles + 3) / 4;
+    pl->blocks = 8ll * ((pl->n_super + 7) / 8) * pl->n_groups;
   }
-  // tiled from lik_tiled_min points up (default 1024), and already from three quarters of that when there are enough particles
-  // to fill the GPU with (tile, group) pairs (4096 x 1000: 30.6 us tiled against 34.9 us; 64 x 1000 and 4096 x 512: no gain)
-  pl->rows = mode.rows;
-  pl->group_size = group_size;
-  pl->small = !pl->tiled && ns <= 32 && np >= 256 && ctx->lik_small;
-  if (pl->small)
+  else
   {
-    int W = 1;
-    while (W < ns)
-      W <<= 1;
-    pl->W = W;
-    pl->blocks = (static_cast<long long>(np) * W + 255) / 256;
+    // rows of eight tiles, no shared-out remainder (likelihood_tiled_kernel<..., CHAIN>)
+    pl->lik = LikRoute::Chain;
+    pl->blocks = 8ll * ((pl->n_tiles + 7) / 8) * pl->n_groups;
+  }
+  if (pl->blocks > 0x7fffffffLL)
+    return ctx->fail(-3, "too many work-groups for the tiled likelihood kernel");
+  return ensure_chain(ctx, n_p, n_handoffs, &pl->chain_tag0);
+}
+
+// the likelihood side of the plan for np particles x ns > 0 points
+int plan_lik(mcl3dl_hip_ctx* ctx, size_t n_p, int ns, MeasurePlan* pl)
+{
+  const int np = static_cast<int>(n_p);
+  const LikMode mode = lik_mode(ctx, np, ns);
+  pl->rows = mode.rows;
+  pl->mode = ctx->lik_index == 2 ? 2 : 0;
+  pl->coop = lik_coop_active(ctx);
+  pl->group_size = plan_group_size(ctx, np, ns);
+  const bool chain = ctx->strict_order == 3;
+  if (chain && pl->group_size > 16)
+    pl->group_size = 16;
+  const bool strict = mode.replay && (ctx->strict_order != 2 || auto_replay_affordable(ctx, strict_plan_bytes(ctx, n_p, ns, pl->group_size)));
+  if (lik_small_applies(ctx, mode, np, ns))
+  {
+    pl->lik = LikRoute::Small;
+    while (pl->W < ns)
+      pl->W <<= 1;
+    pl->blocks = (static_cast<long long>(np) * pl->W + 255) / 256;
     if (pl->blocks > 0x7fffffffLL)
       return ctx->fail(-3, "too many work-groups for the small-scan likelihood kernel");
+    return 0;
   }
-  else if (pl->tiled)
+  if (!mode.tiled)
   {
-    pl->n_tiles = (ns + 255) / 256;
-    pl->n_groups = (np + group_size - 1) / group_size;
-    // per XCD: the interleaved tiles of the largest multiple of eight, then an eighth of the remaining (tile, group) pairs
-    const long long full_tiles = pl->n_tiles & ~7, rem_items = static_cast<long long>(pl->n_tiles - full_tiles) * pl->n_groups;
-    pl->blocks = 8 * ((full_tiles / 8) * pl->n_groups + (rem_items + 7) / 8);
-    if (chain)
-    {
-      // few particles on a long scan (default kernel family only): four tiles per work-group, a quarter of the hand-offs
-      // (likelihood_chain_multi.h). chain_ppl: 0 = by size, 1 = never, 4 = whenever the family allows.
-      const bool family = ctx->lik_coop && ctx->lik_index == 2 && ctx->match_dist_min > 1e-5f && lik_defer_active(ctx) && ctx->lik_group == 0;
-      if (family && (ctx->chain_ppl == 4 || (ctx->chain_ppl == 0 && pl->n_tiles >= 16 && np <= ctx->chain_multi_max)))
-      {
-        pl->chain_ppl = 4;
-        pl->group_size = 4;
-        pl->n_groups = (np + 3) / 4;
-        pl->n_super = (pl->n_tiles + 3) / 4;
-        pl->blocks = 8ll * ((pl->n_super + 7) / 8) * pl->n_groups;
-        if (pl->blocks > 0x7fffffffLL)
-          return ctx->fail(-3, "too many work-groups for the tiled likelihood kernel");
-        pl->chain = true;
-        return ensure_chain(ctx, n_p, pl->n_super, &pl->chain_tag0);
-      }
-      // rows of eight tiles, no shared-out remainder (likelihood_tiled_kernel<..., CHAIN>)
-      pl->blocks = 8ll * ((pl->n_tiles + 7) / 8) * pl->n_groups;
-      if (pl->blocks > 0x7fffffffLL)
-        return ctx->fail(-3, "too many work-groups for the tiled likelihood kernel");
-      pl->chain = true;
-      return ensure_chain(ctx, n_p, pl->n_tiles, &pl->chain_tag0);
-    }
-    if (pl->blocks > 0x7fffffffLL)
-      return ctx->fail(-3, "too many work-groups for the tiled likelihood kernel");
-    TRY(ensure(ctx, ctx->lik_partial_sum, sizeof(double) * static_cast<size_t>(pl->n_tiles) * n_p));
-    TRY(ensure(ctx, ctx->lik_partial_cnt, sizeof(unsigned) * static_cast<size_t>(pl->n_tiles) * n_p));
-    if (strict)
-    {
-      TRY(ensure(ctx, ctx->strict_terms, strict_plan_bytes(ctx, n_p, ns, group_size)));
-      pl->strict_terms = ctx->strict_terms.as<float>();
-      pl->chunk = (ctx->scan_chunk && static_cast<size_t>(ns) > ctx->scan_chunk) ? ctx->scan_chunk : 0;
-      if (pl->chunk)
-        TRY(ensure_replay_stream(ctx));
-    }
+    pl->lik = LikRoute::Particle;
+    pl->block = lik_particle_block(ctx, np, ns);
+    return 0;
+  }
+  pl->lik = LikRoute::Tiled;
+  pl->defer = pl->coop && lik_defer_active(ctx);
+  pl->n_tiles = (ns + 255) / 256;
+  pl->n_groups = (np + pl->group_size - 1) / pl->group_size;
+  if (chain)
+    return plan_chain(ctx, n_p, pl);
+  pl->blocks = tiled_blocks(pl->n_tiles, pl->n_groups);
+  if (pl->blocks > 0x7fffffffLL)
+    return ctx->fail(-3, "too many work-groups for the tiled likelihood kernel");
+  TRY(ensure(ctx, ctx->lik_partial_sum, sizeof(double) * static_cast<size_t>(pl->n_tiles) * n_p));
+  TRY(ensure(ctx, ctx->lik_partial_cnt, sizeof(unsigned) * static_cast<size_t>(pl->n_tiles) * n_p));
+  if (strict)
+  {
+    TRY(ensure(ctx, ctx->strict_terms, strict_plan_bytes(ctx, n_p, ns, pl->group_size)));
+    pl->strict_terms = ctx->strict_terms.as<float>();
+    pl->chunk = (ctx->scan_chunk && static_cast<size_t>(ns) > ctx->scan_chunk) ? ctx->scan_chunk : 0;
+    if (pl->chunk)
+      TRY(ensure_replay_stream(ctx));
   }
   return 0;
 }
 
-// lik_strict_sum_rows_kernel with as many particle groups per work-group as keep the launch in ONE round of work-groups, up to a
-// full adder wavefront (64 lanes / GG particles per group)
-template <int GG>
-void launch_strict_sum(mcl3dl_hip_ctx* ctx, const float* strict_terms, int ns, int np, int n_groups, float* d_lik,
-                       hipStream_t on = nullptr, int accumulate = 0)
+// size check and buffers of a beam launch of n_p particles x n_b > 0 points (statistics and production path alike)
+int prepare_beam(mcl3dl_hip_ctx* ctx, size_t n_p, long long* n_rays, long long* blocks)
 {
-  if (!on)
-    on = ctx->stream;
-  constexpr int MAX_GPW = 64 / GG >= 4 ? 4 : (64 / GG >= 2 ? 2 : 1);
-  int gpw = n_groups <= ctx->n_cus ? 1 : (n_groups <= 2 * ctx->n_cus ? 2 : 4);
-  gpw = std::min(gpw, MAX_GPW);
-  const int skew = STRICT_SKEW4;
-#define LAUNCH_STRICT(CHUNK, GPW, GRID)                                                                               \
-  hipLaunchKernelGGL((lik_strict_sum_rows_kernel<GG, CHUNK, GPW>), dim3(GRID), dim3(1024), 0, on, strict_terms, ns, np, \
-                     n_groups, d_lik, skew, accumulate)
-  if constexpr (MAX_GPW >= 4)
-    if (gpw == 4)
-    {
-      LAUNCH_STRICT(16384, 4, (n_groups + 3) / 4);
-      return;
-    }
-  if constexpr (MAX_GPW >= 2)
-    if (gpw >= 2)
-    {
-      LAUNCH_STRICT(32768, 2, (n_groups + 1) / 2);
-      return;
-    }
-  LAUNCH_STRICT(65536, 1, n_groups);
-#undef LAUNCH_STRICT
+  TRY(ensure_pow_table(ctx));
+  *n_rays = static_cast<long long>(n_p) * static_cast<long long>(ctx->n_b);
+  *blocks = (*n_rays + 255) / 256;
+  if (*blocks > 0x7fffffffLL)
+    return ctx->fail(-3, "too many rays for one launch");
+  const size_t cap0 = ctx->penalty.cap;
+  TRY(ensure(ctx, ctx->penalty, sizeof(unsigned) * n_p));
+  if (ctx->penalty.cap != cap0)
+    ctx->penalty_clean_n = 0;  // (a new allocation: nothing is known about its content)
+  return 0;
 }
 
+// the beam side of the plan; with_lik: a likelihood kernel runs in this call (pl holds its plan already)
+int plan_beam(mcl3dl_hip_ctx* ctx, size_t n_p, bool with_lik, MeasurePlan* pl)
+{
+  if (ctx->n_b == 0)
+  {
+    // (1, 0) for every particle; with the tiled likelihood kernel behind it the per-particle finalize writes the ones
+    pl->beam = with_lik && pl->tiled() ? BeamRoute::OnesByFinalize : BeamRoute::OnesByFill;
+    return 0;
+  }
+  TRY(prepare_beam(ctx, n_p, &pl->n_rays, &pl->beam_blocks));
+  const long long n_rays = pl->n_rays, blocks = pl->beam_blocks;
+  // (the prepared origins and the launches of both models below are the DDA walk's: the kd-tree caster runs as a launch of
+  // its own, behind or — from overlap_min_rays rays — beside the likelihood kernel on the second stream)
+  pl->kd = ctx->beam_raycast == 1;
+  pl->prepared = !pl->kd && ctx->beam_prepare && n_rays >= ctx->beam_prepare_min_rays &&
+                 static_cast<long long>(n_p) * static_cast<long long>(ctx->n_o) < 0x7fffffffLL;
+  if (pl->prepared)
+    TRY(ensure(ctx, ctx->beam_origin, sizeof(BeamOrigin) * n_p * ctx->n_o));
+  // Both models in ONE launch (lik_beam_kernel, update_kernels.h: the two kernels' work-groups interleaved, so that every CU
+  // hosts both all the way) whenever the likelihood side is the tiled kernel's cooperative fp64-tree form (G <= 16) and the beam side is large
+  // enough to be worth interleaving: the beam kernel is NOT launched on its own but with the tiled kernel.
+  // Not in front of a LONG caller-order replay (replay_is_long below): on two streams that replay — memory-bound, VALU idle —
+  // overlaps the rest of the beam kernel, which the lock-step interleave cannot offer (C5 shard: 3.09 against 3.14 ms).
+  // Measured, C3: 0.3446 (two streams) -> 0.3313 ms; 4096 rays per particle: 1.0855 -> 1.0070 (profiles/r06s_lik_beam_one_launch.txt).
+  // (the beam kernel's map-update-overlay form needs 66 VGPRs: it would spill inside the 64 of the merged launch)
+  const bool mergeable = !pl->kd && ctx->overlap_models && with_lik && ctx->dg.ov_n == 0;
+  const bool with_tiled = mergeable && pl->group_size <= 16 && pl->coop && blocks >= 64 && blocks < 0x3fffffffLL &&
+                          pl->blocks < 0x3fffffffLL;
+  // (in front of the caller-order replay: two streams only where they would be used — from overlap_min_rays rays — AND the replay
+  // is long enough to hide the beam kernel's tail behind: a term array of at least half a gigabyte. Measured, merged against
+  // streams: 4096 x 4096 + 128 rays - 12 %, 16384 x 4096 + 512 (268 MB) - 3 %, 8192 x 32768 + 512 (1 GB) + 1 %, the C5 shard + 2 %:
+  // profiles/r06s_lik_beam_one_launch.txt)
+  pl->replay_is_long = pl->strict_terms != nullptr && n_rays >= ctx->overlap_min_rays &&
+                       strict_terms_bytes(n_p, static_cast<int>(ctx->n_s), pl->group_size) >= (static_cast<size_t>(512) << 20);
+  if (with_tiled && pl->lik == LikRoute::Tiled && !pl->chunk && !pl->replay_is_long)
+    pl->beam = BeamRoute::MergedTiled;
+  // (the in-kernel chain's single-tile form, strict_order 3, rides the same way: a consumer's producer keeps its lower block index)
+  else if (with_tiled && pl->lik == LikRoute::Chain)
+    pl->beam = BeamRoute::MergedChain;
+  // (the per-particle likelihood kernel's 64- and 256-thread forms take the beam kernel's work-groups along the same way:
+  // lik_particle_beam_kernel)
+  else if (mergeable && pl->lik == LikRoute::Particle && ctx->lik_index == 2 && pl->block != 1024 && blocks >= 16 && blocks < 0x0fffffffLL)
+    pl->beam = BeamRoute::MergedParticle;
+  // the second stream pays only for large launches: the fork / join events cost ~35 us (64 particles x 96 + 3 points:
+  // 52 us per update with them, 17 without), the overlap itself is worth ~5 % at C3 (2.1 M rays)
+  else if (ctx->overlap_models && with_lik && n_rays >= ctx->overlap_min_rays)
+    pl->beam = BeamRoute::Aux;
+  else
+    pl->beam = BeamRoute::Main;
+  return 0;
+}
+
+// The plan of one call (the map structures are in place: lik_defer_active, ctx->dg.ov_n and ctx->rg are valid).
+int plan_measure(mcl3dl_hip_ctx* ctx, size_t n_p, bool want_lik, bool have_lik_out, bool want_beam, MeasurePlan* pl)
+{
+  if (want_lik)
+  {
+    pl->lik = LikRoute::Ones;
+    if (ctx->n_s > 0)
+      TRY(plan_lik(ctx, n_p, static_cast<int>(ctx->n_s), pl));
+    ctx->lik_exact = pl->lik_exact = ctx->n_s == 0 || pl->rows || pl->chain() || pl->strict_terms != nullptr;
+  }
+  if (want_beam)
+    TRY(plan_beam(ctx, n_p, want_lik && ctx->n_s > 0, pl));
+  if (pl->chain() && !have_lik_out)  // (only the match ratio was asked for: the chain's sum still has somewhere to go)
+    TRY(ensure(ctx, ctx->chain_lik, sizeof(float) * n_p));
+  return 0;
+}
+
+// ---- the launchers: one per route ---------------------------------------------------------------------------------------
 // What launch_measure leaves to the kernel behind it when the caller asks for it (`want`: the split pf::measure follows on the
 // same stream): the sum over the tiled kernel's per-tile partials — d_lik / d_ratio (and d_beam's ones, `beam_fill`) are then NOT
 // written by launch_measure but by lik_pf_partial_kernel (pf_kernels.h: LikTiles), one launch less per update.
@@ -502,8 +670,439 @@ struct LikTail
   bool want_beam = false, beam_pending = false;
 };
 
+// one launch_measure call as its launchers see it
+struct MeasureCall
+{
+  mcl3dl_hip_ctx* ctx;
+  const MeasurePlan& plan;
+  const float* d_pose;
+  size_t n_p;
+  int np;
+  float *d_lik, *d_ratio, *d_beam;
+  LikTail* tail;
+  LikParams lp;
+  const float4* scan;
+  int ns;
+
+  // d_beam where whatever finishes the tiled kernel's sums also writes the beam model's ones
+  float* beam_ones() const
+  {
+    return plan.beam == BeamRoute::OnesByFinalize ? d_beam : nullptr;
+  }
+};
+
+// any return between the fork and the join of launch_measure (a failing HIP call) first waits for the second stream, so the
+// caller never gets control back with beam kernels still writing its buffers
+struct ForkGuard
+{
+  mcl3dl_hip_ctx* c;
+  bool armed = false;
+  ~ForkGuard()
+  {
+    if (armed)
+      (void)hipStreamSynchronize(c->aux_stream);
+  }
+};
+
+// the beam model's last step (penalty counts -> scores): left to the update's tail kernel, or a launch of its own
+void finish_beam(const MeasureCall& c, hipStream_t on)
+{
+  const mcl3dl_hip_ctx* ctx = c.ctx;
+  if (c.tail && c.tail->want_beam)
+    c.tail->beam_pending = true;
+  else
+    hipLaunchKernelGGL(beam_finalize_kernel, dim3((c.np + 255) / 256), dim3(256), 0, on, ctx->penalty.as<unsigned>(),
+                       ctx->pow_table.as<float>(), ctx->beam_likelihood_min, c.d_beam, c.np);
+}
+
+// the penalty counters of np particles to zero on stream `on`
+void zero_penalty(mcl3dl_hip_ctx* ctx, int np, hipStream_t on)
+{
+  // a kernel, not hipMemsetAsync: a memset node at the head of a single-stream captured update faulted on its third
+  // replay (ROCm 7.2; 700 particles x 3 rays, 128 x 48), the same zeroing as a kernel node does not
+  hipLaunchKernelGGL(fill_kernel, dim3((np + 255) / 256), dim3(256), 0, on, reinterpret_cast<float*>(ctx->penalty.p), 0.0f,
+                     static_cast<float*>(nullptr), 0.0f, np);
+}
+
+// The beam model: its ones, or — on the main or the second stream — counter zeroing, origin preparation, the caster and the
+// last step; with a merged route the rays ride in the likelihood kernel's launch, which also takes the last step behind itself.
+int launch_beam(const MeasureCall& c, ForkGuard* fork_guard)
+{
+  mcl3dl_hip_ctx* ctx = c.ctx;
+  const MeasurePlan& pl = c.plan;
+  if (pl.beam == BeamRoute::OnesByFinalize)
+    return 0;
+  if (pl.beam == BeamRoute::OnesByFill)
+  {
+    hipLaunchKernelGGL(fill_kernel, dim3((c.np + 255) / 256), dim3(256), 0, ctx->stream, c.d_beam, 1.0f,
+                       static_cast<float*>(nullptr), 0.0f, c.np);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
+  const bool overlap = pl.beam == BeamRoute::Aux;
+  hipStream_t bs = overlap ? ctx->aux_stream : ctx->stream;
+  if (overlap)
+  {
+    HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
+    HIP_TRY(hipStreamWaitEvent(bs, ctx->ev_fork, 0));
+    fork_guard->armed = true;
+  }
+  EventPair ep{};
+  TRY(timing_begin(ctx, MCL3DL_KERNEL_BEAM, &ep, bs));
+  // (beam_origin_kernel zeroes the counters itself; the update's tail kernel leaves them zeroed behind itself)
+  const bool counters_clean = ctx->penalty_clean_n >= c.n_p;
+  ctx->penalty_clean_n = 0;  // ... and from here on they are in use
+  if (!pl.prepared && !counters_clean)
+    zero_penalty(ctx, c.np, bs);
+  // what depends only on (particle, origin) is computed once per pair when the launch is large enough to pay for
+  // one more kernel
+  const BeamOrigin* prepared = nullptr;
+  if (pl.prepared)
+  {
+    const long long n_pairs = static_cast<long long>(c.n_p) * static_cast<long long>(ctx->n_o);
+    hipLaunchKernelGGL(beam_origin_kernel, dim3(static_cast<unsigned>((n_pairs + 255) / 256)), dim3(256), 0, bs, c.d_pose,
+                       c.np, ctx->origins.as<float4>(), static_cast<int>(ctx->n_o), ctx->dg,
+                       ctx->beam_origin.as<BeamOrigin>(), ctx->penalty.as<unsigned>());
+    prepared = ctx->beam_origin.as<BeamOrigin>();
+  }
+  if (pl.beam == BeamRoute::Main || pl.beam == BeamRoute::Aux)  // (merged: the rays ride in the likelihood kernel's launch)
+  {
+    const dim3 grid(static_cast<unsigned>(pl.beam_blocks));
+    if (pl.kd)
+      hipLaunchKernelGGL(beam_kd_kernel, grid, dim3(256), 0, bs, c.d_pose, ctx->scan_beam.as<float4>(),
+                         static_cast<int>(ctx->n_b), ctx->origins.as<float4>(), pl.n_rays, ctx->lg, kd_ray_params(ctx),
+                         beam_params(ctx), ctx->penalty.as<unsigned>());
+    else
+    {
+      // (a map update rides on the DDA grid as an overlay: the kernel that looks it up is chosen only then)
+      const auto kernel = ctx->dg.ov_n > 0 ? beam_kernel<false, true> : beam_kernel<false, false>;
+      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, bs, c.d_pose, ctx->scan_beam.as<float4>(), static_cast<int>(ctx->n_b),
+                         ctx->origins.as<float4>(), pl.n_rays, ctx->dg, beam_params(ctx), ctx->penalty.as<unsigned>(),
+                         static_cast<RayStats*>(nullptr), prepared, static_cast<int>(ctx->n_o));
+    }
+    finish_beam(c, bs);
+  }
+  TRY(timing_end(ctx, ep, bs));
+  if (overlap)
+    HIP_TRY(hipEventRecord(ctx->ev_join, bs));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// What a launch of both models has in common: the poses, the likelihood model's grids and the beam side with the interleave
+// of n_beam beam work-groups with n_other of the likelihood kernel's (LikBeamArgs / LikParticleBeamArgs).
+template <class Args>
+Interleave merged_args(const MeasureCall& c, long long n_beam, long long n_other, Args* a)
+{
+  mcl3dl_hip_ctx* ctx = c.ctx;
+  const Interleave il = interleave(n_beam, n_other);
+  a->pose7 = c.d_pose;
+  a->n_p = c.np;
+  a->g = ctx->lg;
+  a->rg = ctx->rg;
+  a->prm = c.lp;
+  a->scan_beam = ctx->scan_beam.as<float4>();
+  a->n_b = static_cast<int>(ctx->n_b);
+  a->origins = ctx->origins.as<float4>();
+  a->n_rays = c.plan.n_rays;
+  a->dg = ctx->dg;
+  a->bp = beam_params(ctx);
+  a->penalty = ctx->penalty.as<unsigned>();
+  a->prepared = c.plan.prepared ? ctx->beam_origin.as<BeamOrigin>() : nullptr;
+  a->n_o = static_cast<int>(ctx->n_o);
+  a->beam8 = il.beam8;
+  a->n_beam_blocks = static_cast<uint32_t>(n_beam);
+  return il;
+}
+
+// lik_beam_kernel<G, DEFER, false, CHAIN>: the tiled kernel over n_s points from `scan` (t_blocks work-groups) with the beam
+// kernel's work-groups in between, and the beam model's last step behind it. The caller sets a's partials / terms / chain.
+template <bool CHAIN>
+void launch_lik_beam(const MeasureCall& c, long long t_blocks, const float4* scan, int n_s, int n_tiles, LikBeamArgs& a)
+{
+  mcl3dl_hip_ctx* ctx = c.ctx;
+  const Interleave il = merged_args(c, c.plan.beam_blocks, t_blocks, &a);
+  a.n_groups = c.plan.n_groups;
+  a.strict_skew4 = STRICT_SKEW4;
+  a.tiled8 = il.other8;
+  a.n_tiled_blocks = static_cast<uint32_t>(t_blocks);
+  a.scan = scan;
+  a.n_s = n_s;
+  a.n_tiles = n_tiles;
+  dispatch_int<4, 8, 16>(c.plan.group_size, [&](auto g) {
+    dispatch_int<1, 0>(c.plan.defer, [&](auto defer) {
+      hipLaunchKernelGGL((lik_beam_kernel<decltype(g)::value, decltype(defer)::value != 0, false, CHAIN>),
+                         dim3(static_cast<unsigned>(il.grid)), dim3(256), 0, ctx->stream, a);
+    });
+  });
+  finish_beam(c, ctx->stream);
+}
+
+// f(MODE, COOP, DEFER) of the tiled kernel, as constants
+template <class F>
+void dispatch_form(const MeasurePlan& pl, F&& f)
+{
+  using Mode2 = std::integral_constant<int, 2>;
+  if (pl.coop && pl.defer)
+    f(Mode2{}, std::true_type{}, std::true_type{});
+  else if (pl.coop)
+    f(Mode2{}, std::true_type{}, std::false_type{});
+  else if (pl.mode == 2)
+    f(Mode2{}, std::false_type{}, std::false_type{});
+  else
+    f(std::integral_constant<int, 0>{}, std::false_type{}, std::false_type{});
+}
+
+void launch_small(const MeasureCall& c)
+{
+  mcl3dl_hip_ctx* ctx = c.ctx;
+  const MeasurePlan& pl = c.plan;
+  const uint32_t* row_perm = pl.rows ? ctx->scan_perm.as<uint32_t>() : nullptr;
+  dispatch_int<1, 2, 4, 8, 16, 32>(pl.W, [&](auto w) {
+    dispatch_int<2, 0>(pl.mode, [&](auto m) {
+      hipLaunchKernelGGL((likelihood_small_kernel<decltype(w)::value, decltype(m)::value>), dim3(static_cast<unsigned>(pl.blocks)),
+                         dim3(256), 0, ctx->stream, c.d_pose, c.np, c.scan, c.ns, ctx->lg, ctx->rg, c.lp, c.d_lik, c.d_ratio,
+                         pl.coop ? 1 : 0, row_perm);
+    });
+  });
+}
+
+// one launch of the tiled kernel over t_ns points starting at t_scan (the whole scan, or one chunk of it), alone or with
+// the beam kernel's work-groups
+void launch_tiled(const MeasureCall& c, const float4* t_scan, int t_ns, int t_tiles, double* t_psum, unsigned* t_pcnt,
+                  const uint32_t* t_perm, float* t_terms)
+{
+  mcl3dl_hip_ctx* ctx = c.ctx;
+  const MeasurePlan& pl = c.plan;
+  const long long t_blocks = tiled_blocks(t_tiles, pl.n_groups);
+  if (pl.beam == BeamRoute::MergedTiled)
+  {
+    LikBeamArgs a{};
+    a.partial_sum = t_psum;
+    a.partial_cnt = t_pcnt;
+    a.scan_perm = t_perm;
+    a.strict_terms = t_terms;
+    launch_lik_beam<false>(c, t_blocks, t_scan, t_ns, t_tiles, a);
+    return;
+  }
+  dispatch_int<4, 8, 32, 16>(pl.group_size, [&](auto g) {
+    dispatch_form(pl, [&](auto mode, auto coop, auto defer) {
+      constexpr int G = decltype(g)::value;
+      constexpr int MINW = G == 32 ? 4 : 8;  // G = 32: 33 KB of LDS per work-group, 4 wavefronts per SIMD at most
+      hipLaunchKernelGGL((likelihood_tiled_kernel<G, decltype(mode)::value, MINW, decltype(coop)::value, decltype(defer)::value>), dim3(static_cast<unsigned>(t_blocks)),
+                         dim3(256), 0, ctx->stream, c.d_pose, c.np, t_scan, t_ns, t_tiles, pl.n_groups, ctx->lg, ctx->rg, c.lp,
+                         t_psum, t_pcnt, t_perm, t_terms, STRICT_SKEW4);
+    });
+  });
+}
+
+// lik_strict_sum_rows_kernel with as many particle groups per work-group as keep the launch in ONE round of work-groups, up to a
+// full adder wavefront (64 lanes / GG particles per group)
+template <int GG>
+void launch_strict_sum(mcl3dl_hip_ctx* ctx, const float* strict_terms, int ns, int np, int n_groups, float* d_lik, hipStream_t on,
+                       int accumulate)
+{
+  constexpr int MAX_GPW = 64 / GG >= 4 ? 4 : (64 / GG >= 2 ? 2 : 1);
+  int gpw = n_groups <= ctx->n_cus ? 1 : (n_groups <= 2 * ctx->n_cus ? 2 : 4);
+  gpw = std::min(gpw, MAX_GPW);
+  const auto launch = [&](auto chunk, auto per_wg) {
+    constexpr int GPW = decltype(per_wg)::value;
+    hipLaunchKernelGGL((lik_strict_sum_rows_kernel<GG, decltype(chunk)::value, GPW>), dim3((n_groups + GPW - 1) / GPW), dim3(1024),
+                       0, on, strict_terms, ns, np, n_groups, d_lik, STRICT_SKEW4, accumulate);
+  };
+  using std::integral_constant;
+  if constexpr (MAX_GPW >= 4)
+    if (gpw == 4)
+      return launch(integral_constant<int, 16384>{}, integral_constant<int, 4>{});
+  if constexpr (MAX_GPW >= 2)
+    if (gpw >= 2)
+      return launch(integral_constant<int, 32768>{}, integral_constant<int, 2>{});
+  launch(integral_constant<int, 65536>{}, integral_constant<int, 1>{});
+}
+
+// the float-order replay of r_ns points' terms into d_lik (accumulate: continued from the sums already there)
+void launch_replay(const MeasureCall& c, const float* terms, int r_ns, hipStream_t on, int accumulate)
+{
+  dispatch_int<4, 8, 32, 16>(c.plan.group_size, [&](auto g) {
+    launch_strict_sum<decltype(g)::value>(c.ctx, terms, r_ns, c.np, c.plan.n_groups, c.d_lik, on, accumulate);
+  });
+}
+
+// The tiled kernel over the whole scan, then whatever adds its tiles up: the caller's tail kernel, lik_finalize_kernel, and the
+// float-order replay of the term array.
+void launch_tiled_scan(const MeasureCall& c)
+{
+  mcl3dl_hip_ctx* ctx = c.ctx;
+  const MeasurePlan& pl = c.plan;
+  double* const psum = ctx->lik_partial_sum.as<double>();
+  unsigned* const pcnt = ctx->lik_partial_cnt.as<unsigned>();
+  // (a chunk-ordered scan whose likelihoods nobody asked for: its permutation is chunk-relative, no terms are kept)
+  launch_tiled(c, c.scan, c.ns, pl.n_tiles, psum, pcnt, ctx->scan_perm.as<uint32_t>(), pl.chunk ? nullptr : pl.strict_terms);
+  if (c.tail && c.tail->want && !pl.strict_terms && c.d_lik && c.d_ratio)
+  {
+    c.tail->pending = true;  // lik_pf_partial_kernel adds the tiles up
+    c.tail->n_tiles = pl.n_tiles;
+    c.tail->beam_fill = pl.beam == BeamRoute::OnesByFinalize;
+  }
+  else
+    hipLaunchKernelGGL(lik_finalize_kernel, dim3((c.np + 31) / 32), dim3(256), 0, ctx->stream, psum, pcnt, pl.n_tiles, c.np, c.ns,
+                       c.d_lik, c.d_ratio, c.beam_ones());
+  if (pl.strict_terms && c.d_lik && !pl.chunk)
+    launch_replay(c, pl.strict_terms, c.ns, ctx->stream, 0);
+}
+
+// The scan was ordered in chunks of the caller's order (host_cloud.h:device_order_scans). Chunk c is evaluated on the
+// context's stream into term buffer c % 2 while chunk c - 1 is replayed — the reference's float recurrence continued
+// from the sums chunk c - 2 ... left in d_lik — on a stream of its own: the replay streams its terms at memory speed,
+// the evaluation is bound by VALU issue, and the two share the GPU well; the buffer holds two chunks, not the scan.
+int launch_chunked_replay(const MeasureCall& c)
+{
+  mcl3dl_hip_ctx* ctx = c.ctx;
+  const MeasurePlan& pl = c.plan;
+  const size_t chunk = pl.chunk, n_p = c.n_p;
+  const int ns = c.ns, np = c.np;
+  const int n_chunks = static_cast<int>((static_cast<size_t>(ns) + chunk - 1) / chunk);
+  double* const psum = ctx->lik_partial_sum.as<double>();
+  unsigned* const pcnt = ctx->lik_partial_cnt.as<unsigned>();
+  float* const buf[2] = { pl.strict_terms,
+                          pl.strict_terms + strict_terms_bytes(n_p, static_cast<int>(chunk), pl.group_size) / sizeof(float) };
+  bool failed = false;
+  for (int k = 0; k < n_chunks && !failed; ++k)
+  {
+    const size_t first = static_cast<size_t>(k) * chunk;
+    const int c_ns = static_cast<int>(std::min(chunk, static_cast<size_t>(ns) - first));
+    const int c_tiles = (c_ns + 255) / 256, tile0 = static_cast<int>(first / 256);
+    if (k >= 2)
+      failed = failed || hipStreamWaitEvent(ctx->stream, ctx->ev_replay[k & 1], 0) != hipSuccess;  // its buffer is free again
+    launch_tiled(c, c.scan + first, c_ns, c_tiles, psum + static_cast<size_t>(tile0) * n_p, pcnt + static_cast<size_t>(tile0) * n_p,
+                 ctx->scan_perm.as<uint32_t>() + first, buf[k & 1]);
+    failed = failed || hipEventRecord(ctx->ev_tiled[k & 1], ctx->stream) != hipSuccess ||
+             hipStreamWaitEvent(ctx->replay_stream, ctx->ev_tiled[k & 1], 0) != hipSuccess;
+    launch_replay(c, buf[k & 1], c_ns, ctx->replay_stream, k > 0 ? 1 : 0);
+    failed = failed || hipEventRecord(ctx->ev_replay[k & 1], ctx->replay_stream) != hipSuccess;
+  }
+  // match ratios (and nothing else: the likelihoods are the replay's) from the per-tile counts
+  hipLaunchKernelGGL(lik_finalize_kernel, dim3((np + 31) / 32), dim3(256), 0, ctx->stream, psum, pcnt, pl.n_tiles, np, ns,
+                     static_cast<float*>(nullptr), c.d_ratio, c.beam_ones());
+  if (failed || hipStreamWaitEvent(ctx->stream, ctx->ev_replay[(n_chunks - 1) & 1], 0) != hipSuccess)
+  {
+    const int r = ctx->fail(-2, "stream / event call failed in the chunked float-order replay: %s", hipGetErrorString(hipGetLastError()));
+    (void)hipStreamSynchronize(ctx->replay_stream);  // (nothing of the replay is still in flight when the caller hears of it)
+    return r;
+  }
+  return 0;
+}
+
+// strict_order 3: the chain forms of the tiled kernel, one launch of one device at a time (ChainSerial)
+int launch_chain(const MeasureCall& c)
+{
+  mcl3dl_hip_ctx* ctx = c.ctx;
+  const MeasurePlan& pl = c.plan;
+  ChainSerial& cs = chain_serial(ctx->device);
+  std::lock_guard<std::mutex> chain_lock(cs.m);
+  if (cs.ev)
+    HIP_TRY(hipStreamWaitEvent(ctx->stream, cs.ev, 0));
+  else
+    HIP_TRY(hipEventCreateWithFlags(&cs.ev, hipEventDisableTiming));
+  struct ChainDone  // (recorded behind the launch on every way out of this function)
+  {
+    hipEvent_t ev;
+    hipStream_t st;
+    ~ChainDone()
+    {
+      (void)hipEventRecord(ev, st);
+    }
+  } chain_done{ cs.ev, ctx->stream };
+  // (only the match ratio was asked for: the sum still has somewhere to go)
+  float* const lik_out = c.d_lik ? c.d_lik : ctx->chain_lik.as<float>();
+  const LikChain lc{ ctx->chain_carry.as<unsigned long long>(), pl.chain_tag0, lik_out, c.d_ratio, c.beam_ones(), ctx->chain_err };
+  const dim3 grid(static_cast<unsigned>(pl.blocks));
+  if (pl.lik == LikRoute::ChainMulti)
+    hipLaunchKernelGGL((likelihood_chain_multi_kernel<4, 4>), grid, dim3(256), 0, ctx->stream, c.d_pose, c.np, c.scan, c.ns,
+                       pl.n_tiles, pl.n_super, pl.n_groups, ctx->rg, c.lp, lc);
+  else if (pl.beam == BeamRoute::MergedChain)
+  {
+    LikBeamArgs a{};
+    a.ch = lc;
+    launch_lik_beam<true>(c, pl.blocks, c.scan, c.ns, pl.n_tiles, a);
+  }
+  else
+    dispatch_int<4, 8, 16>(pl.group_size, [&](auto g) {
+      dispatch_form(pl, [&](auto mode, auto coop, auto defer) {
+        hipLaunchKernelGGL((likelihood_tiled_kernel<decltype(g)::value, decltype(mode)::value, 8, decltype(coop)::value, decltype(defer)::value, true>),
+                           grid, dim3(256), 0, ctx->stream, c.d_pose, c.np, c.scan, c.ns, pl.n_tiles, pl.n_groups, ctx->lg, ctx->rg, c.lp,
+                           static_cast<double*>(nullptr), static_cast<unsigned*>(nullptr), static_cast<const uint32_t*>(nullptr),
+                           static_cast<float*>(nullptr), 0, lc);
+      });
+    });
+  return 0;
+}
+
+// the per-particle kernel, alone or with the beam kernel's work-groups (rays per beam work-group = its work-group size)
+void launch_particle(const MeasureCall& c)
+{
+  mcl3dl_hip_ctx* ctx = c.ctx;
+  const MeasurePlan& pl = c.plan;
+  // caller-order float sums inside the kernel: the permutation (device index -> caller's index) and the LDS row of
+  // chain_row_floats(ns) floats
+  const uint32_t* row_perm = pl.rows ? ctx->scan_perm.as<uint32_t>() : nullptr;
+  const size_t row_bytes = pl.rows ? sizeof(float) * static_cast<size_t>(chain_row_floats(c.ns)) : 0;
+  if (pl.beam == BeamRoute::MergedParticle)
+  {
+    LikParticleBeamArgs a{};
+    const Interleave il = merged_args(c, (pl.n_rays + pl.block - 1) / pl.block, c.np, &a);
+    a.scan = c.scan;
+    a.n_s = c.ns;
+    a.out_lik = c.d_lik;
+    a.out_ratio = c.d_ratio;
+    a.coop = pl.coop ? 1 : 0;
+    a.perm = row_perm;
+    a.lik8 = il.other8;
+    dispatch_int<64, 256>(pl.block, [&](auto b) {
+      constexpr int BLOCK = decltype(b)::value;
+      hipLaunchKernelGGL(lik_particle_beam_kernel<BLOCK>, dim3(static_cast<unsigned>(il.grid)), dim3(BLOCK), row_bytes, ctx->stream, a);
+    });
+    finish_beam(c, ctx->stream);
+    return;
+  }
+  dispatch_particle(pl.block, pl.mode, [&](auto b, auto m) {
+    constexpr int BLOCK = decltype(b)::value;
+    hipLaunchKernelGGL((likelihood_kernel<BLOCK, decltype(m)::value, false>), dim3(c.np), dim3(BLOCK), row_bytes, ctx->stream, c.d_pose,
+                       c.scan, c.ns, ctx->lg, ctx->rg, c.lp, c.d_lik, c.d_ratio, nullptr, pl.coop ? 1 : 0, row_perm);
+  });
+}
+
+int launch_lik(const MeasureCall& c)
+{
+  mcl3dl_hip_ctx* ctx = c.ctx;
+  const MeasurePlan& pl = c.plan;
+  if (pl.lik == LikRoute::Ones)
+  {
+    hipLaunchKernelGGL(fill_kernel, dim3((c.np + 255) / 256), dim3(256), 0, ctx->stream, c.d_lik, 1.0f, c.d_ratio, 0.0f, c.np);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
+  EventPair ep{};
+  TRY(timing_begin(ctx, MCL3DL_KERNEL_LIKELIHOOD, &ep));
+  if (pl.lik == LikRoute::Small)
+    launch_small(c);
+  else if (pl.chain())
+    TRY(launch_chain(c));
+  else if (pl.lik == LikRoute::Tiled && pl.strict_terms && pl.chunk && c.d_lik)
+    TRY(launch_chunked_replay(c));
+  else if (pl.lik == LikRoute::Tiled)
+    launch_tiled_scan(c);
+  else
+    launch_particle(c);
+  TRY(timing_end(ctx, ep));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// One scan update's likelihoods, match ratios and beam scores of n_p poses (each output may be null): ensure the map
+// structures, plan, enqueue the beam model, enqueue the likelihood-field model, join.
 int launch_measure(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, float* d_lik, float* d_ratio, float* d_beam,
-                   bool stats, double* stats6, LikTail* tail = nullptr)
+                   LikTail* tail = nullptr)
 {
   if (!ctx->has_scan)
     return ctx->fail(-5, "no scan uploaded: call mcl3dl_hip_upload_scan first");
@@ -511,648 +1110,74 @@ int launch_measure(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, float* 
     return 0;
   if (n_p > 0x7fffffffu)
     return ctx->fail(-3, "too many particles");
-  const bool want_lik = (d_lik || d_ratio || stats);
-  const bool want_beam = (d_beam || stats);
-  // (the ray statistics are the DDA walk's: that launch stays on the DDA caster)
-  const bool kd = ctx->beam_raycast == 1 && !stats;
-  if (kd)
-    TRY(ensure_caster_structures(ctx, want_lik && ctx->n_s > 0, want_beam && ctx->n_b > 0, stats));
-  else
-    TRY(ensure_structures(ctx, want_lik && ctx->n_s > 0, want_beam && ctx->n_b > 0, stats));
-  const int np = static_cast<int>(n_p);
-  bool beam_forked = false, beam_ones_by_finalize = false;
-  bool merged = false;  // the beam kernel's work-groups ride in the tiled likelihood kernel's launch (lik_beam_kernel)
-  bool merged_particle = false;  // ... in the per-particle likelihood kernel's (lik_particle_beam_kernel)
-  bool merged_chain = false;     // ... in the tiled kernel's in-kernel-chain form (strict_order 3)
-  struct
-  {
-    long long n_rays = 0, blocks = 0;
-    BeamParams bp{};
-    const BeamOrigin* prepared = nullptr;
-  } merged_beam;
-  // any return between the fork and the join below (a failing HIP call) first waits for the second stream, so the caller
-  // never gets control back with beam kernels still writing its buffers
-  struct ForkGuard
-  {
-    mcl3dl_hip_ctx* c;
-    bool armed = false;
-    ~ForkGuard()
-    {
-      if (armed)
-        (void)hipStreamSynchronize(c->aux_stream);
-    }
-  } fork_guard{ ctx };
-  LikPlan plan;
-  if (want_lik && !stats && ctx->n_s > 0)
-    TRY(plan_lik(ctx, n_p, static_cast<int>(ctx->n_s), &plan));
-  // are the likelihoods of this launch the reference's floats bit for bit (caller-order rows, the float-order replay, the
-  // in-kernel chain, or no terms at all)? pf::measure then adds the weights as the reference does, too (pf_float_order)
-  if (want_lik && !stats)
-    ctx->lik_exact = ctx->n_s == 0 || plan.rows || plan.chain || plan.strict_terms != nullptr;
-  if (stats && ctx->n_s > 0)
-    TRY(ensure(ctx, ctx->tested, sizeof(double) * n_p));
-  // ---- beam model (enqueued first: on its own stream when both models run, see mcl3dl_hip_ctx::aux_stream)
+  const bool want_lik = d_lik || d_ratio, want_beam = d_beam != nullptr;
+  TRY(ensure_caster_structures(ctx, want_lik && ctx->n_s > 0, want_beam && ctx->n_b > 0));
+  MeasurePlan plan;
+  TRY(plan_measure(ctx, n_p, want_lik, d_lik != nullptr, want_beam, &plan));
+  const MeasureCall c{ ctx,  plan, d_pose, n_p, static_cast<int>(n_p), d_lik, d_ratio, d_beam, tail, lik_params(ctx),
+                       ctx->scan_lik.as<float4>(), static_cast<int>(ctx->n_s) };
+  ForkGuard fork_guard{ ctx };
+  // (the beam model is enqueued first: on its own stream when both models run, see mcl3dl_hip_ctx::aux_stream)
   if (want_beam)
-  {
-    if (ctx->n_b == 0)
-    {
-      // (1, 0) for every particle; with the tiled likelihood kernel behind it the per-particle finalize writes the ones
-      beam_ones_by_finalize = !stats && d_beam && want_lik && ctx->n_s > 0 && plan.tiled;
-      if (!stats && !beam_ones_by_finalize)
-        hipLaunchKernelGGL(fill_kernel, dim3((np + 255) / 256), dim3(256), 0, ctx->stream, d_beam, 1.0f,
-                           static_cast<float*>(nullptr), 0.0f, np);
-    }
-    else
-    {
-      TRY(ensure_pow_table(ctx));
-      const BeamParams bp = beam_params(ctx);
-      const long long n_rays = static_cast<long long>(n_p) * static_cast<long long>(ctx->n_b);
-      const long long blocks = (n_rays + 255) / 256;
-      if (blocks > 0x7fffffffLL)
-        return ctx->fail(-3, "too many rays for one launch");
-      {
-        const size_t cap0 = ctx->penalty.cap;
-        TRY(ensure(ctx, ctx->penalty, sizeof(unsigned) * n_p));
-        if (ctx->penalty.cap != cap0)
-          ctx->penalty_clean_n = 0;  // (a new allocation: nothing is known about its content)
-      }
-      // (the prepared origins and the launches of both models below are the DDA walk's: the kd-tree caster runs as a launch of
-      // its own, behind or — from overlap_min_rays rays — beside the likelihood kernel on the second stream)
-      const bool beam_prepared = !kd && !stats && ctx->beam_prepare && n_rays >= ctx->beam_prepare_min_rays &&
-                                 static_cast<long long>(n_p) * static_cast<long long>(ctx->n_o) < 0x7fffffffLL;
-      if (beam_prepared)
-        TRY(ensure(ctx, ctx->beam_origin, sizeof(BeamOrigin) * n_p * ctx->n_o));
-      if (stats)
-        TRY(ensure(ctx, ctx->ray_stats, sizeof(RayStats)));
-      // Both models in ONE launch (lik_beam_kernel, update_kernels.h: the two kernels' work-groups interleaved, so that every CU
-      // hosts both all the way) whenever the likelihood side is the tiled kernel's cooperative fp64-tree form (G <= 16) and the beam side is large
-      // enough to be worth interleaving: the beam kernel is NOT launched here but with the tiled kernel below.
-      // Not in front of a LONG caller-order replay (replay_is_long below): on two streams that replay — memory-bound, VALU idle —
-      // overlaps the rest of the beam kernel, which the lock-step interleave cannot offer (C5 shard: 3.09 against 3.14 ms).
-      // Measured, C3: 0.3446 (two streams) -> 0.3313 ms; 4096 rays per particle: 1.0855 -> 1.0070 (profiles/r06s_lik_beam_one_launch.txt).
-      // (the per-particle likelihood kernel's 256-thread form takes the beam kernel's work-groups along the same way:
-      // lik_particle_beam_kernel)
-      merged_particle = !kd && ctx->overlap_models && !stats && want_lik && ctx->n_s > 0 && !plan.tiled && !plan.small && !plan.chain &&
-                        ctx->lik_index == 2 && !(np <= ctx->lik_wide_max_particles && ctx->n_s > 512) && blocks >= 16 &&
-                        blocks < 0x0fffffffLL && ctx->dg.ov_n == 0;
-      // (the in-kernel chain's single-tile form, strict_order 3, rides the same way: a consumer's producer keeps its lower block index)
-      merged_chain = !kd && ctx->overlap_models && !stats && want_lik && ctx->n_s > 0 && plan.tiled && plan.chain && plan.chain_ppl != 4 &&
-                     plan.group_size <= 16 && ctx->lik_coop && ctx->lik_index == 2 && ctx->match_dist_min > 1e-5f && blocks >= 64 &&
-                     blocks < 0x3fffffffLL && plan.blocks < 0x3fffffffLL && ctx->dg.ov_n == 0;
-      // (in front of the caller-order replay: two streams only where they would be used — from overlap_min_rays rays — AND the replay
-      // is long enough to hide the beam kernel's tail behind: a term array of at least half a gigabyte. Measured, merged against
-      // streams: 4096 x 4096 + 128 rays - 12 %, 16384 x 4096 + 512 (268 MB) - 3 %, 8192 x 32768 + 512 (1 GB) + 1 %, the C5 shard + 2 %:
-      // profiles/r06s_lik_beam_one_launch.txt)
-      const bool replay_is_long = plan.strict_terms != nullptr && n_rays >= ctx->overlap_min_rays &&
-                                  strict_terms_bytes(n_p, static_cast<int>(ctx->n_s), plan.group_size) >= (static_cast<size_t>(512) << 20);
-      merged = !kd && ctx->overlap_models && !stats && want_lik && ctx->n_s > 0 && plan.tiled && !plan.chain && !plan.chunk &&
-               !replay_is_long && plan.group_size <= 16 && ctx->lik_coop && ctx->lik_index == 2 && ctx->match_dist_min > 1e-5f &&
-               blocks >= 64 && blocks < 0x3fffffffLL && plan.blocks < 0x3fffffffLL &&
-               ctx->dg.ov_n == 0;  // (the beam kernel's map-update-overlay form needs 66 VGPRs: it would spill inside the 64 of the merged launch)
-      // the second stream pays only for large launches: the fork / join events cost ~35 us (64 particles x 96 + 3 points:
-      // 52 us per update with them, 17 without), the overlap itself is worth ~5 % at C3 (2.1 M rays)
-      const bool overlap = !merged && !merged_particle && !merged_chain && ctx->overlap_models && !stats && want_lik && ctx->n_s > 0 && n_rays >= ctx->overlap_min_rays;
-      hipStream_t bs = overlap ? ctx->aux_stream : ctx->stream;
-      if (overlap)
-      {
-        HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
-        HIP_TRY(hipStreamWaitEvent(bs, ctx->ev_fork, 0));
-        fork_guard.armed = true;
-      }
-      EventPair ep{};
-      if (!stats)
-        TRY(timing_begin(ctx, MCL3DL_KERNEL_BEAM, &ep, bs));
-      // (beam_origin_kernel zeroes the counters itself; the update's tail kernel leaves them zeroed behind itself)
-      const bool counters_clean = ctx->penalty_clean_n >= n_p;
-      ctx->penalty_clean_n = 0;  // ... and from here on they are in use
-      if (!beam_prepared && !counters_clean)
-      {
-        // a kernel, not hipMemsetAsync: a memset node at the head of a single-stream captured update faulted on its third
-        // replay (ROCm 7.2; 700 particles x 3 rays, 128 x 48), the same zeroing as a kernel node does not
-        hipLaunchKernelGGL(fill_kernel, dim3((np + 255) / 256), dim3(256), 0, bs, reinterpret_cast<float*>(ctx->penalty.p), 0.0f,
-                           static_cast<float*>(nullptr), 0.0f, np);
-      }
-      if (stats)
-      {
-        HIP_TRY(hipMemsetAsync(ctx->ray_stats.p, 0, sizeof(RayStats), bs));
-        hipLaunchKernelGGL((beam_kernel<true>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, bs, d_pose,
-                           ctx->scan_beam.as<float4>(), static_cast<int>(ctx->n_b), ctx->origins.as<float4>(), n_rays,
-                           ctx->dg, bp, ctx->penalty.as<unsigned>(), ctx->ray_stats.as<RayStats>(),
-                           static_cast<const BeamOrigin*>(nullptr), static_cast<int>(ctx->n_o));
-      }
-      else
-      {
-        // what depends only on (particle, origin) is computed once per pair when the launch is large enough to pay for
-        // one more kernel
-        const BeamOrigin* prepared = nullptr;
-        if (beam_prepared)
-        {
-          const long long n_pairs = static_cast<long long>(n_p) * static_cast<long long>(ctx->n_o);
-          hipLaunchKernelGGL(beam_origin_kernel, dim3(static_cast<unsigned>((n_pairs + 255) / 256)), dim3(256), 0, bs, d_pose,
-                             np, ctx->origins.as<float4>(), static_cast<int>(ctx->n_o), ctx->dg,
-                             ctx->beam_origin.as<BeamOrigin>(), ctx->penalty.as<unsigned>());
-          prepared = ctx->beam_origin.as<BeamOrigin>();
-        }
-        if (merged || merged_particle || merged_chain)
-        {
-          // (the rays ride in the likelihood kernel's launch below; the beam model's last step comes behind that launch)
-          merged_beam.n_rays = n_rays;
-          merged_beam.blocks = blocks;
-          merged_beam.bp = bp;
-          merged_beam.prepared = prepared;
-        }
-        else
-        {
-        if (kd)
-        {
-          hipLaunchKernelGGL(beam_kd_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, bs, d_pose,
-                             ctx->scan_beam.as<float4>(), static_cast<int>(ctx->n_b), ctx->origins.as<float4>(), n_rays, ctx->lg,
-                             kd_ray_params(ctx), bp, ctx->penalty.as<unsigned>());
-        }
-        else
-        {
-        // (a map update rides on the DDA grid as an overlay: the kernel that looks it up is chosen only then)
-        const auto kernel = ctx->dg.ov_n > 0 ? beam_kernel<false, true> : beam_kernel<false, false>;
-        hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, bs, d_pose,
-                           ctx->scan_beam.as<float4>(), static_cast<int>(ctx->n_b), ctx->origins.as<float4>(), n_rays,
-                           ctx->dg, bp, ctx->penalty.as<unsigned>(), static_cast<RayStats*>(nullptr), prepared,
-                           static_cast<int>(ctx->n_o));
-        }
-        if (tail && tail->want_beam)
-          tail->beam_pending = true;
-        else
-          hipLaunchKernelGGL(beam_finalize_kernel, dim3((np + 255) / 256), dim3(256), 0, bs,
-                             ctx->penalty.as<unsigned>(), ctx->pow_table.as<float>(), ctx->beam_likelihood_min, d_beam,
-                             np);
-        }
-        TRY(timing_end(ctx, ep, bs));
-      }
-      if (overlap)
-      {
-        HIP_TRY(hipEventRecord(ctx->ev_join, bs));
-        beam_forked = true;
-      }
-    }
-    HIP_TRY(hipGetLastError());
-  }
-  // ---- likelihood-field model
+    TRY(launch_beam(c, &fork_guard));
   if (want_lik)
-  {
-    if (ctx->n_s == 0)
-    {
-      if (!stats)
-        hipLaunchKernelGGL(fill_kernel, dim3((np + 255) / 256), dim3(256), 0, ctx->stream, d_lik, 1.0f, d_ratio, 0.0f,
-                           np);
-    }
-    else
-    {
-      const LikParams lp = lik_params(ctx);
-      const int ns = static_cast<int>(ctx->n_s);
-      EventPair ep{};
-      if (stats)
-      {
-        hipLaunchKernelGGL((likelihood_kernel<256, 0, true>), dim3(np), dim3(256), 0, ctx->stream, d_pose,
-                           ctx->scan_lik.as<float4>(), ns, ctx->lg, ctx->rg, lp, nullptr, nullptr,
-                           ctx->tested.as<double>(), 0);
-      }
-      else
-      {
-        TRY(timing_begin(ctx, MCL3DL_KERNEL_LIKELIHOOD, &ep));
-        const float4* scan = ctx->scan_lik.as<float4>();
-        const bool tiled = plan.tiled, small = plan.small;
-        // the cooperative form's sqrt needs match_dist_min > 1.2e-7 m (likelihood_kernels.h:sqrt_in_radius)
-        const int coop_arg = (ctx->lik_coop && ctx->lik_index == 2 && ctx->match_dist_min > 1e-5f) ? 1 : 0;
-        const int group_size = plan.group_size;
-        float* strict_terms = plan.strict_terms;
-        // caller-order float sums inside the per-particle kernels: the permutation (device index -> caller's index) and the
-        // LDS row of chain_row_floats(ns) floats
-        const uint32_t* row_perm = plan.rows ? ctx->scan_perm.as<uint32_t>() : nullptr;
-        const size_t row_bytes = plan.rows ? sizeof(float) * static_cast<size_t>(chain_row_floats(ns)) : 0;
-        if (small)
-        {
-          const int W = plan.W;
-          const long long blocks = plan.blocks;
-#define LAUNCH_SMALL(WW, MODE)                                                                                         \
-  hipLaunchKernelGGL((likelihood_small_kernel<WW, MODE>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0,           \
-                     ctx->stream, d_pose, np, scan, ns, ctx->lg, ctx->rg, lp, d_lik, d_ratio, coop_arg, row_perm)
-#define LAUNCH_SMALL_W(MODE)       \
-  switch (W)                       \
-  {                                \
-    case 1: LAUNCH_SMALL(1, MODE); break;   \
-    case 2: LAUNCH_SMALL(2, MODE); break;   \
-    case 4: LAUNCH_SMALL(4, MODE); break;   \
-    case 8: LAUNCH_SMALL(8, MODE); break;   \
-    case 16: LAUNCH_SMALL(16, MODE); break; \
-    default: LAUNCH_SMALL(32, MODE); break; \
-  }
-          if (ctx->lik_index == 2)
-          {
-            LAUNCH_SMALL_W(2)
-          }
-          else
-          {
-            LAUNCH_SMALL_W(0)
-          }
-#undef LAUNCH_SMALL_W
-#undef LAUNCH_SMALL
-        }
-        else if (tiled)
-        {
-          const int G = group_size;
-          const int n_tiles = plan.n_tiles, n_groups = plan.n_groups;
-          const long long blocks = plan.blocks;
-#define LAUNCH_TILED(GG, MODE, WW, CC, DD)                                                                             \
-  hipLaunchKernelGGL((likelihood_tiled_kernel<GG, MODE, WW, CC, DD>), dim3(static_cast<unsigned>(t_blocks)), dim3(256), 0, \
-                     ctx->stream, d_pose, np, t_scan, t_ns, t_tiles, n_groups, ctx->lg, ctx->rg, lp, t_psum, t_pcnt, \
-                     t_perm, t_terms, STRICT_SKEW4)
-          const bool coop = coop_arg != 0;
-          const bool defer = coop && lik_defer_active(ctx);
-          // the launch of both models (lik_beam_kernel): the beam side and the interleave for a tiled grid of t_blocks work-groups —
-          // rounds of beam8 x 8 beam work-groups + tiled8 x 8 tiled ones, beam8 : tiled8 ~ the two grids' ratio (each at most 8)
-          const auto merged_args = [&](long long t_blocks, LikBeamArgs& a) -> long long
-          {
-            const long long nbb = merged_beam.blocks;
-            uint32_t beam8 = 1, tiled8 = 1;
-            if (nbb >= t_blocks)
-              beam8 = static_cast<uint32_t>(std::min<long long>(8, (nbb + t_blocks / 2) / t_blocks));
-            else
-              tiled8 = static_cast<uint32_t>(std::min<long long>(8, (t_blocks + nbb / 2) / nbb));
-            const long long rounds = std::max((nbb + 8 * beam8 - 1) / (8 * beam8), (t_blocks + 8 * tiled8 - 1) / (8 * tiled8));
-            a.pose7 = d_pose;
-            a.n_p = np;
-            a.n_groups = plan.n_groups;
-            a.g = ctx->lg;
-            a.rg = ctx->rg;
-            a.prm = lp;
-            a.strict_skew4 = STRICT_SKEW4;
-            a.scan_beam = ctx->scan_beam.as<float4>();
-            a.n_b = static_cast<int>(ctx->n_b);
-            a.origins = ctx->origins.as<float4>();
-            a.n_rays = merged_beam.n_rays;
-            a.dg = ctx->dg;
-            a.bp = merged_beam.bp;
-            a.penalty = ctx->penalty.as<unsigned>();
-            a.prepared = merged_beam.prepared;
-            a.n_o = static_cast<int>(ctx->n_o);
-            a.beam8 = beam8;
-            a.tiled8 = tiled8;
-            a.n_beam_blocks = static_cast<uint32_t>(nbb);
-            a.n_tiled_blocks = static_cast<uint32_t>(t_blocks);
-            return rounds * 8 * (beam8 + tiled8);
-          };
-          // the beam model's last step behind such a launch: left to the update's tail kernel, or a launch of its own
-          const auto merged_beam_done = [&]()
-          {
-            if (tail && tail->want_beam)
-              tail->beam_pending = true;
-            else
-              hipLaunchKernelGGL(beam_finalize_kernel, dim3((np + 255) / 256), dim3(256), 0, ctx->stream, ctx->penalty.as<unsigned>(),
-                                 ctx->pow_table.as<float>(), ctx->beam_likelihood_min, d_beam, np);
-          };
-          if (plan.chain)
-          {
-            ChainSerial& cs = chain_serial(ctx->device);
-            std::lock_guard<std::mutex> chain_lock(cs.m);
-            if (cs.ev)
-              HIP_TRY(hipStreamWaitEvent(ctx->stream, cs.ev, 0));
-            else
-              HIP_TRY(hipEventCreateWithFlags(&cs.ev, hipEventDisableTiming));
-            struct ChainDone  // (recorded behind the launch on every way out of this block)
-            {
-              hipEvent_t ev;
-              hipStream_t st;
-              ~ChainDone()
-              {
-                (void)hipEventRecord(ev, st);
-              }
-            } chain_done{ cs.ev, ctx->stream };
-            float* lik_out = d_lik;
-            if (!lik_out)  // (only the match ratio was asked for: the sum still has somewhere to go)
-            {
-              TRY(ensure(ctx, ctx->chain_lik, sizeof(float) * n_p));
-              lik_out = ctx->chain_lik.as<float>();
-            }
-            const LikChain lc{ ctx->chain_carry.as<unsigned long long>(), plan.chain_tag0, lik_out, d_ratio,
-                               beam_ones_by_finalize ? d_beam : static_cast<float*>(nullptr), ctx->chain_err };
-            if (plan.chain_ppl == 4)
-            {
-              hipLaunchKernelGGL((likelihood_chain_multi_kernel<4, 4>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, ctx->stream,
-                                 d_pose, np, scan, ns, n_tiles, plan.n_super, n_groups, ctx->rg, lp, lc);
-            }
-            else if (merged_chain)
-            {
-              LikBeamArgs a{};
-              const long long grid = merged_args(blocks, a);
-              a.scan = scan;
-              a.n_s = ns;
-              a.n_tiles = n_tiles;
-              a.ch = lc;
-#define LAUNCH_MERGED_CHAIN(GG)                                                                                                 \
-  do                                                                                                                            \
-  {                                                                                                                             \
-    if (defer)                                                                                                                  \
-      hipLaunchKernelGGL((lik_beam_kernel<GG, true, false, true>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, ctx->stream, a);  \
-    else                                                                                                                        \
-      hipLaunchKernelGGL((lik_beam_kernel<GG, false, false, true>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, ctx->stream, a); \
-  } while (0)
-              switch (G)
-              {
-                case 4:
-                  LAUNCH_MERGED_CHAIN(4);
-                  break;
-                case 8:
-                  LAUNCH_MERGED_CHAIN(8);
-                  break;
-                default:
-                  LAUNCH_MERGED_CHAIN(16);
-                  break;
-              }
-#undef LAUNCH_MERGED_CHAIN
-              merged_beam_done();
-            }
-            else
-            {
-#define LAUNCH_CHAIN(GG, MODE, CC, DD)                                                                                  \
-  hipLaunchKernelGGL((likelihood_tiled_kernel<GG, MODE, 8, CC, DD, true>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, \
-                     ctx->stream, d_pose, np, scan, ns, n_tiles, n_groups, ctx->lg, ctx->rg, lp,              \
-                     static_cast<double*>(nullptr), static_cast<unsigned*>(nullptr),                                   \
-                     static_cast<const uint32_t*>(nullptr), static_cast<float*>(nullptr), 0, lc)
-#define LAUNCH_CHAIN_G(GG)              \
-  do                                    \
-  {                                     \
-    if (coop && defer)                  \
-      LAUNCH_CHAIN(GG, 2, true, true);  \
-    else if (coop)                      \
-      LAUNCH_CHAIN(GG, 2, true, false); \
-    else if (ctx->lik_index == 2)       \
-      LAUNCH_CHAIN(GG, 2, false, false);\
-    else                                \
-      LAUNCH_CHAIN(GG, 0, false, false);\
-  } while (0)
-            switch (G)
-            {
-              case 4:
-                LAUNCH_CHAIN_G(4);
-                break;
-              case 8:
-                LAUNCH_CHAIN_G(8);
-                break;
-              default:
-                LAUNCH_CHAIN_G(16);
-                break;
-            }
-#undef LAUNCH_CHAIN_G
-#undef LAUNCH_CHAIN
-            }
-          }
-          else
-          {
-#define LAUNCH_TILED_G(GG, WW)         \
-  do                                   \
-  {                                    \
-    if (coop && defer)                 \
-      LAUNCH_TILED(GG, 2, WW, true, true);   \
-    else if (coop)                     \
-      LAUNCH_TILED(GG, 2, WW, true, false);  \
-    else if (ctx->lik_index == 2)      \
-      LAUNCH_TILED(GG, 2, WW, false, false); \
-    else                               \
-      LAUNCH_TILED(GG, 0, WW, false, false); \
-  } while (0)
-          // one launch of the tiled kernel over t_ns points starting at t_scan (the whole scan, or one chunk of it)
-          const auto launch_tiled = [&](const float4* t_scan, int t_ns, int t_tiles, double* t_psum, unsigned* t_pcnt,
-                                        const uint32_t* t_perm, float* t_terms)
-          {
-            const long long full = t_tiles & ~7, rem = static_cast<long long>(t_tiles - full) * n_groups;
-            const long long t_blocks = 8 * ((full / 8) * n_groups + (rem + 7) / 8);  // (plan_lik's count, for this many tiles)
-            if (merged)
-            {
-              LikBeamArgs a{};
-              const long long grid = merged_args(t_blocks, a);
-              a.scan = t_scan;
-              a.n_s = t_ns;
-              a.n_tiles = t_tiles;
-              a.partial_sum = t_psum;
-              a.partial_cnt = t_pcnt;
-              a.scan_perm = t_perm;
-              a.strict_terms = t_terms;
-#define LAUNCH_MERGED_G(GG)                                                                                              \
-  do                                                                                                                     \
-  {                                                                                                                      \
-    if (defer)                                                                                                           \
-      hipLaunchKernelGGL((lik_beam_kernel<GG, true, false>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, ctx->stream, a);  \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((lik_beam_kernel<GG, false, false>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, ctx->stream, a); \
-  } while (0)
-              switch (G)
-              {
-                case 4:
-                  LAUNCH_MERGED_G(4);
-                  break;
-                case 8:
-                  LAUNCH_MERGED_G(8);
-                  break;
-                default:
-                  LAUNCH_MERGED_G(16);
-                  break;
-              }
-#undef LAUNCH_MERGED_G
-              merged_beam_done();
-              return;
-            }
-            switch (G)
-            {
-              case 4:
-                LAUNCH_TILED_G(4, 8);
-                break;
-              case 8:
-                LAUNCH_TILED_G(8, 8);
-                break;
-              case 32:
-                LAUNCH_TILED_G(32, 4);  // 33 KB of LDS per work-group: 4 wavefronts per SIMD at most
-                break;
-              default:
-                LAUNCH_TILED_G(16, 8);
-                break;
-            }
-          };
-          const auto launch_replay = [&](const float* terms, int r_ns, hipStream_t on, int accumulate)
-          {
-            switch (G)
-            {
-              case 4:
-                launch_strict_sum<4>(ctx, terms, r_ns, np, n_groups, d_lik, on, accumulate);
-                break;
-              case 8:
-                launch_strict_sum<8>(ctx, terms, r_ns, np, n_groups, d_lik, on, accumulate);
-                break;
-              case 32:
-                launch_strict_sum<32>(ctx, terms, r_ns, np, n_groups, d_lik, on, accumulate);
-                break;
-              default:
-                launch_strict_sum<16>(ctx, terms, r_ns, np, n_groups, d_lik, on, accumulate);
-                break;
-            }
-          };
-          double* const psum = ctx->lik_partial_sum.as<double>();
-          unsigned* const pcnt = ctx->lik_partial_cnt.as<unsigned>();
-          if (strict_terms && plan.chunk && d_lik)
-          {
-            // The scan was ordered in chunks of the caller's order (host_cloud.h:device_order_scans). Chunk c is evaluated on the
-            // context's stream into term buffer c % 2 while chunk c - 1 is replayed — the reference's float recurrence continued
-            // from the sums chunk c - 2 ... left in d_lik — on a stream of its own: the replay streams its terms at memory speed,
-            // the evaluation is bound by VALU issue, and the two share the GPU well; the buffer holds two chunks, not the scan.
-            const size_t chunk = plan.chunk;
-            const int n_chunks = static_cast<int>((static_cast<size_t>(ns) + chunk - 1) / chunk);
-            float* const buf[2] = { strict_terms,
-                                    strict_terms + strict_terms_bytes(n_p, static_cast<int>(chunk), G) / sizeof(float) };
-            struct ReplayGuard
-            {
-              mcl3dl_hip_ctx* c;
-              ~ReplayGuard()
-              {
-                (void)hipStreamSynchronize(c->replay_stream);
-              }
-            };
-            bool failed = false;
-            for (int c = 0; c < n_chunks && !failed; ++c)
-            {
-              const size_t first = static_cast<size_t>(c) * chunk;
-              const int c_ns = static_cast<int>(std::min(chunk, static_cast<size_t>(ns) - first));
-              const int c_tiles = (c_ns + 255) / 256, tile0 = static_cast<int>(first / 256);
-              if (c >= 2)
-                failed = failed || hipStreamWaitEvent(ctx->stream, ctx->ev_replay[c & 1], 0) != hipSuccess;  // its buffer is free again
-              launch_tiled(scan + first, c_ns, c_tiles, psum + static_cast<size_t>(tile0) * n_p, pcnt + static_cast<size_t>(tile0) * n_p,
-                           ctx->scan_perm.as<uint32_t>() + first, buf[c & 1]);
-              failed = failed || hipEventRecord(ctx->ev_tiled[c & 1], ctx->stream) != hipSuccess ||
-                       hipStreamWaitEvent(ctx->replay_stream, ctx->ev_tiled[c & 1], 0) != hipSuccess;
-              launch_replay(buf[c & 1], c_ns, ctx->replay_stream, c > 0 ? 1 : 0);
-              failed = failed || hipEventRecord(ctx->ev_replay[c & 1], ctx->replay_stream) != hipSuccess;
-            }
-            // match ratios (and nothing else: the likelihoods are the replay's) from the per-tile counts
-            hipLaunchKernelGGL(lik_finalize_kernel, dim3((np + 31) / 32), dim3(256), 0, ctx->stream, psum, pcnt, n_tiles, np, ns,
-                               static_cast<float*>(nullptr), d_ratio, beam_ones_by_finalize ? d_beam : static_cast<float*>(nullptr));
-            if (failed || hipStreamWaitEvent(ctx->stream, ctx->ev_replay[(n_chunks - 1) & 1], 0) != hipSuccess)
-            {
-              ReplayGuard drain{ ctx };
-              return ctx->fail(-2, "stream / event call failed in the chunked float-order replay: %s", hipGetErrorString(hipGetLastError()));
-            }
-          }
-          else
-          {
-          // (a chunk-ordered scan whose likelihoods nobody asked for: its permutation is chunk-relative, no terms are kept)
-          launch_tiled(scan, ns, n_tiles, psum, pcnt, ctx->scan_perm.as<uint32_t>(), plan.chunk ? nullptr : strict_terms);
-          if (tail && tail->want && !strict_terms && d_lik && d_ratio)
-          {
-            tail->pending = true;  // lik_pf_partial_kernel adds the tiles up
-            tail->n_tiles = n_tiles;
-            tail->beam_fill = beam_ones_by_finalize;
-          }
-          else
-          hipLaunchKernelGGL(lik_finalize_kernel, dim3((np + 31) / 32), dim3(256), 0, ctx->stream, psum, pcnt, n_tiles, np, ns,
-                               d_lik, d_ratio, beam_ones_by_finalize ? d_beam : static_cast<float*>(nullptr));
-          if (strict_terms && d_lik && !plan.chunk)
-            launch_replay(strict_terms, ns, ctx->stream, 0);
-          }
-#undef LAUNCH_TILED_G
-#undef LAUNCH_TILED
-          }
-        }
-        else
-        {
-#define LAUNCH_LIK(BLOCK, MODE)                                                                                   \
-  hipLaunchKernelGGL((likelihood_kernel<BLOCK, MODE, false>), dim3(np), dim3(BLOCK), row_bytes, ctx->stream, d_pose, scan, ns, \
-                     ctx->lg, ctx->rg, lp, d_lik, d_ratio, nullptr, coop_arg, row_perm)
-        if (merged_particle)
-        {
-          const int lik_block = ns <= 128 ? 64 : 256;  // (the work-group size LAUNCH_LIK below would take)
-          const long long nbb = (merged_beam.n_rays + lik_block - 1) / lik_block, npl = np;
-          uint32_t beam8 = 1, lik8 = 1;
-          if (nbb >= npl)
-            beam8 = static_cast<uint32_t>(std::min<long long>(8, (nbb + npl / 2) / npl));
-          else
-            lik8 = static_cast<uint32_t>(std::min<long long>(8, (npl + nbb / 2) / nbb));
-          const long long rounds = std::max((nbb + 8 * beam8 - 1) / (8 * beam8), (npl + 8 * lik8 - 1) / (8 * lik8));
-          LikParticleBeamArgs a{};
-          a.pose7 = d_pose;
-          a.n_p = np;
-          a.scan = scan;
-          a.n_s = ns;
-          a.g = ctx->lg;
-          a.rg = ctx->rg;
-          a.prm = lp;
-          a.out_lik = d_lik;
-          a.out_ratio = d_ratio;
-          a.coop = coop_arg;
-          a.perm = row_perm;
-          a.scan_beam = ctx->scan_beam.as<float4>();
-          a.n_b = static_cast<int>(ctx->n_b);
-          a.origins = ctx->origins.as<float4>();
-          a.n_rays = merged_beam.n_rays;
-          a.dg = ctx->dg;
-          a.bp = merged_beam.bp;
-          a.penalty = ctx->penalty.as<unsigned>();
-          a.prepared = merged_beam.prepared;
-          a.n_o = static_cast<int>(ctx->n_o);
-          a.beam8 = beam8;
-          a.lik8 = lik8;
-          a.n_beam_blocks = static_cast<uint32_t>(nbb);
-          if (lik_block == 64)
-            hipLaunchKernelGGL(lik_particle_beam_kernel<64>, dim3(static_cast<unsigned>(rounds * 8 * (beam8 + lik8))), dim3(64), row_bytes,
-                               ctx->stream, a);
-          else
-            hipLaunchKernelGGL(lik_particle_beam_kernel<256>, dim3(static_cast<unsigned>(rounds * 8 * (beam8 + lik8))), dim3(256), row_bytes,
-                               ctx->stream, a);
-          if (tail && tail->want_beam)
-            tail->beam_pending = true;
-          else
-            hipLaunchKernelGGL(beam_finalize_kernel, dim3((np + 255) / 256), dim3(256), 0, ctx->stream, ctx->penalty.as<unsigned>(),
-                               ctx->pow_table.as<float>(), ctx->beam_likelihood_min, d_beam, np);
-        }
-        else if (ctx->lik_index == 2)
-        {
-          if (ns <= 128)
-            LAUNCH_LIK(64, 2);
-          else if (np <= ctx->lik_wide_max_particles && ns > 512)
-            LAUNCH_LIK(1024, 2);  // few particles: 16 wavefronts share a scan — a quarter of the dependent load chains per lane
-          else
-            LAUNCH_LIK(256, 2);
-        }
-        else
-        {
-          if (ns <= 128)
-            LAUNCH_LIK(64, 0);
-          else
-            LAUNCH_LIK(256, 0);
-        }
-#undef LAUNCH_LIK
-        }
-        TRY(timing_end(ctx, ep));
-      }
-    }
-    HIP_TRY(hipGetLastError());
-  }
-  if (beam_forked)
+    TRY(launch_lik(c));
+  if (fork_guard.armed)
   {
     HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));  // later work on `stream` sees the beam scores
     fork_guard.armed = false;
   }
-  if (stats)
+  return 0;
+}
+
+// mcl3dl_hip_workload_stats: the work one update does — candidates tested by the likelihood model, steps / occupied cells /
+// tests of the beam model's DDA walk (the ray statistics are that walk's: this path stays on the DDA caster whatever
+// beam_raycast says) — counted by instrumented kernels; no result array is written.
+int measure_stats(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, double* stats6)
+{
+  if (!ctx->has_scan)
+    return ctx->fail(-5, "no scan uploaded: call mcl3dl_hip_upload_scan first");
+  if (n_p == 0)
+    return 0;
+  if (n_p > 0x7fffffffu)
+    return ctx->fail(-3, "too many particles");
+  TRY(ensure_structures(ctx, ctx->n_s > 0, ctx->n_b > 0, true));
+  const int np = static_cast<int>(n_p);
+  if (ctx->n_s > 0)
+    TRY(ensure(ctx, ctx->tested, sizeof(double) * n_p));
+  if (ctx->n_b > 0)
   {
-    std::vector<double> tested(ctx->n_s ? n_p : 0);
-    RayStats rs{ 0, 0, 0 };
-    if (ctx->n_s)
-      TRY(d2h(ctx, tested.data(), ctx->tested.p, sizeof(double) * n_p));
-    if (ctx->n_b)
-      TRY(d2h(ctx, &rs, ctx->ray_stats.p, sizeof(RayStats)));
-    TRY(sync_stream(ctx));
-    stats6[0] = std::accumulate(tested.begin(), tested.end(), 0.0);
-    stats6[1] = static_cast<double>(n_p) * static_cast<double>(ctx->n_s);
-    stats6[2] = static_cast<double>(rs.steps);
-    stats6[3] = static_cast<double>(rs.occupied);
-    stats6[4] = static_cast<double>(rs.tested);
-    stats6[5] = static_cast<double>(n_p) * static_cast<double>(ctx->n_b);
+    long long n_rays = 0, blocks = 0;
+    TRY(prepare_beam(ctx, n_p, &n_rays, &blocks));
+    TRY(ensure(ctx, ctx->ray_stats, sizeof(RayStats)));
+    const bool counters_clean = ctx->penalty_clean_n >= n_p;
+    ctx->penalty_clean_n = 0;
+    if (!counters_clean)
+      zero_penalty(ctx, np, ctx->stream);
+    HIP_TRY(hipMemsetAsync(ctx->ray_stats.p, 0, sizeof(RayStats), ctx->stream));
+    hipLaunchKernelGGL((beam_kernel<true>), dim3(static_cast<unsigned>(blocks)), dim3(256), 0, ctx->stream, d_pose,
+                       ctx->scan_beam.as<float4>(), static_cast<int>(ctx->n_b), ctx->origins.as<float4>(), n_rays, ctx->dg,
+                       beam_params(ctx), ctx->penalty.as<unsigned>(), ctx->ray_stats.as<RayStats>(),
+                       static_cast<const BeamOrigin*>(nullptr), static_cast<int>(ctx->n_o));
   }
+  HIP_TRY(hipGetLastError());
+  if (ctx->n_s > 0)
+    hipLaunchKernelGGL((likelihood_kernel<256, 0, true>), dim3(np), dim3(256), 0, ctx->stream, d_pose, ctx->scan_lik.as<float4>(),
+                       static_cast<int>(ctx->n_s), ctx->lg, ctx->rg, lik_params(ctx), nullptr, nullptr, ctx->tested.as<double>(), 0);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> tested(ctx->n_s ? n_p : 0);
+  RayStats rs{ 0, 0, 0 };
+  if (ctx->n_s)
+    TRY(d2h(ctx, tested.data(), ctx->tested.p, sizeof(double) * n_p));
+  if (ctx->n_b)
+    TRY(d2h(ctx, &rs, ctx->ray_stats.p, sizeof(RayStats)));
+  TRY(sync_stream(ctx));
+  stats6[0] = std::accumulate(tested.begin(), tested.end(), 0.0);
+  stats6[1] = static_cast<double>(n_p) * static_cast<double>(ctx->n_s);
+  stats6[2] = static_cast<double>(rs.steps);
+  stats6[3] = static_cast<double>(rs.occupied);
+  stats6[4] = static_cast<double>(rs.tested);
+  stats6[5] = static_cast<double>(n_p) * static_cast<double>(ctx->n_b);
   return 0;
 }
 
@@ -1161,7 +1186,6 @@ int pf_blocks(size_t n)
   const size_t b = (n + PF_BLOCK - 1) / PF_BLOCK;
   return static_cast<int>(std::min<size_t>(std::max<size_t>(b, 1), 1024));
 }
-
 
 // Does pf::measure on ONE GPU add the un-normalised weights as the reference does (pf.h:255-260: float, sequentially, particle
 // order; float_chain.h) instead of the fp64 tree? strict_order 1: always. The default (2): up to pf_fused_max = 1024 particles —
@@ -1187,16 +1211,11 @@ int launch_update_small(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, fl
     return 0;
   if (ctx->beam_raycast == 1 && ctx->n_b > 0)
     return 0;  // the one-launch kernel casts with the DDA walk: the kd-tree caster runs through the separate kernels
-  const int ns = static_cast<int>(ctx->n_s);
-  if (ns > 0)
-  {
-    // (decided without plan_lik's buffer allocations: the tiled form needs per-tile partials this path never touches)
-    const int np = static_cast<int>(n_p);
-    const bool tiled = lik_mode(ctx, np, ns).tiled;
-    const bool small = !tiled && ns <= 32 && np >= 256 && ctx->lik_small;
-    if (tiled || small)
-      return 0;
-  }
+  const int np = static_cast<int>(n_p), ns = static_cast<int>(ctx->n_s);
+  // (decided without plan_lik's buffer allocations: the tiled form needs per-tile partials this path never touches)
+  const LikMode mode = ns > 0 ? lik_mode(ctx, np, ns) : LikMode{};
+  if (ns > 0 && (mode.tiled || lik_small_applies(ctx, mode, np, ns)))
+    return 0;
   TRY(ensure_structures(ctx, ns > 0, ctx->n_b > 0));
   if (ctx->n_b > 0 && ctx->dg.ov_n > 0)
     return 0;  // a map update rides on the DDA grid: the one-launch kernel is compiled without the overlay lookup
@@ -1210,7 +1229,7 @@ int launch_update_small(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, fl
   if (ctx->us_tickets.cap < sizeof(unsigned) * n_tickets)
   {
     TRY(ensure(ctx, ctx->us_tickets, sizeof(unsigned) * n_tickets));
-    // (a kernel, not hipMemsetAsync: see launch_measure — a memset node in a captured update faulted on replay)
+    // (a kernel, not hipMemsetAsync: see zero_penalty — a memset node in a captured update faulted on replay)
     const int n_words = static_cast<int>(ctx->us_tickets.cap / sizeof(unsigned));
     hipLaunchKernelGGL(fill_kernel, dim3((n_words + 255) / 256), dim3(256), 0, ctx->stream,
                        reinterpret_cast<float*>(ctx->us_tickets.p), 0.0f, static_cast<float*>(nullptr), 0.0f,
@@ -1218,13 +1237,13 @@ int launch_update_small(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, fl
   }
   UpdateSmallArgs a{};
   a.pose7 = d_pose;
-  a.n_p = static_cast<int>(n_p);
+  a.n_p = np;
   a.scan_lik = ctx->scan_lik.as<float4>();
   a.n_s = ns;
   a.g = ctx->lg;
   a.rg = ctx->rg;
   a.prm = lik_params(ctx);
-  a.coop = (ctx->lik_coop && ctx->lik_index == 2 && ctx->match_dist_min > 1e-5f) ? 1 : 0;
+  a.coop = lik_coop_active(ctx) ? 1 : 0;
   a.scan_beam = ctx->scan_beam.as<float4>();
   a.n_b = static_cast<int>(ctx->n_b);
   a.origins = ctx->origins.as<float4>();
@@ -1246,38 +1265,19 @@ int launch_update_small(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, fl
   a.emit = ho ? *ho : PfEmit{};
   // the reference's float recurrences, in its own order: the likelihood terms over the caller's scan (lik_particle's row) and —
   // where this launch also finishes pf::measure — the weights over the particles (pf.h:255-260)
-  const bool rows = ns > 0 && lik_mode(ctx, static_cast<int>(n_p), ns).rows;
-  const bool float_w = pf_float_order(ctx, n_p);
+  const bool rows = mode.rows, float_w = pf_float_order(ctx, n_p);
   a.perm = rows ? ctx->scan_perm.as<uint32_t>() : nullptr;
   a.float_order_w = float_w ? 1 : 0;
   ctx->lik_exact = rows || ns == 0;
-  const size_t row_floats = std::max<size_t>(rows ? chain_row_floats(ns) : 0, float_w ? chain_row_floats(static_cast<int>(n_p)) : 0);
-  const size_t row_bytes = sizeof(float) * row_floats;
+  const size_t row_bytes = sizeof(float) * std::max<size_t>(rows ? chain_row_floats(ns) : 0, float_w ? chain_row_floats(np) : 0);
   EventPair ep{};
   TRY(timing_begin(ctx, MCL3DL_KERNEL_UPDATE, &ep));
-  const unsigned grid = static_cast<unsigned>(n_p);
-#define LAUNCH_US(BLOCK, MODE) \
-  hipLaunchKernelGGL((update_small_kernel<BLOCK, MODE>), dim3(grid), dim3(BLOCK), row_bytes, ctx->stream, a)
-  // the work-group size the separate likelihood kernel would get (launch_measure), so that the lanes add in the same order
-  const bool narrow = ns <= 128 && ctx->n_b <= 128;
-  if (ctx->lik_index == 2)
-  {
-    if (ns <= 128)
-      LAUNCH_US(64, 2);
-    else if (static_cast<int>(n_p) <= ctx->lik_wide_max_particles && ns > 512)
-      LAUNCH_US(1024, 2);
-    else
-      LAUNCH_US(256, 2);
-  }
-  else
-  {
-    if (ns <= 128)
-      LAUNCH_US(64, 0);
-    else
-      LAUNCH_US(256, 0);
-  }
-  (void)narrow;
-#undef LAUNCH_US
+  // (the separate likelihood kernel's work-group size, so that the lanes add in the same order)
+  dispatch_particle(lik_particle_block(ctx, np, ns), ctx->lik_index == 2 ? 2 : 0, [&](auto b, auto m) {
+    constexpr int BLOCK = decltype(b)::value;
+    hipLaunchKernelGGL((update_small_kernel<BLOCK, decltype(m)::value>), dim3(static_cast<unsigned>(n_p)), dim3(BLOCK), row_bytes,
+                       ctx->stream, a);
+  });
   TRY(timing_end(ctx, ep));
   HIP_TRY(hipGetLastError());
   return 1;
