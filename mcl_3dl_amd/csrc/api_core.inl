@@ -443,12 +443,23 @@ static int push_scan(mcl3dl_hip_ctx* ctx, const OrderedScan& o, bool sync_at_end
   return 0;
 }
 
-static int upload_scan_impl(mcl3dl_hip_ctx* ctx, const float* scan_lik_xyz, size_t n_s, const float* scan_beam_xyz,
-                            const uint32_t* scan_beam_origin, size_t n_b, const float* origins, size_t n_o,
-                            bool sync_at_end)
+// the raw scan of a host-buffer call, as the caller handed it over
+struct HostScan
+{
+  const float* scan_lik_xyz;
+  size_t n_s;
+  const float* scan_beam_xyz;
+  const uint32_t* scan_beam_origin;
+  size_t n_b;
+  const float* origins;
+  size_t n_o;
+};
+
+static int upload_scan_impl(mcl3dl_hip_ctx* ctx, const HostScan& scan, bool sync_at_end)
 {
   if (!ctx)
     return -1;
+  const auto& [scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o] = scan;
   // Large scans are ordered on the device (host_cloud.h:device_order_scans: raw points up, min / key / stable radix sort /
   // gather there — same keys, same order, same bits as the host ordering, which costs ~0.1 ms of one core at 16 k points);
   // small ones on the host, where a dozen launches would cost more than the sort.
@@ -490,7 +501,7 @@ static int upload_scan_impl(mcl3dl_hip_ctx* ctx, const float* scan_lik_xyz, size
 int mcl3dl_hip_upload_scan(mcl3dl_hip_ctx* ctx, const float* scan_lik_xyz, size_t n_s, const float* scan_beam_xyz,
                            const uint32_t* scan_beam_origin, size_t n_b, const float* origins, size_t n_o)
 {
-  return upload_scan_impl(ctx, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o, true);
+  return upload_scan_impl(ctx, { scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o }, true);
 }
 
 int mcl3dl_hip_scan_order_host(const float* scan_lik_xyz, size_t n_s, uint32_t* order)
@@ -556,21 +567,10 @@ int mcl3dl_hip_pf_partial_device(mcl3dl_hip_ctx* ctx, const float* d_weight, con
   if (world < 1 || rank < 0 || rank >= world || world > 4096)
     return ctx->fail(-3, "bad rank/world (%d/%d)", rank, world);
   HIP_TRY(hipSetDevice(ctx->device));
-  const int nb = pf_blocks(n_p);
-  TRY(ensure(ctx, ctx->wnew, sizeof(float) * n_p));
-  TRY(ensure(ctx, ctx->block_partials, sizeof(double) * 4 * nb));
-  EventPair ep{};
-  TRY(timing_begin(ctx, MCL3DL_KERNEL_PF, &ep));
-  hipLaunchKernelGGL(pf_partial_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_weight, d_lik, d_beam, d_extra,
-                     d_match_ratio, static_cast<int>(n_p), ctx->wnew.as<float>(), ctx->block_partials.as<double>());
-  hipLaunchKernelGGL(pf_reduce_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->block_partials.as<double>(), nb, rank,
-                     world, d_packed);
-  if (world == 1 && pf_float_order(ctx, n_p))
-    hipLaunchKernelGGL(pf_strict_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->wnew.as<float>(),
-                       static_cast<int>(n_p), d_packed);
-  TRY(timing_end(ctx, ep));
-  HIP_TRY(hipGetLastError());
-  return 0;
+  // (the first half reads its inputs only)
+  const PfCall c{ ctx, const_cast<float*>(d_weight), const_cast<float*>(d_lik), const_cast<float*>(d_beam), d_extra,
+                  const_cast<float*>(d_match_ratio), n_p, nullptr };
+  return pf_first_half(c, rank, world, d_packed);
 }
 
 int mcl3dl_hip_pf_apply_device(mcl3dl_hip_ctx* ctx, float* d_weight_inout, size_t n_p, int world,
@@ -583,159 +583,13 @@ int mcl3dl_hip_pf_apply_device(mcl3dl_hip_ctx* ctx, float* d_weight_inout, size_
   if (world < 1 || world > 4096)
     return ctx->fail(-3, "bad world size %d", world);
   HIP_TRY(hipSetDevice(ctx->device));
-  EventPair ep{};
-  TRY(timing_begin(ctx, MCL3DL_KERNEL_PF, &ep));
-  hipLaunchKernelGGL(pf_apply_kernel, dim3(pf_blocks(n_p)), dim3(PF_BLOCK), 0, ctx->stream, d_weight_inout,
-                     ctx->wnew.as<float>(), static_cast<int>(n_p), world, d_packed, d_stats4);
-  TRY(timing_end(ctx, ep));
-  HIP_TRY(hipGetLastError());
-  return 0;
+  const PfCall c{ ctx, d_weight_inout, nullptr, nullptr, nullptr, nullptr, n_p, d_stats4 };
+  return pf_second_half(c, world, d_packed);
 }
 
 // ---- host entry points -------------------------------------------------------------------------------------
 namespace
 {
-bool pf_is_split(const mcl3dl_hip_ctx* ctx, size_t n_p)
-{
-  return !(n_p <= static_cast<size_t>(std::min(ctx->pf_fused_max, PF_FUSED_MAX)) && ctx->pf_fused);
-}
-// is pf::measure of n_p particles on this GPU the split form with the fp64 sum of the weights? Then launch_measure may leave the
-// sum over the tiled kernel's per-tile partials to lik_pf_partial_kernel (LikTail).
-bool pf_takes_tiles(const mcl3dl_hip_ctx* ctx, size_t n_p)
-{
-  const bool fused = n_p <= static_cast<size_t>(std::min(ctx->pf_fused_max, PF_FUSED_MAX)) && ctx->pf_fused;
-  return !fused && !pf_float_order(ctx, n_p) && n_p <= static_cast<size_t>(1024) * PF_BLOCK;  // (one particle per thread of the grid)
-}
-
-// pf::measure on one GPU: the fused single-work-group kernel up to pf_fused_max particles (default 1024; the kernel takes up
-// to PF_FUSED_MAX = 4096 — same bits as the split form), the split form beyond.
-// ho (optional): page-locked arrays the last kernel writes the results to as well (PfEmit).
-// The split form on one GPU with the fp64 sum of the weights is TWO launches since round 6 (five with lik_finalize_kernel in
-// front until then): lik_pf_partial_kernel / pf_partial_kernel, then pf_apply_kernel whose every work-group runs pf_reduce_kernel's
-// reduction itself. Same arithmetic in the same association as the launches apart (the multi-GPU protocol still runs them apart,
-// the all-reduce between them): the same bits. Measured on one box, C2: 0.2344 -> 0.2303 ms per update, C3 0.3448 -> 0.3409
-// (profiles/r06p_tail_ab.txt); the earlier forms of the idea that LOST are in profiles/r06o_pf_two_launch_ab.txt.
-int pf_measure_single(mcl3dl_hip_ctx* ctx, float* d_weight, float* d_lik, float* d_beam, const float* d_extra,
-                      float* d_ratio, size_t n_p, float* d_stats4, const PfEmit* ho = nullptr, const LikTail* tail = nullptr)
-{
-  const PfEmit emit = ho ? *ho : PfEmit{};
-  const bool float_w = pf_float_order(ctx, n_p);
-  // the beam score from the penalty counts on the way (beam_finalize_kernel's step; the kernel zeroes every counter it reads)
-  const bool counts = tail && tail->beam_pending && (tail->pending || !float_w || !pf_is_split(ctx, n_p));
-  const BeamCounts bc = counts ? BeamCounts{ ctx->penalty.as<unsigned>(), ctx->pow_table.as<float>(), ctx->beam_likelihood_min, d_beam }
-                               : BeamCounts{ nullptr, nullptr, 0.0f, nullptr };
-  if (tail && tail->pending)
-  {
-    // launch_measure left the tiled kernel's per-tile partials where they are: lik_finalize_kernel's sum and pf_partial_kernel's
-    // product in one launch, one wavefront of pf_partial_kernel's blocks per work-group (pf_kernels.h)
-    const int n_waves = static_cast<int>((n_p + 63) / 64), nb = pf_blocks(n_p);
-    TRY(ensure(ctx, ctx->wnew, sizeof(float) * n_p));
-    TRY(ensure(ctx, ctx->block_partials, sizeof(double) * 16 * nb));  // (whole blocks of four wavefront partials)
-    const LikTiles lt{ ctx->lik_partial_sum.as<double>(), ctx->lik_partial_cnt.as<unsigned>(), tail->n_tiles, static_cast<int>(ctx->n_s),
-                       d_lik, d_ratio, tail->beam_fill ? d_beam : static_cast<float*>(nullptr), bc };
-    EventPair ep{};
-    TRY(timing_begin(ctx, MCL3DL_KERNEL_PF, &ep));
-    hipLaunchKernelGGL(lik_pf_partial_kernel, dim3(n_waves), dim3(256), 0, ctx->stream, lt, d_weight, d_beam, d_extra,
-                       static_cast<int>(n_p), ctx->wnew.as<float>(), ctx->block_partials.as<double>());
-    hipLaunchKernelGGL(pf_apply_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_weight, ctx->wnew.as<float>(),
-                       static_cast<int>(n_p), 1, static_cast<const double*>(nullptr), d_stats4, emit, d_lik, d_ratio, d_beam,
-                       ctx->block_partials.as<double>(), nb, n_waves, ctx->partial4.as<double>());
-    if (counts)
-      ctx->penalty_clean_n = n_p;  // (launched: the kernel zeroes every counter it reads)
-    TRY(timing_end(ctx, ep));
-    HIP_TRY(hipGetLastError());
-    return 0;
-  }
-  if (tail && tail->beam_pending && !counts)  // (the float-order split form: the beam model's last step as a launch after all)
-    hipLaunchKernelGGL(beam_finalize_kernel, dim3((static_cast<unsigned>(n_p) + 255) / 256), dim3(256), 0, ctx->stream,
-                       ctx->penalty.as<unsigned>(), ctx->pow_table.as<float>(), ctx->beam_likelihood_min, d_beam,
-                       static_cast<int>(n_p));
-  if (n_p <= static_cast<size_t>(std::min(ctx->pf_fused_max, PF_FUSED_MAX)) && ctx->pf_fused)
-  {
-    TRY(ensure(ctx, ctx->wnew, sizeof(float) * n_p));
-    EventPair ep{};
-    TRY(timing_begin(ctx, MCL3DL_KERNEL_PF, &ep));
-    hipLaunchKernelGGL(pf_fused_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_weight, d_lik, d_beam, d_extra, d_ratio,
-                       static_cast<int>(n_p), ctx->wnew.as<float>(), ctx->partial4.as<double>(), d_stats4, emit, float_w ? 1 : 0, bc);
-    if (counts)
-      ctx->penalty_clean_n = n_p;  // (launched: the kernel zeroes every counter it reads)
-    TRY(timing_end(ctx, ep));
-    HIP_TRY(hipGetLastError());
-    return 0;
-  }
-  if (!float_w)
-  {
-    const int nb = pf_blocks(n_p);
-    TRY(ensure(ctx, ctx->wnew, sizeof(float) * n_p));
-    TRY(ensure(ctx, ctx->block_partials, sizeof(double) * 4 * nb));
-    EventPair ep{};
-    TRY(timing_begin(ctx, MCL3DL_KERNEL_PF, &ep));
-    hipLaunchKernelGGL(pf_partial_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_weight, d_lik, d_beam, d_extra, d_ratio,
-                       static_cast<int>(n_p), ctx->wnew.as<float>(), ctx->block_partials.as<double>(), bc);
-    hipLaunchKernelGGL(pf_apply_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_weight, ctx->wnew.as<float>(),
-                       static_cast<int>(n_p), 1, static_cast<const double*>(nullptr), d_stats4, emit, d_lik, d_ratio, d_beam,
-                       ctx->block_partials.as<double>(), nb, 0, ctx->partial4.as<double>());
-    if (counts)
-      ctx->penalty_clean_n = n_p;  // (launched: the kernel zeroes every counter it reads)
-    TRY(timing_end(ctx, ep));
-    HIP_TRY(hipGetLastError());
-    return 0;
-  }
-  // the reference's float recurrence over the weights between the two (pf_strict_sum_kernel replaces the sum in `packed`)
-  TRY(mcl3dl_hip_pf_partial_device(ctx, d_weight, d_lik, d_beam, d_extra, d_ratio, n_p, 0, 1, ctx->partial4.as<double>()));
-  if (!ho)
-    return mcl3dl_hip_pf_apply_device(ctx, d_weight, n_p, 1, ctx->partial4.as<double>(), d_stats4);
-  EventPair ep{};
-  TRY(timing_begin(ctx, MCL3DL_KERNEL_PF, &ep));
-  hipLaunchKernelGGL(pf_apply_kernel, dim3(pf_blocks(n_p)), dim3(PF_BLOCK), 0, ctx->stream, d_weight, ctx->wnew.as<float>(),
-                     static_cast<int>(n_p), 1, ctx->partial4.as<double>(), d_stats4, emit, d_lik, d_ratio, d_beam);
-  TRY(timing_end(ctx, ep));
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
-// The first half of pf::measure behind launch_measure for a rank of a device group (rank / world: the packed layout of the update's
-// one all-reduce): what mcl3dl_hip_pf_partial_device launches, with the two steps launch_measure may have left to it (tail):
-// lik_finalize_kernel's sum over the tiled kernel's per-tile partials (lik_pf_partial_kernel, wavefront partials) and the beam
-// model's penalty count -> score (BeamCounts). Same arithmetic in the same association: the same bits.
-int pf_partial_behind_measure(mcl3dl_hip_ctx* ctx, const float* d_weight, float* d_lik, float* d_beam, const float* d_extra,
-                              float* d_ratio, size_t n_p, int rank, int world, double* d_packed, const LikTail& tail)
-{
-  if (!tail.pending && !tail.beam_pending)
-    return mcl3dl_hip_pf_partial_device(ctx, d_weight, d_lik, d_beam, d_extra, d_ratio, n_p, rank, world, d_packed);
-  const int nb = pf_blocks(n_p), n_waves = static_cast<int>((n_p + 63) / 64);
-  TRY(ensure(ctx, ctx->wnew, sizeof(float) * n_p));
-  TRY(ensure(ctx, ctx->block_partials, sizeof(double) * 16 * nb));
-  const BeamCounts bc = tail.beam_pending ? BeamCounts{ ctx->penalty.as<unsigned>(), ctx->pow_table.as<float>(), ctx->beam_likelihood_min, d_beam }
-                                          : BeamCounts{ nullptr, nullptr, 0.0f, nullptr };
-  EventPair ep{};
-  TRY(timing_begin(ctx, MCL3DL_KERNEL_PF, &ep));
-  if (tail.pending)
-  {
-    const LikTiles lt{ ctx->lik_partial_sum.as<double>(), ctx->lik_partial_cnt.as<unsigned>(), tail.n_tiles, static_cast<int>(ctx->n_s),
-                       d_lik, d_ratio, tail.beam_fill ? d_beam : static_cast<float*>(nullptr), bc };
-    hipLaunchKernelGGL(lik_pf_partial_kernel, dim3(n_waves), dim3(256), 0, ctx->stream, lt, d_weight, d_beam, d_extra,
-                       static_cast<int>(n_p), ctx->wnew.as<float>(), ctx->block_partials.as<double>());
-    hipLaunchKernelGGL(pf_reduce_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->block_partials.as<double>(), nb, rank, world,
-                       d_packed, n_waves);
-  }
-  else
-  {
-    hipLaunchKernelGGL(pf_partial_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_weight, d_lik, d_beam, d_extra, d_ratio,
-                       static_cast<int>(n_p), ctx->wnew.as<float>(), ctx->block_partials.as<double>(), bc);
-    hipLaunchKernelGGL(pf_reduce_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->block_partials.as<double>(), nb, rank, world,
-                       d_packed);
-  }
-  if (world == 1 && pf_float_order(ctx, n_p))
-    hipLaunchKernelGGL(pf_strict_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->wnew.as<float>(), static_cast<int>(n_p),
-                       d_packed);
-  if (tail.beam_pending)
-    ctx->penalty_clean_n = n_p;  // (launched: the kernel zeroes every counter it reads)
-  TRY(timing_end(ctx, ep));
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
-
 // ho (optional): page-locked arrays for the results; *host_written comes back true when the update's last kernel wrote
 // them — otherwise the caller copies the device arrays home.
 int enqueue_update(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, float* d_weight, const float* d_extra,
@@ -751,8 +605,10 @@ int enqueue_update(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, float* 
   tail.want = pf_takes_tiles(ctx, n_p) && d_lik && d_ratio && d_beam;
   tail.want_beam = d_beam != nullptr;
   TRY(launch_measure(ctx, d_pose, n_p, d_lik, d_ratio, d_beam, &tail));
-  TRY(pf_measure_single(ctx, d_weight, d_lik, d_beam, d_extra, d_ratio, n_p, d_stats4, ho, &tail));
-  return 0;
+  PfCall c{ ctx, d_weight, d_lik, d_beam, d_extra, d_ratio, n_p, d_stats4 };
+  c.tail = &tail;
+  c.emit = ho;
+  return pf_one_gpu(c);
 }
 
 }  // namespace
@@ -814,17 +670,354 @@ int mcl3dl_hip_upload_poses(mcl3dl_hip_ctx* ctx, const float* pose, size_t n_p)
 
 namespace
 {
-// slice = STAGE_FRONT_ONLY: only the front half of measure_update_staged — inputs taken over and scans ordered by the staging
-// launch(es) — and return 3 (0: not eligible, nothing done). What a rank of a device group runs ahead of its kernels.
-constexpr size_t STAGE_FRONT_ONLY = ~static_cast<size_t>(0);
-int measure_update_staged(mcl3dl_hip_ctx* ctx, const float* pose, const float* extra, float* weight_inout, size_t n_p,
-                          const float* scan_lik_xyz, size_t n_s, const float* scan_beam_xyz, const uint32_t* scan_beam_origin,
-                          size_t n_b, const float* origins, size_t n_o, float* out_lik, float* out_match_ratio,
-                          float* out_beam, float* st4, bool with_pf = true, size_t slice = 0);
-// where the staging launch left the weights it took over
-inline float* staged_weights(mcl3dl_hip_ctx* ctx)
+// { stats4 | weights | lik | ratio | beam } of n_p particles, each part on a 64-byte boundary, in ONE allocation: the device
+// block of a host-buffer update (ctx->upd_block — its results go home in one copy instead of five, ~5 us each at C2's sizes) and
+// the page-locked block the update's last kernel writes them to
+struct UpdBlock
 {
-  return reinterpret_cast<float*>(ctx->upd_block.as<char>() + 64);
+  char* base;
+  size_t fb, rpart;  // bytes of a part, and from one part to the next
+  UpdBlock(void* block, size_t n_p) : base(static_cast<char*>(block)), fb(sizeof(float) * n_p), rpart(stride(n_p))
+  {
+  }
+  static size_t stride(size_t n_p)
+  {
+    return (sizeof(float) * n_p + 63) & ~static_cast<size_t>(63);
+  }
+  static size_t bytes(size_t n_p)
+  {
+    return 64 + 4 * stride(n_p);
+  }
+  float* stats4() const
+  {
+    return reinterpret_cast<float*>(base);
+  }
+  float* part(int k) const  // 0: weights, 1: lik, 2: ratio, 3: beam
+  {
+    return reinterpret_cast<float*>(base + 64 + k * rpart);
+  }
+  // the block home in one copy, up to the last part the caller asked for
+  int copy_home(mcl3dl_hip_ctx* ctx, float* st4, float* w, float* lik, float* ratio, float* beam) const
+  {
+    const D2hPiece pieces[5] = { { st4, 0, 4 * sizeof(float) },
+                                 { w, 64, fb },
+                                 { lik, 64 + rpart, fb },
+                                 { ratio, 64 + 2 * rpart, fb },
+                                 { beam, 64 + 3 * rpart, fb } };
+    const size_t upto = 64 + (beam ? 3 : ratio ? 2 : lik ? 1 : 0) * rpart + fb;
+    return d2h_block(ctx, base, upto, pieces, 5);
+  }
+};
+// where the staging launch left the weights it took over
+inline float* staged_weights(mcl3dl_hip_ctx* ctx, size_t n_p)
+{
+  return UpdBlock(ctx->upd_block.p, n_p).part(0);
+}
+
+// Where a kernel writes `bytes` of results for the caller's array `user`: the array itself where it is page-locked, else `slot`
+// (page-locked staging memory) — copy_home: handed to the caller's array at the next synchronisation of the stream.
+float* host_target(mcl3dl_hip_ctx* ctx, float* user, void* slot, size_t bytes, bool copy_home)
+{
+  if (ctx->is_pinned(user, bytes))
+    return user;
+  if (copy_home)
+    ctx->stage_out.push_back({ user, slot, bytes });
+  return static_cast<float*>(slot);
+}
+
+// pf::measure's four statistics { entropy, min match ratio, max match ratio, weights restored } into the caller's variables
+void unpack_stats4(const float* st, float* entropy, float* match_ratio_min, float* match_ratio_max, int* restored)
+{
+  if (entropy)
+    *entropy = st[0];
+  if (match_ratio_min)
+    *match_ratio_min = st[1];
+  if (match_ratio_max)
+    *match_ratio_max = st[2];
+  if (restored)
+    *restored = st[3] != 0.0f;
+}
+
+// The front of a host-buffer call with scan_stage_kernel: one launch takes over scans, poses (may be null: those
+// mcl3dl_hip_upload_poses left on the device), weights and odometry factors (either may be null), ordering included. Returns 1
+// when the inputs were taken over this way — poses in ctx->pose, weights at staged_weights(), factors in ctx->extra, the
+// context's scan installed —, 0 when the call is not eligible (nothing done: the caller runs the general path), < 0 on error.
+// A device group's rank runs this ahead of its own kernels.
+int stage_inputs(mcl3dl_hip_ctx* ctx, const float* pose, const float* extra, const float* weight, size_t n_p, HostScan scan)
+{
+  auto& [scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o] = scan;
+  if (!ctx->update_stage || n_s > 0x0fffffffu || n_b > 0x0fffffffu || n_o > 4096 || n_p > 0x7fffffffu / 8)
+    return 0;
+  if ((n_s && !scan_lik_xyz) || (n_b && (!scan_beam_xyz || !origins || n_o == 0)))
+    return ctx->fail(-3, "null scan array");
+  if (scan_beam_origin)
+    for (size_t i = 0; i < n_b; ++i)
+      if (scan_beam_origin[i] >= n_o)
+        return ctx->fail(-3, "beam point %zu names origin %u but only %zu origins were given", i, scan_beam_origin[i], n_o);
+  if (!origins)
+    n_o = 0;
+  // Whatever has to be (re)built lazily — the index after a map change, the DDA grid, the penalty table — is built NOW: a
+  // build synchronises the stream, recycles the staging memory and (polled) uses up completion sequence numbers, none of which
+  // may happen between the allocations below and the kernels that read and write them.
+  // (test hook "test_late_structures", MCL3DL_HIP_TEST_HOOKS=1 only: leave the builds to launch_measure as round 4's last but
+  // one commit did — the hazard tests/test_gpu_api_fuzz.py is asked to find again)
+  if (!ctx->test_late_structures)
+  {
+    TRY(ensure_caster_structures(ctx, n_s > 0, n_b > 0));
+    if (n_b > 0)
+      TRY(ensure_pow_table(ctx, n_b));
+  }
+  const size_t fb = sizeof(float) * n_p;
+  // ---- the input block: { poses | weights | odometry factor | likelihood xyz | beam xyz | beam origin ids | origins }
+  struct Part
+  {
+    const void* src;
+    size_t bytes;
+    const void* dev;  // where the kernel reads it
+  };
+  Part part[7] = { { pose, pose ? 7 * fb : 0, nullptr },
+                   { weight, weight ? fb : 0, nullptr },
+                   { extra, extra ? fb : 0, nullptr },
+                   { scan_lik_xyz, sizeof(float) * 3 * n_s, nullptr },
+                   { scan_beam_xyz, sizeof(float) * 3 * n_b, nullptr },
+                   { scan_beam_origin, scan_beam_origin ? sizeof(uint32_t) * n_b : 0, nullptr },
+                   { origins, sizeof(float) * 3 * n_o, nullptr } };
+  const bool zero_copy = ctx->zero_copy();
+  const auto up = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
+  size_t staged_bytes = 0, off[7];
+  for (int k = 0; k < 7; ++k)
+  {
+    off[k] = staged_bytes;
+    if (part[k].bytes && !(zero_copy && ctx->is_pinned(part[k].src, part[k].bytes)))
+      staged_bytes += up(part[k].bytes);
+  }
+  char* staged = nullptr;
+  if (staged_bytes)
+  {
+    if (staged_bytes > STAGE_MAX_COPY)
+      return 0;
+    staged = static_cast<char*>(stage_alloc(ctx, staged_bytes));
+    if (!staged)
+      return 0;
+  }
+  // ---- device arrays
+  TRY(ensure(ctx, ctx->pose, 7 * fb));
+  TRY(ensure(ctx, ctx->upd_block, UpdBlock::bytes(n_p)));
+  TRY(ensure(ctx, ctx->extra, fb));
+  TRY(ensure(ctx, ctx->partial4, sizeof(double) * 4));
+  TRY(ensure(ctx, ctx->sp_samp[0], sizeof(float4) * std::max<size_t>(n_s, 1)));
+  TRY(ensure(ctx, ctx->sp_samp[1], sizeof(float4) * std::max<size_t>(n_b, 1)));
+  TRY(ensure(ctx, ctx->cl_minmax, sizeof(float) * 6 + sizeof(unsigned long long)));
+  TRY(ensure(ctx, ctx->cl_err, sizeof(int)));
+  TRY(ensure_scan_block(ctx, n_s, n_b, n_o));
+  if (!zero_copy && staged_bytes)
+    TRY(ensure(ctx, ctx->stage_in_dev, staged_bytes));
+  for (int k = 0; k < 7; ++k)
+  {
+    if (!part[k].bytes)
+      continue;
+    if (zero_copy && ctx->is_pinned(part[k].src, part[k].bytes))
+    {
+      part[k].dev = part[k].src;
+      continue;
+    }
+    memcpy(staged + off[k], part[k].src, part[k].bytes);
+    part[k].dev = zero_copy ? staged + off[k] : ctx->stage_in_dev.as<char>() + off[k];
+  }
+  if (!zero_copy && staged_bytes)
+  {
+    HIP_TRY(hipMemcpyAsync(ctx->stage_in_dev.p, staged, staged_bytes, hipMemcpyHostToDevice, ctx->stream));
+    ctx->stage_pending += staged_bytes;
+  }
+  StageArgs a{};
+  a.presorted = ctx->scan_presorted;
+  a.in_pose = static_cast<const float*>(part[0].dev);
+  a.in_w = static_cast<const float*>(part[1].dev);
+  a.in_extra = static_cast<const float*>(part[2].dev);
+  a.d_pose = ctx->pose.as<float>();
+  a.d_w = staged_weights(ctx, n_p);
+  a.d_extra = ctx->extra.as<float>();
+  a.n_p = static_cast<int>(n_p);
+  a.in_lik_xyz = static_cast<const float*>(part[3].dev);
+  a.n_s = static_cast<int>(n_s);
+  a.raw_lik = ctx->sp_samp[0].as<float4>();
+  a.mm6 = ctx->cl_minmax.as<float>();
+  a.mm_cnt = reinterpret_cast<unsigned long long*>(ctx->cl_minmax.as<float>() + 6);
+  a.out_lik = ctx->scan_lik.as<float4>();
+  a.out_perm = ctx->scan_perm.as<uint32_t>();
+  a.in_beam_xyz = static_cast<const float*>(part[4].dev);
+  a.in_beam_origin = static_cast<const uint32_t*>(part[5].dev);
+  a.n_b = static_cast<int>(n_b);
+  a.raw_beam = ctx->sp_samp[1].as<float4>();
+  a.out_beam = ctx->scan_beam.as<float4>();
+  a.in_origins = static_cast<const float*>(part[6].dev);
+  a.n_o = static_cast<int>(n_o);
+  a.d_origins = ctx->origins.as<float4>();
+  a.d_err = ctx->cl_err.as<int>();
+  const size_t n_copy = 9 * n_p;
+  const size_t n_max = std::max(n_s, n_b);
+  EventPair ep{};
+  TRY(timing_begin(ctx, MCL3DL_KERNEL_STAGE, &ep));
+  if (n_max <= static_cast<size_t>(ST_MAX_POINTS))
+  {
+    // everything in one launch: one work-group orders each scan
+    const unsigned grid = 2u + static_cast<unsigned>(std::min<size_t>(std::max<size_t>((n_copy + RS_THREADS - 1) / RS_THREADS, 1), 64));
+    hipLaunchKernelGGL((scan_stage_kernel<ST_MAX_ROUNDS>), dim3(grid), dim3(RS_THREADS), 0, ctx->stream, a);
+    HIP_TRY(hipGetLastError());
+  }
+  else
+  {
+    // larger scans: one launch brings the arrays over (+ the min / max the Morton keys need), the chip-wide sort orders them
+    // (256 points per work-group and round; the copies 16 bytes per thread: stage_kernels.h)
+    const unsigned nb_lik = n_s ? static_cast<unsigned>(std::min<size_t>((n_s + 255) / 256, 256)) : 0u;
+    const unsigned nb_beam = n_b ? static_cast<unsigned>(std::min<size_t>((n_b + 255) / 256, 64)) : (n_o ? 1u : 0u);
+    const unsigned nb_copy = static_cast<unsigned>(std::min<size_t>(std::max<size_t>((7 * n_p + 1023) / 1024, 1), 64));
+    MinMaxOut mm{};
+    if (nb_lik)
+      TRY(minmax_out(ctx, nb_lik, &mm));
+    hipLaunchKernelGGL(stage_pack_kernel, dim3(nb_lik + nb_beam + nb_copy), dim3(256), 0, ctx->stream, a, mm, nb_lik, nb_beam);
+    HIP_TRY(hipGetLastError());
+    TRY(device_order_scans(ctx, n_s, n_b, nullptr, n_o, true, ctx->cl_err.as<int>()));
+  }
+  TRY(timing_end(ctx, ep));
+  // the context's scan state, as upload_scan_impl leaves it
+  if (n_b > ctx->pow_table_len)
+    ctx->pow_table_dirty = true;
+  if (n_s != ctx->n_s || n_b != ctx->n_b || n_o != ctx->n_o || !ctx->has_scan)
+    ++ctx->generation;
+  ctx->n_s = n_s;
+  ctx->n_b = n_b;
+  ctx->n_o = n_o;
+  ctx->has_scan = true;
+  ctx->sp_n_samp[0] = n_s;
+  ctx->sp_n_samp[1] = n_b;
+  if (pose)
+    ctx->poses_set(n_p);
+  return 1;
+}
+
+// page-locked room for the two models' three result arrays (null: no zero-copy, or the staging memory is used up)
+char* models_block(mcl3dl_hip_ctx* ctx, size_t n_p)
+{
+  return ctx->zero_copy() ? static_cast<char*>(stage_alloc(ctx, 3 * UpdBlock::stride(n_p))) : nullptr;
+}
+
+// Behind stage_inputs, the two models only: their per-particle results go home through a copy kernel into page-locked memory
+// (blk3: models_block) or D2H copies; the stream is synchronised.
+int deliver_models(mcl3dl_hip_ctx* ctx, size_t n_p, float* out_lik, float* out_match_ratio, float* out_beam, char* blk3)
+{
+  const UpdBlock dev(ctx->upd_block.p, n_p);
+  const bool lik_wanted = out_lik || out_match_ratio;
+  float* const user[3] = { out_lik, out_match_ratio, out_beam };
+  TRY(launch_measure(ctx, ctx->pose.as<float>(), n_p, lik_wanted ? dev.part(1) : nullptr, lik_wanted ? dev.part(2) : nullptr,
+                     out_beam ? dev.part(3) : nullptr));
+  if (blk3)
+  {
+    PfEmit e{};
+    float** slot[3] = { &e.lik, &e.ratio, &e.beam };
+    for (int k = 0; k < 3; ++k)
+      if (user[k])
+        *slot[k] = host_target(ctx, user[k], blk3 + k * dev.rpart, dev.fb, true);
+    hipLaunchKernelGGL(emit3_kernel, dim3(pf_blocks(n_p)), dim3(PF_BLOCK), 0, ctx->stream, e, dev.part(1), dev.part(2), dev.part(3),
+                       static_cast<int>(n_p));
+    HIP_TRY(hipGetLastError());
+    return sync_stream(ctx, true);
+  }
+  for (int k = 0; k < 3; ++k)
+    if (user[k])
+      TRY(d2h(ctx, user[k], dev.part(1 + k), dev.fb));
+  return sync_stream(ctx);
+}
+
+// ... in slices (mcl3dl_hip_measure_batch_begin; the completion word exists): the particles are evaluated slice by slice, each
+// slice's results leave for page-locked memory as soon as its kernels are through and a completion word follows them, so the
+// caller's per-particle loop (the reference's pf::measure, pf.h:255-260) runs while the later slices are still on the GPU.
+// Nothing is waited for: ctx->prog describes the batch in flight.
+int deliver_models_sliced(mcl3dl_hip_ctx* ctx, size_t n_p, size_t slice, float* out_lik, float* out_match_ratio, float* out_beam,
+                          char* blk3)
+{
+  const UpdBlock dev(ctx->upd_block.p, n_p);
+  const bool lik_wanted = out_lik || out_match_ratio;
+  float* const user[3] = { out_lik, out_match_ratio, out_beam };
+  mcl3dl_hip_ctx::BatchProgress& pg = ctx->prog;
+  pg = mcl3dl_hip_ctx::BatchProgress();
+  pg.n_p = n_p;
+  pg.slice = slice;
+  pg.n_slices = (n_p + slice - 1) / slice;
+  pg.seq0 = ctx->done_seq;
+  PfEmit e{};
+  float** slot[3] = { &e.lik, &e.ratio, &e.beam };
+  for (int k = 0; k < 3; ++k)
+    if (user[k])
+    {
+      *slot[k] = host_target(ctx, user[k], blk3 + k * dev.rpart, dev.fb, false);  // (progress_wait hands the slices over)
+      pg.user[k] = user[k];
+      pg.host[k] = *slot[k];
+    }
+  // both models of a slice on ONE stream: the second stream's fork / join events cost ~35 us of host time per launch
+  // (host_measure.h), which the caller's thread would pay once per slice before it can start on the results
+  struct OverlapOff
+  {
+    mcl3dl_hip_ctx* c;
+    int saved;
+    ~OverlapOff()
+    {
+      c->overlap_models = saved;
+    }
+  } overlap_off{ ctx, ctx->overlap_models };
+  ctx->overlap_models = 0;
+  for (size_t lo = 0; lo < n_p; lo += slice)
+  {
+    const size_t n = std::min(slice, n_p - lo);
+    TRY(launch_measure(ctx, ctx->pose.as<float>() + 7 * lo, n, lik_wanted ? dev.part(1) + lo : nullptr,
+                       lik_wanted ? dev.part(2) + lo : nullptr, out_beam ? dev.part(3) + lo : nullptr));
+    PfEmit es{};
+    es.lik = e.lik ? e.lik + lo : nullptr;
+    es.ratio = e.ratio ? e.ratio + lo : nullptr;
+    es.beam = e.beam ? e.beam + lo : nullptr;
+    hipLaunchKernelGGL(emit3_kernel, dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, ctx->stream, es, dev.part(1) + lo, dev.part(2) + lo,
+                       dev.part(3) + lo, static_cast<int>(n));
+    hipLaunchKernelGGL(done_flag_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->done_flag, ++ctx->done_seq);
+    HIP_TRY(hipGetLastError());
+    ++ctx->batch_slices_run;
+  }
+  pg.active = true;
+  return 0;
+}
+
+// Behind stage_inputs, the full update: the results written by the update's last kernel into page-locked memory (the caller's
+// own arrays where they are page-locked), or copied home in one block; the stream is synchronised.
+int deliver_update(mcl3dl_hip_ctx* ctx, bool with_extra, float* weight_inout, size_t n_p, float* out_lik, float* out_match_ratio,
+                   float* out_beam, float* st4)
+{
+  const UpdBlock dev(ctx->upd_block.p, n_p);
+  HostOut ho{};
+  void* out_mem = ctx->zero_copy() ? stage_alloc(ctx, UpdBlock::bytes(n_p)) : nullptr;
+  const UpdBlock out(out_mem, n_p);
+  float* const user[4] = { weight_inout, out_lik, out_match_ratio, out_beam };
+  float** const slot[4] = { &ho.w, &ho.lik, &ho.ratio, &ho.beam };
+  if (out_mem)
+  {
+    if (st4)
+      ho.stats4 = out.stats4();
+    for (int k = 0; k < 4; ++k)
+      if (user[k])
+        *slot[k] = host_target(ctx, user[k], out.part(k), dev.fb, false);  // (copied home once the update is enqueued)
+  }
+  bool host_written = false;
+  TRY(enqueue_update(ctx, ctx->pose.as<float>(), n_p, dev.part(0), with_extra ? ctx->extra.as<float>() : nullptr, dev.part(1),
+                     dev.part(2), dev.part(3), dev.stats4(), out_mem ? &ho : nullptr, &host_written));
+  if (host_written)
+  {
+    if (st4)
+      ctx->stage_out.push_back({ st4, ho.stats4, 4 * sizeof(float) });
+    for (int k = 0; k < 4; ++k)
+      if (user[k] && *slot[k] != user[k])
+        ctx->stage_out.push_back({ user[k], *slot[k], dev.fb });
+  }
+  else
+    TRY(dev.copy_home(ctx, st4, weight_inout, out_lik, out_match_ratio, out_beam));
+  return sync_stream(ctx, host_written);  // (results behind a D2H copy: the stream itself is waited for)
 }
 }  // namespace
 
@@ -840,15 +1033,14 @@ int mcl3dl_hip_measure_batch(mcl3dl_hip_ctx* ctx, const float* pose, size_t n_p,
     return ctx->fail(-3, "null pose array (and mcl3dl_hip_upload_poses holds %zu poses, not %zu)", ctx->n_pose_uploaded,
                      n_p);
   HIP_TRY(hipSetDevice(ctx->device));
-  {
-    // scans (and poses) taken over by one launch, results written into page-locked memory (stage_kernels.h)
-    const int staged = measure_update_staged(ctx, pose, nullptr, nullptr, n_p, scan_lik_xyz, n_s, scan_beam_xyz,
-                                             scan_beam_origin, n_b, origins, n_o, out_lik, out_match_ratio, out_beam, nullptr,
-                                             false);
-    if (staged != 0)
-      return staged < 0 ? staged : 0;
-  }
-  TRY(upload_scan_impl(ctx, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o, false));
+  const HostScan scan{ scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o };
+  // scans (and poses) taken over by one launch, results written into page-locked memory (stage_kernels.h)
+  const int staged = stage_inputs(ctx, pose, nullptr, nullptr, n_p, scan);
+  if (staged < 0)
+    return staged;
+  if (staged)
+    return deliver_models(ctx, n_p, out_lik, out_match_ratio, out_beam, models_block(ctx, n_p));
+  TRY(upload_scan_impl(ctx, scan, false));
   TRY(ensure(ctx, ctx->lik, sizeof(float) * n_p));
   TRY(ensure(ctx, ctx->ratio, sizeof(float) * n_p));
   TRY(ensure(ctx, ctx->beam, sizeof(float) * n_p));
@@ -896,9 +1088,19 @@ int mcl3dl_hip_measure_batch_begin(mcl3dl_hip_ctx* ctx, const float* pose, size_
   slice = (slice + 15) & ~static_cast<size_t>(15);
   if (slice < n_p)
   {
-    const int staged = measure_update_staged(ctx, pose, nullptr, nullptr, n_p, scan_lik_xyz, n_s, scan_beam_xyz,
-                                             scan_beam_origin, n_b, origins, n_o, out_lik, out_match_ratio, out_beam, nullptr,
-                                             false, slice);
+    int staged = stage_inputs(ctx, pose, nullptr, nullptr, n_p, { scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o });
+    if (staged > 0)
+    {
+      char* blk3 = models_block(ctx, n_p);
+      staged = (blk3 && ctx->poll_mode() && ensure_done_flag(ctx)) ?
+                   deliver_models_sliced(ctx, n_p, slice, out_lik, out_match_ratio, out_beam, blk3) :
+                   deliver_models(ctx, n_p, out_lik, out_match_ratio, out_beam, blk3);  // (everything at once)
+      if (staged == 0)
+      {
+        ctx->prog.n_p = n_p;
+        return 0;
+      }
+    }
     if (staged < 0)
     {
       // (slices already enqueued write page-locked staging memory or the caller's page-locked arrays: drained before the
@@ -906,11 +1108,6 @@ int mcl3dl_hip_measure_batch_begin(mcl3dl_hip_ctx* ctx, const float* pose, size_
       (void)hipStreamSynchronize(ctx->stream);
       ctx->prog = mcl3dl_hip_ctx::BatchProgress();
       return staged;
-    }
-    if (staged != 0)
-    {
-      ctx->prog.n_p = n_p;  // (staged == 1: the path delivered everything at once)
-      return 0;
     }
   }
   // not eligible for slices: the whole batch now
@@ -972,320 +1169,16 @@ int mcl3dl_hip_pf_measure(mcl3dl_hip_ctx* ctx, float* weight_inout, const float*
     TRY(h2d(ctx, ctx->extra.p, extra, fb));
   if (match_ratio)
     TRY(h2d(ctx, ctx->ratio.p, match_ratio, fb));
-  TRY(pf_measure_single(ctx, ctx->weightb.as<float>(), ctx->lik.as<float>(), beam ? ctx->beam.as<float>() : nullptr,
-                        extra ? ctx->extra.as<float>() : nullptr, match_ratio ? ctx->ratio.as<float>() : nullptr, n_p,
-                        ctx->stats4.as<float>()));
+  TRY(pf_one_gpu(PfCall{ ctx, ctx->weightb.as<float>(), ctx->lik.as<float>(), beam ? ctx->beam.as<float>() : nullptr,
+                          extra ? ctx->extra.as<float>() : nullptr, match_ratio ? ctx->ratio.as<float>() : nullptr, n_p,
+                          ctx->stats4.as<float>() }));
   float st[4];
   TRY(d2h(ctx, weight_inout, ctx->weightb.p, fb));
   TRY(d2h(ctx, st, ctx->stats4.p, sizeof(st)));
   TRY(sync_stream(ctx));
-  if (entropy)
-    *entropy = st[0];
-  if (match_ratio_min)
-    *match_ratio_min = st[1];
-  if (match_ratio_max)
-    *match_ratio_max = st[2];
-  if (restored)
-    *restored = st[3] != 0.0f;
+  unpack_stats4(st, entropy, match_ratio_min, match_ratio_max, restored);
   return 0;
 }
-
-namespace
-{
-// The host-buffer update with scan_stage_kernel in front (one launch takes over scans, poses and weights: ordering included)
-// and the results written straight into page-locked memory by the kernel that normalises the weights. Returns 1 when the update was run
-// this way (results delivered, stream synchronised), 0 when it is not eligible (the caller runs the general path), < 0 on
-// error.
-// with_pf = false: mcl3dl_hip_measure_batch — the two models only (no weights, no pf::measure); pose may then be null (the
-// poses mcl3dl_hip_upload_poses left on the device).
-int measure_update_staged(mcl3dl_hip_ctx* ctx, const float* pose, const float* extra, float* weight_inout, size_t n_p,
-                          const float* scan_lik_xyz, size_t n_s, const float* scan_beam_xyz, const uint32_t* scan_beam_origin,
-                          size_t n_b, const float* origins, size_t n_o, float* out_lik, float* out_match_ratio,
-                          float* out_beam, float* st4, bool with_pf, size_t slice)
-{
-  if (!ctx->update_stage || n_s > 0x0fffffffu || n_b > 0x0fffffffu || n_o > 4096 || n_p > 0x7fffffffu / 8)
-    return 0;
-  if ((n_s && !scan_lik_xyz) || (n_b && (!scan_beam_xyz || !origins || n_o == 0)))
-    return ctx->fail(-3, "null scan array");
-  if (scan_beam_origin)
-    for (size_t i = 0; i < n_b; ++i)
-      if (scan_beam_origin[i] >= n_o)
-        return ctx->fail(-3, "beam point %zu names origin %u but only %zu origins were given", i, scan_beam_origin[i], n_o);
-  if (!origins)
-    n_o = 0;
-  // Whatever has to be (re)built lazily — the index after a map change, the DDA grid, the penalty table — is built NOW: a
-  // build synchronises the stream, recycles the staging memory and (polled) uses up completion sequence numbers, none of which
-  // may happen between the allocations below and the kernels that read and write them.
-  // (test hook "test_late_structures", MCL3DL_HIP_TEST_HOOKS=1 only: leave the builds to launch_measure as round 4's last but
-  // one commit did — the hazard tests/test_gpu_api_fuzz.py is asked to find again)
-  if (!ctx->test_late_structures)
-  {
-    TRY(ensure_caster_structures(ctx, n_s > 0, n_b > 0));
-    if (n_b > 0)
-      TRY(ensure_pow_table(ctx, n_b));
-  }
-  const size_t fb = sizeof(float) * n_p;
-  // ---- the input block: { poses | weights | odometry factor | likelihood xyz | beam xyz | beam origin ids | origins }
-  struct Part
-  {
-    const void* src;
-    size_t bytes;
-    const void* dev;  // where the kernel reads it
-  };
-  Part part[7] = { { pose, pose ? 7 * fb : 0, nullptr },
-                   { weight_inout, weight_inout ? fb : 0, nullptr },
-                   { extra, extra ? fb : 0, nullptr },
-                   { scan_lik_xyz, sizeof(float) * 3 * n_s, nullptr },
-                   { scan_beam_xyz, sizeof(float) * 3 * n_b, nullptr },
-                   { scan_beam_origin, scan_beam_origin ? sizeof(uint32_t) * n_b : 0, nullptr },
-                   { origins, sizeof(float) * 3 * n_o, nullptr } };
-  const bool zero_copy = ctx->zero_copy();
-  const auto up = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
-  size_t staged_bytes = 0, off[7];
-  for (int k = 0; k < 7; ++k)
-  {
-    off[k] = staged_bytes;
-    if (part[k].bytes && !(zero_copy && ctx->is_pinned(part[k].src, part[k].bytes)))
-      staged_bytes += up(part[k].bytes);
-  }
-  char* staged = nullptr;
-  if (staged_bytes)
-  {
-    if (staged_bytes > STAGE_MAX_COPY)
-      return 0;
-    staged = static_cast<char*>(stage_alloc(ctx, staged_bytes));
-    if (!staged)
-      return 0;
-  }
-  // ---- device arrays
-  const size_t rpart = (fb + 63) & ~static_cast<size_t>(63);
-  TRY(ensure(ctx, ctx->pose, 7 * fb));
-  TRY(ensure(ctx, ctx->upd_block, 64 + 4 * rpart));
-  TRY(ensure(ctx, ctx->extra, fb));
-  TRY(ensure(ctx, ctx->partial4, sizeof(double) * 4));
-  TRY(ensure(ctx, ctx->sp_samp[0], sizeof(float4) * std::max<size_t>(n_s, 1)));
-  TRY(ensure(ctx, ctx->sp_samp[1], sizeof(float4) * std::max<size_t>(n_b, 1)));
-  TRY(ensure(ctx, ctx->cl_minmax, sizeof(float) * 6 + sizeof(unsigned long long)));
-  TRY(ensure(ctx, ctx->cl_err, sizeof(int)));
-  TRY(ensure_scan_block(ctx, n_s, n_b, n_o));
-  if (!zero_copy && staged_bytes)
-    TRY(ensure(ctx, ctx->stage_in_dev, staged_bytes));
-  for (int k = 0; k < 7; ++k)
-  {
-    if (!part[k].bytes)
-      continue;
-    if (zero_copy && ctx->is_pinned(part[k].src, part[k].bytes))
-    {
-      part[k].dev = part[k].src;
-      continue;
-    }
-    memcpy(staged + off[k], part[k].src, part[k].bytes);
-    part[k].dev = zero_copy ? staged + off[k] : ctx->stage_in_dev.as<char>() + off[k];
-  }
-  if (!zero_copy && staged_bytes)
-  {
-    HIP_TRY(hipMemcpyAsync(ctx->stage_in_dev.p, staged, staged_bytes, hipMemcpyHostToDevice, ctx->stream));
-    ctx->stage_pending += staged_bytes;
-  }
-  char* blk = ctx->upd_block.as<char>();
-  float* d_stats = reinterpret_cast<float*>(blk);
-  float* d_w = reinterpret_cast<float*>(blk + 64);
-  float* d_lik = reinterpret_cast<float*>(blk + 64 + rpart);
-  float* d_ratio = reinterpret_cast<float*>(blk + 64 + 2 * rpart);
-  float* d_beam = reinterpret_cast<float*>(blk + 64 + 3 * rpart);
-  StageArgs a{};
-  a.presorted = ctx->scan_presorted;
-  a.in_pose = static_cast<const float*>(part[0].dev);
-  a.in_w = static_cast<const float*>(part[1].dev);
-  a.in_extra = static_cast<const float*>(part[2].dev);
-  a.d_pose = ctx->pose.as<float>();
-  a.d_w = d_w;
-  a.d_extra = ctx->extra.as<float>();
-  a.n_p = static_cast<int>(n_p);
-  a.in_lik_xyz = static_cast<const float*>(part[3].dev);
-  a.n_s = static_cast<int>(n_s);
-  a.raw_lik = ctx->sp_samp[0].as<float4>();
-  a.mm6 = ctx->cl_minmax.as<float>();
-  a.mm_cnt = reinterpret_cast<unsigned long long*>(ctx->cl_minmax.as<float>() + 6);
-  a.out_lik = ctx->scan_lik.as<float4>();
-  a.out_perm = ctx->scan_perm.as<uint32_t>();
-  a.in_beam_xyz = static_cast<const float*>(part[4].dev);
-  a.in_beam_origin = static_cast<const uint32_t*>(part[5].dev);
-  a.n_b = static_cast<int>(n_b);
-  a.raw_beam = ctx->sp_samp[1].as<float4>();
-  a.out_beam = ctx->scan_beam.as<float4>();
-  a.in_origins = static_cast<const float*>(part[6].dev);
-  a.n_o = static_cast<int>(n_o);
-  a.d_origins = ctx->origins.as<float4>();
-  a.d_err = ctx->cl_err.as<int>();
-  const size_t n_copy = 9 * n_p;
-  const size_t n_max = std::max(n_s, n_b);
-  EventPair ep{};
-  TRY(timing_begin(ctx, MCL3DL_KERNEL_STAGE, &ep));
-  if (n_max <= static_cast<size_t>(ST_MAX_POINTS))
-  {
-    // everything in one launch: one work-group orders each scan
-    const unsigned grid = 2u + static_cast<unsigned>(std::min<size_t>(std::max<size_t>((n_copy + RS_THREADS - 1) / RS_THREADS, 1), 64));
-    hipLaunchKernelGGL((scan_stage_kernel<ST_MAX_ROUNDS>), dim3(grid), dim3(RS_THREADS), 0, ctx->stream, a);
-    HIP_TRY(hipGetLastError());
-  }
-  else
-  {
-    // larger scans: one launch brings the arrays over (+ the min / max the Morton keys need), the chip-wide sort orders them
-    // (256 points per work-group and round; the copies 16 bytes per thread: stage_kernels.h)
-    const unsigned nb_lik = n_s ? static_cast<unsigned>(std::min<size_t>((n_s + 255) / 256, 256)) : 0u;
-    const unsigned nb_beam = n_b ? static_cast<unsigned>(std::min<size_t>((n_b + 255) / 256, 64)) : (n_o ? 1u : 0u);
-    const unsigned nb_copy = static_cast<unsigned>(std::min<size_t>(std::max<size_t>((7 * n_p + 1023) / 1024, 1), 64));
-    MinMaxOut mm{};
-    if (nb_lik)
-      TRY(minmax_out(ctx, nb_lik, &mm));
-    hipLaunchKernelGGL(stage_pack_kernel, dim3(nb_lik + nb_beam + nb_copy), dim3(256), 0, ctx->stream, a, mm, nb_lik, nb_beam);
-    HIP_TRY(hipGetLastError());
-    TRY(device_order_scans(ctx, n_s, n_b, nullptr, n_o, true, ctx->cl_err.as<int>()));
-  }
-  TRY(timing_end(ctx, ep));
-  // the context's scan state, as upload_scan_impl leaves it
-  if (n_b > ctx->pow_table_len)
-    ctx->pow_table_dirty = true;
-  if (n_s != ctx->n_s || n_b != ctx->n_b || n_o != ctx->n_o || !ctx->has_scan)
-    ++ctx->generation;
-  ctx->n_s = n_s;
-  ctx->n_b = n_b;
-  ctx->n_o = n_o;
-  ctx->has_scan = true;
-  ctx->sp_n_samp[0] = n_s;
-  ctx->sp_n_samp[1] = n_b;
-  if (pose)
-    ctx->poses_set(n_p);
-  if (slice == STAGE_FRONT_ONLY)
-    return 3;  // the caller (a device group's rank) goes on from here: poses in ctx->pose, weights at staged_weights(ctx)
-  if (!with_pf)
-  {
-    // the two models only: their per-particle results go home through a copy kernel into page-locked memory (or one D2H copy)
-    const bool lik_wanted = out_lik || out_match_ratio;
-    float* const user[3] = { out_lik, out_match_ratio, out_beam };
-    const float* const dev[3] = { d_lik, d_ratio, d_beam };
-    char* blk3 = zero_copy ? static_cast<char*>(stage_alloc(ctx, 3 * rpart)) : nullptr;
-    if (blk3 && slice > 0 && slice < n_p && ctx->poll_mode() && ensure_done_flag(ctx))
-    {
-      // progressive delivery (mcl3dl_hip_measure_batch_begin): the particles are evaluated slice by slice, each slice's
-      // results leave for page-locked memory as soon as its kernels are through and a completion word follows them, so the
-      // caller's per-particle loop (the reference's pf::measure, pf.h:255-260) runs while the later slices are still on the GPU
-      mcl3dl_hip_ctx::BatchProgress& pg = ctx->prog;
-      pg = mcl3dl_hip_ctx::BatchProgress();
-      pg.n_p = n_p;
-      pg.slice = slice;
-      pg.n_slices = (n_p + slice - 1) / slice;
-      pg.seq0 = ctx->done_seq;
-      PfEmit e{};
-      float** slot[3] = { &e.lik, &e.ratio, &e.beam };
-      for (int k = 0; k < 3; ++k)
-        if (user[k])
-        {
-          *slot[k] = ctx->is_pinned(user[k], fb) ? user[k] : reinterpret_cast<float*>(blk3 + k * rpart);
-          pg.user[k] = user[k];
-          pg.host[k] = *slot[k];
-        }
-      // both models of a slice on ONE stream: the second stream's fork / join events cost ~35 us of host time per launch
-      // (host_measure.h), which the caller's thread would pay once per slice before it can start on the results
-      struct OverlapOff
-      {
-        mcl3dl_hip_ctx* c;
-        int saved;
-        ~OverlapOff()
-        {
-          c->overlap_models = saved;
-        }
-      } overlap_off{ ctx, ctx->overlap_models };
-      ctx->overlap_models = 0;
-      for (size_t lo = 0; lo < n_p; lo += slice)
-      {
-        const size_t n = std::min(slice, n_p - lo);
-        TRY(launch_measure(ctx, ctx->pose.as<float>() + 7 * lo, n, lik_wanted ? d_lik + lo : nullptr,
-                           lik_wanted ? d_ratio + lo : nullptr, out_beam ? d_beam + lo : nullptr));
-        PfEmit es{};
-        es.lik = e.lik ? e.lik + lo : nullptr;
-        es.ratio = e.ratio ? e.ratio + lo : nullptr;
-        es.beam = e.beam ? e.beam + lo : nullptr;
-        hipLaunchKernelGGL(emit3_kernel, dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, ctx->stream, es, d_lik + lo, d_ratio + lo,
-                           d_beam + lo, static_cast<int>(n));
-        hipLaunchKernelGGL(done_flag_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->done_flag, ++ctx->done_seq);
-        HIP_TRY(hipGetLastError());
-        ++ctx->batch_slices_run;
-      }
-      pg.active = true;
-      return 2;
-    }
-    TRY(launch_measure(ctx, ctx->pose.as<float>(), n_p, lik_wanted ? d_lik : nullptr, lik_wanted ? d_ratio : nullptr,
-                       out_beam ? d_beam : nullptr));
-    if (blk3)
-    {
-      PfEmit e{};
-      float** slot[3] = { &e.lik, &e.ratio, &e.beam };
-      for (int k = 0; k < 3; ++k)
-        if (user[k])
-        {
-          *slot[k] = ctx->is_pinned(user[k], fb) ? user[k] : reinterpret_cast<float*>(blk3 + k * rpart);
-          if (*slot[k] != user[k])
-            ctx->stage_out.push_back({ user[k], *slot[k], fb });
-        }
-      hipLaunchKernelGGL(emit3_kernel, dim3(pf_blocks(n_p)), dim3(PF_BLOCK), 0, ctx->stream, e, d_lik, d_ratio, d_beam,
-                         static_cast<int>(n_p));
-      HIP_TRY(hipGetLastError());
-      TRY(sync_stream(ctx, true));
-    }
-    else
-    {
-      for (int k = 0; k < 3; ++k)
-        if (user[k])
-          TRY(d2h(ctx, user[k], dev[k], fb));
-      TRY(sync_stream(ctx));
-    }
-    return 1;
-  }
-  // ---- results: written by the update's last kernel into page-locked memory (the caller's own arrays where they are
-  // page-locked), or copied home in one block
-  HostOut ho{};
-  char* out_blk = zero_copy ? static_cast<char*>(stage_alloc(ctx, 64 + 4 * rpart)) : nullptr;
-  struct Res
-  {
-    float* user;
-    size_t offset, bytes;
-    float** slot;
-  };
-  const Res res[5] = { { st4, 0, 4 * sizeof(float), &ho.stats4 },
-                       { weight_inout, 64, fb, &ho.w },
-                       { out_lik, 64 + rpart, fb, &ho.lik },
-                       { out_match_ratio, 64 + 2 * rpart, fb, &ho.ratio },
-                       { out_beam, 64 + 3 * rpart, fb, &ho.beam } };
-  if (out_blk)
-    for (int k = 0; k < 5; ++k)
-      if (res[k].user)
-        *res[k].slot = (k > 0 && ctx->is_pinned(res[k].user, res[k].bytes)) ? res[k].user
-                                                                            : reinterpret_cast<float*>(out_blk + res[k].offset);
-  bool host_written = false;
-  TRY(enqueue_update(ctx, ctx->pose.as<float>(), n_p, d_w, extra ? ctx->extra.as<float>() : nullptr, d_lik, d_ratio, d_beam,
-                     d_stats, out_blk ? &ho : nullptr, &host_written));
-  if (host_written)
-  {
-    for (int k = 0; k < 5; ++k)
-      if (res[k].user && *res[k].slot != res[k].user)
-        ctx->stage_out.push_back({ res[k].user, *res[k].slot, res[k].bytes });
-  }
-  else
-  {
-    const D2hPiece pieces[5] = { { st4, 0, 4 * sizeof(float) },
-                                 { weight_inout, 64, fb },
-                                 { out_lik, 64 + rpart, fb },
-                                 { out_match_ratio, 64 + 2 * rpart, fb },
-                                 { out_beam, 64 + 3 * rpart, fb } };
-    const size_t upto = out_beam ? 64 + 3 * rpart + fb : out_match_ratio ? 64 + 2 * rpart + fb : out_lik ? 64 + rpart + fb : 64 + fb;
-    TRY(d2h_block(ctx, blk, upto, pieces, 5));
-  }
-  TRY(sync_stream(ctx, host_written));  // (results behind a D2H copy: the stream itself is waited for)
-  return 1;
-}
-}  // namespace
 
 int mcl3dl_hip_measure_update(mcl3dl_hip_ctx* ctx, const float* pose, const float* extra, float* weight_inout,
                               size_t n_p, const float* scan_lik_xyz, size_t n_s, const float* scan_beam_xyz,
@@ -1301,64 +1194,35 @@ int mcl3dl_hip_measure_update(mcl3dl_hip_ctx* ctx, const float* pose, const floa
     return ctx->fail(-3, "null pose / weight array");
   HIP_TRY(hipSetDevice(ctx->device));
   const size_t fb = sizeof(float) * n_p;
+  const HostScan scan{ scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o };
+  float st[4] = { 0.f, 0.f, 0.f, 0.f };
+  const int staged = stage_inputs(ctx, pose, extra, weight_inout, n_p, scan);
+  if (staged < 0)
+    return staged;
+  if (staged)
   {
-    float st[4] = { 0.f, 0.f, 0.f, 0.f };
-    const int staged = measure_update_staged(ctx, pose, extra, weight_inout, n_p, scan_lik_xyz, n_s, scan_beam_xyz,
-                                             scan_beam_origin, n_b, origins, n_o, out_lik, out_match_ratio, out_beam, st);
-    if (staged < 0)
-      return staged;
-    if (staged == 1)
-    {
-      if (entropy)
-        *entropy = st[0];
-      if (match_ratio_min)
-        *match_ratio_min = st[1];
-      if (match_ratio_max)
-        *match_ratio_max = st[2];
-      if (restored)
-        *restored = st[3] != 0.0f;
-      return 0;
-    }
+    // the results written straight into page-locked memory by the kernel that normalises the weights
+    TRY(deliver_update(ctx, extra != nullptr, weight_inout, n_p, out_lik, out_match_ratio, out_beam, st));
+    unpack_stats4(st, entropy, match_ratio_min, match_ratio_max, restored);
+    return 0;
   }
-  TRY(upload_scan_impl(ctx, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o, false));
-  // { stats4 | weights (in / out) | lik | ratio | beam }, each part on a 64-byte boundary, in ONE allocation: the results go
-  // home in one copy instead of five (~5 us each at C2's sizes)
-  const size_t part = (fb + 63) & ~static_cast<size_t>(63);
+  TRY(upload_scan_impl(ctx, scan, false));
   TRY(ensure(ctx, ctx->pose, sizeof(float) * 7 * n_p));
-  TRY(ensure(ctx, ctx->upd_block, 64 + 4 * part));
+  TRY(ensure(ctx, ctx->upd_block, UpdBlock::bytes(n_p)));
   TRY(ensure(ctx, ctx->extra, fb));
   TRY(ensure(ctx, ctx->partial4, sizeof(double) * 4));
-  char* blk = ctx->upd_block.as<char>();
-  float* d_stats = reinterpret_cast<float*>(blk);
-  float* d_w = reinterpret_cast<float*>(blk + 64);
-  float* d_lik = reinterpret_cast<float*>(blk + 64 + part);
-  float* d_ratio = reinterpret_cast<float*>(blk + 64 + 2 * part);
-  float* d_beam = reinterpret_cast<float*>(blk + 64 + 3 * part);
+  const UpdBlock dev(ctx->upd_block.p, n_p);
   ctx->poses_set(0);
   TRY(h2d(ctx, ctx->pose.p, pose, sizeof(float) * 7 * n_p));
   ctx->poses_set(n_p);
-  TRY(h2d(ctx, d_w, weight_inout, fb));
+  TRY(h2d(ctx, dev.part(0), weight_inout, fb));
   if (extra)
     TRY(h2d(ctx, ctx->extra.p, extra, fb));
-  TRY(enqueue_update(ctx, ctx->pose.as<float>(), n_p, d_w, extra ? ctx->extra.as<float>() : nullptr, d_lik, d_ratio, d_beam,
-                     d_stats));
-  float st[4];
-  const D2hPiece pieces[5] = { { st, 0, sizeof(st) },
-                               { weight_inout, 64, fb },
-                               { out_lik, 64 + part, fb },
-                               { out_match_ratio, 64 + 2 * part, fb },
-                               { out_beam, 64 + 3 * part, fb } };
-  const size_t upto = out_beam ? 64 + 3 * part + fb : out_match_ratio ? 64 + 2 * part + fb : out_lik ? 64 + part + fb : 64 + fb;
-  TRY(d2h_block(ctx, blk, upto, pieces, 5));
+  TRY(enqueue_update(ctx, ctx->pose.as<float>(), n_p, dev.part(0), extra ? ctx->extra.as<float>() : nullptr, dev.part(1),
+                     dev.part(2), dev.part(3), dev.stats4()));
+  TRY(dev.copy_home(ctx, st, weight_inout, out_lik, out_match_ratio, out_beam));
   TRY(sync_stream(ctx));
-  if (entropy)
-    *entropy = st[0];
-  if (match_ratio_min)
-    *match_ratio_min = st[1];
-  if (match_ratio_max)
-    *match_ratio_max = st[2];
-  if (restored)
-    *restored = st[3] != 0.0f;
+  unpack_stats4(st, entropy, match_ratio_min, match_ratio_max, restored);
   return 0;
 }
 

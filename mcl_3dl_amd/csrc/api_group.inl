@@ -21,14 +21,6 @@ int group_comms(mcl3dl_hip_group* g)
   return 0;
 }
 
-// the shard's share of the 2 + 2N-double record when it holds no particle: sums 0, max ratio 0, -min ratio -1
-int pack_empty(mcl3dl_hip_ctx* ctx, int rank, int world, double* d_packed)
-{
-  hipLaunchKernelGGL(pf_reduce_kernel, dim3(1), dim3(64), 0, ctx->stream, static_cast<const double*>(nullptr), 0, rank, world,
-                     d_packed);
-  HIP_TRY(hipGetLastError());
-  return 0;
-}
 }  // namespace
 
 int mcl3dl_hip_group_create(mcl3dl_hip_group** out, const int* device_ids, int n_devices)
@@ -260,6 +252,7 @@ int mcl3dl_hip_group_measure_batch(mcl3dl_hip_group* g, const float* pose, size_
     return rc ? g->fail_rank(rc, 0) : 0;
   }
   const bool device_order = g->ctx[0]->scan_order_device > 0 && n_s + n_b >= static_cast<size_t>(g->ctx[0]->scan_order_device);
+  const HostScan scan{ scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o };
   std::string err;
   if (!device_order &&
       order_scan(err, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o, g->scan, g->ctx[0]->scan_presorted != 0) != 0)
@@ -276,7 +269,7 @@ int mcl3dl_hip_group_measure_batch(mcl3dl_hip_group* g, const float* pose, size_
         shard_bounds(n_p, N, r, &lo, &hi);
         const size_t n = hi - lo;
         if (device_order)
-          TRY(upload_scan_impl(ctx, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o, false));
+          TRY(upload_scan_impl(ctx, scan, false));
         else
           TRY(push_scan(ctx, g->scan, false));
         if (n == 0)
@@ -512,6 +505,7 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
   // there — the same order as the host's, bit for bit): N redundant sorts of ~0.05 ms that run side by side, instead of
   // 0.15 ms of one host core at 16 k points ahead of any GPU work. Small scans are ordered once on the host and pushed.
   const bool device_order = g->ctx[0]->scan_order_device > 0 && n_s + n_b >= static_cast<size_t>(g->ctx[0]->scan_order_device);
+  const HostScan scan{ scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o };
   // (a rank whose staging launch is not eligible and whose scan is small pushes a copy ordered ONCE on the host, by whichever
   // rank needs it first)
   std::string host_order_error;
@@ -541,35 +535,26 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
       // the normalising kernel writes the shard's results straight into page-locked memory (the caller's arrays where they
       // are page-locked, a staging block otherwise) and the rank learns of its completion from a polled word — instead of up
       // to five D2H copies and a hipStreamSynchronize per rank
-      const size_t rpart = (fb + 63) & ~static_cast<size_t>(63);
-      char* blk = (ctx->zero_copy() && ctx->poll_mode() && 64 + 4 * rpart <= STAGE_MAX_COPY) ?
-                      static_cast<char*>(stage_alloc(ctx, 64 + 4 * rpart)) : nullptr;
+      void* blk = (ctx->zero_copy() && ctx->poll_mode() && UpdBlock::bytes(n) <= STAGE_MAX_COPY) ?
+                      stage_alloc(ctx, UpdBlock::bytes(n)) : nullptr;
+      PfCall c{ ctx, d_w, ctx->lik.as<float>(), ctx->beam.as<float>(), nullptr, ctx->ratio.as<float>(), n, ctx->stats4.as<float>() };
+      PfEmit e{};
       if (blk)
       {
-        PfEmit e{};
-        e.stats4 = reinterpret_cast<float*>(blk);
+        const UpdBlock out(blk, n);
+        e.stats4 = out.stats4();
         ctx->stage_out.push_back({ &stats[4 * r], e.stats4, sizeof(float) * 4 });
         float* const user[4] = { weight_inout, out_lik, out_match_ratio, out_beam };
         float** const slot[4] = { &e.w, &e.lik, &e.ratio, &e.beam };
         for (int k = 0; k < 4; ++k)
           if (user[k])
-          {
-            float* u = user[k] + lo;
-            *slot[k] = ctx->is_pinned(u, fb) ? u : reinterpret_cast<float*>(blk + 64 + k * rpart);
-            if (*slot[k] != u)
-              ctx->stage_out.push_back({ u, *slot[k], fb });
-          }
-        HIP_TRY(hipSetDevice(ctx->device));
-        EventPair ep{};
-        TRY(timing_begin(ctx, MCL3DL_KERNEL_PF, &ep));
-        hipLaunchKernelGGL(pf_apply_kernel, dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, ctx->stream, d_w, ctx->wnew.as<float>(),
-                           static_cast<int>(n), N, ctx->packed.as<double>(), ctx->stats4.as<float>(), e, ctx->lik.as<float>(),
-                           ctx->ratio.as<float>(), ctx->beam.as<float>());
-        TRY(timing_end(ctx, ep));
-        HIP_TRY(hipGetLastError());
-        return sync_stream(ctx, true);
+            *slot[k] = host_target(ctx, user[k] + lo, out.part(k), fb, true);
+        c.emit = &e;
       }
-      TRY(mcl3dl_hip_pf_apply_device(ctx, d_w, n, N, ctx->packed.as<double>(), ctx->stats4.as<float>()));
+      HIP_TRY(hipSetDevice(ctx->device));
+      TRY(pf_second_half(c, N, ctx->packed.as<double>()));
+      if (blk)
+        return sync_stream(ctx, true);
       if (weight_inout)
         TRY(d2h(ctx, weight_inout + lo, d_w, fb));
       TRY(d2h(ctx, &stats[4 * r], ctx->stats4.p, sizeof(float) * 4));
@@ -612,18 +597,16 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
           bool staged = false;
           if (n)
           {
-            const int st = measure_update_staged(ctx, resident ? nullptr : pose + 7 * lo, extra ? extra + lo : nullptr,
-                                                 resident ? nullptr : weight_inout + lo, n, scan_lik_xyz, n_s, scan_beam_xyz,
-                                                 scan_beam_origin, n_b, origins, n_o, nullptr, nullptr, nullptr, nullptr, true,
-                                                 STAGE_FRONT_ONLY);
+            const int st = stage_inputs(ctx, resident ? nullptr : pose + 7 * lo, extra ? extra + lo : nullptr,
+                                        resident ? nullptr : weight_inout + lo, n, scan);
             if (st < 0)
               return st;
-            staged = st == 3;
+            staged = st != 0;
           }
           if (!staged)
           {
             if (device_order)
-              TRY(upload_scan_impl(ctx, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o, false));
+              TRY(upload_scan_impl(ctx, scan, false));
             else
             {
               std::call_once(host_order_once,
@@ -654,7 +637,7 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
               ctx->poses_set(n);
               TRY(h2d(ctx, ctx->weightb.p, weight_inout + lo, fb));
             }
-            float* d_w = resident ? ctx->gs_weight.as<float>() : (staged ? staged_weights(ctx) : ctx->weightb.as<float>());
+            float* d_w = resident ? ctx->gs_weight.as<float>() : (staged ? staged_weights(ctx, n) : ctx->weightb.as<float>());
             rank_weights[r] = d_w;
             if (extra && !staged)
               TRY(h2d(ctx, ctx->extra.p, extra + lo, fb));
@@ -667,16 +650,17 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
             // (the sum over the tiled kernel's per-tile partials and the beam model's last step ride in the first pf::measure kernel,
             // as on one GPU: one launch less per model and rank)
             LikTail tail;
-            tail.want = n <= static_cast<size_t>(1024) * PF_BLOCK;
+            tail.want = pf_tiles_fit(n);
             tail.want_beam = true;
             TRY(launch_measure(ctx, ctx->pose.as<float>(), n, ctx->lik.as<float>(), ctx->ratio.as<float>(),
                                ctx->beam.as<float>(), &tail));
-            TRY(pf_partial_behind_measure(ctx, d_w, ctx->lik.as<float>(), ctx->beam.as<float>(),
-                                          (extra || device_extra) ? ctx->extra.as<float>() : nullptr, ctx->ratio.as<float>(), n, r, N,
-                                          ctx->packed.as<double>(), tail));
+            PfCall c{ ctx, d_w, ctx->lik.as<float>(), ctx->beam.as<float>(), (extra || device_extra) ? ctx->extra.as<float>() : nullptr,
+                      ctx->ratio.as<float>(), n, nullptr };
+            c.tail = &tail;
+            TRY(pf_first_half(c, r, N, ctx->packed.as<double>()));
           }
           else
-            TRY(pack_empty(ctx, r, N, ctx->packed.as<double>()));
+            TRY(pf_first_half_empty(ctx, r, N, ctx->packed.as<double>()));
           if (r == inject)
             return ctx->fail(-9, "injected failure ahead of the collective (test hook)");
           return 0;
@@ -771,14 +755,7 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
       break;
     }
   }
-  if (entropy)
-    *entropy = stats[4 * src + 0];
-  if (match_ratio_min)
-    *match_ratio_min = stats[4 * src + 1];
-  if (match_ratio_max)
-    *match_ratio_max = stats[4 * src + 2];
-  if (restored)
-    *restored = stats[4 * src + 3] != 0.0f;
+  unpack_stats4(&stats[4 * src], entropy, match_ratio_min, match_ratio_max, restored);
   return 0;
 }
 }  // namespace

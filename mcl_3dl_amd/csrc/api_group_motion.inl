@@ -236,7 +236,7 @@ int group_measure_resident(mcl3dl_hip_group* g, const char* what, const ShardMod
   int bad = 0;
   if (no_collective)
   {
-    // one device: pf::measure as mcl3dl_hip_group_update_resident's single-GPU form runs it (pf_measure_single: the fused
+    // one device: pf::measure as mcl3dl_hip_group_update_resident's single-GPU form runs it (pf_one_gpu: the fused
     // work-group up to pf_fused_max particles, else partial + apply), the likelihood formed inside — one or two launches
     mcl3dl_hip_ctx* ctx = g->ctx[0];
     const int rc = [&]() -> int
@@ -245,46 +245,16 @@ int group_measure_resident(mcl3dl_hip_group* g, const char* what, const ShardMod
       const size_t n = ctx->gs_n;
       if (n != n_p)
         return ctx->fail(-5, "this device holds %zu resident particles, not %zu", n, n_p);
-      const int nb = pf_blocks(n);
       TRY(ensure(ctx, ctx->lik, sizeof(float) * n));
-      TRY(ensure(ctx, ctx->wnew, sizeof(float) * n));
-      TRY(ensure(ctx, ctx->block_partials, sizeof(double) * 4 * nb));
       TRY(ensure(ctx, ctx->partial4, sizeof(double) * 4));
       TRY(ensure(ctx, ctx->stats4, sizeof(float) * 4));
       ImuGravity m{};
       const float* d_lik = nullptr;
       TRY(model(ctx, n, &d_lik, &m));
-      float* d_w = ctx->gs_weight.as<float>();
-      const bool float_w = pf_float_order(ctx, n);
-      const int ni = static_cast<int>(n);
-      const float* none = nullptr;
-      EventPair ep{};
-      TRY(timing_begin(ctx, MCL3DL_KERNEL_PF, &ep));
-      if (n <= static_cast<size_t>(std::min(ctx->pf_fused_max, PF_FUSED_MAX)) && ctx->pf_fused)
-        hipLaunchKernelGGL(pf_fused_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_w, d_lik, none, none, none, ni,
-                           ctx->wnew.as<float>(), ctx->partial4.as<double>(), ctx->stats4.as<float>(), PfEmit{}, float_w ? 1 : 0,
-                           BeamCounts{}, m);
-      else
-      {
-        hipLaunchKernelGGL(pf_partial_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_w, d_lik, none, none, none, ni,
-                           ctx->wnew.as<float>(), ctx->block_partials.as<double>(), BeamCounts{}, m);
-        if (!float_w)
-          hipLaunchKernelGGL(pf_apply_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_w, ctx->wnew.as<float>(), ni, 1,
-                             static_cast<const double*>(nullptr), ctx->stats4.as<float>(), PfEmit{}, none, none, none,
-                             ctx->block_partials.as<double>(), nb, 0, ctx->partial4.as<double>());
-        else
-        {
-          // the reference's float recurrence over the weights (strict_order 1 beyond pf_fused_max) between the two
-          hipLaunchKernelGGL(pf_reduce_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->block_partials.as<double>(), nb, 0, 1,
-                             ctx->partial4.as<double>());
-          hipLaunchKernelGGL(pf_strict_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->wnew.as<float>(), ni,
-                             ctx->partial4.as<double>());
-          hipLaunchKernelGGL(pf_apply_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, d_w, ctx->wnew.as<float>(), ni, 1,
-                             ctx->partial4.as<double>(), ctx->stats4.as<float>());
-        }
-      }
-      TRY(timing_end(ctx, ep));
-      HIP_TRY(hipGetLastError());
+      // (the first kernel reads the likelihoods only)
+      PfCall c{ ctx, ctx->gs_weight.as<float>(), const_cast<float*>(d_lik), nullptr, nullptr, nullptr, n, ctx->stats4.as<float>() };
+      c.model = &m;
+      TRY(pf_one_gpu(c));
       return fetch(ctx, 0, 0, n);
     }();
     if (rc)
@@ -300,9 +270,9 @@ int group_measure_resident(mcl3dl_hip_group* g, const char* what, const ShardMod
     {
       if (n == 0)
         return sync_stream(ctx);
-      hipLaunchKernelGGL(pf_apply_kernel, dim3(pf_blocks(n)), dim3(PF_BLOCK), 0, ctx->stream, ctx->gs_weight.as<float>(),
-                         ctx->wnew.as<float>(), static_cast<int>(n), N, ctx->packed.as<double>(), ctx->stats4.as<float>());
-      HIP_TRY(hipGetLastError());
+      PfCall c{ ctx, ctx->gs_weight.as<float>(), nullptr, nullptr, nullptr, nullptr, n, ctx->stats4.as<float>() };
+      c.timed = false;
+      TRY(pf_second_half(c, N, ctx->packed.as<double>()));
       return fetch(ctx, r, lo, n);
     };
     int rc = g->pool.run_all(
@@ -318,27 +288,17 @@ int group_measure_resident(mcl3dl_hip_group* g, const char* what, const ShardMod
             TRY(ensure(ctx, ctx->packed, sizeof(double) * n_pack));
             TRY(ensure(ctx, ctx->stats4, sizeof(float) * 4));
             if (n == 0)
-              return pack_empty(ctx, r, N, ctx->packed.as<double>());
+              return pf_first_half_empty(ctx, r, N, ctx->packed.as<double>());
             if (ctx->gs_n != n)
               return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, n);
-            const int nb = pf_blocks(n);
             TRY(ensure(ctx, ctx->lik, sizeof(float) * n));
-            TRY(ensure(ctx, ctx->wnew, sizeof(float) * n));
-            TRY(ensure(ctx, ctx->block_partials, sizeof(double) * 4 * nb));
-            const float* none = nullptr;
             ImuGravity m{};
             const float* d_lik = nullptr;
             TRY(model(ctx, n, &d_lik, &m));
-            hipLaunchKernelGGL(pf_partial_kernel, dim3(nb), dim3(PF_BLOCK), 0, ctx->stream, ctx->gs_weight.as<float>(), d_lik, none,
-                               none, none, static_cast<int>(n), ctx->wnew.as<float>(), ctx->block_partials.as<double>(),
-                               BeamCounts{}, m);
-            hipLaunchKernelGGL(pf_reduce_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->block_partials.as<double>(), nb, r, N,
-                               ctx->packed.as<double>());
-            if (N == 1 && pf_float_order(ctx, n))
-              hipLaunchKernelGGL(pf_strict_sum_kernel, dim3(1), dim3(256), 0, ctx->stream, ctx->wnew.as<float>(),
-                                 static_cast<int>(n), ctx->packed.as<double>());
-            HIP_TRY(hipGetLastError());
-            return 0;
+            PfCall c{ ctx, ctx->gs_weight.as<float>(), const_cast<float*>(d_lik), nullptr, nullptr, nullptr, n, nullptr };
+            c.model = &m;
+            c.timed = false;
+            return pf_first_half(c, r, N, ctx->packed.as<double>());
           };
           int rc_a = phase_a();
           const bool all_ok = g->vote.vote(rc_a == 0);
@@ -414,10 +374,7 @@ int group_measure_resident(mcl3dl_hip_group* g, const char* what, const ShardMod
       break;
     }
   }
-  if (entropy)
-    *entropy = stats[4 * src + 0];
-  if (restored)
-    *restored = stats[4 * src + 3] != 0.0f;
+  unpack_stats4(&stats[4 * src], entropy, nullptr, nullptr, restored);
   return 0;
 }
 }  // namespace

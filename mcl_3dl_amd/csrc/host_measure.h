@@ -666,7 +666,7 @@ struct LikTail
   bool pending = false, beam_fill = false;
   int n_tiles = 0;
   // the beam model's last step (penalty count -> score, beam_finalize_kernel) left to that kernel as well: ctx->penalty holds the
-  // counts, d_beam is NOT written yet (pf_measure_single runs beam_finalize_kernel itself when its kernel cannot take the counts)
+  // counts, d_beam is NOT written yet (pf_one_gpu runs beam_finalize_kernel itself when its kernel cannot take the counts)
   bool want_beam = false, beam_pending = false;
 };
 
@@ -1181,22 +1181,7 @@ int measure_stats(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, double* 
   return 0;
 }
 
-int pf_blocks(size_t n)
-{
-  const size_t b = (n + PF_BLOCK - 1) / PF_BLOCK;
-  return static_cast<int>(std::min<size_t>(std::max<size_t>(b, 1), 1024));
-}
-
-// Does pf::measure on ONE GPU add the un-normalised weights as the reference does (pf.h:255-260: float, sequentially, particle
-// order; float_chain.h) instead of the fp64 tree? strict_order 1: always. The default (2): up to pf_fused_max = 1024 particles —
-// the reference's operating range; pf::measure is then the reference's arithmetic bit for bit given its inputs, inside the
-// fused kernel / the one-launch update at no extra launch. Beyond that the recurrence needs a launch of its own
-// (pf_strict_sum_kernel: +10 us at 4096 particles, a third of a 4096 x 96 update, profiles/r06d_rows_vs_replay.txt) for weights
-// that agree to ~1e-7 anyway. Independent of pf_fused, so that the fused and the split form give the same bits.
-bool pf_float_order(const mcl3dl_hip_ctx* ctx, size_t n_p)
-{
-  return ctx->strict_order == 1 || (ctx->strict_order == 2 && n_p <= static_cast<size_t>(std::min(ctx->pf_fused_max, PF_FUSED_MAX)));
-}
+bool pf_float_order(const mcl3dl_hip_ctx* ctx, size_t n_p);  // host_pf.h
 
 // The whole update — both models and pf::measure — as ONE launch (update_kernels.h) where the sizes are launch-bound:
 // returns 1 when it was enqueued, 0 when this update is not eligible (the caller then runs the separate kernels), < 0 on

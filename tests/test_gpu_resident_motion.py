@@ -208,6 +208,40 @@ def test_imu_measure(cfg, n_p, oracle_kind):
         g.close()
 
 
+@pytest.mark.parametrize("strict_order", [1, 2])
+@pytest.mark.parametrize("n_p", [600, 1100])
+def test_imu_measure_pf_forms_same_bits(n_p, strict_order):
+    """pf::measure behind the resident IMU update on one device, in every form it takes there — the fused work-group (600
+    particles, pf_fused 1), partial + self-reducing apply (pf_fused 0 or 1100 particles, fp64 sum), partial / reduce / strict sum
+    / apply (the float recurrence: strict_order 1, or 2 up to 1024 particles, with pf_fused 0 or beyond pf_fused_max) — gives
+    the bits of the context's own pf::measure on the returned likelihoods under the same two options, and the same bits with
+    and without the fused kernel (1100: either side of pf_fused_max = 1024, more than four work-groups of 256)."""
+    st = states(n_p, 14, spread=0.15)
+    w0 = np.random.default_rng(15).uniform(0.5, 1.5, n_p).astype(np.float32)
+    w0 /= w0.sum()
+    acc = np.array([0.3, -0.2, 9.7], np.float32)
+    got = {}
+    for pf_fused in (0, 1):
+        g, eng = group(([0], None, 1)), capi.Engine(0)
+        try:
+            for obj in (g, eng):
+                obj.set_option("pf_fused", pf_fused)
+                obj.set_option("strict_order", strict_order)
+            g.upload_state(st, w0)
+            got[pf_fused] = g.measure_imu(acc, 0.5)
+            want = eng.pf_measure(w0, got[pf_fused]["lik"])
+        finally:
+            g.close()
+            eng.close()
+        np.testing.assert_array_equal(got[pf_fused]["weights"], want["weights"])
+        assert got[pf_fused]["entropy"] == want["entropy"]
+        assert got[pf_fused]["restored"] == want["restored"] and not want["restored"]
+    np.testing.assert_array_equal(got[0]["lik"], got[1]["lik"])
+    np.testing.assert_array_equal(got[0]["weights"], got[1]["weights"])
+    assert got[0]["entropy"] == got[1]["entropy"]
+    assert got[0]["restored"] == got[1]["restored"]
+
+
 @pytest.mark.parametrize("cfg", CONFIGS, ids=IDS)
 def test_device_odometry_factor(scene, cfg):
     sc = scene
