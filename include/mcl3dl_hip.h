@@ -640,9 +640,12 @@ int mcl3dl_hip_memory_footprint(mcl3dl_hip_ctx* ctx, uint64_t* bytes8);
 /* Options (no reference counterpart). Round 6 pruned the switchboard: what lost its A/B is gone (the two-launch pf::measure tail,
  * the one-launch sorts, the completion word folded into the last kernel, the device-side resampling prefix, the CSR form of the
  * candidate index, sharper pruning of crowded voxels, the replay's A/B knobs, the dense record grid) and the thresholds nobody
- * needs to move are constants (HISTORY.md R6-7). The 39 keys left are ALL drawn, in combination, by tests/test_gpu_api_fuzz.py
- * (tests/test_abi.py keeps that pool and this list in step). Except for "strict_order" and its thresholds — which select HOW the
- * sums are rounded — results are the same bits for every setting. Every key can be read back with mcl3dl_hip_get_option.
+ * needs to move are constants (HISTORY.md R6-7). The 39 keys left — 38 and the test hook at the end of this list — are ALL
+ * drawn, in combination, by tests/test_gpu_api_fuzz.py. Each is one row of the table in mcl_3dl_amd/csrc/host_options.h (field,
+ * value rule, error text, what it makes the engine rebuild); tests/test_abi.py keeps the fuzz's pool and that table in step.
+ * Except for "strict_order" and its thresholds — which select HOW the sums are rounded — results are the same bits for every
+ * setting. Every key but the hook can be read back with mcl3dl_hip_get_option. A value outside a key's rule is refused with
+ * -3 and changes nothing.
  *
  * -- how the sums are added up
  *   "strict_order"      2 (default) = the likelihood terms are added up as the reference adds them — float, sequentially, in the
@@ -712,7 +715,7 @@ int mcl3dl_hip_memory_footprint(mcl3dl_hip_ctx* ctx, uint64_t* bytes8);
  *                       hipStreamSynchronize); spin that long (2000 us) before napping between looks
  *   "scan_order_device" scans of at least this many points are ordered on the device (4096; 0 = always on the host)
  *   "batch_slice"       particles per slice of mcl3dl_hip_measure_batch_begin when slice_particles is 0
- *   "timing_mask"       bit k set = kernel group k is timed while kernel timing is on
+ *   "timing_mask"       bit k set = kernel group k is timed while kernel timing is on; a value in [0, 2^32)
  *   "test_late_structures"  fault injection for the API-sequence fuzz only */
 int mcl3dl_hip_set_option(mcl3dl_hip_ctx* ctx, const char* name, double value);
 int mcl3dl_hip_get_option(mcl3dl_hip_ctx* ctx, const char* name, double* value);

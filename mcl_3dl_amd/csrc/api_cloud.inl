@@ -105,8 +105,6 @@ int mcl3dl_hip_scan_finish(mcl3dl_hip_ctx* ctx, const uint32_t* idx_lik, size_t 
   ctx->sp_n_samp[1] = n_b;
   if (n_b > ctx->pow_table_len)
     ctx->pow_table_dirty = true;
-  if (n_s != ctx->n_s || n_b != ctx->n_b || n_o != ctx->n_o || !ctx->has_scan)
-    ++ctx->generation;
   ctx->n_s = n_s;
   ctx->n_b = n_b;
   ctx->n_o = n_o;
@@ -209,7 +207,6 @@ int install_base_map(mcl3dl_hip_ctx* ctx, size_t n_in, const float* leaf3, uint6
   if (n_out > 0xfffffff0u)
     return ctx->fail(-3, "map too large (index must fit 32 bits)");
   TRY(map_from_device(ctx, ctx->sp_full.as<float4>(), n_out, 0));
-  ++ctx->generation;
   ctx->stamp = stamp;
   ctx->has_weight = dist_weight != nullptr;
   for (int a = 0; a < 3; ++a)
@@ -239,14 +236,13 @@ int install_map_update(mcl3dl_hip_ctx* ctx, size_t n_in, const float* leaf3, uin
   if (n_base + n_out > 0xfffffff0u)
     return ctx->fail(-3, "map too large (index must fit 32 bits)");
   TRY(map_from_device(ctx, ctx->sp_full.as<float4>(), n_out, n_base));  // pc_map2 = pc_map + pc_update
-  ++ctx->generation;
   ctx->n_base = n_base;
   ctx->stamp = stamp;
   ctx->lik_dirty = true;  // the cell grid (matched / unmatched, lik_index 0) is rebuilt on next use: a linear-time build
   // the DDA grid keeps its arrays when the update stays inside the bounds it was laid out for: the update's points replace the
   // previous overlay (host_grid_builders.h:dda_overlay_apply). Otherwise it is rebuilt on next use.
   bool dda_kept = false;
-  if (!ctx->dda_dirty && ctx->dda_overlay && ctx->dda_overlay_ok)
+  if (!ctx->dda_dirty && ctx->opt.dda_overlay && ctx->dda_overlay_ok)
   {
     const DdaGrid& d = ctx->dg;
     const float* u = ctx->map_xyz.data() + 3 * n_base;

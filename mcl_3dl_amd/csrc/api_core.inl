@@ -138,7 +138,6 @@ int mcl3dl_hip_set_stream(mcl3dl_hip_ctx* ctx, void* hip_stream)
 {
   if (!ctx)
     return -1;
-  ++ctx->generation;
   TRY(sync_stream(ctx));
   ctx->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->own_stream;
   return 0;
@@ -162,7 +161,6 @@ int mcl3dl_hip_set_map(mcl3dl_hip_ctx* ctx, const float* xyz, const uint32_t* la
 {
   if (!ctx)
     return -1;
-  ++ctx->generation;
   if (!xyz || n_m == 0)
     return ctx->fail(-3, "empty map");
   if (n_m > 0xfffffff0u)
@@ -192,7 +190,6 @@ int mcl3dl_hip_set_likelihood_params(mcl3dl_hip_ctx* ctx, float match_dist_min, 
 {
   if (!ctx)
     return -1;
-  ++ctx->generation;
   if (!(match_dist_min > 0.f))
     return ctx->fail(-3, "match_dist_min must be > 0");
   if (match_dist_min != ctx->match_dist_min)
@@ -228,7 +225,6 @@ int mcl3dl_hip_set_beam_params(mcl3dl_hip_ctx* ctx, float map_grid_x, float map_
                              (add_penalty_short_only_mode ? 1 : 0) != ctx->short_only;
   if (!dda_changed && !derived_changed && !other_changed)
     return 0;
-  ++ctx->generation;
   ctx->map_grid[0] = map_grid_x;
   ctx->map_grid[1] = map_grid_y;
   ctx->map_grid[2] = map_grid_z;
@@ -255,7 +251,6 @@ int mcl3dl_hip_set_beam_raycast(mcl3dl_hip_ctx* ctx, int mode)
     return ctx->fail(-3, "beam raycast mode must be 0 (RaycastUsingDDA) or 1 (RaycastUsingKDTree), not %d", mode);
   if (mode == ctx->beam_raycast)
     return 0;
-  ++ctx->generation;
   ctx->beam_raycast = mode;  // (nothing is built or dropped here: each caster's structures are built when it first casts)
   return 0;
 }
@@ -434,8 +429,6 @@ static int push_scan(mcl3dl_hip_ctx* ctx, const OrderedScan& o, bool sync_at_end
     TRY(sync_stream(ctx));
   if (n_b > ctx->pow_table_len)
     ctx->pow_table_dirty = true;  // table[k] = beam_likelihood^k is a prefix property: a shorter scan reuses it
-  if (n_s != ctx->n_s || n_b != ctx->n_b || n_o != ctx->n_o || !ctx->has_scan)
-    ++ctx->generation;
   ctx->n_s = n_s;
   ctx->n_b = n_b;
   ctx->n_o = n_o;
@@ -463,7 +456,7 @@ static int upload_scan_impl(mcl3dl_hip_ctx* ctx, const HostScan& scan, bool sync
   // Large scans are ordered on the device (host_cloud.h:device_order_scans: raw points up, min / key / stable radix sort /
   // gather there — same keys, same order, same bits as the host ordering, which costs ~0.1 ms of one core at 16 k points);
   // small ones on the host, where a dozen launches would cost more than the sort.
-  if (ctx->scan_order_device > 0 && n_s + n_b >= static_cast<size_t>(ctx->scan_order_device))
+  if (ctx->opt.scan_order_device > 0 && n_s + n_b >= static_cast<size_t>(ctx->opt.scan_order_device))
   {
     if ((n_s && !scan_lik_xyz) || (n_b && (!scan_beam_xyz || !origins || n_o == 0)))
       return ctx->fail(-3, "null scan array");
@@ -482,8 +475,6 @@ static int upload_scan_impl(mcl3dl_hip_ctx* ctx, const HostScan& scan, bool sync
       TRY(sync_stream(ctx));
     if (n_b > ctx->pow_table_len)
       ctx->pow_table_dirty = true;
-    if (n_s != ctx->n_s || n_b != ctx->n_b || n_o != ctx->n_o || !ctx->has_scan)
-      ++ctx->generation;
     ctx->n_s = n_s;
     ctx->n_b = n_b;
     ctx->n_o = n_o;
@@ -493,7 +484,7 @@ static int upload_scan_impl(mcl3dl_hip_ctx* ctx, const HostScan& scan, bool sync
     return 0;
   }
   std::string err;
-  if (order_scan(err, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o, ctx->h_scan, ctx->scan_presorted != 0) != 0)
+  if (order_scan(err, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o, ctx->h_scan, ctx->opt.scan_presorted != 0) != 0)
     return ctx->fail(-3, "%s", err.c_str());
   return push_scan(ctx, ctx->h_scan, sync_at_end);
 }
@@ -746,7 +737,7 @@ void unpack_stats4(const float* st, float* entropy, float* match_ratio_min, floa
 int stage_inputs(mcl3dl_hip_ctx* ctx, const float* pose, const float* extra, const float* weight, size_t n_p, HostScan scan)
 {
   auto& [scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o] = scan;
-  if (!ctx->update_stage || n_s > 0x0fffffffu || n_b > 0x0fffffffu || n_o > 4096 || n_p > 0x7fffffffu / 8)
+  if (!ctx->opt.update_stage || n_s > 0x0fffffffu || n_b > 0x0fffffffu || n_o > 4096 || n_p > 0x7fffffffu / 8)
     return 0;
   if ((n_s && !scan_lik_xyz) || (n_b && (!scan_beam_xyz || !origins || n_o == 0)))
     return ctx->fail(-3, "null scan array");
@@ -761,7 +752,7 @@ int stage_inputs(mcl3dl_hip_ctx* ctx, const float* pose, const float* extra, con
   // may happen between the allocations below and the kernels that read and write them.
   // (test hook "test_late_structures", MCL3DL_HIP_TEST_HOOKS=1 only: leave the builds to launch_measure as round 4's last but
   // one commit did — the hazard tests/test_gpu_api_fuzz.py is asked to find again)
-  if (!ctx->test_late_structures)
+  if (!ctx->opt.test_late_structures)
   {
     TRY(ensure_caster_structures(ctx, n_s > 0, n_b > 0));
     if (n_b > 0)
@@ -830,7 +821,7 @@ int stage_inputs(mcl3dl_hip_ctx* ctx, const float* pose, const float* extra, con
     ctx->stage_pending += staged_bytes;
   }
   StageArgs a{};
-  a.presorted = ctx->scan_presorted;
+  a.presorted = ctx->opt.scan_presorted;
   a.in_pose = static_cast<const float*>(part[0].dev);
   a.in_w = static_cast<const float*>(part[1].dev);
   a.in_extra = static_cast<const float*>(part[2].dev);
@@ -883,8 +874,6 @@ int stage_inputs(mcl3dl_hip_ctx* ctx, const float* pose, const float* extra, con
   // the context's scan state, as upload_scan_impl leaves it
   if (n_b > ctx->pow_table_len)
     ctx->pow_table_dirty = true;
-  if (n_s != ctx->n_s || n_b != ctx->n_b || n_o != ctx->n_o || !ctx->has_scan)
-    ++ctx->generation;
   ctx->n_s = n_s;
   ctx->n_b = n_b;
   ctx->n_o = n_o;
@@ -962,10 +951,10 @@ int deliver_models_sliced(mcl3dl_hip_ctx* ctx, size_t n_p, size_t slice, float* 
     int saved;
     ~OverlapOff()
     {
-      c->overlap_models = saved;
+      c->opt.overlap_models = saved;
     }
-  } overlap_off{ ctx, ctx->overlap_models };
-  ctx->overlap_models = 0;
+  } overlap_off{ ctx, ctx->opt.overlap_models };
+  ctx->opt.overlap_models = 0;
   for (size_t lo = 0; lo < n_p; lo += slice)
   {
     const size_t n = std::min(slice, n_p - lo);
@@ -1082,7 +1071,7 @@ int mcl3dl_hip_measure_batch_begin(mcl3dl_hip_ctx* ctx, const float* pose, size_
   if (!pose && ctx->n_pose_uploaded != n_p)
     return ctx->fail(-3, "null pose array (and mcl3dl_hip_upload_poses holds %zu poses, not %zu)", ctx->n_pose_uploaded,
                      n_p);
-  size_t slice = slice_particles ? slice_particles : static_cast<size_t>(ctx->batch_slice);
+  size_t slice = slice_particles ? slice_particles : static_cast<size_t>(ctx->opt.batch_slice);
   if (slice == 0)
     slice = n_p >= 1024 ? std::max<size_t>(512, ((n_p + 3) / 4 + 63) & ~static_cast<size_t>(63)) : n_p;  // four slices
   slice = (slice + 15) & ~static_cast<size_t>(15);

@@ -180,8 +180,7 @@ int mcl3dl_hip_group_set_option(mcl3dl_hip_group* g, const char* name, double va
   {
     // test hook (only with MCL3DL_HIP_TEST_HOOKS=1 in the environment): the next sharded update fails on that rank after its
     // kernels are enqueued and before the collective
-    const char* hooks = getenv("MCL3DL_HIP_TEST_HOOKS");
-    if (!hooks || std::string(hooks) != "1")
+    if (!test_hooks_enabled())
       return g->fail(-3, "inject_failure_rank is a test hook: set MCL3DL_HIP_TEST_HOOKS=1 in the environment to enable it");
     g->inject_failure_rank = static_cast<int>(value);
     return 0;
@@ -251,11 +250,11 @@ int mcl3dl_hip_group_measure_batch(mcl3dl_hip_group* g, const float* pose, size_
                                             origins, n_o, out_lik, out_match_ratio, out_beam);
     return rc ? g->fail_rank(rc, 0) : 0;
   }
-  const bool device_order = g->ctx[0]->scan_order_device > 0 && n_s + n_b >= static_cast<size_t>(g->ctx[0]->scan_order_device);
+  const bool device_order = g->ctx[0]->opt.scan_order_device > 0 && n_s + n_b >= static_cast<size_t>(g->ctx[0]->opt.scan_order_device);
   const HostScan scan{ scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o };
   std::string err;
   if (!device_order &&
-      order_scan(err, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o, g->scan, g->ctx[0]->scan_presorted != 0) != 0)
+      order_scan(err, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o, g->scan, g->ctx[0]->opt.scan_presorted != 0) != 0)
     return g->fail(-3, "%s", err.c_str());
   if (pose)
     g->n_pose_uploaded = 0;
@@ -504,7 +503,7 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
   // Large scans are ordered by every device for itself (upload_scan_impl: raw points up, keys / stable radix sort / gather
   // there — the same order as the host's, bit for bit): N redundant sorts of ~0.05 ms that run side by side, instead of
   // 0.15 ms of one host core at 16 k points ahead of any GPU work. Small scans are ordered once on the host and pushed.
-  const bool device_order = g->ctx[0]->scan_order_device > 0 && n_s + n_b >= static_cast<size_t>(g->ctx[0]->scan_order_device);
+  const bool device_order = g->ctx[0]->opt.scan_order_device > 0 && n_s + n_b >= static_cast<size_t>(g->ctx[0]->opt.scan_order_device);
   const HostScan scan{ scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o };
   // (a rank whose staging launch is not eligible and whose scan is small pushes a copy ordered ONCE on the host, by whichever
   // rank needs it first)
@@ -613,7 +612,7 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
                              [&]
                              {
                                host_ordered = order_scan(host_order_error, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b,
-                                                         origins, n_o, g->scan, g->ctx[0]->scan_presorted != 0) == 0;
+                                                         origins, n_o, g->scan, g->ctx[0]->opt.scan_presorted != 0) == 0;
                              });
               if (!host_ordered)
                 return ctx->fail(-3, "%s", host_order_error.c_str());

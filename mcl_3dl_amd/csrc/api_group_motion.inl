@@ -210,7 +210,7 @@ namespace
 using ShardModel = std::function<int(mcl3dl_hip_ctx*, size_t, const float**, ImuGravity*)>;
 
 // pf::measure (pf.h:252-279) over the resident particles with the likelihoods of `model`: one device — the fused work-group up
-// to pf_fused_max particles, else partial + apply; N shards — vote, partial sums, the 2 + 2N-double record all-reduced (RCCL, or
+// to PF_FUSED_MAX_PARTICLES particles, else partial + apply; N shards — vote, partial sums, the 2 + 2N-double record all-reduced (RCCL, or
 // through the host), apply: the steps of mcl3dl_hip_group_update_resident. `what` names the update in error texts.
 int group_measure_resident(mcl3dl_hip_group* g, const char* what, const ShardModel& model, float* out_weight, float* out_lik,
                            float* entropy, int* restored)
@@ -237,7 +237,7 @@ int group_measure_resident(mcl3dl_hip_group* g, const char* what, const ShardMod
   if (no_collective)
   {
     // one device: pf::measure as mcl3dl_hip_group_update_resident's single-GPU form runs it (pf_one_gpu: the fused
-    // work-group up to pf_fused_max particles, else partial + apply), the likelihood formed inside — one or two launches
+    // work-group up to PF_FUSED_MAX_PARTICLES particles, else partial + apply), the likelihood formed inside — one or two launches
     mcl3dl_hip_ctx* ctx = g->ctx[0];
     const int rc = [&]() -> int
     {

@@ -449,9 +449,9 @@ int device_order_scans(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b, const float*
       TRY(cloud_minmax(ctx, ctx->sp_samp[0].as<float4>(), ns, nullptr, nullptr));
     // a scan whose terms will be replayed in the caller's order (strict_order 1, or 2 from strict_auto_min points) and that is
     // at least two chunks long: ordered chunk by chunk of the caller's order (same keys, same bounding box for every chunk)
-    const size_t chunk = (ctx->strict_chunk >= 1024 && (ctx->strict_order == 1 || (ctx->strict_order == 2 && ns >= ctx->strict_auto_min)) &&
-                          n_s >= 2 * static_cast<size_t>(ctx->strict_chunk)) ? static_cast<size_t>(ctx->strict_chunk) & ~static_cast<size_t>(255) : 0;
-    if (ctx->scan_presorted)
+    const size_t chunk = (ctx->opt.strict_chunk >= 1024 && (ctx->opt.strict_order == 1 || (ctx->opt.strict_order == 2 && ns >= ctx->opt.strict_auto_min)) &&
+                          n_s >= 2 * static_cast<size_t>(ctx->opt.strict_chunk)) ? static_cast<size_t>(ctx->opt.strict_chunk) & ~static_cast<size_t>(255) : 0;
+    if (ctx->opt.scan_presorted)
     {
       // option scan_presorted: the caller holds its scans in the engine's order (mcl3dl_hip_scan_order_host) — installed as
       // they are, permutation = identity, no ordering launches
@@ -468,7 +468,7 @@ int device_order_scans(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b, const float*
       const RsFinal fin{ ctx->sp_samp[0].as<float4>() + first, ctx->scan_lik.as<float4>() + first, ctx->scan_perm.as<uint32_t>() + first, 1 };
       TRY(radix_sort<RS_KEY_MORTON>(ctx, kg, static_cast<long long>(n), MCL3DL_MORTON_BITS, &fin));
     }
-    ctx->scan_chunk = ctx->scan_presorted ? 0 : chunk;
+    ctx->scan_chunk = ctx->opt.scan_presorted ? 0 : chunk;
   }
   if (n_o && origins)  // (origins == nullptr: the caller's kernel has put them into ctx->origins already)
   {

@@ -1,5 +1,6 @@
 // host_context.h — part of the single translation unit mcl3dl_hip.hip (included there, nowhere else): the context
-// object behind mcl3dl_hip_ctx, error macros, device-buffer / staging helpers, hipEvent kernel timing.
+// object behind mcl3dl_hip_ctx (what the caller set is its `opt`: host_options.h), error macros, device-buffer / staging
+// helpers, hipEvent kernel timing.
 #pragma once
 
 namespace
@@ -54,8 +55,7 @@ struct mcl3dl_hip_ctx
   // kernel leaves idle while it waits on L2.
   hipStream_t aux_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  int overlap_models = 1;
-  long long overlap_min_rays = 262144;  // launches below this many rays keep both models on one stream
+  Options opt;  // everything mcl3dl_hip_set_option sets (host_options.h); the rest of this object is the engine's own state
   std::string err;
 
   // host copy of the map (kept to rebuild the device structures when parameters change)
@@ -103,96 +103,32 @@ struct mcl3dl_hip_ctx
   uint64_t lik_grid_merges = 0, lik_grid_rebuilds = 0;
   std::vector<float4> lik_upd_host;  // the update's rescaled points (host staging of the merge)
   LikGrid lg{};
-  // lik_index 2 = the candidate-voxel records (map_compiler.h) serve measure(), 0 = 27-cell scan of the cell grid (the canonical
-  // structure of SURVEY.md 8d, also what STATS counts on)
-  int lik_index = 2;
-  int lik_small = 1;       // 1 = several particles share a wavefront when the scan has <= 32 points
-  int lik_tiled = 1;       // 1 = tile-major XCD-aware kernel for large scans, 0 = one work-group per particle always
-  int lik_tiled_min = 1024;  // scans of at least this many points take the tiled kernel
-  int lik_group = 0;       // particles per work-group of the tiled kernel: 0 = chosen per launch, or 4 / 8 / 16 / 32
-  // up to this many particles a scan of > 512 points gets 1024 threads per particle: 512 x 16 wavefronts are ONE round of the
-  // chip's 8192 wavefront slots (profiles/r06m_wide_threshold.txt: 64 x 4096 27 -> 16 us, 300 x 3000 27 -> 22, 512 x 4096 34 -> 29;
-  // 1024 particles and more: 1.2 x SLOWER). Round 2 had set 64 from scans of ~1000 points; since round 6 this kernel serves
-  // every default-mode scan up to 4096 points below 2048 particles (caller-order rows)
-  int lik_wide_max_particles = 512;
-  int lik_coop = 1;        // tiled kernel: 1 = quad-cooperative record fetch + VALU-trimmed evaluation (same results)
   DevBuf lik_partial_sum, lik_partial_cnt;
-  int pf_fused = 1;        // 1 = pf::measure as ONE kernel up to pf_fused_max particles on one GPU (same bits, two launches fewer)
-  int pf_fused_max = 1024;  // measured: one work-group beats three launches up to 1024 particles, ties at 2048, loses at 4096
-  // 1 = add the likelihood terms AND the weights in the reference's float order (single GPU; bit-identical results);
-  // 2 (default) = replay the likelihood terms in that order for scans of at least strict_auto_min points, where the
-  // reference's own float rounding (a random walk of n_s roundings) reaches the 1e-5 tolerance of north_star; 0 = never
-  int strict_order = 2;
-  // strict_order 2: exact caller-order float sums for scans of at most strict_exact_max points and of at least strict_auto_min.
-  // strict_auto_min comes from a bound, not from a measurement: the reference's float recurrence over n positive terms
-  // differs from the exact sum by a random walk of n roundings, each within half an ulp of the running sum — relative
-  // standard deviation <= 2^-24 sqrt(n) / 3 (ulp(s_i) <= 2^-23 s_i, s_i ~ (i / n) S) — while the fp64 tree is the exact sum
-  // rounded once. Three standard deviations stay inside north_star's 1e-5 up to n = (1e-5 x 2^24)^2 = 28 147 points; from
-  // there on the default replays the reference's own order. (A bound on the WORST case, n x 2^-24, would put that limit at
-  // 168 points: sums of equal terms can drift systematically — which is what strict_exact_max and strict_order 1 are for.)
-  int strict_auto_min = 28147;
-  int strict_exact_max = 4096;
-  int strict_rows_max_particles = 2048;  // exact sums by the per-particle kernels' LDS rows below this many particles, by the tiled kernel + replay from it
   // the likelihoods the last launch_measure / one-launch update enqueued are the reference's floats bit for bit (caller-order
-  // rows, replay, in-kernel chain): pf::measure on one GPU then adds the weights in the reference's float order as well
+  // rows, replay, in-kernel chain). A diagnostic (read-only key "lik_exact"): how pf::measure adds the weights does not depend on
+  // it (host_pf.h:pf_float_order asks the options and the particle count alone)
   bool lik_exact = false;
-  double strict_auto_max_bytes = 0.0;  // > 0: the automatic replay is also skipped when its buffer would exceed this many bytes
   uint64_t strict_auto_skipped = 0;  // launches of the automatic mode that summed in fp64 because the replay buffer did not fit
   DevBuf scan_block;  // { perm | lik scan | beam scan | origins } of the current update in ONE allocation (ensure_scan_block)
   DevBuf scan_perm, strict_terms;
-  // Option strict_chunk > 0: a scan whose terms will be replayed in the caller's order is ORDERED in chunks of that order
-  // (strict_chunk points each, Morton order inside a chunk; scan_perm then holds indices relative to the chunk): chunk c + 1 is
-  // evaluated while chunk c is replayed on a stream of its own, and the term buffer holds two chunks instead of the whole scan
-  // (host_measure.h). Measured and OFF by default (profiles/r05g_chunked_replay.txt): the term buffer of C5 shrinks from 17 GB to
-  // 4.3 GB, but the update takes 27.9 instead of 25.6 ms — the replay's 1024-thread, 128 KB work-groups find no room next to
-  // the tiled kernel's (eight 19 KB work-groups per CU), so the two do not overlap and the shorter launches cost their tails.
-  // scan_chunk = chunk size the scan in place was ordered with (0 = one piece).
+  // chunk size the scan in place was ordered with (opt.strict_chunk; 0 = one piece)
   size_t scan_chunk = 0;
-  int strict_chunk = 0;
-  int scan_presorted = 0;  // option: likelihood scans arrive in the engine's order already — no ordering pass (see include/mcl3dl_hip.h)
   hipStream_t replay_stream = nullptr;
   hipEvent_t ev_tiled[2] = { nullptr, nullptr }, ev_replay[2] = { nullptr, nullptr };
-  // the whole update as one launch (update_kernels.h) up to update_small_max particles when the per-particle likelihood
-  // kernel would run anyway: same bits, two to four launches fewer. Measured (profiles/r03*_update_small.txt): ahead of the
-  // separate kernels up to ~500 particles (64 x 96 + 3: 26.9 -> 22.4 us, 64 x 1000: 13.7 -> 10.3), behind from 1024 on —
-  // every work-group's arrival is an atomic the memory side serialises, and there are as many as particles
-  int update_small = 1;
-  int update_small_max = 512;
-  int update_small_conformant = 0;  // 1 = acq_rel arrival tickets at agent scope (update_kernels.h:last_arrival)
   DevBuf us_tickets;
-  // host-buffer updates (mcl3dl_hip_measure_update): update_stage = 1: the caller's scans / poses / weights are taken over by
-  // ONE launch (stage_kernels.h:scan_stage_kernel — ordering included) for scans up to ST_MAX_POINTS points per model;
-  // update_zero_copy = 1: that kernel reads them where they lie in page-locked host memory and the last kernel of the update
-  // writes the results there (no DMA copy either way), 0 = one H2D copy of the staged block, one D2H copy of the results.
-  // (Rounds 4-5 also carried a two-launch tail — pf_norm_kernel, every work-group recomputing the reduction — and a
-  // per-particle-only form of the one-launch update; both measured slower than the split kernels and are gone: HISTORY.md.)
-  int update_stage = 1;
-  int update_zero_copy = 1;
-  // host-buffer updates end by POLLING a word in page-locked memory that a one-thread kernel behind the update's last kernel
-  // writes, instead of hipStreamSynchronize: 6.3 against 12.2 us for launch + completion of one kernel on this part
-  // (profiles/r04e_launch_cost.txt). 2 (default) = every synchronisation of the context's stream is that word (scan
-  // preparation -5..10 %, the post-update reductions -10 %, a whole filter iteration -8 %: profiles/r04ad_poll_all.txt),
-  // 1 = only the host-buffer update and its relatives, 0 = hipStreamSynchronize everywhere.
-  int poll_sync = 2;
-  // what the PLATFORM can do, set by pinned_alloc alone: page-locked memory visible to the device at the host's address. The
-  // two options above are what the caller asked for; what runs is option && capability (an option could
-  // switch a mode back on that the platform had ruled out, and update_zero_copy = 0 used to switch the polled word off for good)
+  // what the PLATFORM can do, set by pinned_alloc alone: page-locked memory visible to the device at the host's address.
+  // opt.update_zero_copy and opt.poll_sync are what the caller asked for; what runs is option && capability (an
+  // option could switch a mode back on that the platform had ruled out, and update_zero_copy = 0 used to switch the polled
+  // word off for good)
   bool zero_copy_supported = true;
   bool zero_copy() const
   {
-    return update_zero_copy != 0 && zero_copy_supported;
+    return opt.update_zero_copy != 0 && zero_copy_supported;
   }
   int poll_mode() const
   {
-    return zero_copy_supported ? poll_sync : 0;
+    return zero_copy_supported ? opt.poll_sync : 0;
   }
-  // completion waits: the polled word is spun on for at most poll_spin_us microseconds (covers every update up to a few
-  // thousand particles), then polled between naps that grow with the time already waited (a 25 ms update of 65 536 particles
-  // costs its caller ~2 ms of CPU, not 25), with hipStreamQuery looked at every few milliseconds so that a faulted queue
-  // comes back as an error instead of an endless wait
-  double poll_spin_us = 2000.0;
-  double poll_query_us = 5000.0;  // interval of the hipStreamQuery health checks while napping (option "poll_query_us")
-  bool test_late_structures = false;  // fault injection for the API-sequence fuzz (option of the same name, test hooks only)
   volatile unsigned* done_flag = nullptr;
   unsigned done_seq = 0;
   // strict_order = 3 (likelihood_kernels.h: LikChain): hand-off words, their tag counter, the page-locked error word
@@ -209,8 +145,6 @@ struct mcl3dl_hip_ctx
     float* user[3] = { nullptr, nullptr, nullptr };
     const float* host[3] = { nullptr, nullptr, nullptr };  // page-locked source of each (== user when that is page-locked)
   } prog;
-  int cand_prune_coop = 1;  // option "cand_prune_coop": 16 lanes per voxel in the map compiler's pruning pass (0 = one thread)
-  int batch_slice = 0;  // option "batch_slice": particles per slice of a progressive batch (0 = automatic)
   uint64_t batch_slices_run = 0;
   DevBuf stage_in_dev;
   // page-locked host memory handed out by mcl3dl_hip_host_alloc: arrays inside it are read / written in place
@@ -228,23 +162,12 @@ struct mcl3dl_hip_ctx
         return true;
     return false;
   }
-  double cand_voxel_ratio = 0.0;  // voxel edge / match_dist_min; 0 = chosen per map (host_map_compilers.h:build_cand_grid)
-  double cand_phase = 0.5;        // grid origin shifted by this fraction of a voxel (see build_cand_grid)
-  int cand_aniso = 2;             // option: voxel edges follow the dist_weight axis by axis (host_map_compilers.h:cand_axis_stretch): 0 never, 1 always, 2 when cubes exceed the budget
-  bool cand_aniso_active = false; // ... what the index in place was built with
-  double cand_aniso_max = 8.0;    // ... up to this factor over the base edge
-  double index_budget_opt = -1.0;   // option index_budget_bytes: upper bound of the candidate records; -1 = a quarter of the device's memory, 0 = none
-  double index_budget_bytes = 0.0;  // ... resolved at build time
+  bool cand_aniso_active = false;   // opt.cand_aniso as the index in place was built
+  double index_budget_bytes = 0.0;  // opt.index_budget_opt resolved at build time
   double cand_need_bytes = 0.0;     // record bytes the last priced voxel edge needs
   double cand_edge_ratio[3] = { 0.5, 0.5, 0.5 };  // voxel edge / match_dist_min of the index in place, per axis
-  int cand_record_parts = 0;      // inline candidates per voxel record: 4 (64 bytes), 8 (128 bytes), 0 = chosen per map
-  uint32_t cand_parts = 4;        // what the current index was built with
+  uint32_t cand_parts = 4;        // inline candidates per voxel record the current index was built with (opt.cand_record_parts)
   int n_cus = 256;                // compute units of the device (hipDeviceAttributeMultiprocessorCount)
-  int cand_packed = 1;            // option: packed w words in the voxel records when the map allows it (map_compiler.h)
-  int cand_bound = 1;             // option: ... with the skip bound of the overflow candidates (the bounded form) when the map allows it
-  int lik_defer = 1;              // option: overflow rounds of the tiled kernel deferred and run densely: 0 never, 1 always
-                                  // (packed 64-byte records), 2 = when more than lik_defer_min_frac of the voxels overflow
-  double lik_defer_min_frac = 0.03;
   double cand_over8 = 0;          // voxels with more than eight candidates (index statistics)
   DevBuf cand_table, cand_start, cand_pts, cand_rec, cand_ovf;
   // kept for map updates (host_map_compilers.h:update_cand_grid): geometry, sizes, every rescaled map point
@@ -259,18 +182,17 @@ struct mcl3dl_hip_ctx
   // records, voxel edge / match_dist_min actually used
   double cand_stats[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
   DevBuf dda_bits, dda_start, dda_pts, dda_index;
-  // the map update as an overlay of the DDA grid (DdaGrid::ov_*): option "dda_overlay"; dda_overlay_ok = the arrays above
+  // the map update as an overlay of the DDA grid (DdaGrid::ov_*, opt.dda_overlay); dda_overlay_ok = the arrays above
   // hold the base map only and the grid's bounds are the base map's, so an update inside them needs no rebuild
   DevBuf dda_ov_key, dda_ov_pts, dda_ov_idx;
-  int dda_overlay = 1;
   bool dda_overlay_ok = false;
   uint64_t dda_overlay_updates = 0;
   DdaGeom dda_geom{};
-  // the map as a device cloud (host_grid_builders.h); 1 = build the cell grid / the DDA grid on the host instead
+  // the map as a device cloud (host_grid_builders.h); opt.grid_build_host = 1: the cell grid / the DDA grid are built on the
+  // host instead
   DevBuf map_dev;
   bool map_dev_valid = false;
   size_t map_dev_n = 0;
-  int grid_build_host = 0;
   double grid_build_ms[2] = { 0, 0 };       // device time of the last cell-grid / DDA-grid build (device builders)
   double grid_build_wall_ms[2] = { 0, 0 };  // host wall time of the last build, either builder (upload of the map included)
   DdaGrid dg{};
@@ -278,10 +200,8 @@ struct mcl3dl_hip_ctx
 
   // scans of the current update
   DevBuf scan_lik, scan_beam, origins, pow_table;
-  // per-(particle, origin) ray constants (beam_origin_kernel) for launches of at least beam_prepare_min_rays rays
+  // per-(particle, origin) ray constants (beam_origin_kernel, opt.beam_prepare) for launches of at least BEAM_PREPARE_MIN_RAYS rays
   DevBuf beam_origin;
-  int beam_prepare = 1;
-  long long beam_prepare_min_rays = 32768;
   size_t n_s = 0, n_b = 0, n_o = 0;
   bool has_scan = false;
   bool pow_table_dirty = true;
@@ -316,9 +236,6 @@ struct mcl3dl_hip_ctx
   uint32_t sp_kept32[2] = { 0, 0 };                 // their counts, delivered by one synchronisation
   size_t sp_n_full = 0, sp_n_clip[2] = { 0, 0 }, sp_n_samp[2] = { 0, 0 };
   bool sp_ready = false;
-  int chain_ppl = 0;          // strict_order = 3: tiles per work-group (0 = by size, 1, 4: likelihood_chain_multi.h)
-  int chain_multi_max = 1536; // ... the four-tile form up to this many particles (profiles/r05r_chain_multi.txt: slower from 2048)
-  int scan_order_device = 4096;  // scans of at least this many points (both models together) are ordered on the device; 0 = never
   size_t n_base = 0;  // points of the base map; anything behind them in map_xyz is the current map update
   DevBuf ms_xyz, ms_out, ms_flag[2];
   // global localisation (api_global_loc.inl): VoxelGrid centroids of the base map, their private cell grid (rescaled points
@@ -350,9 +267,6 @@ struct mcl3dl_hip_ctx
       rs_d_ws, rs_d_dup8;
   bool rs_sorted = false;  // std::sort had ties to order: rs_order is not the identity
 
-  // counts everything that can change what an update enqueues (parameters, options, map, stream, scan sizes, reallocated
-  // buffers); kept as a cheap change stamp for diagnostics
-  uint64_t generation = 0;
   std::string index_note;  // why the map compiler fell back to a coarser / plainer index form (diagnostics)
 
   // Pinned staging for the host-buffer entry points: small copies go through page-locked memory so that
@@ -386,7 +300,6 @@ struct mcl3dl_hip_ctx
 
   // timing
   bool timing = false;
-  unsigned timing_mask = 0xffffffffu;  // bit k = time kernel group k (MCL3DL_KERNEL_*); each timed group costs two event records
   std::vector<EventPair> pending;
   std::vector<hipEvent_t> free_events;
   double kernel_ms[MCL3DL_KERNEL_COUNT] = {};
@@ -487,7 +400,6 @@ int ensure(mcl3dl_hip_ctx* ctx, DevBuf& b, size_t bytes)
   const size_t cap = bytes + bytes / 4;
   HIP_TRY(hipMalloc(&b.p, cap));
   b.cap = cap;
-  ++ctx->generation;  // a captured update graph holds the old address
   return 0;
 }
 
@@ -504,11 +416,9 @@ int ensure_scan_block(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b, size_t n_o, s
   ctx->scan_chunk = 0;  // (device_order_scans sets it again when it orders the scan in chunks)
   DevBuf* view[4] = { &ctx->scan_perm, &ctx->scan_lik, &ctx->scan_beam, &ctx->origins };
   size_t off = 0;
-  bool moved = false;
   for (int k = 0; k < 4; ++k)
   {
     void* at = ctx->scan_block.as<char>() + off;
-    moved = moved || view[k]->p != at;
     view[k]->p = at;
     view[k]->cap = part[k];
     view[k]->view = true;
@@ -516,8 +426,6 @@ int ensure_scan_block(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b, size_t n_o, s
       off4[k] = off;
     off += part[k];
   }
-  if (moved)
-    ++ctx->generation;  // a captured update graph holds the old addresses
   return 0;
 }
 
@@ -699,7 +607,7 @@ int spin_done_flag(mcl3dl_hip_ctx* ctx, unsigned seq)
     cpu_relax();
   }
   const double t0 = mono_us();
-  double next_query = ctx->poll_query_us;
+  double next_query = POLL_QUERY_US;
   for (;;)
   {
     for (int spin = 0; spin < 64; ++spin)
@@ -712,7 +620,7 @@ int spin_done_flag(mcl3dl_hip_ctx* ctx, unsigned seq)
       cpu_relax();
     }
     const double waited = mono_us() - t0;
-    if (waited < ctx->poll_spin_us)
+    if (waited < ctx->opt.poll_spin_us)
       continue;
     if (waited >= next_query)
     {
@@ -730,7 +638,7 @@ int spin_done_flag(mcl3dl_hip_ctx* ctx, unsigned seq)
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         return 0;
       }
-      next_query = waited + ctx->poll_query_us;
+      next_query = waited + POLL_QUERY_US;
     }
     const double nap_us = std::min(1000.0, waited / 32.0);
     timespec ts{ 0, static_cast<long>(nap_us * 1e3) };
@@ -853,7 +761,7 @@ int timing_begin(mcl3dl_hip_ctx* ctx, int kernel, EventPair* ep, hipStream_t on 
   if (!on)
     on = ctx->stream;
   ep->start = nullptr;
-  if (!ctx->timing || !(ctx->timing_mask & (1u << kernel)))
+  if (!ctx->timing || !(ctx->opt.timing_mask & (1u << kernel)))
     return 0;
   hipEvent_t ev[2];
   for (int i = 0; i < 2; ++i)

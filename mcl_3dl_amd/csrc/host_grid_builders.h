@@ -253,7 +253,7 @@ int build_dda_grid_device(mcl3dl_hip_ctx* ctx)
   const size_t n_base = (ctx->n_base && ctx->n_base <= n) ? ctx->n_base : n;
   const size_t n_upd = n - n_base;
   bool overlay = false;
-  if (n_upd > 0 && ctx->dda_overlay)
+  if (n_upd > 0 && ctx->opt.dda_overlay)
   {
     float mb[6];
     unsigned long long nf = 0;
@@ -330,7 +330,7 @@ int build_dda_grid_device(mcl3dl_hip_ctx* ctx)
   HIP_TRY(hipEventSynchronize(tm.ev1));  // (the stream may have been waited for through the polled word: the event is past, the runtime has to look)
   HIP_TRY(hipEventElapsedTime(&ms, tm.ev0, tm.ev1));
   ctx->grid_build_ms[1] = ms;
-  ctx->dda_overlay_ok = ctx->dda_overlay && (n_upd == 0 || overlay);
+  ctx->dda_overlay_ok = ctx->opt.dda_overlay && (n_upd == 0 || overlay);
   dda_ray_constants(ctx, d);
   ctx->footprint[2] = sizeof(unsigned long long) * n_bricks;
   ctx->footprint[3] = sizeof(uint32_t) * (total + 1);
@@ -342,7 +342,7 @@ int build_dda_grid_device(mcl3dl_hip_ctx* ctx)
 int build_lik_grid(mcl3dl_hip_ctx* ctx)
 {
   const auto t0 = std::chrono::steady_clock::now();
-  const int rc = ctx->grid_build_host ? build_lik_grid_host(ctx) : build_lik_grid_device(ctx);
+  const int rc = ctx->opt.grid_build_host ? build_lik_grid_host(ctx) : build_lik_grid_device(ctx);
   ctx->grid_build_wall_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return rc;
 }
@@ -350,7 +350,7 @@ int build_lik_grid(mcl3dl_hip_ctx* ctx)
 int build_dda_grid(mcl3dl_hip_ctx* ctx)
 {
   const auto t0 = std::chrono::steady_clock::now();
-  const int rc = ctx->grid_build_host ? build_dda_grid_host(ctx) : build_dda_grid_device(ctx);
+  const int rc = ctx->opt.grid_build_host ? build_dda_grid_host(ctx) : build_dda_grid_device(ctx);
   ctx->grid_build_wall_ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return rc;
 }

@@ -366,7 +366,7 @@ void cand_axis_stretch(const mcl3dl_hip_ctx* ctx, double stretch[3])
   for (int a = 0; a < 3; ++a)
   {
     const double w = std::fabs(static_cast<double>(ctx->weight[a]));
-    stretch[a] = std::min(std::max(w / wmin, 1.0), ctx->cand_aniso_max);
+    stretch[a] = std::min(std::max(w / wmin, 1.0), ctx->opt.cand_aniso_max);
   }
 }
 
@@ -407,7 +407,7 @@ int cand_geometry(mcl3dl_hip_ctx* ctx, double voxel_ratio, const double stretch[
     // Phase: maps that come out of a voxel filter sit on a lattice; with the origin ON that lattice every voxel face
     // coincides with a Voronoi face of the map and each voxel keeps 3 candidates per axis instead of the 2 a generic
     // position needs. Half a voxel of phase puts lattice maps in the generic position; arbitrary maps do not care.
-    o[a] = mn[a] - static_cast<float>((reach[a] + 1 + ctx->cand_phase) * ed[a]);
+    o[a] = mn[a] - static_cast<float>((reach[a] + 1 + ctx->opt.cand_phase) * ed[a]);
     nv[a] = static_cast<int>(std::floor((static_cast<double>(mx[a]) - o[a]) / ed[a])) + reach[a] + 2;
     nb[a] = (nv[a] + 7) / 8;
     n_table_d *= nb[a];
@@ -537,7 +537,7 @@ int compile_bricks(mcl3dl_hip_ctx* ctx, const CompileParams& cp, const float4* p
                        static_cast<const uint32_t*>(d_d2.p), static_cast<uint32_t*>(d_count.p),
                        static_cast<const uint32_t*>(d_pstart.p), static_cast<uint32_t*>(d_prelim.p), n_threads);
   // prune; d_count becomes the kept count per voxel
-  if (ctx->cand_prune_coop)
+  if (ctx->opt.cand_prune_coop)
   {
     // runs of up to 32: sixteen lanes per voxel; 33 .. 256: one wavefront per voxel, from a list the first kernel writes; the
     // rest: one thread per voxel
@@ -593,7 +593,7 @@ int compile_bricks(mcl3dl_hip_ctx* ctx, const CompileParams& cp, const float4* p
   if (want_packed >= 0)
     out->packed = want_packed;
   else
-    out->packed = (can_bound && ctx->cand_packed && ctx->cand_bound) ? 2 : (can_pack && ctx->cand_packed) ? 1 : 0;
+    out->packed = (can_bound && ctx->opt.cand_packed && ctx->opt.cand_bound) ? 2 : (can_pack && ctx->opt.cand_packed) ? 1 : 0;
   TRY(scratch_alloc(ctx, out->d_ovf_data, 64ull * (n_ovf ? n_ovf : 1)));
   {
     // unused candidate slots of an overflow record hold the sentinel, like those of a voxel record
@@ -664,7 +664,7 @@ int build_cand_grid_at(mcl3dl_hip_ctx* ctx, double voxel_ratio, uint32_t cap = 4
   if (n_bricks == 0 || n_bricks > (1u << 22))
     return ctx->fail(-4, "candidate index: %u bricks", n_bricks);
   ctx->cand_need_bytes = static_cast<double>(rec_bytes) * 512.0 * n_bricks;
-  if (ctx->lik_index == 2 && ctx->index_budget_bytes > 0.0 && ctx->cand_need_bytes > ctx->index_budget_bytes)
+  if (ctx->opt.lik_index == 2 && ctx->index_budget_bytes > 0.0 && ctx->cand_need_bytes > ctx->index_budget_bytes)
     return RC_OVER_BUDGET;
   // one entry more than the grid has bricks: entry n_table is always -1, the entry lanes without a voxel read (eval_coop)
   TRY(ensure(ctx, ctx->cand_table, sizeof(int) * (n_table + 1)));
@@ -676,7 +676,7 @@ int build_cand_grid_at(mcl3dl_hip_ctx* ctx, double voxel_ratio, uint32_t cap = 4
   hipLaunchKernelGGL(mc_brick_coords, dim3(static_cast<unsigned>((n_table + 255) / 256)), dim3(256), 0, ctx->stream,
                      table, cp.nbx, cp.nby, n_table, static_cast<int*>(d_bxyz.p));
   const long long n_vox = static_cast<long long>(n_bricks) * 512;
-  const bool records = ctx->lik_index == 2;
+  const bool records = ctx->opt.lik_index == 2;
   if (records)
     TRY(ensure(ctx, ctx->cand_rec, rec_bytes * static_cast<size_t>(n_vox)));
   CompileOutput co;
@@ -757,7 +757,7 @@ int build_cand_grid_at(mcl3dl_hip_ctx* ctx, double voxel_ratio, uint32_t cap = 4
 int build_cand_grid_budgeted(mcl3dl_hip_ctx* ctx, double ratio, uint32_t cap, double* ratio_used = nullptr)
 {
   // the budget: option index_budget_bytes; -1 (default) = a quarter of the device's memory, 0 = none
-  if (ctx->index_budget_opt < 0.0)
+  if (ctx->opt.index_budget_opt < 0.0)
   {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess)
@@ -768,11 +768,11 @@ int build_cand_grid_budgeted(mcl3dl_hip_ctx* ctx, double ratio, uint32_t cap, do
     ctx->index_budget_bytes = 0.25 * static_cast<double>(total_b);
   }
   else
-    ctx->index_budget_bytes = ctx->index_budget_opt;
+    ctx->index_budget_bytes = ctx->opt.index_budget_opt;
   // cubes first (fastest: profiles/r05e_aniso_ab.txt); boxes that follow the dist_weight when the cubes do not fit the budget
   // (option cand_aniso = 2, the default; 1 = always boxes, 0 = never); then coarser voxels
-  const bool can_stretch = ctx->has_weight && ctx->cand_aniso != 0;
-  ctx->cand_aniso_active = ctx->cand_aniso == 1 && can_stretch;
+  const bool can_stretch = ctx->has_weight && ctx->opt.cand_aniso != 0;
+  ctx->cand_aniso_active = ctx->opt.cand_aniso == 1 && can_stretch;
   const double asked = ratio;
   const bool asked_aniso = ctx->cand_aniso_active;
   // (every step either switches to boxes — once — or coarsens the edge by at least 8 %, so the loop reaches 1.5 r within 20
@@ -811,13 +811,13 @@ int build_cand_grid_budgeted(mcl3dl_hip_ctx* ctx, double ratio, uint32_t cap, do
 
 int build_cand_grid(mcl3dl_hip_ctx* ctx)
 {
-  const uint32_t forced = ctx->cand_record_parts == 8 ? 8u : ctx->cand_record_parts == 4 ? 4u : 0u;
-  if (ctx->cand_voxel_ratio > 0.0)
-    return build_cand_grid_budgeted(ctx, ctx->cand_voxel_ratio, forced ? forced : 4u);
+  const uint32_t forced = ctx->opt.cand_record_parts == 8 ? 8u : ctx->opt.cand_record_parts == 4 ? 4u : 0u;
+  if (ctx->opt.cand_voxel_ratio > 0.0)
+    return build_cand_grid_budgeted(ctx, ctx->opt.cand_voxel_ratio, forced ? forced : 4u);
   double base = 0.5;
   TRY(build_cand_grid_budgeted(ctx, 0.5, forced ? forced : 4u, &base));
   const double crowded = forced == 8 ? ctx->cand_over8 : ctx->cand_stats[5];  // voxels whose candidates do not fit the record
-  if (base == 0.5 && ctx->lik_index == 2 && ctx->cand_stats[4] > 0 && crowded / ctx->cand_stats[4] > 0.25)
+  if (base == 0.5 && ctx->opt.lik_index == 2 && ctx->cand_stats[4] > 0 && crowded / ctx->cand_stats[4] > 0.25)
   {
     // a crowded map (voxel-filter centroids rather than a lattice): smaller voxels, and — unless the record size is forced
     // or the tiled kernel queues its overflow rounds (below) — 128-byte records with eight inline candidates when they stay
@@ -825,7 +825,7 @@ int build_cand_grid(mcl3dl_hip_ctx* ctx)
     // the jittered C2 map with immediate overflow rounds: 0.42 ms (0.5 r, 64 B) -> 0.364 (0.36 r, 64 B) -> 0.338 (0.36 r,
     // 128 B); on a lattice the wide record costs 20 %, so it is never the default there.
     const double first_ms = ctx->cand_stats[3];
-    const bool defer = ctx->lik_defer != 0 && ctx->cand_packed != 0 && ctx->rg.packed != 0;
+    const bool defer = ctx->opt.lik_defer != 0 && ctx->opt.cand_packed != 0 && ctx->rg.packed != 0;
     const double fine = 0.36;  // with the queue: 0.30 r measured 1.6 % faster at +-0.045 m, 2.6 % slower at +-0.02 m, twice the memory
     const double est_bricks = ctx->cand_stats[0] * std::pow(0.5 / fine, 3.0);
     const double est_bytes = 128.0 * 512.0 * est_bricks;
@@ -875,7 +875,6 @@ int ensure_keep(mcl3dl_hip_ctx* ctx, DevBuf& b, size_t keep_bytes, size_t bytes)
     HIP_TRY(hipFree(old));
   b.p = fresh;
   b.cap = cap;
-  ++ctx->generation;
   return 0;
 }
 
@@ -915,7 +914,6 @@ int compact_overflow(mcl3dl_hip_ctx* ctx)
   ctx->footprint[7] = 64ull * live;
   ctx->cand_stats[6] = live;
   ++ctx->cand_ovf_compactions;
-  ++ctx->generation;
   return 0;
 }
 
@@ -932,10 +930,10 @@ int update_cand_grid(mcl3dl_hip_ctx* ctx, size_t n_base, const std::vector<float
   if (stats5)
     for (int i = 0; i < 6; ++i)
       stats5[i] = 0;
-  if (ctx->cand_dirty || ctx->lik_index != 2 || ctx->cand_n_points != n_base + old_update.size())
+  if (ctx->cand_dirty || ctx->opt.lik_index != 2 || ctx->cand_n_points != n_base + old_update.size())
   {
     if (stats5)
-      stats5[5] = ctx->cand_dirty ? 1 : ctx->lik_index != 2 ? 2 : 3;
+      stats5[5] = ctx->cand_dirty ? 1 : ctx->opt.lik_index != 2 ? 2 : 3;
     ctx->cand_dirty = true;
     return 0;
   }
@@ -1103,7 +1101,6 @@ int update_cand_grid(mcl3dl_hip_ctx* ctx, size_t n_base, const std::vector<float
   ctx->footprint[7] = 64ull * ctx->cand_n_ovf;
   ctx->cand_stats[0] = n_bricks;
   ctx->cand_stats[6] = ctx->cand_n_ovf;
-  ++ctx->generation;
   if (stats5)
   {
     stats5[0] = n_dirty;

@@ -13,18 +13,18 @@ int ensure_structures(mcl3dl_hip_ctx* ctx, bool need_lik, bool need_dda, bool ne
   bool built = false;
   // a cell grid laid out for the kd-tree caster's radius (lik_cell_edge) does not serve the likelihood model's 27-cell
   // search: that model running on its default parameters counts as having set them
-  if (need_lik && ctx->lik_index == 0 && !need_cells && !ctx->lik_params_set && (ctx->lik_cell_from_beam || lik_cell_is_beams(ctx)))
+  if (need_lik && ctx->opt.lik_index == 0 && !need_cells && !ctx->lik_params_set && (ctx->lik_cell_from_beam || lik_cell_is_beams(ctx)))
   {
     ctx->lik_params_set = true;
     if (ctx->lik_cell_from_beam)
       ctx->lik_dirty = ctx->lik_base_dirty = true;
   }
-  if (need_lik && (ctx->lik_index == 0 || need_cells) && ctx->lik_dirty)
+  if (need_lik && (ctx->opt.lik_index == 0 || need_cells) && ctx->lik_dirty)
   {
     TRY(build_lik_grid(ctx));
     built = true;
   }
-  if (need_lik && ctx->lik_index >= 1 && !need_cells && ctx->cand_dirty)
+  if (need_lik && ctx->opt.lik_index >= 1 && !need_cells && ctx->cand_dirty)
   {
     TRY(build_cand_grid(ctx));
     built = true;
@@ -95,7 +95,6 @@ int ensure_caster_structures(mcl3dl_hip_ctx* ctx, bool need_lik, bool need_beam,
                          n_cells, ctx->kd_occ.as<unsigned long long>());
       HIP_TRY(hipGetLastError());
       ctx->kd_occ_reach = k.reach1;
-      ++ctx->generation;
     }
   }
   return 0;
@@ -176,7 +175,6 @@ int ensure_pow_table(mcl3dl_hip_ctx* ctx, size_t n_b_coming = 0)
   TRY(sync_stream(ctx));
   ctx->pow_table_dirty = false;
   ctx->pow_table_len = len;
-  ++ctx->generation;
   return 0;
 }
 
@@ -216,25 +214,25 @@ LikMode lik_mode(const mcl3dl_hip_ctx* ctx, int np, int ns)
   LikMode m;
   // tiled from lik_tiled_min points up (default 1024), and already from three quarters of that when there are enough particles
   // to fill the GPU with (tile, group) pairs (4096 x 1000: 30.6 us tiled against 34.9 us; 64 x 1000 and 4096 x 512: no gain)
-  const bool by_size = ctx->lik_tiled && np >= 4 &&
-                       (ns >= ctx->lik_tiled_min || (np >= 256 && 4 * static_cast<long long>(ns) >= 3ll * ctx->lik_tiled_min));
-  if (ctx->strict_order == 3)
+  const bool by_size = ctx->opt.lik_tiled && np >= 4 &&
+                       (ns >= ctx->opt.lik_tiled_min || (np >= 256 && 4 * static_cast<long long>(ns) >= 3ll * ctx->opt.lik_tiled_min));
+  if (ctx->opt.strict_order == 3)
   {
     m.tiled = true;  // the in-kernel chain, in the engine's scan order
     return m;
   }
-  const bool exact = ctx->strict_order == 1 ||
-                     (ctx->strict_order == 2 && (ns <= ctx->strict_exact_max || ns >= ctx->strict_auto_min));
+  const bool exact = ctx->opt.strict_order == 1 ||
+                     (ctx->opt.strict_order == 2 && (ns <= ctx->opt.strict_exact_max || ns >= ctx->opt.strict_auto_min));
   // (a scan ordered in chunks of the caller's order — option strict_chunk — carries chunk-relative indices: the replay's business)
   const bool rows_fit = ns <= LIK_ROW_MAX && ctx->scan_chunk == 0;
   if (!exact)
   {
     m.tiled = by_size;
     // where a per-particle kernel runs anyway the rows cost a few per cent: exact there too (unless told not to: strict_order 0)
-    m.rows = !by_size && ctx->strict_order == 2 && rows_fit;
+    m.rows = !by_size && ctx->opt.strict_order == 2 && rows_fit;
     return m;
   }
-  if (rows_fit && (!by_size || np < ctx->strict_rows_max_particles))
+  if (rows_fit && (!by_size || np < STRICT_ROWS_MAX_PARTICLES))
     m.rows = true;
   else
     m.tiled = m.replay = true;
@@ -244,13 +242,13 @@ LikMode lik_mode(const mcl3dl_hip_ctx* ctx, int np, int ns)
 // the small-scan kernel (likelihood_small_kernel: W lanes per particle) takes what the tiled kernel leaves of short scans
 bool lik_small_applies(const mcl3dl_hip_ctx* ctx, const LikMode& m, int np, int ns)
 {
-  return !m.tiled && ns <= 32 && np >= 256 && ctx->lik_small;
+  return !m.tiled && ns <= 32 && np >= 256 && ctx->opt.lik_small;
 }
 
 // the likelihood kernels' cooperative form: its sqrt needs match_dist_min > 1.2e-7 m (likelihood_kernels.h:sqrt_in_radius)
 bool lik_coop_active(const mcl3dl_hip_ctx* ctx)
 {
-  return ctx->lik_coop && ctx->lik_index == 2 && ctx->match_dist_min > 1e-5f;
+  return ctx->opt.lik_coop && ctx->opt.lik_index == 2 && ctx->match_dist_min > 1e-5f;
 }
 
 // Work-group size of the per-particle likelihood kernel — and of whatever carries it (lik_particle_beam_kernel, the one-launch
@@ -260,7 +258,7 @@ int lik_particle_block(const mcl3dl_hip_ctx* ctx, int np, int ns)
   if (ns <= 128)
     return 64;
   // few particles: 16 wavefronts share a scan — a quarter of the dependent load chains per lane
-  if (ctx->lik_index == 2 && np <= ctx->lik_wide_max_particles && ns > 512)
+  if (ctx->opt.lik_index == 2 && np <= LIK_WIDE_MAX_PARTICLES && ns > 512)
     return 1024;
   return 256;
 }
@@ -307,12 +305,12 @@ Interleave interleave(long long n_beam, long long n_other)
 // on maps where enough voxels overflow for a wavefront to meet one in nearly every round
 bool lik_defer_active(const mcl3dl_hip_ctx* ctx)
 {
-  if (ctx->lik_defer == 0 || ctx->lik_index != 2 || !ctx->rg.packed || ctx->rg.rec_parts != 4)
+  if (ctx->opt.lik_defer == 0 || ctx->opt.lik_index != 2 || !ctx->rg.packed || ctx->rg.rec_parts != 4)
     return false;
-  if (ctx->lik_defer == 1)
+  if (ctx->opt.lik_defer == 1)
     return true;
   const double with_cand = ctx->cand_stats[4], over4 = ctx->cand_stats[5];
-  return with_cand > 0 && over4 / with_cand > ctx->lik_defer_min_frac;
+  return with_cand > 0 && over4 / with_cand > LIK_DEFER_MIN_FRAC;
 }
 
 // hand-off words + error word of the in-kernel chain for n_p particles and n_tiles tiles; *tag0 = tag of tile 0
@@ -391,7 +389,7 @@ int plan_group_size(const mcl3dl_hip_ctx* ctx, int np, int ns)
 {
   // particles per work-group of the tiled kernel: the largest of 16 / 8 / 4 that still gives the 256 CUs x 8
   // work-group slots something to do (few particles x a long scan would otherwise leave most of the GPU idle)
-  int group_size = ctx->lik_group;
+  int group_size = ctx->opt.lik_group;
   if (group_size == 0)
   {
     const long long n_tiles_ll = (ns + 255) / 256;
@@ -473,7 +471,7 @@ struct MeasurePlan
 // explicitly — still fails loudly.)
 bool auto_replay_affordable(mcl3dl_hip_ctx* ctx, size_t need)
 {
-  const bool over_cap = ctx->strict_auto_max_bytes > 0.0 && static_cast<double>(need) > ctx->strict_auto_max_bytes;
+  const bool over_cap = ctx->opt.strict_auto_max_bytes > 0.0 && static_cast<double>(need) > ctx->opt.strict_auto_max_bytes;
   if (!over_cap && need <= ctx->strict_terms.cap)
     return true;
   if (!over_cap)
@@ -500,9 +498,9 @@ int plan_chain(mcl3dl_hip_ctx* ctx, size_t n_p, MeasurePlan* pl)
   const int np = static_cast<int>(n_p);
   // few particles on a long scan (default kernel family only): four tiles per work-group, a quarter of the hand-offs
   // (likelihood_chain_multi.h). chain_ppl: 0 = by size, 1 = never, 4 = whenever the family allows.
-  const bool family = pl->coop && pl->defer && ctx->lik_group == 0;
+  const bool family = pl->coop && pl->defer && ctx->opt.lik_group == 0;
   int n_handoffs = pl->n_tiles;
-  if (family && (ctx->chain_ppl == 4 || (ctx->chain_ppl == 0 && pl->n_tiles >= 16 && np <= ctx->chain_multi_max)))
+  if (family && (ctx->opt.chain_ppl == 4 || (ctx->opt.chain_ppl == 0 && pl->n_tiles >= 16 && np <= CHAIN_MULTI_MAX)))
   {
     pl->lik = LikRoute::ChainMulti;
     pl->group_size = 4;
@@ -527,13 +525,13 @@ int plan_lik(mcl3dl_hip_ctx* ctx, size_t n_p, int ns, MeasurePlan* pl)
   const int np = static_cast<int>(n_p);
   const LikMode mode = lik_mode(ctx, np, ns);
   pl->rows = mode.rows;
-  pl->mode = ctx->lik_index == 2 ? 2 : 0;
+  pl->mode = ctx->opt.lik_index == 2 ? 2 : 0;
   pl->coop = lik_coop_active(ctx);
   pl->group_size = plan_group_size(ctx, np, ns);
-  const bool chain = ctx->strict_order == 3;
+  const bool chain = ctx->opt.strict_order == 3;
   if (chain && pl->group_size > 16)
     pl->group_size = 16;
-  const bool strict = mode.replay && (ctx->strict_order != 2 || auto_replay_affordable(ctx, strict_plan_bytes(ctx, n_p, ns, pl->group_size)));
+  const bool strict = mode.replay && (ctx->opt.strict_order != 2 || auto_replay_affordable(ctx, strict_plan_bytes(ctx, n_p, ns, pl->group_size)));
   if (lik_small_applies(ctx, mode, np, ns))
   {
     pl->lik = LikRoute::Small;
@@ -599,9 +597,9 @@ int plan_beam(mcl3dl_hip_ctx* ctx, size_t n_p, bool with_lik, MeasurePlan* pl)
   TRY(prepare_beam(ctx, n_p, &pl->n_rays, &pl->beam_blocks));
   const long long n_rays = pl->n_rays, blocks = pl->beam_blocks;
   // (the prepared origins and the launches of both models below are the DDA walk's: the kd-tree caster runs as a launch of
-  // its own, behind or — from overlap_min_rays rays — beside the likelihood kernel on the second stream)
+  // its own, behind or — from OVERLAP_MIN_RAYS rays — beside the likelihood kernel on the second stream)
   pl->kd = ctx->beam_raycast == 1;
-  pl->prepared = !pl->kd && ctx->beam_prepare && n_rays >= ctx->beam_prepare_min_rays &&
+  pl->prepared = !pl->kd && ctx->opt.beam_prepare && n_rays >= BEAM_PREPARE_MIN_RAYS &&
                  static_cast<long long>(n_p) * static_cast<long long>(ctx->n_o) < 0x7fffffffLL;
   if (pl->prepared)
     TRY(ensure(ctx, ctx->beam_origin, sizeof(BeamOrigin) * n_p * ctx->n_o));
@@ -612,14 +610,14 @@ int plan_beam(mcl3dl_hip_ctx* ctx, size_t n_p, bool with_lik, MeasurePlan* pl)
   // overlaps the rest of the beam kernel, which the lock-step interleave cannot offer (C5 shard: 3.09 against 3.14 ms).
   // Measured, C3: 0.3446 (two streams) -> 0.3313 ms; 4096 rays per particle: 1.0855 -> 1.0070 (profiles/r06s_lik_beam_one_launch.txt).
   // (the beam kernel's map-update-overlay form needs 66 VGPRs: it would spill inside the 64 of the merged launch)
-  const bool mergeable = !pl->kd && ctx->overlap_models && with_lik && ctx->dg.ov_n == 0;
+  const bool mergeable = !pl->kd && ctx->opt.overlap_models && with_lik && ctx->dg.ov_n == 0;
   const bool with_tiled = mergeable && pl->group_size <= 16 && pl->coop && blocks >= 64 && blocks < 0x3fffffffLL &&
                           pl->blocks < 0x3fffffffLL;
-  // (in front of the caller-order replay: two streams only where they would be used — from overlap_min_rays rays — AND the replay
+  // (in front of the caller-order replay: two streams only where they would be used — from OVERLAP_MIN_RAYS rays — AND the replay
   // is long enough to hide the beam kernel's tail behind: a term array of at least half a gigabyte. Measured, merged against
   // streams: 4096 x 4096 + 128 rays - 12 %, 16384 x 4096 + 512 (268 MB) - 3 %, 8192 x 32768 + 512 (1 GB) + 1 %, the C5 shard + 2 %:
   // profiles/r06s_lik_beam_one_launch.txt)
-  pl->replay_is_long = pl->strict_terms != nullptr && n_rays >= ctx->overlap_min_rays &&
+  pl->replay_is_long = pl->strict_terms != nullptr && n_rays >= OVERLAP_MIN_RAYS &&
                        strict_terms_bytes(n_p, static_cast<int>(ctx->n_s), pl->group_size) >= (static_cast<size_t>(512) << 20);
   if (with_tiled && pl->lik == LikRoute::Tiled && !pl->chunk && !pl->replay_is_long)
     pl->beam = BeamRoute::MergedTiled;
@@ -628,11 +626,11 @@ int plan_beam(mcl3dl_hip_ctx* ctx, size_t n_p, bool with_lik, MeasurePlan* pl)
     pl->beam = BeamRoute::MergedChain;
   // (the per-particle likelihood kernel's 64- and 256-thread forms take the beam kernel's work-groups along the same way:
   // lik_particle_beam_kernel)
-  else if (mergeable && pl->lik == LikRoute::Particle && ctx->lik_index == 2 && pl->block != 1024 && blocks >= 16 && blocks < 0x0fffffffLL)
+  else if (mergeable && pl->lik == LikRoute::Particle && ctx->opt.lik_index == 2 && pl->block != 1024 && blocks >= 16 && blocks < 0x0fffffffLL)
     pl->beam = BeamRoute::MergedParticle;
   // the second stream pays only for large launches: the fork / join events cost ~35 us (64 particles x 96 + 3 points:
   // 52 us per update with them, 17 without), the overlap itself is worth ~5 % at C3 (2.1 M rays)
-  else if (ctx->overlap_models && with_lik && n_rays >= ctx->overlap_min_rays)
+  else if (ctx->opt.overlap_models && with_lik && n_rays >= OVERLAP_MIN_RAYS)
     pl->beam = BeamRoute::Aux;
   else
     pl->beam = BeamRoute::Main;
@@ -1190,9 +1188,9 @@ bool pf_float_order(const mcl3dl_hip_ctx* ctx, size_t n_p);  // host_pf.h
 int launch_update_small(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, float* d_weight, const float* d_extra,
                         float* d_lik, float* d_ratio, float* d_beam, float* d_stats4, const PfEmit* ho = nullptr)
 {
-  if (!ctx->update_small || n_p == 0 || ctx->n_b > 256 || ctx->strict_order == 3 || !ctx->has_scan || !d_lik || !d_ratio || !d_beam)
+  if (!ctx->opt.update_small || n_p == 0 || ctx->n_b > 256 || ctx->opt.strict_order == 3 || !ctx->has_scan || !d_lik || !d_ratio || !d_beam)
     return 0;
-  if (n_p > static_cast<size_t>(ctx->update_small_max))
+  if (n_p > static_cast<size_t>(ctx->opt.update_small_max))
     return 0;
   if (ctx->beam_raycast == 1 && ctx->n_b > 0)
     return 0;  // the one-launch kernel casts with the DDA walk: the kd-tree caster runs through the separate kernels
@@ -1246,7 +1244,7 @@ int launch_update_small(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, fl
   a.tickets = ctx->us_tickets.as<unsigned>();
   a.packed = ctx->partial4.as<double>();
   a.stats4 = d_stats4;
-  a.conformant = ctx->update_small_conformant;
+  a.conformant = ctx->opt.update_small_conformant;
   a.emit = ho ? *ho : PfEmit{};
   // the reference's float recurrences, in its own order: the likelihood terms over the caller's scan (lik_particle's row) and —
   // where this launch also finishes pf::measure — the weights over the particles (pf.h:255-260)
@@ -1258,7 +1256,7 @@ int launch_update_small(mcl3dl_hip_ctx* ctx, const float* d_pose, size_t n_p, fl
   EventPair ep{};
   TRY(timing_begin(ctx, MCL3DL_KERNEL_UPDATE, &ep));
   // (the separate likelihood kernel's work-group size, so that the lanes add in the same order)
-  dispatch_particle(lik_particle_block(ctx, np, ns), ctx->lik_index == 2 ? 2 : 0, [&](auto b, auto m) {
+  dispatch_particle(lik_particle_block(ctx, np, ns), ctx->opt.lik_index == 2 ? 2 : 0, [&](auto b, auto m) {
     constexpr int BLOCK = decltype(b)::value;
     hipLaunchKernelGGL((update_small_kernel<BLOCK, decltype(m)::value>), dim3(static_cast<unsigned>(n_p)), dim3(BLOCK), row_bytes,
                        ctx->stream, a);

@@ -10,24 +10,26 @@ int pf_blocks(size_t n)
 }
 
 // ---- the decisions ------------------------------------------------------------------------------------------------------
-// the particle counts of the fused work-group: up to pf_fused_max (default 1024; the kernel takes up to PF_FUSED_MAX = 4096)
-bool pf_fused_range(const mcl3dl_hip_ctx* ctx, size_t n_p)
+// the particle counts of the fused work-group: up to the constant PF_FUSED_MAX_PARTICLES (1024, host_options.h; the kernel takes up
+// to PF_FUSED_MAX = 4096)
+static_assert(PF_FUSED_MAX_PARTICLES <= PF_FUSED_MAX, "the fused kernel's LDS row holds PF_FUSED_MAX weights");
+bool pf_fused_range(size_t n_p)
 {
-  return n_p <= static_cast<size_t>(std::min(ctx->pf_fused_max, PF_FUSED_MAX));
+  return n_p <= static_cast<size_t>(PF_FUSED_MAX_PARTICLES);
 }
 
 // Does pf::measure on ONE GPU add the un-normalised weights as the reference does (pf.h:255-260: float, sequentially, particle
-// order; float_chain.h) instead of the fp64 tree? strict_order 1: always. The default (2): up to pf_fused_max = 1024 particles —
+// order; float_chain.h) instead of the fp64 tree? strict_order 1: always. The default (2): up to PF_FUSED_MAX_PARTICLES = 1024 particles —
 // the reference's operating range; pf::measure is then the reference's arithmetic bit for bit given its inputs, inside the
 // fused kernel / the one-launch update at no extra launch. Beyond that the recurrence needs a launch of its own
 // (pf_strict_sum_kernel: +10 us at 4096 particles, a third of a 4096 x 96 update, profiles/r06d_rows_vs_replay.txt) for weights
 // that agree to ~1e-7 anyway. Independent of pf_fused, so that the fused and the split form give the same bits.
 bool pf_float_order(const mcl3dl_hip_ctx* ctx, size_t n_p)
 {
-  return ctx->strict_order == 1 || (ctx->strict_order == 2 && pf_fused_range(ctx, n_p));
+  return ctx->opt.strict_order == 1 || (ctx->opt.strict_order == 2 && pf_fused_range(n_p));
 }
 
-// pf::measure on one GPU: the fused single-work-group kernel up to pf_fused_max particles (same bits as the split form), the
+// pf::measure on one GPU: the fused single-work-group kernel up to PF_FUSED_MAX_PARTICLES particles (same bits as the split form), the
 // split form beyond — with the fp64 tree over the weights TWO launches since round 6 (five with lik_finalize_kernel in front
 // until then): lik_pf_partial_kernel / pf_partial_kernel, then pf_apply_kernel whose every work-group runs pf_reduce_kernel's
 // reduction itself. Same arithmetic in the same association as the launches apart (the multi-GPU protocol still runs them apart,
@@ -42,7 +44,7 @@ enum class PfForm
 };
 PfForm pf_form(const mcl3dl_hip_ctx* ctx, size_t n_p)
 {
-  if (ctx->pf_fused && pf_fused_range(ctx, n_p))
+  if (ctx->opt.pf_fused && pf_fused_range(n_p))
     return PfForm::Fused;
   return pf_float_order(ctx, n_p) ? PfForm::SplitFloat : PfForm::SplitTree;
 }

@@ -11,7 +11,7 @@
 // super-tiles, one per XCD; a producer always has a lower block index), same hand-off words and tags (tag0 + super-tile).
 // Measured (profiles/r05r_chain_multi.txt, 16 384 points): 64 particles 0.122 -> 0.096 ms, 1024 particles 0.139 -> 0.122 ms (fp64
 // sums: 0.072), 1024 x 65 536 points 0.480 -> 0.358 ms; SLOWER from 2048 particles (groups of four particles, a longer start-up),
-// so the host uses it up to chain_multi_max = 1536 particles.
+// so the host uses it up to CHAIN_MULTI_MAX = 1536 particles (a constant: host_options.h).
 // Only the default kernel family (packed 64-byte records, quad-cooperative fetch, deferred overflow rounds); everything else
 // and every launch with enough particles stays with likelihood_tiled_kernel<..., CHAIN>.
 #pragma once

@@ -26,6 +26,7 @@
 
 using namespace mcl3dl;
 
+#include "host_options.h"
 #include "host_context.h"
 #include "host_map_compilers.h"
 #include "host_measure.h"

@@ -88,16 +88,18 @@ def test_header_is_plain_c_and_links_from_c(tmp_path):
 
 def test_every_option_is_in_the_api_fuzz_pool():
     """no runtime switch without a test that draws it in combination with the others. Every key
-    mcl3dl_hip_set_option accepts (parsed from api_support.inl) is in tests/test_gpu_api_fuzz.py's CHOICES — the fault-injection
-    hook aside — and can be read back (the getter table)."""
+    mcl3dl_hip_set_option accepts (the rows of the table in host_options.h) is in tests/test_gpu_api_fuzz.py's CHOICES — the
+    fault-injection hook aside — and can be read back (mcl3dl_hip_get_option reads the same rows, the hook's aside)."""
     import ast
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "mcl_3dl_amd", "csrc", "api_support.inl")).read()
-    a = src.index("int mcl3dl_hip_set_option(")
-    b = src.index("kOptionGetters[]")
-    settable = set(re.findall(r'key == "([a-z_0-9]+)"', src[a:b]))
-    readable = set(re.findall(r'\{ "([a-z_0-9]+)", \[\]', src[b:]))
+    src = open(os.path.join(root, "mcl_3dl_amd", "csrc", "host_options.h")).read()
+    table = src[src.index("kOptions[] = {"):]
+    table = table[:table.index("\n};")]
+    rows = re.findall(r'^  \{ "([a-z_0-9]+)", &Options::\w+, .*?(, true)? \},$', table, flags=re.M)
+    settable = {name for name, _ in rows}
+    readable = {name for name, hook in rows if not hook}
+    assert len(settable) == len(rows) == table.count("\n  { ")   # one name per row, no row the pattern missed
     fuzz = open(os.path.join(root, "tests", "test_gpu_api_fuzz.py")).read()
     tree = ast.parse(fuzz)
     pools = {}
@@ -107,4 +109,5 @@ def test_every_option_is_in_the_api_fuzz_pool():
     assert pools["DEFAULTS"] == pools["CHOICES"]
     assert settable - {"test_late_structures"} == pools["CHOICES"], (sorted(settable - pools["CHOICES"]), sorted(pools["CHOICES"] - settable))
     assert settable - {"test_late_structures"} <= readable, sorted(settable - readable)
+    assert settable - readable == {"test_late_structures"}
     assert len(settable) <= 40

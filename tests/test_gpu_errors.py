@@ -46,6 +46,32 @@ def test_bad_arguments_return_codes(fresh):
     assert lib.mcl3dl_hip_create(C.byref(out), 12345) != 0 and not out  # no such device
 
 
+def test_every_option_round_trips(fresh):
+    """A fresh engine reads every key back at the DEFAULTS of tests/test_gpu_api_fuzz.py; every value of its CHOICES reads back as
+    stored (flags as 0 / 1, counts as whole numbers: the pool holds nothing a conversion would change); a value outside a key's
+    rule leaves the read-back as it was, and the error names the key. No kernel is launched."""
+    from test_options_table import fuzz_pools
+    defaults, choices = fuzz_pools()
+    for key, want in defaults.items():
+        assert fresh.get_option(key) == float(want), key
+    bad = dict(lik_index=7, lik_group=5, cand_phase=1.0, cand_voxel_ratio=0.1, strict_chunk=512, index_budget_bytes=-2,
+               batch_slice=float("nan"), timing_mask=-1, poll_sync=3, strict_order=float("nan"), update_small_max=0,
+               lik_tiled_min=float("nan"), cand_aniso_max=65, strict_auto_max_bytes=-1.0)
+    for key, values in choices.items():
+        for v in values:
+            fresh.set_option(key, v)
+            assert fresh.get_option(key) == float(v), (key, v)
+        if key in bad:
+            assert fresh.lib.mcl3dl_hip_set_option(fresh.h, key.encode(), float(bad[key])) == -3, key
+            text = fresh.lib.mcl3dl_hip_last_error(fresh.h).decode()
+            assert text.startswith(key + " must "), (key, text)
+            assert fresh.get_option(key) == float(values[-1]), key
+    assert fresh.lib.mcl3dl_hip_set_option(fresh.h, b"timing_mask", float(2 ** 32)) == -3
+    assert fresh.get_option("timing_mask") == float(choices["timing_mask"][-1])
+    with pytest.raises(capi.EngineError, match="unknown option 'test_late_structures'"):
+        fresh.get_option("test_late_structures")   # the hook is not readable
+
+
 def test_beam_origin_out_of_range(fresh):
     sc = make_scene(n=21, n_p=4, n_s=16, n_b=8)
     fresh.set_map(sc.map_xyz, sc.map_label)
