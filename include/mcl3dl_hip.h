@@ -250,6 +250,9 @@ int mcl3dl_hip_covariance_device(mcl3dl_hip_ctx* ctx, const float* d_pose, const
  *              max w*bias, its index, 0, 0}      -> all-gather, then mcl3dl_hip_moments_finish (host arithmetic of
  *              ParticleWeightedMeanQuat::getMean, state_6dof.h:345-350; index_offset[r] = first particle of shard r)
  *   covariance 22 doubles {21 upper-triangular sums, sum w} -> all-reduce(SUM), then mcl3dl_hip_covariance_finish.
+ * An empty shard (n == 0; its particle arrays may be NULL) is no error for either *_partial_device: its covariance record is
+ * 22 zeros, its moments record ten zero sums with both maxima at -1 (indices 0), which mcl3dl_hip_moments_finish never picks.
+ * (mcl3dl_hip_expectation_device / _covariance_device, which divide by the sum, keep rejecting n == 0.)
  * The *_finish functions are pure host functions (no context). */
 int mcl3dl_hip_moments_partial_device(mcl3dl_hip_ctx* ctx, const float* d_pose, const float* d_weight,
                                       const float* d_bias /*or NULL*/, size_t n, double* d_out16);

@@ -141,6 +141,19 @@ int mcl3dl_hip_moments_partial_device(mcl3dl_hip_ctx* ctx, const float* d_pose, 
 {
   if (!ctx)
     return -1;
+  if (n == 0)
+  {
+    // the record the device group writes for an empty shard (api_group_state.inl): it never holds a maximum; the particle
+    // arrays may be null, as for the covariance record below
+    if (!d_out16)
+      return ctx->fail(-3, "bad arguments to moments_partial");
+    HIP_TRY(hipSetDevice(ctx->device));
+    double rec[16] = { 0 };
+    rec[10] = -1.0;
+    rec[12] = -1.0;
+    TRY(h2d(ctx, d_out16, rec, sizeof(rec)));
+    return sync_stream(ctx);  // `rec` leaves scope
+  }
   return moments_partial_launch(ctx, d_pose, d_weight, d_bias, nullptr, n, d_out16);
 }
 
@@ -196,14 +209,16 @@ int mcl3dl_hip_covariance_partial_device(mcl3dl_hip_ctx* ctx, const float* d_pos
   if (!ctx)
     return -1;
   const size_t n = d_subset ? n_subset : n_particles;
-  if (n > 0x7fffffffu || !d_pose || !d_weight || !mean7 || !d_out22)
+  if (n > 0x7fffffffu || !mean7 || !d_out22)
     return ctx->fail(-3, "bad arguments to covariance_partial");
   HIP_TRY(hipSetDevice(ctx->device));
-  if (n == 0)
+  if (n == 0)  // (an empty shard has no particle arrays to point at: an empty torch tensor's address is null)
   {
     HIP_TRY(hipMemsetAsync(d_out22, 0, sizeof(double) * COV_N, ctx->stream));
     return 0;
   }
+  if (!d_pose || !d_weight)
+    return ctx->fail(-3, "bad arguments to covariance_partial");
   const int nb = pf_blocks(n);
   TRY(ensure(ctx, ctx->mom_blocks, sizeof(double) * COV_N * nb));
   const Vec3f exp_rpy = quat_get_rpy(Quat{ mean7[3], mean7[4], mean7[5], mean7[6] });

@@ -50,7 +50,8 @@ def test_larger_filters_still_take_the_split_path(engine):
     np.testing.assert_allclose(got["weights"].sum(dtype=np.float64), 1.0, rtol=1e-6)
 
 
-@pytest.mark.parametrize("n_p,n_s,n_b", [(1025, 4352, 0), (4096, 4352, 0), (4100, 5000, 7), (4159, 4608, 0), (16387, 4352, 3)])
+@pytest.mark.parametrize("n_p,n_s,n_b", [(1025, 4352, 0), (4096, 4352, 0), (4100, 5000, 7), (4159, 4608, 0), (16387, 4352, 3),
+                                         (262144, 4352, 3), (262145, 4352, 3)])
 def test_the_two_launch_tail_behind_the_tiled_kernel_equals_the_launches_apart(engine, n_p, n_s, n_b):
     """Round 6: behind the tiled likelihood kernel (default mode, 4097 .. 28 146 points, more than 1024 particles) lik_finalize's
     sum and pf_partial's product are ONE launch (lik_pf_partial_kernel: wavefront partials) and pf_reduce runs inside pf_apply.
