@@ -549,6 +549,39 @@ int mcl3dl_hip_group_add_noise(mcl3dl_hip_group* g, const float* noise13 /*n_p*1
 int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float acc_var, float* out_weight /*n_p or NULL*/,
                                  float* out_lik /*n_p or NULL*/, float* entropy, int* restored);
 int mcl3dl_hip_group_set_odom_error_sigma(mcl3dl_hip_group* g, float sigma);
+/* ---- the noise drawn on the devices, from the reference's engine ---------------------------------------------------------
+ * The draws above (noise13 of resample_apply and add_noise, noise4 of set_odom_noise) and pf::init, without the host drawing or
+ * uploading anything: std::default_random_engine as libstdc++ defines it (minstd_rand0, x <- 16807 x mod (2^31 - 1); the
+ * library the reference oracle is built with: another standard library uses another engine) and its
+ * normal_distribution<float>, evaluated for every position of the stream at once. engine_state is in / out:
+ * the engine's state in [1, 2^31 - 2]; behind a call it holds what the reference's engine_ would hold, so any mix of these
+ * calls with the caller's own draws stays on the reference's stream. A std::default_random_engine gives and takes its state
+ * through operator<< / operator>>. The logarithm of the polar method is taken in double and rounded to float (the rule above for
+ * the transcendentals): accept / reject decisions and the engine state are the reference's exactly, the values are within
+ * 1 ulp-of-log of a faithful logf.
+ *   rng_seed              engine(seed)'s state. Host only.
+ *   rng_uniform           uniform_real_distribution<float>(a, b)(engine), pf::resample's initial_p (pf.h:199): one engine call.
+ *                         Host only. NaN for a NULL state or one outside [1, 2^31 - 2].
+ *   add_noise_drawn       add_noise with generateNoise(engine, DiagonalNoiseGenerator(State6DOF(), sigma6)) per particle
+ *                         (sigma6 = {x, y, z, roll, pitch, yaw}; a zero sigma draws nothing, diagonal_noise_generator.h:69-73).
+ *   init_drawn            pf::init(mean, sigma) (pf.h:169-181): n_p states generateNoise(engine, DiagonalNoiseGenerator(mean7,
+ *                         sigma6)), weights 1 / n_p; the particles become resident as after upload_state. mean7 = {pos 3, rot
+ *                         x, y, z, w}; its getRPY is formed once on the host.
+ *   draw_odom_noise       set_odom_noise with update_noise_func's draws (src/mcl_3dl.cpp:817-825): ONE normal_distribution<float>
+ *                         (0, 1) per call, four values per particle in the order ll, la, aa, al, each times its odom_err4 entry
+ *                         {lin_lin, lin_ang, ang_ang, ang_lin}.
+ *   resample_apply_drawn  resample_apply with generateNoise per duplicated slot in slot order (pf.h:216); duplicated particles
+ *                         get zero odometry noise, as there.
+ * On N devices every rank evaluates the accept decisions of the whole stream (deterministic replicas, no collective) and forms
+ * the values of its own shard only. -3: NULL or non-finite sigma6 / mean7 / odom_err4, a negative sigma, engine_state NULL or
+ * outside [1, 2^31 - 2]. -5: no resident particles; resample_apply_drawn without a plan. All six sigmas zero is legal: nothing
+ * is drawn, engine_state is unchanged and the noise states are the means. */
+uint32_t mcl3dl_hip_rng_seed(uint32_t seed);
+float mcl3dl_hip_rng_uniform(uint32_t* state, float a, float b);
+int mcl3dl_hip_group_add_noise_drawn(mcl3dl_hip_group* g, const float* sigma6, uint32_t* engine_state);
+int mcl3dl_hip_group_init_drawn(mcl3dl_hip_group* g, const float* mean7, const float* sigma6, size_t n_p, uint32_t* engine_state);
+int mcl3dl_hip_group_draw_odom_noise(mcl3dl_hip_group* g, const float* odom_err4, uint32_t* engine_state);
+int mcl3dl_hip_group_resample_apply_drawn(mcl3dl_hip_group* g, const float* sigma6, uint32_t* engine_state);
 int mcl3dl_hip_group_measure_landmark(mcl3dl_hip_group* g, const float* measured7, const double* cov36,
                                       float* out_weight /*n_p or NULL*/, float* out_lik /*n_p or NULL*/, float* entropy,
                                       int* restored);

@@ -130,6 +130,12 @@ SIGNATURES = {
     "mcl3dl_hip_scan_normal_weights": (_i, [_p, _i, _d, _p, _d, _p, _p, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
     "mcl3dl_hip_get_option": (_i, [_p, C.c_char_p, C.POINTER(_d)]),
     "mcl3dl_hip_index_stats": (_i, [_p, _p]),
+    "mcl3dl_hip_rng_seed": (_u32, [_u32]),
+    "mcl3dl_hip_rng_uniform": (_f, [C.POINTER(_u32), _f, _f]),
+    "mcl3dl_hip_group_add_noise_drawn": (_i, [_p, _p, C.POINTER(_u32)]),
+    "mcl3dl_hip_group_init_drawn": (_i, [_p, _p, _p, _sz, C.POINTER(_u32)]),
+    "mcl3dl_hip_group_draw_odom_noise": (_i, [_p, _p, C.POINTER(_u32)]),
+    "mcl3dl_hip_group_resample_apply_drawn": (_i, [_p, _p, C.POINTER(_u32)]),
 }
 
 _lib = None
@@ -470,6 +476,32 @@ class Group:
         """pf::noise with caller-drawn noise states (State6DOF::operator+)."""
         nz = _np_f32(noise13, 13)
         self._check(self.lib.mcl3dl_hip_group_add_noise(self.h, _ptr(nz), len(nz)))
+
+    # ---- the same draws made on the devices from the reference's engine; engine_state in, the state behind the call out ----
+    def add_noise_drawn(self, sigma6, engine_state):
+        """pf::noise with the noise drawn on the devices. Returns the engine state behind the call."""
+        st = _u32(int(engine_state))
+        self._check(self.lib.mcl3dl_hip_group_add_noise_drawn(self.h, _ptr(_np_f32(sigma6)), C.byref(st)))
+        return int(st.value)
+
+    def init_drawn(self, mean7, sigma6, n_p, engine_state):
+        """pf::init(mean, sigma): n_p resident particles about mean7 = {pos 3, rot x, y, z, w}, weights 1 / n_p."""
+        st = _u32(int(engine_state))
+        self._check(self.lib.mcl3dl_hip_group_init_drawn(self.h, _ptr(_np_f32(mean7)), _ptr(_np_f32(sigma6)), int(n_p),
+                                                         C.byref(st)))
+        return int(st.value)
+
+    def draw_odom_noise(self, odom_err4, engine_state):
+        """update_noise_func: odom_err4 = {lin_lin, lin_ang, ang_ang, ang_lin}, the draw order ll, la, aa, al."""
+        st = _u32(int(engine_state))
+        self._check(self.lib.mcl3dl_hip_group_draw_odom_noise(self.h, _ptr(_np_f32(odom_err4)), C.byref(st)))
+        return int(st.value)
+
+    def resample_apply_drawn(self, sigma6, engine_state):
+        """resample_apply with the duplicated slots' noise drawn on the devices, in slot order."""
+        st = _u32(int(engine_state))
+        self._check(self.lib.mcl3dl_hip_group_resample_apply_drawn(self.h, _ptr(_np_f32(sigma6)), C.byref(st)))
+        return int(st.value)
 
     def measure_imu(self, acc, acc_var, fetch=True):
         """cbImu's pf_->measure with ImuMeasurementModelGravity(acc_var) after setAccMeasure(acc)."""
@@ -1077,3 +1109,15 @@ class Engine:
                     record_parts=int(self.get_option("cand_record_parts_in_use")),
                     packed_words=int(self.get_option("cand_packed_active")),
                     deferred_overflow=int(self.get_option("lik_defer_active")))
+
+
+def rng_seed(seed):
+    """std::default_random_engine(seed)'s state (libstdc++: minstd_rand0)."""
+    return int(load_library().mcl3dl_hip_rng_seed(int(seed) & 0xFFFFFFFF))
+
+
+def rng_uniform(engine_state, a, b):
+    """uniform_real_distribution<float>(a, b)(engine) on the host: (value, engine state behind the draw)."""
+    st = _u32(int(engine_state))
+    v = load_library().mcl3dl_hip_rng_uniform(C.byref(st), float(a), float(b))
+    return float(v), int(st.value)

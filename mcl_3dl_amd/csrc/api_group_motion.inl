@@ -165,6 +165,21 @@ int mcl3dl_hip_group_reset_odom_integ(mcl3dl_hip_group* g)
                           });
 }
 
+namespace
+{
+// pf::noise behind the noise rows' arrival in ctx->rs_d_noise (copied from the host, or drawn there: api_rng.inl)
+int add_noise_launch(mcl3dl_hip_ctx* ctx, size_t n)
+{
+  TRY(ensure(ctx, ctx->pose, sizeof(float) * 7 * n));
+  hipLaunchKernelGGL(add_noise_kernel, grid_of(n), dim3(256), 0, ctx->stream, ctx->gs_state[ctx->gs_cur].as<float>(),
+                     ctx->rs_d_noise.as<float>(), static_cast<int>(n), ctx->pose.as<float>());
+  HIP_TRY(hipGetLastError());
+  ctx->poses_set(n);
+  ctx->pose_resident = true;
+  return sync_stream(ctx);
+}
+}  // namespace
+
 int mcl3dl_hip_group_add_noise(mcl3dl_hip_group* g, const float* noise13, size_t n_p)
 {
   if (!g)
@@ -178,14 +193,7 @@ int mcl3dl_hip_group_add_noise(mcl3dl_hip_group* g, const float* noise13, size_t
                                   {
                                     TRY(ensure(ctx, ctx->rs_d_noise, sizeof(float) * 13 * n));
                                     TRY(h2d(ctx, ctx->rs_d_noise.p, noise13 + 13 * lo, sizeof(float) * 13 * n));
-                                    TRY(ensure(ctx, ctx->pose, sizeof(float) * 7 * n));
-                                    hipLaunchKernelGGL(add_noise_kernel, grid_of(n), dim3(256), 0, ctx->stream,
-                                                       ctx->gs_state[ctx->gs_cur].as<float>(), ctx->rs_d_noise.as<float>(),
-                                                       static_cast<int>(n), ctx->pose.as<float>());
-                                    HIP_TRY(hipGetLastError());
-                                    ctx->poses_set(n);
-                                    ctx->pose_resident = true;
-                                    return sync_stream(ctx);
+                                    return add_noise_launch(ctx, n);
                                   });
   // operator+ returns a fresh State6DOF: every particle's odometry noise is 0 now (the node redraws it after the next scan)
   g->noise_on = false;

@@ -383,14 +383,14 @@ int mcl3dl_hip_group_resample_plan(mcl3dl_hip_group* g, int mode, float initial_
   return 0;
 }
 
-int mcl3dl_hip_group_resample_apply(mcl3dl_hip_group* g, const float* noise13, size_t n_noise)
+namespace
 {
-  if (!g)
-    return -1;
-  if (!g->rs_planned)
-    return g->fail(-5, "group_resample_apply before group_resample_plan");
-  if (n_noise < g->rs_n_dup || (g->rs_n_dup && !noise13))
-    return g->fail(-3, "group_resample_apply: %zu duplicated particles need noise, %zu given", g->rs_n_dup, n_noise);
+// fills ctx->rs_d_noise of rank r with the noise rows its output slots [olo, olo + n_new) read (api_rng.inl draws them there)
+using ShardNoise = std::function<int(mcl3dl_hip_ctx*, int, size_t, size_t)>;
+
+// drawn == null: the rows are the caller's noise13; else every rank forms its own rows in device memory
+int group_resample_apply_impl(mcl3dl_hip_group* g, const float* noise13, size_t n_noise, const ShardNoise* drawn)
+{
   const size_t n_p = g->n_resident, n_out = g->rs_n_out;
   const int N = g->n();
   const bool single = N == 1 && g->direct_single;
@@ -514,7 +514,14 @@ int mcl3dl_hip_group_resample_apply(mcl3dl_hip_group* g, const float* noise13, s
         (void)n;
         if (n_new)
         {
-          TRY(mcl3dl_hip_resample_apply_slice_device(ctx, d_all, noise13, n_noise, olo, n_new, ctx->gs_state[other].as<float>()));
+          if (drawn)
+          {
+            TRY(resample_slice_check(ctx, d_all, olo, n_new, ctx->gs_state[other].as<float>()));
+            TRY((*drawn)(ctx, r, olo, n_new));
+            TRY(resample_slice_launch(ctx, d_all, olo, n_new, ctx->gs_state[other].as<float>()));
+          }
+          else
+            TRY(mcl3dl_hip_resample_apply_slice_device(ctx, d_all, noise13, n_noise, olo, n_new, ctx->gs_state[other].as<float>()));
           if (with_noise)
           {
             hipLaunchKernelGGL(resample_noise_kernel, dim3((static_cast<int>(n_new) + 255) / 256), dim3(256), 0, ctx->stream,
@@ -557,4 +564,16 @@ int mcl3dl_hip_group_resample_apply(mcl3dl_hip_group* g, const float* noise13, s
   g->n_resident = n_out;
   g->n_pose_uploaded = n_out;
   return 0;
+}
+}  // namespace
+
+int mcl3dl_hip_group_resample_apply(mcl3dl_hip_group* g, const float* noise13, size_t n_noise)
+{
+  if (!g)
+    return -1;
+  if (!g->rs_planned)
+    return g->fail(-5, "group_resample_apply before group_resample_plan");
+  if (n_noise < g->rs_n_dup || (g->rs_n_dup && !noise13))
+    return g->fail(-3, "group_resample_apply: %zu duplicated particles need noise, %zu given", g->rs_n_dup, n_noise);
+  return group_resample_apply_impl(g, noise13, n_noise, nullptr);
 }

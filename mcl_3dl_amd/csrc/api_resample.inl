@@ -139,11 +139,11 @@ int mcl3dl_hip_resample_begin_device(mcl3dl_hip_ctx* ctx, const float* d_weight,
   return mcl3dl_hip_resample_begin(ctx, w.data(), n, n_out, out_pstep);
 }
 
-int mcl3dl_hip_resample_apply_slice_device(mcl3dl_hip_ctx* ctx, const float* d_state13_in, const float* noise13,
-                                           size_t n_noise, size_t out_begin, size_t out_count, float* d_state13_out)
+namespace
 {
-  if (!ctx)
-    return -1;
+int resample_slice_check(mcl3dl_hip_ctx* ctx, const float* d_state13_in, size_t out_begin, size_t out_count,
+                         const float* d_state13_out)
+{
   if (!ctx->rs_planned)
     return ctx->fail(-5, "resample_apply before resample_plan");
   if (!d_state13_in || !d_state13_out || d_state13_in == d_state13_out)
@@ -151,6 +151,28 @@ int mcl3dl_hip_resample_apply_slice_device(mcl3dl_hip_ctx* ctx, const float* d_s
   if (out_begin > ctx->rs_n_out || out_count > ctx->rs_n_out - out_begin)
     return ctx->fail(-3, "resample_apply: slice [%zu, %zu) is outside the %zu planned slots", out_begin,
                      out_begin + out_count, ctx->rs_n_out);
+  return 0;
+}
+
+// what lies behind the noise rows' arrival in ctx->rs_d_noise (copied from the host, or drawn there: api_rng.inl)
+int resample_slice_launch(mcl3dl_hip_ctx* ctx, const float* d_state13_in, size_t out_begin, size_t out_count,
+                          float* d_state13_out)
+{
+  const int no = static_cast<int>(out_count);
+  hipLaunchKernelGGL(resample_apply_kernel, dim3((no + 255) / 256), dim3(256), 0, ctx->stream, d_state13_in,
+                     ctx->rs_d_source.as<uint32_t>() + out_begin, ctx->rs_d_slot.as<uint32_t>() + out_begin,
+                     ctx->rs_d_noise.as<float>(), no, d_state13_out);
+  HIP_TRY(hipGetLastError());
+  return sync_stream(ctx);  // (the noise rows may be the caller's host buffer)
+}
+}  // namespace
+
+int mcl3dl_hip_resample_apply_slice_device(mcl3dl_hip_ctx* ctx, const float* d_state13_in, const float* noise13,
+                                           size_t n_noise, size_t out_begin, size_t out_count, float* d_state13_out)
+{
+  if (!ctx)
+    return -1;
+  TRY(resample_slice_check(ctx, d_state13_in, out_begin, out_count, d_state13_out));
   if (n_noise < ctx->rs_n_dup || (ctx->rs_n_dup && !noise13))
     return ctx->fail(-3, "resample_apply: %zu duplicated particles need noise, %zu given", ctx->rs_n_dup, n_noise);
   if (out_count == 0)
@@ -158,13 +180,7 @@ int mcl3dl_hip_resample_apply_slice_device(mcl3dl_hip_ctx* ctx, const float* d_s
   HIP_TRY(hipSetDevice(ctx->device));
   TRY(ensure(ctx, ctx->rs_d_noise, sizeof(float) * 13 * ctx->rs_n_dup));
   TRY(h2d(ctx, ctx->rs_d_noise.p, noise13, sizeof(float) * 13 * ctx->rs_n_dup));
-  const int no = static_cast<int>(out_count);
-  hipLaunchKernelGGL(resample_apply_kernel, dim3((no + 255) / 256), dim3(256), 0, ctx->stream, d_state13_in,
-                     ctx->rs_d_source.as<uint32_t>() + out_begin, ctx->rs_d_slot.as<uint32_t>() + out_begin,
-                     ctx->rs_d_noise.as<float>(), no, d_state13_out);
-  HIP_TRY(hipGetLastError());
-  TRY(sync_stream(ctx));  // noise13 is the caller's host buffer
-  return 0;
+  return resample_slice_launch(ctx, d_state13_in, out_begin, out_count, d_state13_out);
 }
 
 int mcl3dl_hip_resample_apply_device(mcl3dl_hip_ctx* ctx, const float* d_state13_in, const float* noise13,

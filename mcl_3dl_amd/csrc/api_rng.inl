@@ -1,0 +1,244 @@
+// api_rng.inl — included inside the extern "C" block of mcl3dl_hip.hip after api_group_motion.inl: the filter's noise drawn ON THE
+// DEVICES from the reference's engine (rng_polar.h: libstdc++'s minstd_rand0 + normal_distribution<float>, restated per attempt;
+// host_rng.h: the rounds). Each call equals its counterpart fed with the host-drawn array — the same kernels behind the noise
+// buffer, the same pose-mirror refresh, the same noise_on bookkeeping — and leaves *engine_state where the reference's engine_
+// would stand.
+//
+//   mcl3dl_hip_rng_seed / _rng_uniform          engine(seed) / uniform_real_distribution<float>(a, b)(engine): host arithmetic
+//   mcl3dl_hip_group_add_noise_drawn            pf::noise (pf.h:226-237)
+//   mcl3dl_hip_group_init_drawn                 pf::init (pf.h:169-181)
+//   mcl3dl_hip_group_draw_odom_noise            update_noise_func (src/mcl_3dl.cpp:817-825)
+//   mcl3dl_hip_group_resample_apply_drawn       pf::resample's generateNoise per duplicated slot, in slot order (pf.h:216)
+namespace
+{
+int rng_check_state(mcl3dl_hip_group* g, const uint32_t* engine_state)
+{
+  if (!engine_state)
+    return g->fail(-3, "null engine_state");
+  if (*engine_state < 1u || *engine_state > rng::MINSTD_M - 1u)
+    return g->fail(-3, "engine_state %u is outside [1, 2^31 - 2]", *engine_state);
+  return 0;
+}
+
+// DiagonalNoiseGenerator(mean, sigma) for State6DOF; mean6 == null: State6DOF()
+int rng_generator(mcl3dl_hip_group* g, const float* mean6, const float* sigma6, rng::NoiseGen6* gen)
+{
+  if (!sigma6)
+    return g->fail(-3, "null sigma6");
+  gen->dims = 0;
+  for (int k = 0; k < 6; ++k)
+  {
+    if (!std::isfinite(sigma6[k]) || sigma6[k] < 0.f)
+      return g->fail(-3, "sigma6[%d] must be finite and >= 0", k);
+    gen->sigma[k] = sigma6[k];
+    gen->mean[k] = mean6 ? mean6[k] : 0.0f;
+    gen->dims += sigma6[k] != 0.f ? 1 : 0;
+  }
+  return 0;
+}
+
+// every rank ran the same count pass over the same stream: one engine state
+int rng_hand_back(mcl3dl_hip_group* g, const std::vector<uint32_t>& states, const std::vector<char>& drew,
+                  uint32_t* engine_state)
+{
+  for (size_t r = 1; r < states.size(); ++r)
+    if (drew[r] && drew[0] && states[r] != states[0])
+      return g->fail(-4, "the ranks disagree on the engine state behind the draw (%u and %u)", states[0], states[r]);
+  if (drew[0])
+    *engine_state = states[0];
+  return 0;
+}
+}  // namespace
+
+uint32_t mcl3dl_hip_rng_seed(uint32_t seed)
+{
+  return rng::minstd_seed(seed);
+}
+
+float mcl3dl_hip_rng_uniform(uint32_t* state, float a, float b)
+{
+  if (!state || *state < 1u || *state > rng::MINSTD_M - 1u)
+    return std::numeric_limits<float>::quiet_NaN();
+  return rng::uniform_draw(state, a, b);
+}
+
+int mcl3dl_hip_group_add_noise_drawn(mcl3dl_hip_group* g, const float* sigma6, uint32_t* engine_state)
+{
+  if (!g)
+    return -1;
+  rng::NoiseGen6 gen;
+  TRY(rng_generator(g, nullptr, sigma6, &gen));
+  TRY(rng_check_state(g, engine_state));
+  const size_t n_p = g->n_resident;
+  std::vector<uint32_t> states(g->n(), 0u);
+  std::vector<char> drew(g->n(), 0);
+  const uint32_t x0 = *engine_state;
+  const int rc = group_each_shard(g,
+                                  [&](mcl3dl_hip_ctx* ctx, int r, size_t lo, size_t n) -> int
+                                  {
+                                    TRY(ensure(ctx, ctx->rs_d_noise, sizeof(float) * 13 * n));
+                                    TRY(rng_noise_rows(ctx, x0, gen, n_p, lo, n, ctx->rs_d_noise.as<float>(), &states[r]));
+                                    drew[r] = 1;
+                                    return add_noise_launch(ctx, n);
+                                  });
+  if (n_p)
+    g->noise_on = false;  // as mcl3dl_hip_group_add_noise: operator+ returns a fresh State6DOF
+  if (rc)
+    return rc;
+  return rng_hand_back(g, states, drew, engine_state);
+}
+
+int mcl3dl_hip_group_draw_odom_noise(mcl3dl_hip_group* g, const float* odom_err4, uint32_t* engine_state)
+{
+  if (!g)
+    return -1;
+  if (!odom_err4)
+    return g->fail(-3, "null odom_err4");
+  for (int k = 0; k < 4; ++k)
+    if (!std::isfinite(odom_err4[k]))
+      return g->fail(-3, "odom_err4[%d] is not finite", k);
+  TRY(rng_check_state(g, engine_state));
+  const size_t n_p = g->n_resident;
+  const int N = g->n();
+  std::vector<uint32_t> states(N, 0u);
+  std::vector<char> drew(N, 0);
+  const uint32_t x0 = *engine_state;
+  const int rc = group_each_shard(
+      g,
+      [&](mcl3dl_hip_ctx* ctx, int r, size_t lo, size_t n) -> int
+      {
+        // (room for the largest shard, as set_odom_noise: the resampling step's all-gather sends that many)
+        TRY(ensure(ctx, ctx->gs_noise[ctx->gs_cur], sizeof(float) * 4 * ((n_p + N - 1) / N)));
+        // one shared normal_distribution: accepted attempt k yields values 2k and 2k + 1, four values per particle
+        TRY(rng_draw(ctx, x0, 2 * static_cast<uint64_t>(n_p), true, 2 * static_cast<uint64_t>(lo),
+                     2 * static_cast<uint64_t>(lo + n), &states[r]));
+        drew[r] = 1;
+        hipLaunchKernelGGL(rng::rng_odom_noise_kernel, grid_of(n), dim3(256), 0, ctx->stream, ctx->rng_values.as<float>(),
+                           odom_err4[0], odom_err4[1], odom_err4[2], odom_err4[3], static_cast<int>(n),
+                           ctx->gs_noise[ctx->gs_cur].as<float>());
+        HIP_TRY(hipGetLastError());
+        return sync_stream(ctx);
+      });
+  if (rc)
+  {
+    if (n_p)
+      g->noise_on = false;  // (some shards may hold the new noise, others none: the caller draws it again)
+    return rc;
+  }
+  // an empty shard still needs its buffer for the all-gather
+  for (int r = 0; r < N; ++r)
+    if (!drew[r])
+    {
+      mcl3dl_hip_ctx* ctx = g->ctx[r];
+      const int rc_e = [&]() -> int
+      {
+        HIP_TRY(hipSetDevice(ctx->device));
+        return ensure(ctx, ctx->gs_noise[ctx->gs_cur], sizeof(float) * 4 * ((n_p + N - 1) / N));
+      }();
+      if (rc_e)
+      {
+        g->noise_on = false;
+        return g->fail_rank(rc_e, r);
+      }
+    }
+  TRY(rng_hand_back(g, states, drew, engine_state));
+  g->noise_on = true;
+  return 0;
+}
+
+int mcl3dl_hip_group_init_drawn(mcl3dl_hip_group* g, const float* mean7, const float* sigma6, size_t n_p, uint32_t* engine_state)
+{
+  if (!g)
+    return -1;
+  if (!mean7)
+    return g->fail(-3, "null mean7");
+  for (int k = 0; k < 7; ++k)
+    if (!std::isfinite(mean7[k]))
+      return g->fail(-3, "mean7[%d] is not finite", k);
+  float mean6[6];
+  rng_mean6(mean7, mean6);
+  rng::NoiseGen6 gen;
+  TRY(rng_generator(g, mean6, sigma6, &gen));
+  TRY(rng_check_state(g, engine_state));
+  if (n_p == 0 || n_p > 0x7fffffffu / 16)
+    return g->fail(-3, "init_drawn: %zu particles asked for", n_p);
+  g->n_resident = 0;
+  g->rs_begun = g->rs_planned = false;
+  g->noise_on = false;
+  const int N = g->n();
+  std::vector<uint32_t> states(N, 0u);
+  std::vector<char> drew(N, 0);
+  const uint32_t x0 = *engine_state;
+  const float weight = static_cast<float>(1.0 / static_cast<double>(n_p));  // pf.h:179
+  int bad = 0;
+  const int rc = g->pool.run_all(
+      [&](int r) -> int
+      {
+        mcl3dl_hip_ctx* ctx = g->ctx[r];
+        size_t lo, hi;
+        shard_bounds(n_p, N, r, &lo, &hi);
+        const size_t n = hi - lo;
+        HIP_TRY(hipSetDevice(ctx->device));
+        ctx->gs_n = 0;
+        ctx->gs_cur = 0;
+        if (n == 0)
+          return 0;
+        const size_t cap_count = (n_p + N - 1) / N;  // as upload_state
+        TRY(ensure(ctx, ctx->gs_state[0], sizeof(float) * 13 * cap_count));
+        TRY(ensure(ctx, ctx->gs_weight, sizeof(float) * cap_count));
+        // p.state_ = generateNoise(engine_, generator): the row IS the state
+        TRY(rng_noise_rows(ctx, x0, gen, n_p, lo, n, ctx->gs_state[0].as<float>(), &states[r]));
+        drew[r] = 1;
+        hipLaunchKernelGGL(fill_kernel, grid_of(n), dim3(256), 0, ctx->stream, ctx->gs_weight.as<float>(), weight,
+                           static_cast<float*>(nullptr), 0.0f, static_cast<int>(n));
+        HIP_TRY(hipGetLastError());
+        TRY(rebuild_pose(ctx, n));
+        ctx->gs_n = n;
+        return sync_stream(ctx);
+      },
+      &bad);
+  if (rc)
+    return g->fail_rank(rc, bad);
+  TRY(rng_hand_back(g, states, drew, engine_state));
+  g->n_resident = n_p;
+  g->n_pose_uploaded = n_p;
+  return 0;
+}
+
+int mcl3dl_hip_group_resample_apply_drawn(mcl3dl_hip_group* g, const float* sigma6, uint32_t* engine_state)
+{
+  if (!g)
+    return -1;
+  rng::NoiseGen6 gen;
+  TRY(rng_generator(g, nullptr, sigma6, &gen));
+  TRY(rng_check_state(g, engine_state));
+  if (g->n_resident == 0)
+    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  if (!g->rs_planned)
+    return g->fail(-5, "group_resample_apply_drawn before group_resample_plan");
+  const size_t n_dup = g->rs_n_dup, n_out = g->rs_n_out;
+  std::vector<uint32_t> states(g->n(), 0u);
+  std::vector<char> drew(g->n(), 0);
+  const uint32_t x0 = *engine_state;
+  const ShardNoise drawn = [&](mcl3dl_hip_ctx* ctx, int r, size_t olo, size_t n_new) -> int
+  {
+    // the duplicates among this rank's slots are rows [d_lo, d_hi) of the n_dup the reference draws in slot order: the
+    // exclusive scan of the duplicate flags is still where resample_plan left it
+    uint32_t d_lo = 0, d_hi = 0;
+    TRY(d2h(ctx, &d_lo, ctx->rs_d_flag.as<uint32_t>() + olo, sizeof(uint32_t)));
+    TRY(d2h(ctx, &d_hi, ctx->rs_d_flag.as<uint32_t>() + olo + n_new, sizeof(uint32_t)));
+    TRY(sync_stream(ctx));
+    if (d_lo > d_hi || d_hi > n_dup || olo + n_new > n_out)
+      return ctx->fail(-4, "internal: duplicate rows [%u, %u) of %zu", d_lo, d_hi, n_dup);
+    // resample_apply_kernel indexes the rows by their global number
+    TRY(ensure(ctx, ctx->rs_d_noise, sizeof(float) * 13 * n_dup));
+    if (d_hi == d_lo && r != 0)
+      return 0;
+    TRY(rng_noise_rows(ctx, x0, gen, n_dup, d_lo, d_hi - d_lo, ctx->rs_d_noise.as<float>() + 13 * static_cast<size_t>(d_lo),
+                       &states[r]));
+    drew[r] = 1;
+    return 0;
+  };
+  TRY(group_resample_apply_impl(g, nullptr, 0, &drawn));
+  return rng_hand_back(g, states, drew, engine_state);
+}

@@ -266,6 +266,9 @@ struct mcl3dl_hip_ctx
   DevBuf rs_d_keys, rs_d_pscan, rs_d_it, rs_d_source, rs_d_slot, rs_d_noise, rs_d_in, rs_d_out, rs_d_order, rs_d_flag,
       rs_d_ws, rs_d_dup8;
   bool rs_sorted = false;  // std::sort had ties to order: rs_order is not the identity
+  // api_rng.inl: jump table, work-group counts (+ total + result word), scan workspace, this rank's window of the values
+  DevBuf rng_table, rng_counts, rng_ws, rng_values;
+  bool rng_table_set = false;
 
   std::string index_note;  // why the map compiler fell back to a coarser / plainer index form (diagnostics)
 

@@ -21,6 +21,8 @@
 //   cloud_keys.h          the sort keys (VoxelGrid leaf index, Morton key, range key)
 //   global_loc_kernels.h  global localisation: the blocked-above test over the VoxelGrid centroids of the base map, and the seeding
 //                         of points x div_yaw particles into a shard of resident particles
+//   rng_kernels.h         the filter's noise from the reference's engine: polar-method attempts counted, scanned and emitted in
+//                         stream order (rng_polar.h: the restatement both the device and the CPU emulation compile)
 //   stage_kernels.h       head and tail of a host-buffer update as one launch each: scan ordering + pose / weight take-over
 //                         from page-locked host memory; lik_finalize + pf::measure with the results written back there
 //
@@ -42,3 +44,4 @@
 #include "grid_kernels.h"
 #include "global_loc_kernels.h"
 #include "sampler_kernels.h"
+#include "rng_kernels.h"

@@ -31,6 +31,7 @@ using namespace mcl3dl;
 #include "host_map_compilers.h"
 #include "host_measure.h"
 #include "host_pf.h"
+#include "host_rng.h"
 #include "host_cloud.h"
 #include "host_grid_builders.h"
 #include "host_group.h"
@@ -50,4 +51,5 @@ extern "C"
 #include "api_group_motion.inl"
 #include "api_global_loc.inl"
 #include "api_sampler.inl"
+#include "api_rng.inl"
 }  // extern "C"
