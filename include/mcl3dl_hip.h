@@ -656,6 +656,54 @@ int mcl3dl_hip_sampler_normal_direction(const float* mean7 /*px,py,pz,qx,qy,qz,q
 int mcl3dl_hip_scan_normal_weights(mcl3dl_hip_ctx* ctx, int which, double normal_search_range, const float* fpc_local3,
                                    double max_weight, double* out_cumulative /*n or NULL*/, float* out_normal_xyz /*n*3 or NULL*/,
                                    size_t capacity, size_t* n, size_t* n_without_normal /*or NULL*/);
+/* ---- prepared scans on a device group, the uniform sampler drawn on the devices -----------------------------
+ * Replaces: PointCloudUniformSampler::sample (point_cloud_uniform_sampler.h:58-75) for both measurement models, and the scan
+ * take-over of a group's update. measure() (src/mcl_3dl.cpp:377-383) walks lidar_measurements_, a std::map<std::string, ...>:
+ * "beam" filters — and draws — BEFORE "likelihood", both through the one sampler_ and its one std::default_random_engine. One
+ * scan's stream is therefore n_b draws of std::uniform_int_distribution<size_t>(0, n_beam_clipped - 1), then n_s draws over
+ * [0, n_lik_clipped); sample() returns an empty cloud WITHOUT drawing when its input is empty (:63-64), and num == 0 draws
+ * nothing. libstdc++'s uniform_int_distribution over minstd_rand0 is restated per attempt (mcl_3dl_amd/csrc/rng_index.h): ranges
+ * up to 2147483646 values; the up-scaling branch above that is refused. engine_state is in / out as for the drawn noise above and
+ * is left untouched by any error.
+ *   rng_draw_indices           count draws of uniform_int_distribution<size_t>(0, range - 1) from the engine, on one context;
+ *                              out_idx on the host. Introspection and general use.
+ *   scan_finish_drawn          mcl3dl_hip_scan_finish with both index arrays drawn on the device: the indices never exist on the
+ *                              host, and from the index buffer on the call IS scan_finish (same gather, same ordering, same scan
+ *                              state). A model whose clipped cloud is empty or whose count is 0 draws nothing and gets an empty
+ *                              scan; *out_n_s / *out_n_b (may be NULL) report what was installed. Up to 65536 draws take one
+ *                              launch and no synchronisation beyond the one scan_finish has; more run in rounds per model.
+ *   group_scan_begin / _begin_pointcloud2 / _finish / _finish_drawn
+ *                              the context forms on every rank, each on its own replica of the cloud (deterministic, no
+ *                              collective). The sizes and the engine state of all ranks must agree, else -4. With one device and
+ *                              "direct_single" 1 each is the plain call on the context. mcl3dl_hip_scan_download and
+ *                              mcl3dl_hip_scan_normal_weights keep working on mcl3dl_hip_group_context(g, 0) behind a
+ *                              group_scan_begin: the normal-weighted sampler serves a group through group_scan_finish with
+ *                              caller-drawn indices.
+ *   group_update_resident_prepared
+ *                              mcl3dl_hip_group_update_resident on the scans the group's scan_finish (either form) installed:
+ *                              no scan argument, nothing is taken over. The installed scans stay until something installs
+ *                              others (a host-scan update replaces them, as before).
+ * -3: range 0 or above 2147483646, engine_state NULL or outside [1, 2^31 - 2], n_b > 0 without origins, and what scan_finish
+ * refuses. -5: no prepared scan; update_resident_prepared without resident particles, or without installed scans of equal
+ * (n_s, n_b, n_o) on every rank — the message names the rank. */
+int mcl3dl_hip_rng_draw_indices(mcl3dl_hip_ctx* ctx, uint64_t range, size_t count, uint32_t* engine_state,
+                                uint32_t* out_idx /*count*/);
+int mcl3dl_hip_scan_finish_drawn(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b, const float* origins /*n_o*3*/, size_t n_o,
+                                 uint32_t* engine_state, size_t* out_n_s, size_t* out_n_b);
+int mcl3dl_hip_group_scan_begin(mcl3dl_hip_group* g, const float* xyz /*n*3*/, const uint32_t* label /*n or NULL*/, size_t n,
+                                const float* leaf3, const float* clip_lik4, const float* clip_beam4, size_t* n_full,
+                                size_t* n_lik_clipped, size_t* n_beam_clipped);
+int mcl3dl_hip_group_scan_begin_pointcloud2(mcl3dl_hip_group* g, const uint8_t* data, size_t n_points, uint32_t point_step,
+                                            int off_x, int off_y, int off_z, int off_label, uint32_t label_override,
+                                            const float* leaf3, const float* clip_lik4, const float* clip_beam4, size_t* n_full,
+                                            size_t* n_lik_clipped, size_t* n_beam_clipped);
+int mcl3dl_hip_group_scan_finish(mcl3dl_hip_group* g, const uint32_t* idx_lik /*n_s*/, size_t n_s,
+                                 const uint32_t* idx_beam /*n_b*/, size_t n_b, const float* origins /*n_o*3*/, size_t n_o);
+int mcl3dl_hip_group_scan_finish_drawn(mcl3dl_hip_group* g, size_t n_s, size_t n_b, const float* origins /*n_o*3*/, size_t n_o,
+                                       uint32_t* engine_state, size_t* out_n_s, size_t* out_n_b);
+int mcl3dl_hip_group_update_resident_prepared(mcl3dl_hip_group* g, const float* extra /*n_p or NULL*/, float* out_weight,
+                                              float* out_lik, float* out_match_ratio, float* out_beam, float* entropy,
+                                              float* match_ratio_min, float* match_ratio_max, int* restored);
 /* How many updates went through each kind of collective so far. */
 int mcl3dl_hip_group_collective_stats(const mcl3dl_hip_group* g, uint64_t* rccl_all_reduces, uint64_t* host_combines);
 

@@ -136,6 +136,14 @@ SIGNATURES = {
     "mcl3dl_hip_group_init_drawn": (_i, [_p, _p, _p, _sz, C.POINTER(_u32)]),
     "mcl3dl_hip_group_draw_odom_noise": (_i, [_p, _p, C.POINTER(_u32)]),
     "mcl3dl_hip_group_resample_apply_drawn": (_i, [_p, _p, C.POINTER(_u32)]),
+    "mcl3dl_hip_rng_draw_indices": (_i, [_p, _u64, _sz, C.POINTER(_u32), _p]),
+    "mcl3dl_hip_scan_finish_drawn": (_i, [_p, _sz, _sz, _p, _sz, C.POINTER(_u32), C.POINTER(_sz), C.POINTER(_sz)]),
+    "mcl3dl_hip_group_scan_begin": (_i, [_p, _p, _p, _sz, _p, _p, _p, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
+    "mcl3dl_hip_group_scan_begin_pointcloud2": (_i, [_p, _p, _sz, _u32, _i, _i, _i, _i, _u32, _p, _p, _p, C.POINTER(_sz),
+                                                    C.POINTER(_sz), C.POINTER(_sz)]),
+    "mcl3dl_hip_group_scan_finish": (_i, [_p, _p, _sz, _p, _sz, _p, _sz]),
+    "mcl3dl_hip_group_scan_finish_drawn": (_i, [_p, _sz, _sz, _p, _sz, C.POINTER(_u32), C.POINTER(_sz), C.POINTER(_sz)]),
+    "mcl3dl_hip_group_update_resident_prepared": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 _lib = None
@@ -398,6 +406,62 @@ class Group:
         return dict(weights=w, lik=lik, quality=ratio, beam=beam, entropy=float(ent.value),
                     match_ratio_min=float(rmin.value), match_ratio_max=float(rmax.value), restored=bool(rest.value))
 
+    # ---- scan preparation on the group, and the update that reads the scans where it left them ------------------------------
+    def context(self, rank=0):
+        """The context of one rank as an Engine that does not own it (mcl3dl_hip_group_context): scan_download,
+        scan_normal_weights and the other calls on one context, behind the group's own."""
+        h = self.lib.mcl3dl_hip_group_context(self.h, int(rank))
+        if not h:
+            raise EngineError("mcl3dl_hip_group_context: no rank %d" % rank)
+        return Engine._borrowed(h)
+
+    def scan_begin(self, xyz, label=None, leaf=None, clip_lik=(0.5, 10.0, -2.0, 2.0), clip_beam=(0.5, 4.0, -2.0, 2.0)):
+        """Engine.scan_begin on every rank; returns (n_full, n_lik_clipped, n_beam_clipped)."""
+        pts = _np_f32(xyz, 3)
+        lab = None if label is None else np.ascontiguousarray(label, dtype=np.uint32)
+        lf, cl, cb = Engine._f3(leaf), Engine._f3(clip_lik), Engine._f3(clip_beam)
+        a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_group_scan_begin(self.h, _ptr(pts), _ptr(lab), len(pts), _ptr(lf), _ptr(cl), _ptr(cb),
+                                                         C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def scan_begin_pointcloud2(self, data, n_points, point_step, off_x, off_y, off_z, off_label=-1, label_override=0,
+                               leaf=None, clip_lik=(0.5, 10.0, -2.0, 2.0), clip_beam=(0.5, 4.0, -2.0, 2.0)):
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        lf, cl, cb = Engine._f3(leaf), Engine._f3(clip_lik), Engine._f3(clip_beam)
+        a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_group_scan_begin_pointcloud2(self.h, _ptr(buf), n_points, point_step, off_x, off_y, off_z,
+                                                                     off_label, label_override, _ptr(lf), _ptr(cl), _ptr(cb),
+                                                                     C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def scan_finish(self, idx_lik, idx_beam=None, origins=None):
+        il = np.ascontiguousarray(idx_lik if idx_lik is not None else [], dtype=np.uint32)
+        ib = np.ascontiguousarray(idx_beam if idx_beam is not None else [], dtype=np.uint32)
+        og = _np_f32(origins if origins is not None else np.zeros((1, 3)), 3)
+        self._check(self.lib.mcl3dl_hip_group_scan_finish(self.h, _ptr(il), len(il), _ptr(ib), len(ib), _ptr(og), len(og)))
+
+    def scan_finish_drawn(self, n_s, n_b, origins, engine_state):
+        """scan_finish with the uniform sampler drawn on the devices (beam's n_b draws first, then the likelihood's n_s).
+        Returns (n_s installed, n_b installed, engine state behind the draws)."""
+        og = None if origins is None else _np_f32(origins, 3)
+        st, a, b = _u32(int(engine_state)), C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_group_scan_finish_drawn(self.h, int(n_s), int(n_b), _ptr(og), 0 if og is None else len(og),
+                                                                C.byref(st), C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value), int(st.value)
+
+    def update_resident_prepared(self, extra=None, fetch=True):
+        """update_resident on the scans the group's scan_finish / scan_finish_drawn installed."""
+        n_p = self.resident()
+        ex = None if extra is None else _np_f32(extra)
+        w, lik, ratio, beam = ((np.zeros(n_p, np.float32) for _ in range(4)) if fetch else (None, None, None, None))
+        ent, rmin, rmax, rest = C.c_float(0), C.c_float(0), C.c_float(0), C.c_int(0)
+        self._check(self.lib.mcl3dl_hip_group_update_resident_prepared(
+            self.h, _ptr(ex), _ptr(w), _ptr(lik), _ptr(ratio), _ptr(beam), C.byref(ent), C.byref(rmin), C.byref(rmax),
+            C.byref(rest)))
+        return dict(weights=w, lik=lik, quality=ratio, beam=beam, entropy=float(ent.value),
+                    match_ratio_min=float(rmin.value), match_ratio_max=float(rmax.value), restored=bool(rest.value))
+
     def expectation(self, bias=None):
         b = None if bias is None else _np_f32(bias)
         mean = np.zeros(7, np.float32)
@@ -552,9 +616,20 @@ class Engine:
         self.h = h
         self.device_id = device_id
 
+    @classmethod
+    def _borrowed(cls, handle, device_id=0):
+        """An Engine over a context somebody else owns (a device group's): close() leaves it alone."""
+        e = cls.__new__(cls)
+        e.lib = load_library()
+        e.h = C.c_void_p(handle)
+        e.device_id = device_id
+        e._owned = False
+        return e
+
     def close(self):
         if getattr(self, "h", None):
-            self.lib.mcl3dl_hip_destroy(self.h)
+            if getattr(self, "_owned", True):
+                self.lib.mcl3dl_hip_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -919,6 +994,23 @@ class Engine:
         og = _np_f32(origins if origins is not None else np.zeros((1, 3)), 3)
         self._check(self.lib.mcl3dl_hip_scan_finish(self.h, _ptr(il), len(il), _ptr(ib), len(ib), _ptr(og), len(og)))
 
+    def scan_finish_drawn(self, n_s, n_b, origins, engine_state):
+        """scan_finish with the uniform sampler drawn on the device from the reference's engine: beam's n_b draws first, then
+        the likelihood's n_s. Returns (n_s installed, n_b installed, engine state behind the draws)."""
+        og = None if origins is None else _np_f32(origins, 3)
+        st, a, b = _u32(int(engine_state)), C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_scan_finish_drawn(self.h, int(n_s), int(n_b), _ptr(og), 0 if og is None else len(og),
+                                                          C.byref(st), C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value), int(st.value)
+
+    def rng_draw_indices(self, range_, count, engine_state):
+        """count draws of std::uniform_int_distribution<size_t>(0, range_ - 1) from the reference's engine, drawn on the device:
+        (indices uint32[count], engine state behind them)."""
+        st = _u32(int(engine_state))
+        out = np.zeros(int(count), np.uint32)
+        self._check(self.lib.mcl3dl_hip_rng_draw_indices(self.h, int(range_), int(count), C.byref(st), _ptr(out)))
+        return out, int(st.value)
+
     def sort_pairs(self, keys, vals=None, end_bit=32):
         """The device radix sort of the cloud path on its own (stable, ascending by key bits [0, end_bit))."""
         k = np.ascontiguousarray(keys, dtype=np.uint32)
@@ -1121,3 +1213,8 @@ def rng_uniform(engine_state, a, b):
     st = _u32(int(engine_state))
     v = load_library().mcl3dl_hip_rng_uniform(C.byref(st), float(a), float(b))
     return float(v), int(st.value)
+
+
+def rng_draw_indices(engine, range_, count, engine_state):
+    """Engine.rng_draw_indices: the uniform sampler's draws on their own, on `engine`'s device."""
+    return engine.rng_draw_indices(range_, count, engine_state)

@@ -36,6 +36,63 @@ int mcl3dl_hip_scan_begin_pointcloud2(mcl3dl_hip_ctx* ctx, const uint8_t* data, 
   return scan_begin_common(ctx, n_points, leaf3, clip_lik4, clip_beam4, n_full, n_lik_clipped, n_beam_clipped, true);
 }
 
+namespace
+{
+// the checks and the device buffers ahead of scan_finish's index buffer: [error, pad x3][idx_lik n_s][idx_beam n_b]
+int scan_finish_prepare(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b)
+{
+  if (n_s > 0x7fffffffu || n_b > 0x7fffffffu)
+    return ctx->fail(-3, "scan too large");
+  HIP_TRY(hipSetDevice(ctx->device));
+  TRY(ensure(ctx, ctx->sp_samp[0], sizeof(float4) * std::max<size_t>(n_s, 1)));
+  TRY(ensure(ctx, ctx->sp_samp[1], sizeof(float4) * std::max<size_t>(n_b, 1)));
+  return ensure(ctx, ctx->cl_idx, 16 + sizeof(uint32_t) * (n_s + n_b));
+}
+
+// scan_finish behind its host-to-device copy: ctx->cl_idx holds the zeroed error word and both index arrays. Gathers the drawn
+// points of both models (one launch, with the likelihood sample's min corner), orders both scans on the device (same keys
+// and stable order as the host path) and installs them. state_home (optional): the second word of the buffer — where
+// rng_index_single_kernel leaves the engine state — comes home with the error word, in the one synchronisation of the call.
+int scan_finish_launch(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b, const float* origins, size_t n_o, uint32_t* state_home)
+{
+  int* d_err = ctx->cl_idx.as<int>();
+  const uint32_t* d_idx_lik = ctx->cl_idx.as<uint32_t>() + 4;
+  const uint32_t* d_idx_beam = d_idx_lik + n_s;
+  if (n_s + n_b)
+  {
+    const long long na = static_cast<long long>(n_s), nb = static_cast<long long>(n_b);
+    const unsigned blocks = minmax_blocks(na + nb);
+    MinMaxOut mm;
+    TRY(minmax_out(ctx, blocks, &mm));
+    hipLaunchKernelGGL(gather2_minmax_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->sp_clip[0].as<float4>(),
+                       static_cast<long long>(ctx->sp_n_clip[0]), d_idx_lik, na, ctx->sp_samp[0].as<float4>(),
+                       ctx->sp_clip[1].as<float4>(), static_cast<long long>(ctx->sp_n_clip[1]), d_idx_beam, nb,
+                       ctx->sp_samp[1].as<float4>(), d_err, mm);
+  }
+  TRY(device_order_scans(ctx, n_s, n_b, origins, n_o, true, d_err));
+  HIP_TRY(hipGetLastError());
+  uint32_t home[2] = { 0u, 0u };  // {error word, engine state}
+  TRY(d2h(ctx, home, d_err, state_home ? sizeof(home) : sizeof(int)));
+  TRY(sync_stream(ctx));
+  const int err = static_cast<int>(home[0]);
+  if (err == 1)
+    return ctx->fail(-3, "a sample index is outside the clipped cloud");
+  if (err == 2)
+    return ctx->fail(-3, "a beam point names an origin that was not given");
+  if (state_home)
+    *state_home = home[1];
+  ctx->sp_n_samp[0] = n_s;
+  ctx->sp_n_samp[1] = n_b;
+  if (n_b > ctx->pow_table_len)
+    ctx->pow_table_dirty = true;
+  ctx->n_s = n_s;
+  ctx->n_b = n_b;
+  ctx->n_o = n_o;
+  ctx->has_scan = true;
+  return 0;
+}
+}  // namespace
+
 int mcl3dl_hip_scan_finish(mcl3dl_hip_ctx* ctx, const uint32_t* idx_lik, size_t n_s, const uint32_t* idx_beam, size_t n_b,
                            const float* origins, size_t n_o)
 {
@@ -50,17 +107,11 @@ int mcl3dl_hip_scan_finish(mcl3dl_hip_ctx* ctx, const uint32_t* idx_lik, size_t 
   // the sampler draws from a non-empty cloud only (point_cloud_uniform_sampler.h:63-64 returns an empty cloud otherwise)
   if ((n_s && ctx->sp_n_clip[0] == 0) || (n_b && ctx->sp_n_clip[1] == 0))
     return ctx->fail(-3, "indices given for an empty clipped cloud");
-  HIP_TRY(hipSetDevice(ctx->device));
-  // ---- gather the drawn points of both models (one launch, with the likelihood sample's min corner), then order both
-  // scans on the device (same keys and stable order as the host path). ONE host-to-device copy carries the (zeroed) error
-  // word and both index arrays: [error, pad x3][idx_lik n_s][idx_beam n_b]
-  TRY(ensure(ctx, ctx->sp_samp[0], sizeof(float4) * std::max<size_t>(n_s, 1)));
-  TRY(ensure(ctx, ctx->sp_samp[1], sizeof(float4) * std::max<size_t>(n_b, 1)));
+  // ONE host-to-device copy carries the (zeroed) error word and both index arrays: [error, pad x3][idx_lik n_s][idx_beam n_b]
+  TRY(scan_finish_prepare(ctx, n_s, n_b));
   const size_t idx_bytes = 16 + sizeof(uint32_t) * (n_s + n_b);
-  TRY(ensure(ctx, ctx->cl_idx, idx_bytes));
-  int* d_err = ctx->cl_idx.as<int>();
-  const uint32_t* d_idx_lik = ctx->cl_idx.as<uint32_t>() + 4;
-  const uint32_t* d_idx_beam = d_idx_lik + n_s;
+  uint32_t* d_idx_lik = ctx->cl_idx.as<uint32_t>() + 4;
+  uint32_t* d_idx_beam = d_idx_lik + n_s;
   {
     char* st = idx_bytes <= STAGE_MAX_COPY ? static_cast<char*>(stage_alloc(ctx, idx_bytes)) : nullptr;
     if (st)
@@ -76,39 +127,64 @@ int mcl3dl_hip_scan_finish(mcl3dl_hip_ctx* ctx, const uint32_t* idx_lik, size_t 
     {
       HIP_TRY(hipMemsetAsync(ctx->cl_idx.p, 0, 16, ctx->stream));
       if (n_s)
-        TRY(h2d(ctx, const_cast<uint32_t*>(d_idx_lik), idx_lik, sizeof(uint32_t) * n_s));
+        TRY(h2d(ctx, d_idx_lik, idx_lik, sizeof(uint32_t) * n_s));
       if (n_b)
-        TRY(h2d(ctx, const_cast<uint32_t*>(d_idx_beam), idx_beam, sizeof(uint32_t) * n_b));
+        TRY(h2d(ctx, d_idx_beam, idx_beam, sizeof(uint32_t) * n_b));
     }
   }
-  if (n_s + n_b)
+  return scan_finish_launch(ctx, n_s, n_b, origins, n_o, nullptr);
+}
+
+// Replaces: PointCloudUniformSampler::sample (point_cloud_uniform_sampler.h:58-75) for both models of measure()
+// (src/mcl_3dl.cpp:377-383: lidar_measurements_ is a std::map, so "beam" filters — and draws — before "likelihood") + what
+// mcl3dl_hip_scan_finish replaces. The indices never exist on the host.
+int mcl3dl_hip_scan_finish_drawn(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b, const float* origins, size_t n_o,
+                                 uint32_t* engine_state, size_t* out_n_s, size_t* out_n_b)
+{
+  if (!ctx)
+    return -1;
+  if (!ctx->sp_ready)
+    return ctx->fail(-5, "no prepared scan: call mcl3dl_hip_scan_begin first");
+  TRY(rng_check_state_ctx(ctx, engine_state));
+  if (n_b && (!origins || n_o == 0))
+    return ctx->fail(-3, "n_b = %zu beam points asked for but no origins given", n_b);
+  // sample() returns an empty cloud, drawing nothing, from an empty cloud (point_cloud_uniform_sampler.h:63-64)
+  if (ctx->sp_n_clip[0] == 0)
+    n_s = 0;
+  if (ctx->sp_n_clip[1] == 0)
+    n_b = 0;
+  if (ctx->sp_n_clip[0] > rng::INDEX_MAX_RANGE || ctx->sp_n_clip[1] > rng::INDEX_MAX_RANGE)
+    return ctx->fail(-3, "a clipped cloud of more than 2147483646 points: that range of uniform_int_distribution is not restated");
+  TRY(scan_finish_prepare(ctx, n_s, n_b));
+  uint32_t* d_head = ctx->cl_idx.as<uint32_t>();
+  uint32_t* d_idx_lik = d_head + 4;
+  uint32_t* d_idx_beam = d_idx_lik + n_s;
+  HIP_TRY(hipMemsetAsync(d_head, 0, 16, ctx->stream));
+  uint32_t state = *engine_state;
+  const rng::IndexSegment beam{ rng::index_range(std::max<size_t>(ctx->sp_n_clip[1], 1)), static_cast<uint32_t>(n_b), d_idx_beam };
+  const rng::IndexSegment lik{ rng::index_range(std::max<size_t>(ctx->sp_n_clip[0], 1)), static_cast<uint32_t>(n_s), d_idx_lik };
+  const bool single = n_s + n_b <= rng::INDEX_SINGLE_MAX;
+  if (n_s + n_b == 0)
+    TRY(scan_finish_launch(ctx, 0, 0, origins, n_o, nullptr));
+  else if (single)
   {
-    const long long na = static_cast<long long>(n_s), nb = static_cast<long long>(n_b);
-    const unsigned blocks = minmax_blocks(na + nb);
-    MinMaxOut mm;
-    TRY(minmax_out(ctx, blocks, &mm));
-    hipLaunchKernelGGL(gather2_minmax_kernel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->sp_clip[0].as<float4>(),
-                       static_cast<long long>(ctx->sp_n_clip[0]), d_idx_lik, na, ctx->sp_samp[0].as<float4>(),
-                       ctx->sp_clip[1].as<float4>(), static_cast<long long>(ctx->sp_n_clip[1]), d_idx_beam, nb,
-                       ctx->sp_samp[1].as<float4>(), d_err, mm);
+    // one launch; the state rides home in the pad word behind the error word
+    TRY(rng_index_single(ctx, state, beam, lik, d_head + 1));
+    TRY(scan_finish_launch(ctx, n_s, n_b, origins, n_o, &state));
+    if (state < 1u || state > rng::MINSTD_M - 1u)
+      return ctx->fail(-4, "internal: the draw left no engine state");
   }
-  TRY(device_order_scans(ctx, n_s, n_b, origins, n_o, true, d_err));
-  HIP_TRY(hipGetLastError());
-  int err = 0;
-  TRY(d2h(ctx, &err, d_err, sizeof(int)));
-  TRY(sync_stream(ctx));
-  if (err == 1)
-    return ctx->fail(-3, "a sample index is outside the clipped cloud");
-  if (err == 2)
-    return ctx->fail(-3, "a beam point names an origin that was not given");
-  ctx->sp_n_samp[0] = n_s;
-  ctx->sp_n_samp[1] = n_b;
-  if (n_b > ctx->pow_table_len)
-    ctx->pow_table_dirty = true;
-  ctx->n_s = n_s;
-  ctx->n_b = n_b;
-  ctx->n_o = n_o;
-  ctx->has_scan = true;
+  else
+  {
+    TRY(rng_index_rounds(ctx, state, beam.r, n_b, d_idx_beam, &state));
+    TRY(rng_index_rounds(ctx, state, lik.r, n_s, d_idx_lik, &state));
+    TRY(scan_finish_launch(ctx, n_s, n_b, origins, n_o, nullptr));
+  }
+  *engine_state = state;
+  if (out_n_s)
+    *out_n_s = n_s;
+  if (out_n_b)
+    *out_n_b = n_b;
   return 0;
 }
 

@@ -473,12 +473,14 @@ void normal_likelihood_constants(float sigma, float* a, float* sq2)
 // One update over the group's shards. resident = false: mcl3dl_hip_group_measure_update (poses and prior weights come from the
 // host, the weights go back). resident = true: the particles mcl3dl_hip_group_upload_state / _resample_apply left on the
 // devices (pose = first 7 floats of each 13-float state, kept as ctx->pose; weights in ctx->gs_weight, updated in place);
-// weight_inout is then an optional OUTPUT (may be null: nothing but four scalars comes back).
+// weight_inout is then an optional OUTPUT (may be null: nothing but four scalars comes back). prepared (with resident): every
+// rank's scans are those mcl3dl_hip_group_scan_finish installed — nothing is taken over, the context's scan state is left alone
+// (stage_inputs would record the scan it is given), an `extra` shard goes up by a plain copy.
 int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, const float* extra, float* weight_inout,
                       size_t n_p, const float* scan_lik_xyz, size_t n_s, const float* scan_beam_xyz,
                       const uint32_t* scan_beam_origin, size_t n_b, const float* origins, size_t n_o, float* out_lik,
                       float* out_match_ratio, float* out_beam, float* entropy, float* match_ratio_min, float* match_ratio_max,
-                      int* restored)
+                      int* restored, bool prepared = false)
 {
   if (resident && g->n_resident == 0)
     return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
@@ -594,7 +596,7 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
           // pose / weight / odometry-factor shard — out of page-locked memory (stage_kernels.h); where that form is not
           // eligible: uploads + the ordering launches, or the scans ordered once on the host and pushed
           bool staged = false;
-          if (n)
+          if (n && !prepared)
           {
             const int st = stage_inputs(ctx, resident ? nullptr : pose + 7 * lo, extra ? extra + lo : nullptr,
                                         resident ? nullptr : weight_inout + lo, n, scan);
@@ -602,7 +604,7 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
               return st;
             staged = st != 0;
           }
-          if (!staged)
+          if (!staged && !prepared)
           {
             if (device_order)
               TRY(upload_scan_impl(ctx, scan, false));

@@ -155,6 +155,133 @@ int mcl3dl_hip_group_update_resident(mcl3dl_hip_group* g, const float* extra, co
                            restored);
 }
 
+// ---- scan preparation on a group: every rank prepares its own replica of the cloud (deterministic, no collective, as the
+// centroid filter of the global localisation and the count pass of the drawn noise); what comes home must agree ----------------
+namespace
+{
+// f(ctx, rank) on every rank; a group of one device that may call its context directly makes the plain call
+int group_scan_each(mcl3dl_hip_group* g, const std::function<int(mcl3dl_hip_ctx*, int)>& f)
+{
+  if (g->n() == 1 && g->direct_single)
+  {
+    const int rc = f(g->ctx[0], 0);
+    return rc ? g->fail_rank(rc, 0) : 0;
+  }
+  int bad = 0;
+  const int rc = g->pool.run_all([&](int r) -> int { return f(g->ctx[r], r); }, &bad);
+  return rc ? g->fail_rank(rc, bad) : 0;
+}
+
+// three sizes per rank -> the caller's, when all ranks agree (rng_hand_back's rule for the engine state)
+int group_scan_sizes(mcl3dl_hip_group* g, const std::vector<size_t>& got, const char* what, size_t* a, size_t* b, size_t* c)
+{
+  for (int r = 1; r < g->n(); ++r)
+    for (int k = 0; k < 3; ++k)
+      if (got[3 * r + k] != got[k])
+        return g->fail(-4, "the ranks disagree on %s (%zu on rank 0, %zu on rank %d)", what, got[k], got[3 * r + k], r);
+  size_t* out[3] = { a, b, c };
+  for (int k = 0; k < 3; ++k)
+    if (out[k])
+      *out[k] = got[k];
+  return 0;
+}
+}  // namespace
+
+// Replaces: what mcl3dl_hip_scan_begin replaces (src/mcl_3dl.cpp:335-372), for the measurement of a device group
+int mcl3dl_hip_group_scan_begin(mcl3dl_hip_group* g, const float* xyz, const uint32_t* label, size_t n, const float* leaf3,
+                                const float* clip_lik4, const float* clip_beam4, size_t* n_full, size_t* n_lik_clipped,
+                                size_t* n_beam_clipped)
+{
+  if (!g)
+    return -1;
+  std::vector<size_t> got(3 * static_cast<size_t>(g->n()), 0);
+  TRY(group_scan_each(g,
+                      [&](mcl3dl_hip_ctx* ctx, int r) -> int {
+                        return mcl3dl_hip_scan_begin(ctx, xyz, label, n, leaf3, clip_lik4, clip_beam4, &got[3 * r], &got[3 * r + 1],
+                                                     &got[3 * r + 2]);
+                      }));
+  return group_scan_sizes(g, got, "the sizes of the prepared clouds", n_full, n_lik_clipped, n_beam_clipped);
+}
+
+int mcl3dl_hip_group_scan_begin_pointcloud2(mcl3dl_hip_group* g, const uint8_t* data, size_t n_points, uint32_t point_step,
+                                            int off_x, int off_y, int off_z, int off_label, uint32_t label_override,
+                                            const float* leaf3, const float* clip_lik4, const float* clip_beam4, size_t* n_full,
+                                            size_t* n_lik_clipped, size_t* n_beam_clipped)
+{
+  if (!g)
+    return -1;
+  std::vector<size_t> got(3 * static_cast<size_t>(g->n()), 0);
+  TRY(group_scan_each(g,
+                      [&](mcl3dl_hip_ctx* ctx, int r) -> int
+                      {
+                        return mcl3dl_hip_scan_begin_pointcloud2(ctx, data, n_points, point_step, off_x, off_y, off_z, off_label,
+                                                                 label_override, leaf3, clip_lik4, clip_beam4, &got[3 * r],
+                                                                 &got[3 * r + 1], &got[3 * r + 2]);
+                      }));
+  return group_scan_sizes(g, got, "the sizes of the prepared clouds", n_full, n_lik_clipped, n_beam_clipped);
+}
+
+// Replaces: what mcl3dl_hip_scan_finish replaces, on every rank: the sampler's push_back loop (point_cloud_uniform_sampler.h:
+// 66-71, or sampler_with_normal's) with caller-drawn indices, and the scans installed where the group's update reads them
+int mcl3dl_hip_group_scan_finish(mcl3dl_hip_group* g, const uint32_t* idx_lik, size_t n_s, const uint32_t* idx_beam, size_t n_b,
+                                 const float* origins, size_t n_o)
+{
+  if (!g)
+    return -1;
+  return group_scan_each(g, [&](mcl3dl_hip_ctx* ctx, int) -> int
+                         { return mcl3dl_hip_scan_finish(ctx, idx_lik, n_s, idx_beam, n_b, origins, n_o); });
+}
+
+// Replaces: PointCloudUniformSampler::sample for both models (point_cloud_uniform_sampler.h:58-75; beam first,
+// src/mcl_3dl.cpp:377-383) on every rank, each from the same engine state
+int mcl3dl_hip_group_scan_finish_drawn(mcl3dl_hip_group* g, size_t n_s, size_t n_b, const float* origins, size_t n_o,
+                                       uint32_t* engine_state, size_t* out_n_s, size_t* out_n_b)
+{
+  if (!g)
+    return -1;
+  if (!engine_state)
+    return g->fail(-3, "null engine_state");
+  const int N = g->n();
+  std::vector<size_t> got(3 * static_cast<size_t>(N), 0);  // {n_s installed, n_b installed, engine state}
+  TRY(group_scan_each(g,
+                      [&](mcl3dl_hip_ctx* ctx, int r) -> int
+                      {
+                        uint32_t state = *engine_state;
+                        TRY(mcl3dl_hip_scan_finish_drawn(ctx, n_s, n_b, origins, n_o, &state, &got[3 * r], &got[3 * r + 1]));
+                        got[3 * r + 2] = state;
+                        return 0;
+                      }));
+  size_t state = 0;
+  TRY(group_scan_sizes(g, got, "the drawn scans or the engine state behind them", out_n_s, out_n_b, &state));
+  *engine_state = static_cast<uint32_t>(state);
+  return 0;
+}
+
+// Replaces: what mcl3dl_hip_group_update_resident replaces (measure(), src/mcl_3dl.cpp:377-470), on the scans the group's
+// scan_finish installed: no scan argument, nothing but the optional odometry factors goes up
+int mcl3dl_hip_group_update_resident_prepared(mcl3dl_hip_group* g, const float* extra, float* out_weight, float* out_lik,
+                                              float* out_match_ratio, float* out_beam, float* entropy, float* match_ratio_min,
+                                              float* match_ratio_max, int* restored)
+{
+  if (!g)
+    return -1;
+  if (g->n_resident == 0)
+    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  for (int r = 0; r < g->n(); ++r)
+  {
+    const mcl3dl_hip_ctx* c = g->ctx[r];
+    if (!c->has_scan)
+      return g->fail(-5, "rank %d holds no installed scan (mcl3dl_hip_group_scan_finish first)", r);
+    const mcl3dl_hip_ctx* c0 = g->ctx[0];
+    if (c->n_s != c0->n_s || c->n_b != c0->n_b || c->n_o != c0->n_o)
+      return g->fail(-5, "rank %d holds a scan of %zu + %zu points and %zu origins, rank 0 one of %zu + %zu and %zu", r, c->n_s,
+                     c->n_b, c->n_o, c0->n_s, c0->n_b, c0->n_o);
+  }
+  return group_update_impl(g, true, nullptr, extra, out_weight, g->n_resident, nullptr, g->ctx[0]->n_s, nullptr, nullptr,
+                           g->ctx[0]->n_b, nullptr, g->ctx[0]->n_o, out_lik, out_match_ratio, out_beam, entropy, match_ratio_min,
+                           match_ratio_max, restored, true);
+}
+
 namespace
 {
 // pf::expectationBiased + max + maxBiased over the shards. jump == null: probability_bias_ is the caller's array (or 1);

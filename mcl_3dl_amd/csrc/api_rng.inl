@@ -242,3 +242,29 @@ int mcl3dl_hip_group_resample_apply_drawn(mcl3dl_hip_group* g, const float* sigm
   TRY(group_resample_apply_impl(g, nullptr, 0, &drawn));
   return rng_hand_back(g, states, drew, engine_state);
 }
+
+// Replaces: `count` calls of std::uniform_int_distribution<size_t>(0, range - 1)(engine_) — PointCloudUniformSampler::sample's
+// draws (point_cloud_uniform_sampler.h:66-71) on their own, for introspection and general use. The rounds form of
+// rng_index_kernels.h; the indices come home.
+int mcl3dl_hip_rng_draw_indices(mcl3dl_hip_ctx* ctx, uint64_t range, size_t count, uint32_t* engine_state, uint32_t* out_idx)
+{
+  if (!ctx)
+    return -1;
+  if (range < 1 || range > rng::INDEX_MAX_RANGE)
+    return ctx->fail(-3, "range %llu is outside [1, 2147483646]", static_cast<unsigned long long>(range));
+  TRY(rng_check_state_ctx(ctx, engine_state));
+  if (count > 0x7fffffffu)
+    return ctx->fail(-3, "count %zu is more than one call draws", count);
+  if (count && !out_idx)
+    return ctx->fail(-3, "null out_idx");
+  if (count == 0)
+    return 0;
+  HIP_TRY(hipSetDevice(ctx->device));
+  TRY(ensure(ctx, ctx->rng_values, sizeof(uint32_t) * count));
+  uint32_t state = *engine_state;
+  TRY(rng_index_rounds(ctx, state, rng::index_range(range), count, ctx->rng_values.as<uint32_t>(), &state));
+  TRY(d2h(ctx, out_idx, ctx->rng_values.p, sizeof(uint32_t) * count));
+  TRY(sync_stream(ctx));
+  *engine_state = state;
+  return 0;
+}

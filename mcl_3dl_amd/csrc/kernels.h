@@ -23,6 +23,7 @@
 //                         of points x div_yaw particles into a shard of resident particles
 //   rng_kernels.h         the filter's noise from the reference's engine: polar-method attempts counted, scanned and emitted in
 //                         stream order (rng_polar.h: the restatement both the device and the CPU emulation compile)
+//   rng_index_kernels.h   the uniform sampler's index draws from the same engine (rng_index.h: the restatement)
 //   stage_kernels.h       head and tail of a host-buffer update as one launch each: scan ordering + pose / weight take-over
 //                         from page-locked host memory; lik_finalize + pf::measure with the results written back there
 //
@@ -45,3 +46,4 @@
 #include "global_loc_kernels.h"
 #include "sampler_kernels.h"
 #include "rng_kernels.h"
+#include "rng_index_kernels.h"

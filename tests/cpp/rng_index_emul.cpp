@@ -1,0 +1,411 @@
+// rng_index_emul.cpp — rng_index_kernels.h's two decompositions of the uniform sampler's stream, replayed on the CPU from the
+// header the kernels compile (mcl_3dl_amd/csrc/rng_index.h): runs of E attempts per lane behind one jump, 64-lane ballots,
+// 256-thread passes / work-groups; the one-work-group form with its pass loop, its start state carried from pass to pass and its
+// hand-over from the first segment to the second; the rounds form with one count per work-group, the exclusive scan, ranks from
+// group offset + wavefront offset + mbcnt, and the host's rounds with index_attempt_budget. Its yardstick is the standard library
+// itself: std::default_random_engine with std::uniform_int_distribution<size_t> (libstdc++), a fresh distribution per draw as
+// PointCloudUniformSampler::sample makes them.
+//
+//   rng_index_emul selftest                       every case of tests/test_rng_index_cpu.py, "all equal" at the end
+//   rng_index_emul draw <std|single|rounds> <state> <n_b> <range_b> <n_s> <range_s> <out.bin>
+//        one scan's stream: n_b draws over [0, range_b), then n_s draws over [0, range_s) (a count of 0 draws nothing); prints
+//        "state=<engine state behind> rounds=<r> attempts=<a>" and writes the n_b + n_s indices as uint32, in draw order
+// g++ -O2.
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <random>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "../../mcl_3dl_amd/csrc/rng_index.h"
+
+using namespace mcl3dl::rng;
+
+namespace
+{
+uint32_t g_table[64];
+constexpr int E = ATTEMPTS_PER_LANE;
+constexpr int WAVES = GROUP_THREADS / 64;
+
+void set_state(std::default_random_engine& e, uint32_t s)
+{
+  std::stringstream ss;
+  ss << s;
+  ss >> e;
+}
+uint32_t get_state(const std::default_random_engine& e)
+{
+  std::stringstream ss;
+  ss << e;
+  unsigned long v = 0;
+  ss >> v;
+  return static_cast<uint32_t>(v);
+}
+
+struct Segment
+{
+  uint64_t range;
+  uint64_t count;
+};
+
+struct Result
+{
+  uint32_t state;
+  int rounds;         // rounds form: the most rounds any segment took; one-work-group form: 0
+  uint64_t attempts;  // attempts evaluated
+};
+
+// the yardstick: sample()'s loop per segment, an empty segment draws nothing
+Result std_draw(uint32_t state, const Segment* seg, int n_seg, std::vector<uint32_t>& out)
+{
+  std::default_random_engine eng;
+  set_state(eng, state);
+  out.clear();
+  for (int s = 0; s < n_seg; ++s)
+    for (uint64_t i = 0; i < seg[s].count; ++i)
+    {
+      std::uniform_int_distribution<size_t> ud(0, seg[s].range - 1);
+      out.push_back(static_cast<uint32_t>(ud(eng)));
+    }
+  return Result{ get_state(eng), 0, 0 };
+}
+
+struct Lane
+{
+  uint32_t v[E];
+  uint32_t mask;
+};
+
+// rng_index_kernels.h: index_lane_mask
+Lane lane_attempts(uint32_t x0, const IndexRange& r, uint64_t n_att, uint64_t lane)
+{
+  Lane L{};
+  const uint64_t t0 = lane * E;
+  if (t0 >= n_att)
+    return L;
+  uint32_t x = minstd_jump(x0, t0, g_table);
+  for (int e = 0; e < E; ++e)
+  {
+    x = minstd_next(x);
+    L.v[e] = x;
+    if (index_accepted(r, x) && t0 + e < n_att)
+      L.mask |= 1u << e;
+  }
+  return L;
+}
+
+// one work-group's lanes with index_wave_ranks: `before` per thread, the total per wavefront
+void group_lanes(uint32_t x0, const IndexRange& r, uint64_t n_att, uint64_t first_lane, Lane* lanes, uint32_t* before,
+                 uint32_t* wave_total)
+{
+  for (int w = 0; w < WAVES; ++w)
+  {
+    uint64_t ballot[E] = { 0 };
+    wave_total[w] = 0;
+    for (int l = 0; l < 64; ++l)
+    {
+      lanes[w * 64 + l] = lane_attempts(x0, r, n_att, first_lane + w * 64 + l);
+      before[w * 64 + l] = 0;
+      for (int e = 0; e < E; ++e)
+        ballot[e] |= static_cast<uint64_t>((lanes[w * 64 + l].mask >> e) & 1u) << l;
+    }
+    for (int e = 0; e < E; ++e)
+    {
+      wave_total[w] += static_cast<uint32_t>(__builtin_popcountll(ballot[e]));
+      for (int l = 0; l < 64; ++l)  // mbcnt: set bits below lane l
+        before[w * 64 + l] += static_cast<uint32_t>(__builtin_popcountll(ballot[e] & ((1ull << l) - 1ull)));
+    }
+  }
+}
+
+// rng_index_single_kernel
+Result single_draw(uint32_t state, const Segment* seg, int n_seg, std::vector<uint32_t>& out)
+{
+  Result res{ state, 0, 0 };
+  out.clear();
+  uint32_t s_start = state;
+  for (int s = 0; s < n_seg; ++s)
+  {
+    const uint64_t count = seg[s].count;
+    if (count == 0)
+      continue;
+    const IndexRange r = index_range(seg[s].range);
+    const size_t base = out.size();
+    out.resize(base + count);
+    uint64_t accepted = 0;
+    while (accepted < count)
+    {
+      const uint32_t start = s_start;
+      Lane lanes[GROUP_THREADS];
+      uint32_t before[GROUP_THREADS], wave_total[WAVES];
+      group_lanes(start, r, static_cast<uint64_t>(GROUP_THREADS) * E, 0, lanes, before, wave_total);
+      res.attempts += static_cast<uint64_t>(GROUP_THREADS) * E;
+      uint32_t pass_total = 0;
+      for (int w = 0; w < WAVES; ++w)
+        pass_total += wave_total[w];
+      for (int t = 0; t < GROUP_THREADS; ++t)
+      {
+        uint32_t wave_offset = 0;
+        for (int w = 0; w < (t >> 6); ++w)
+          wave_offset += wave_total[w];
+        uint64_t rank = accepted + wave_offset + before[t];
+        for (int e = 0; e < E; ++e)
+        {
+          if (!((lanes[t].mask >> e) & 1u))
+            continue;
+          if (rank < count)
+            out[base + rank] = index_value(r, lanes[t].v[e]);
+          if (rank + 1 == count)
+            s_start = lanes[t].v[e];
+          ++rank;
+        }
+        if (accepted + pass_total < count && t == GROUP_THREADS - 1)
+          s_start = lanes[t].v[E - 1];
+      }
+      accepted += pass_total;
+    }
+  }
+  res.state = s_start;
+  return res;
+}
+
+// host_rng.h: rng_index_rounds per segment, the two kernels and the scan replayed work-group by work-group
+Result rounds_draw(uint32_t state, const Segment* seg, int n_seg, std::vector<uint32_t>& out)
+{
+  Result res{ state, 0, 0 };
+  out.clear();
+  const uint64_t per_group = static_cast<uint64_t>(GROUP_THREADS) * E;
+  for (int s = 0; s < n_seg; ++s)
+  {
+    const uint64_t count = seg[s].count;
+    if (count == 0)
+      continue;
+    const IndexRange r = index_range(seg[s].range);
+    const size_t base = out.size();
+    out.resize(base + count);
+    uint32_t x0 = res.state;
+    uint64_t accepted = 0;
+    int rounds = 0;
+    while (accepted < count)
+    {
+      ++rounds;
+      const uint64_t n_att = index_attempt_budget(count - accepted, r);
+      res.attempts += n_att;
+      const uint64_t n_groups = (n_att + per_group - 1) / per_group;
+      std::vector<uint32_t> counts(n_groups + 1, 0u);
+      Lane lanes[GROUP_THREADS];
+      uint32_t before[GROUP_THREADS], wave_total[WAVES];
+      for (uint64_t g = 0; g < n_groups; ++g)  // count kernel
+      {
+        group_lanes(x0, r, n_att, g * GROUP_THREADS, lanes, before, wave_total);
+        for (int w = 0; w < WAVES; ++w)
+          counts[g] += wave_total[w];
+      }
+      uint32_t run = 0;  // exclusive scan (n_groups + 1 entries: the last one becomes the total)
+      for (uint64_t g = 0; g <= n_groups; ++g)
+      {
+        const uint32_t c = counts[g];
+        counts[g] = run;
+        run += c;
+      }
+      uint32_t result = 0;
+      for (uint64_t g = 0; g < n_groups; ++g)  // emit kernel
+      {
+        group_lanes(x0, r, n_att, g * GROUP_THREADS, lanes, before, wave_total);
+        for (int t = 0; t < GROUP_THREADS; ++t)
+        {
+          uint32_t wave_offset = 0;
+          for (int w = 0; w < (t >> 6); ++w)
+            wave_offset += wave_total[w];
+          uint64_t rank = accepted + counts[g] + wave_offset + before[t];
+          for (int e = 0; e < E; ++e)
+          {
+            if (!((lanes[t].mask >> e) & 1u))
+              continue;
+            if (rank < count)
+              out[base + rank] = index_value(r, lanes[t].v[e]);
+            if (rank + 1 == count)
+              result = lanes[t].v[e];
+            ++rank;
+          }
+        }
+      }
+      accepted += counts[n_groups];
+      if (accepted >= count)
+        res.state = result;
+      else
+        x0 = minstd_jump(x0, n_att, g_table);
+    }
+    res.rounds = std::max(res.rounds, rounds);
+  }
+  return res;
+}
+
+uint32_t modpow(uint32_t a, uint64_t k)
+{
+  uint32_t r = 1;
+  for (; k; k >>= 1, a = minstd_mulmod(a, a))
+    if (k & 1)
+      r = minstd_mulmod(r, a);
+  return r;
+}
+
+int g_fail = 0;
+
+// all three on one stream; prints one line per case
+bool run_case(const char* what, uint32_t state, const Segment* seg, int n_seg, bool print, int* rounds_out = nullptr)
+{
+  std::vector<uint32_t> want, one, rnd;
+  const Result w = std_draw(state, seg, n_seg, want);
+  const Result a = single_draw(state, seg, n_seg, one);
+  const Result b = rounds_draw(state, seg, n_seg, rnd);
+  const bool ok = want == one && want == rnd && w.state == a.state && w.state == b.state;
+  if (rounds_out)
+    *rounds_out = b.rounds;
+  if (print || !ok)
+  {
+    printf("case %s state=%u", what, state);
+    for (int s = 0; s < n_seg; ++s)
+      printf(" range%d=%llu count%d=%llu", s, static_cast<unsigned long long>(seg[s].range), s,
+             static_cast<unsigned long long>(seg[s].count));
+    printf(" rounds=%d attempts=%llu behind=%u %s\n", b.rounds, static_cast<unsigned long long>(b.attempts), w.state,
+           ok ? "equal" : "DIFFERENT");
+  }
+  if (!ok)
+    ++g_fail;
+  return ok;
+}
+
+int selftest()
+{
+  const uint32_t inv = modpow(MINSTD_A, MINSTD_M - 2);           // the state whose next output is 1 (ret = 0)
+  const uint32_t before_max = minstd_mulmod(MINSTD_M - 1, inv);  // ... whose next output is 2^31 - 2 (ret = urngrange)
+  if (minstd_next(inv) != 1u || minstd_next(before_max) != MINSTD_M - 1u)
+  {
+    printf("edge states wrong\n");
+    return 1;
+  }
+  // past / scaling as bits/uniform_int_dist.h forms them
+  for (uint64_t n : { 1ull, 2ull, 3ull, 96ull, 1500000000ull, 2147483645ull, 2147483646ull })
+  {
+    const IndexRange r = index_range(n);
+    const uint64_t scaling = n > INDEX_URNG_RANGE ? 1 : INDEX_URNG_RANGE / n, past = n > INDEX_URNG_RANGE ? INDEX_MAX_RANGE : n * scaling;
+    if (r.scaling != scaling || r.past != past)
+    {
+      printf("index_range %llu DIFFERENT\n", static_cast<unsigned long long>(n));
+      ++g_fail;
+    }
+  }
+  const uint32_t starts[] = { minstd_seed(1u), minstd_seed(12345u), minstd_seed(2147483646u), minstd_seed(109u), inv, before_max };
+  const uint64_t ranges[] = { 1, 2, 3, 96, 4089, 65469, 1000000, 1500000000ull, 2147483645ull, 2147483646ull };
+  const uint64_t per_group = static_cast<uint64_t>(GROUP_THREADS) * E;
+  const uint64_t ks[] = { 1, 2, 63, 64, 65, 255, 256, 257, 2 * per_group - 1, 2 * per_group + 1, 100000 };
+  for (uint32_t s : starts)
+    for (uint64_t range : ranges)
+      for (uint64_t k : ks)
+      {
+        if (k == 100000 && s != starts[1] && s != inv)
+          continue;  // (the long stream from two starts only: it is the same code path from every start)
+        const Segment seg[1] = { { range, k } };
+        run_case("one", s, seg, 1, true);
+      }
+  // two segments back to back, beam first: an empty first or second segment, equal and unequal ranges, a pass boundary inside
+  const Segment twos[][2] = { { { 1507, 3 }, { 2893, 96 } },         { { 1507, 16 }, { 2893, 700 } },
+                              { { 1507, 0 }, { 2893, 96 } },         { { 1507, 3 }, { 2893, 0 } },
+                              { { 1, 5 }, { 1, 7 } },                { { 1500000000ull, 512 }, { 1500000000ull, 16384 } },
+                              { { 2147483646ull, 2047 }, { 3, 2049 } }, { { 1500000000ull, 1434 }, { 96, 1 } },
+                              { { 65469, 65535 }, { 4089, 1 } } };
+  for (uint32_t s : starts)
+    for (const auto& t : twos)
+      run_case("two", s, t, 2, true);
+  // a rejection right in front of segment 1's last accepted attempt ("before"), and the attempt right behind it one that segment
+  // 1's range would have rejected but segment 2 judges by its own ("behind"): found by search over the seeds
+  {
+    const Segment t[2] = { { 1500000000ull, 5 }, { 96, 4 } };
+    const IndexRange r = index_range(t[0].range);
+    int found_before = 0, found_behind = 0;
+    for (uint32_t seed = 1; seed <= 400 && (found_before < 3 || found_behind < 3); ++seed)
+    {
+      uint32_t x = minstd_seed(seed), prev_rejected = 0;
+      uint64_t acc = 0;
+      bool before = false;
+      while (acc < t[0].count)
+      {
+        x = minstd_next(x);
+        if (index_accepted(r, x))
+        {
+          ++acc;
+          before = prev_rejected != 0;
+          prev_rejected = 0;
+        }
+        else
+          prev_rejected = 1;
+      }
+      const bool behind = !index_accepted(r, minstd_next(x));
+      if (before && found_before < 3)
+      {
+        run_case("two-rejected-before-last", minstd_seed(seed), t, 2, true);
+        ++found_before;
+      }
+      if (behind && found_behind < 3)
+      {
+        run_case("two-rejected-behind-last", minstd_seed(seed), t, 2, true);
+        ++found_behind;
+      }
+    }
+  }
+  // small counts over many seeds at a range that rejects three attempts in ten: the budget rule lets a round fall short now and
+  // then (the second round is an ordinary path). Only the cases with more than one round are printed.
+  for (uint64_t k : { 1ull, 2ull, 7ull })
+    for (uint32_t seed = 1; seed <= 1500; ++seed)
+    {
+      const Segment seg[1] = { { 1500000000ull, k } };
+      int rounds = 0;
+      const bool ok = run_case("small", minstd_seed(seed), seg, 1, false, &rounds);
+      if (ok && rounds > 1)
+        run_case("small", minstd_seed(seed), seg, 1, true);
+    }
+  printf(g_fail ? "%d cases DIFFERENT\n" : "all equal\n", g_fail);
+  return g_fail ? 1 : 0;
+}
+}  // namespace
+
+int main(int argc, char** argv)
+{
+  minstd_build_table(g_table);
+  if (argc >= 2 && !strcmp(argv[1], "selftest"))
+    return selftest();
+  if (argc == 9 && !strcmp(argv[1], "draw"))
+  {
+    const std::string impl = argv[2];
+    const uint32_t state = static_cast<uint32_t>(strtoul(argv[3], nullptr, 10));
+    const Segment seg[2] = { { strtoull(argv[5], nullptr, 10), strtoull(argv[4], nullptr, 10) },
+                             { strtoull(argv[7], nullptr, 10), strtoull(argv[6], nullptr, 10) } };
+    if (state < 1u || state > MINSTD_M - 1u)
+      return 2;
+    for (const Segment& s : seg)
+      if (s.count && (s.range < 1 || s.range > INDEX_MAX_RANGE))
+        return 2;
+    std::vector<uint32_t> out;
+    Result r;
+    if (impl == "std")
+      r = std_draw(state, seg, 2, out);
+    else if (impl == "single")
+      r = single_draw(state, seg, 2, out);
+    else if (impl == "rounds")
+      r = rounds_draw(state, seg, 2, out);
+    else
+      return 2;
+    FILE* f = fopen(argv[8], "wb");
+    if (!f || fwrite(out.data(), sizeof(uint32_t), out.size(), f) != out.size())
+      return 3;
+    fclose(f);
+    printf("state=%u rounds=%d attempts=%llu\n", r.state, r.rounds, static_cast<unsigned long long>(r.attempts));
+    return 0;
+  }
+  fprintf(stderr, "usage: %s selftest | draw <std|single|rounds> <state> <n_b> <range_b> <n_s> <range_s> <out.bin>\n", argv[0]);
+  return 2;
+}
