@@ -643,7 +643,8 @@ int mcl3dl_hip_group_global_localization(mcl3dl_hip_group* g, double grid, int d
  *                    the host over the downloaded weights. out_normal_xyz: the normals narrowed to float, sign arbitrary.
  *                    capacity in points. *n = points of the cloud, *n_without_normal = points with fewer than 3 neighbours.
  * The caller runs the draw (:159-177: uniform_real_distribution over [0, out_cumulative[n - 1]), lower_bound, unordered_set) with
- * its own std::default_random_engine and hands the indices to mcl3dl_hip_scan_finish; when the cloud has no more points than
+ * its own std::default_random_engine and hands the indices to mcl3dl_hip_scan_finish — or leaves all of it on the device with
+ * mcl3dl_hip_scan_finish_drawn_normal below; when the cloud has no more points than
  * asked for (:104-108) no weights are needed at all. The prepared clouds, the installed scans, the map's indices and a current
  * global-localisation point set are left as they are.
  * Errors of _normal_weights: -5 without a preceding mcl3dl_hip_scan_begin; -3 for which outside 0..2, a normal_search_range
@@ -704,6 +705,38 @@ int mcl3dl_hip_group_scan_finish_drawn(mcl3dl_hip_group* g, size_t n_s, size_t n
 int mcl3dl_hip_group_update_resident_prepared(mcl3dl_hip_group* g, const float* extra /*n_p or NULL*/, float* out_weight,
                                               float* out_lik, float* out_match_ratio, float* out_beam, float* entropy,
                                               float* match_ratio_min, float* match_ratio_max, int* restored);
+/* ---- the normal-weighted sampler drawn on the device ------------------------------------------------------
+ * Replaces: lines :139-177 of PointCloudSamplerWithNormal::sample — the cumulative weights (a sequential double recurrence), the
+ * std::uniform_real_distribution<double>(0, total) draws, std::lower_bound, the duplicate rejection through a
+ * std::unordered_set<size_t>, and that container's ITERATION order, which is the order of the sampled cloud — pinned to
+ * libstdc++ (mcl_3dl_amd/csrc/rng_weighted.h, double_chain.h). An attempt of the loop takes two engine calls; attempts behind the
+ * one that completes the set are never made. The device weights are the project's own; from the weights on,
+ * every bit is the reference's. engine_state is in / out and is left untouched by any error.
+ *   rng_draw_weighted          weights in, the container's iteration order out (out_idx, num ids), on one context. out_cumulative
+ *                              (may be NULL) receives the n cumulative weights, *out_draws (may be NULL) the attempts made.
+ *                              num == 0 forms only the cumulative array, of ANY doubles (engine_state may be NULL). num > 0
+ *                              needs n > num (a cloud of at most num points is copied by the caller), every weight finite and
+ *                              >= 1 and a total below 2^50 — the conditions under which the reference's loop provably ends
+ *                              (rng_weighted.h) — else -3.
+ *   scan_finish_drawn_normal   mcl3dl_hip_scan_finish with both index arrays made by sample() on the device, "beam" before
+ *                              "likelihood" on one stream. Per model: an empty clipped cloud or a count of 0 installs an empty
+ *                              scan and draws nothing; a clipped cloud of at most the count is installed whole in its own order,
+ *                              nothing drawn, no normals computed; otherwise normals -> weights -> cumulative weights -> draws ->
+ *                              order. Up to 1109 points per model take one launch for both models' draws and no synchronisation
+ *                              beyond the one scan_finish has; more run in rounds per model. From the index buffer on the call
+ *                              IS scan_finish, so group_update_resident_prepared works behind the group form unchanged.
+ *   group_scan_finish_drawn_normal  the context call on every rank, each on its own replica; -4 when sizes or engine states disagree.
+ * -3: what scan_finish_drawn and scan_normal_weights refuse, max_weight < 1, or n_clipped * max_weight >= 2^50. -5: no prepared
+ * scan. */
+int mcl3dl_hip_rng_draw_weighted(mcl3dl_hip_ctx* ctx, const double* weight /*n*/, size_t n, size_t num, uint32_t* engine_state,
+                                 uint32_t* out_idx /*num or NULL*/, double* out_cumulative /*n or NULL*/,
+                                 uint64_t* out_draws /*or NULL*/);
+int mcl3dl_hip_scan_finish_drawn_normal(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b, const float* origins /*n_o*3*/, size_t n_o,
+                                        double normal_search_range, const float* fpc_local3, double max_weight,
+                                        uint32_t* engine_state, size_t* out_n_s, size_t* out_n_b);
+int mcl3dl_hip_group_scan_finish_drawn_normal(mcl3dl_hip_group* g, size_t n_s, size_t n_b, const float* origins /*n_o*3*/,
+                                              size_t n_o, double normal_search_range, const float* fpc_local3, double max_weight,
+                                              uint32_t* engine_state, size_t* out_n_s, size_t* out_n_b);
 /* How many updates went through each kind of collective so far. */
 int mcl3dl_hip_group_collective_stats(const mcl3dl_hip_group* g, uint64_t* rccl_all_reduces, uint64_t* host_combines);
 

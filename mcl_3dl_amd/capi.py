@@ -144,6 +144,11 @@ SIGNATURES = {
     "mcl3dl_hip_group_scan_finish": (_i, [_p, _p, _sz, _p, _sz, _p, _sz]),
     "mcl3dl_hip_group_scan_finish_drawn": (_i, [_p, _sz, _sz, _p, _sz, C.POINTER(_u32), C.POINTER(_sz), C.POINTER(_sz)]),
     "mcl3dl_hip_group_update_resident_prepared": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "mcl3dl_hip_rng_draw_weighted": (_i, [_p, _p, _sz, _sz, C.POINTER(_u32), _p, _p, C.POINTER(_u64)]),
+    "mcl3dl_hip_scan_finish_drawn_normal": (_i, [_p, _sz, _sz, _p, _sz, _d, _p, _d, C.POINTER(_u32), C.POINTER(_sz),
+                                                C.POINTER(_sz)]),
+    "mcl3dl_hip_group_scan_finish_drawn_normal": (_i, [_p, _sz, _sz, _p, _sz, _d, _p, _d, C.POINTER(_u32), C.POINTER(_sz),
+                                                      C.POINTER(_sz)]),
 }
 
 _lib = None
@@ -448,6 +453,19 @@ class Group:
         st, a, b = _u32(int(engine_state)), C.c_size_t(0), C.c_size_t(0)
         self._check(self.lib.mcl3dl_hip_group_scan_finish_drawn(self.h, int(n_s), int(n_b), _ptr(og), 0 if og is None else len(og),
                                                                 C.byref(st), C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value), int(st.value)
+
+    def scan_finish_drawn_normal(self, n_s, n_b, origins, normal_search_range, fpc_local, max_weight, engine_state):
+        """scan_finish with the normal-weighted sampler run on the devices (beam first, then the likelihood): returns (n_s
+        installed, n_b installed, engine state behind the draws)."""
+        og = None if origins is None else _np_f32(origins, 3)
+        f = _np_f32(fpc_local).reshape(-1)
+        if f.size != 3:
+            raise ValueError("scan_finish_drawn_normal: fpc_local must hold 3 floats")
+        st, a, b = _u32(int(engine_state)), C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_group_scan_finish_drawn_normal(
+            self.h, int(n_s), int(n_b), _ptr(og), 0 if og is None else len(og), float(normal_search_range), _ptr(f),
+            float(max_weight), C.byref(st), C.byref(a), C.byref(b)))
         return int(a.value), int(b.value), int(st.value)
 
     def update_resident_prepared(self, extra=None, fetch=True):
@@ -1002,6 +1020,30 @@ class Engine:
         self._check(self.lib.mcl3dl_hip_scan_finish_drawn(self.h, int(n_s), int(n_b), _ptr(og), 0 if og is None else len(og),
                                                           C.byref(st), C.byref(a), C.byref(b)))
         return int(a.value), int(b.value), int(st.value)
+
+    def scan_finish_drawn_normal(self, n_s, n_b, origins, normal_search_range, fpc_local, max_weight, engine_state):
+        """scan_finish with PointCloudSamplerWithNormal::sample run on the device for both models from the reference's engine
+        (beam first, then the likelihood): returns (n_s installed, n_b installed, engine state behind the draws)."""
+        og = None if origins is None else _np_f32(origins, 3)
+        f = _np_f32(fpc_local).reshape(-1)
+        if f.size != 3:
+            raise ValueError("scan_finish_drawn_normal: fpc_local must hold 3 floats")
+        st, a, b = _u32(int(engine_state)), C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_scan_finish_drawn_normal(
+            self.h, int(n_s), int(n_b), _ptr(og), 0 if og is None else len(og), float(normal_search_range), _ptr(f),
+            float(max_weight), C.byref(st), C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value), int(st.value)
+
+    def rng_draw_weighted(self, weight, num, engine_state=1):
+        """The normal-weighted sampler's draw on weights handed in: (ids uint32[num] in the order of the sampled cloud,
+        cumulative float64[n], engine state behind the draws, attempts made). num = 0 forms only the cumulative array."""
+        w = np.ascontiguousarray(weight, dtype=np.float64)
+        st, draws = _u32(int(engine_state)), _u64(0)
+        out = np.zeros(int(num), np.uint32)
+        cum = np.zeros(len(w), np.float64)
+        self._check(self.lib.mcl3dl_hip_rng_draw_weighted(self.h, _ptr(w), len(w), int(num), C.byref(st), _ptr(out), _ptr(cum),
+                                                          C.byref(draws)))
+        return out, cum, int(st.value), int(draws.value)
 
     def rng_draw_indices(self, range_, count, engine_state):
         """count draws of std::uniform_int_distribution<size_t>(0, range_ - 1) from the reference's engine, drawn on the device:

@@ -257,6 +257,33 @@ int mcl3dl_hip_group_scan_finish_drawn(mcl3dl_hip_group* g, size_t n_s, size_t n
   return 0;
 }
 
+// Replaces: PointCloudSamplerWithNormal::sample for both models (point_cloud_sampler_with_normal.h:91-185; beam first) on
+// every rank, each from the same engine state. (mcl3dl_hip_scan_finish_drawn_normal is defined in api_sampler.inl.)
+int mcl3dl_hip_group_scan_finish_drawn_normal(mcl3dl_hip_group* g, size_t n_s, size_t n_b, const float* origins, size_t n_o,
+                                              double normal_search_range, const float* fpc_local3, double max_weight,
+                                              uint32_t* engine_state, size_t* out_n_s, size_t* out_n_b)
+{
+  if (!g)
+    return -1;
+  if (!engine_state)
+    return g->fail(-3, "null engine_state");
+  const int N = g->n();
+  std::vector<size_t> got(3 * static_cast<size_t>(N), 0);  // {n_s installed, n_b installed, engine state}
+  TRY(group_scan_each(g,
+                      [&](mcl3dl_hip_ctx* ctx, int r) -> int
+                      {
+                        uint32_t state = *engine_state;
+                        TRY(mcl3dl_hip_scan_finish_drawn_normal(ctx, n_s, n_b, origins, n_o, normal_search_range, fpc_local3,
+                                                                max_weight, &state, &got[3 * r], &got[3 * r + 1]));
+                        got[3 * r + 2] = state;
+                        return 0;
+                      }));
+  size_t state = 0;
+  TRY(group_scan_sizes(g, got, "the drawn scans or the engine state behind them", out_n_s, out_n_b, &state));
+  *engine_state = static_cast<uint32_t>(state);
+  return 0;
+}
+
 // Replaces: what mcl3dl_hip_group_update_resident replaces (measure(), src/mcl_3dl.cpp:377-470), on the scans the group's
 // scan_finish installed: no scan argument, nothing but the optional odometry factors goes up
 int mcl3dl_hip_group_update_resident_prepared(mcl3dl_hip_group* g, const float* extra, float* out_weight, float* out_lik,

@@ -268,6 +268,11 @@ struct mcl3dl_hip_ctx
   bool rs_sorted = false;  // std::sort had ties to order: rs_order is not the identity
   // api_rng.inl: jump table, work-group counts (+ total + result word), scan workspace, this rank's window of the values
   DevBuf rng_table, rng_counts, rng_ws, rng_values;
+  // the normal-weighted sampler's draw (host_weighted.h): weights handed in, cumulative weights and first-attempt words per model
+  // {beam, likelihood}, a round's drawn ids and new flags (+ result words), scan workspace, inserted ids, the order phases'
+  // ping-pong, bucket heads, chains, per-arrival words, and the result words of the stand-alone call
+  DevBuf wd_w, wd_cum[2], wd_first[2], wd_att, wd_flag, wd_ws, wd_ins, wd_order[2], wd_head, wd_link, wd_first_of, wd_later,
+      wd_size, wd_result, wd_out;
   bool rng_table_set = false;
 
   std::string index_note;  // why the map compiler fell back to a coarser / plainer index form (diagnostics)

@@ -24,6 +24,8 @@
 //   rng_kernels.h         the filter's noise from the reference's engine: polar-method attempts counted, scanned and emitted in
 //                         stream order (rng_polar.h: the restatement both the device and the CPU emulation compile)
 //   rng_index_kernels.h   the uniform sampler's index draws from the same engine (rng_index.h: the restatement)
+//   rng_weighted_kernels.h  the normal-weighted sampler's draw: cumulative weights as the serial double recurrence (double_chain.h),
+//                         draws, lower_bound, duplicate rejection and the unordered_set's iteration order (rng_weighted.h)
 //   stage_kernels.h       head and tail of a host-buffer update as one launch each: scan ordering + pose / weight take-over
 //                         from page-locked host memory; lik_finalize + pf::measure with the results written back there
 //
@@ -47,3 +49,4 @@
 #include "sampler_kernels.h"
 #include "rng_kernels.h"
 #include "rng_index_kernels.h"
+#include "rng_weighted_kernels.h"

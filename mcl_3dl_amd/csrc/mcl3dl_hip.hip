@@ -33,6 +33,7 @@ using namespace mcl3dl;
 #include "host_pf.h"
 #include "host_rng.h"
 #include "host_cloud.h"
+#include "host_weighted.h"
 #include "host_grid_builders.h"
 #include "host_group.h"
 
