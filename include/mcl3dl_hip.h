@@ -737,6 +737,41 @@ int mcl3dl_hip_scan_finish_drawn_normal(mcl3dl_hip_ctx* ctx, size_t n_s, size_t 
 int mcl3dl_hip_group_scan_finish_drawn_normal(mcl3dl_hip_group* g, size_t n_s, size_t n_b, const float* origins /*n_o*3*/,
                                               size_t n_o, double normal_search_range, const float* fpc_local3, double max_weight,
                                               uint32_t* engine_state, size_t* out_n_s, size_t* out_n_b);
+/* ---- the sampled covariance on resident particles, std::shuffle on the device -------------------------------
+ * Replaces: pf::covariance(1.0, random_sample_ratio) with random_sample_ratio < 1 (pf.h:304-360; src/mcl_3dl.cpp:373 and :706 while
+ * there are more particles than num_particles): std::shuffle(iota(p_num), engine_), the first
+ * sample_num = min(p_num, (size_t)((float)p_num * ratio)) indices (a FLOAT product, truncated), the sums over those. Pinned to
+ * libstdc++ (mcl_3dl_amd/csrc/rng_shuffle.h): a shuffle of n <= 46340 elements takes the library's pair path and is made ON THE
+ * HOST by the serial loop (at most 27 000 engine calls; its indices are uploaded); n >= 46341 takes the single path and is made
+ * ON THE DEVICE, by every rank of a group for itself (deterministic, no collective). p_num is n: the early `break` of pf.h:316 once
+ * the float weight sum passes pass_ratio is not reproduced, as in every covariance here. Sums as in mcl3dl_hip_covariance: float
+ * terms, fp64 accumulation in the list's order, mcl3dl_hip_covariance_finish. engine_state is in / out and is left untouched by
+ * any error.
+ *   rng_shuffle_prefix         the first m entries of std::shuffle(iota(n), engine) and the state behind the WHOLE shuffle;
+ *                              n in [1, 2^31 - 2], m <= n; out_idx on the host. (The device path numbers attempts in 32 bits: a
+ *                              shuffle that needs 2^32 attempts or more — n near 2^31 — is refused with -3.)
+ *   covariance_window_partial_device
+ *                              mcl3dl_hip_covariance_partial_device for one shard of a sharded set: d_pose / d_weight hold the
+ *                              particles [window_lo, window_lo + n_window), d_subset names particles of the WHOLE set. Entries
+ *                              outside the window contribute nothing and keep their place in the list: with one shard the 22 sums
+ *                              are those of covariance_partial_device bit for bit. An empty list or window gives 22 zeros.
+ *   group_covariance_sampled   the covariance over caller-drawn indices into the resident particles (global indices, any order,
+ *                              each < n_resident): every rank reduces the entries of its shard, 22 doubles per rank are added in
+ *                              rank order on the host. An empty shard is no error.
+ *   group_covariance_drawn     the same with the shuffle made from *engine_state; *out_n_sampled (may be NULL) = sample_num.
+ *                              ratio >= 1: no shuffle, no draw, mcl3dl_hip_group_covariance. Prefer _sampled where the caller
+ *                              already holds the indices; see DESIGN.md 3.11 for what either route costs.
+ * The installed scans, the map's indices, the resampling plan and the odometry noise are left as they are.
+ * -3: NULL arrays, an index >= n_resident, an empty list, a NaN or negative ratio, a ratio that samples no particle (the
+ * reference divides by zero), engine_state NULL or outside [1, 2^31 - 2]. -5: no resident particles. */
+int mcl3dl_hip_rng_shuffle_prefix(mcl3dl_hip_ctx* ctx, size_t n, size_t m, uint32_t* engine_state, uint32_t* out_idx /*m*/);
+int mcl3dl_hip_covariance_window_partial_device(mcl3dl_hip_ctx* ctx, const float* d_pose, const float* d_weight,
+                                                size_t n_window, const uint32_t* d_subset, size_t n_subset, size_t window_lo,
+                                                const float* mean7, double* d_out22);
+int mcl3dl_hip_group_covariance_sampled(mcl3dl_hip_group* g, const float* mean7, const uint32_t* subset /*n_subset*/,
+                                        size_t n_subset, float* out_cov36);
+int mcl3dl_hip_group_covariance_drawn(mcl3dl_hip_group* g, const float* mean7, float random_sample_ratio, uint32_t* engine_state,
+                                      size_t* out_n_sampled /*or NULL*/, float* out_cov36);
 /* How many updates went through each kind of collective so far. */
 int mcl3dl_hip_group_collective_stats(const mcl3dl_hip_group* g, uint64_t* rccl_all_reduces, uint64_t* host_combines);
 

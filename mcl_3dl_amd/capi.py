@@ -149,6 +149,10 @@ SIGNATURES = {
                                                 C.POINTER(_sz)]),
     "mcl3dl_hip_group_scan_finish_drawn_normal": (_i, [_p, _sz, _sz, _p, _sz, _d, _p, _d, C.POINTER(_u32), C.POINTER(_sz),
                                                       C.POINTER(_sz)]),
+    "mcl3dl_hip_rng_shuffle_prefix": (_i, [_p, _sz, _sz, C.POINTER(_u32), _p]),
+    "mcl3dl_hip_covariance_window_partial_device": (_i, [_p, _p, _p, _sz, _p, _sz, _sz, _p, _p]),
+    "mcl3dl_hip_group_covariance_sampled": (_i, [_p, _p, _p, _sz, _p]),
+    "mcl3dl_hip_group_covariance_drawn": (_i, [_p, _p, _f, C.POINTER(_u32), C.POINTER(_sz), _p]),
 }
 
 _lib = None
@@ -514,6 +518,23 @@ class Group:
         cov = np.zeros((6, 6), np.float32)
         self._check(self.lib.mcl3dl_hip_group_covariance(self.h, _ptr(m), _ptr(cov)))
         return cov
+
+    def covariance_sampled(self, mean7, subset):
+        """pf::covariance(1.0, ratio < 1) over indices the caller drew: global indices into the resident particles, any order."""
+        m = _np_f32(mean7)
+        sub = np.ascontiguousarray(subset, dtype=np.uint32)
+        cov = np.zeros((6, 6), np.float32)
+        self._check(self.lib.mcl3dl_hip_group_covariance_sampled(self.h, _ptr(m), _ptr(sub), len(sub), _ptr(cov)))
+        return cov
+
+    def covariance_drawn(self, mean7, ratio, engine_state):
+        """pf::covariance(1.0, ratio) with std::shuffle(iota(n), engine_) made from the engine state (on the devices from 46341
+        particles on): (covariance, sample_num, engine state behind). ratio >= 1 draws nothing and sums every particle."""
+        m = _np_f32(mean7)
+        st, ns = _u32(int(engine_state)), C.c_size_t(0)
+        cov = np.zeros((6, 6), np.float32)
+        self._check(self.lib.mcl3dl_hip_group_covariance_drawn(self.h, _ptr(m), float(ratio), C.byref(st), C.byref(ns), _ptr(cov)))
+        return cov, int(ns.value), int(st.value)
 
     def resample_begin(self, n_out=0):
         pstep = C.c_float(0)
@@ -898,6 +919,14 @@ class Engine:
         self._check(self.lib.mcl3dl_hip_covariance_partial_device(self.h, _ptr(d_pose), _ptr(d_weight), n,
                                                                   _ptr(d_subset), n_subset, _ptr(m), _ptr(d_out22)))
 
+    def covariance_window_partial_device(self, d_pose, d_weight, n_window, window_lo, mean7, d_out22, d_subset, n_subset):
+        """covariance_partial_device for the shard [window_lo, window_lo + n_window) of a sharded particle set: d_subset names
+        particles of the whole set, the entries outside the window contribute nothing."""
+        m = _np_f32(mean7)
+        self._check(self.lib.mcl3dl_hip_covariance_window_partial_device(self.h, _ptr(d_pose), _ptr(d_weight), int(n_window),
+                                                                         _ptr(d_subset), int(n_subset), int(window_lo), _ptr(m),
+                                                                         _ptr(d_out22)))
+
     def covariance_finish(self, sums22):
         s = np.ascontiguousarray(sums22, np.float64)
         cov = np.zeros((6, 6), np.float32)
@@ -1051,6 +1080,14 @@ class Engine:
         st = _u32(int(engine_state))
         out = np.zeros(int(count), np.uint32)
         self._check(self.lib.mcl3dl_hip_rng_draw_indices(self.h, int(range_), int(count), C.byref(st), _ptr(out)))
+        return out, int(st.value)
+
+    def rng_shuffle_prefix(self, n, m, engine_state):
+        """The first m entries of std::shuffle(iota(n), engine) (libstdc++) and the engine state behind the whole shuffle: made on
+        the device from n = 46341 on, by the library's serial loop on the host below."""
+        st = _u32(int(engine_state))
+        out = np.zeros(int(m), np.uint32)
+        self._check(self.lib.mcl3dl_hip_rng_shuffle_prefix(self.h, int(n), int(m), C.byref(st), _ptr(out)))
         return out, int(st.value)
 
     def sort_pairs(self, keys, vals=None, end_bit=32):

@@ -268,6 +268,9 @@ struct mcl3dl_hip_ctx
   bool rs_sorted = false;  // std::sort had ties to order: rs_order is not the identity
   // api_rng.inl: jump table, work-group counts (+ total + result word), scan workspace, this rank's window of the values
   DevBuf rng_table, rng_counts, rng_ws, rng_values;
+  // the shuffle of the sampled covariance (host_shuffle.h): j_i per step, the doubtful attempts {number, engine output}, the
+  // rejected attempt numbers, the first m entries of the shuffled iota
+  DevBuf sh_target, sh_doubt_t, sh_doubt_v, sh_rejected, sh_idx;
   // the normal-weighted sampler's draw (host_weighted.h): weights handed in, cumulative weights and first-attempt words per model
   // {beam, likelihood}, a round's drawn ids and new flags (+ result words), scan workspace, inserted ids, the order phases'
   // ping-pong, bucket heads, chains, per-arrival words, and the result words of the stand-alone call

@@ -1,0 +1,96 @@
+// host_shuffle.h — part of the single translation unit mcl3dl_hip.hip: the first m entries of std::shuffle(iota(n), engine_) on
+// ONE context (rng_shuffle.h holds the restatement, rng_shuffle_kernels.h the kernels; the entry points are in api_shuffle.inl).
+//
+//   n <= 46340   libstdc++'s pair path: the serial loop of rng_shuffle.h ON THE HOST (at most 27 000 engine calls); the caller
+//                uploads the m indices where a device needs them
+//   n >= 46341   the single path ON THE DEVICE: doubtful attempts counted, compacted and resolved (one small copy home per
+//                launch group: their number, then {rejections, complete}), every step's target written, the pairs sorted with
+//                the cloud path's stable radix sort, one chain walk per entry. A device group runs this on every rank with the
+//                same engine state (deterministic replicas, no collective, as host_rng.h's draws).
+#pragma once
+
+namespace
+{
+// the whole shuffle on the host; the first m entries stay in `a`
+void shuffle_prefix_host(uint64_t n, uint64_t m, uint32_t state_in, std::vector<uint32_t>& a, uint32_t* state_out)
+{
+  a.resize(n);
+  uint32_t state = state_in;
+  rng::shuffle_serial(n, &state, a.data(), false, nullptr);
+  a.resize(m);
+  *state_out = state;
+}
+
+// n >= 2, m in [1, n]: a[0 .. m) of the single path's shuffle into ctx->sh_idx (device); *state_out = the engine state behind
+// the WHOLE shuffle. Nothing is synchronised behind the last launch.
+int shuffle_prefix_device(mcl3dl_hip_ctx* ctx, uint64_t n, uint64_t m, uint32_t state_in, uint32_t* state_out)
+{
+  constexpr uint64_t PER_GROUP = static_cast<uint64_t>(rng::GROUP_THREADS) * rng::ATTEMPTS_PER_LANE;
+  TRY(rng_device_table(ctx));
+  const uint32_t* d_table = ctx->rng_table.as<uint32_t>();
+  TRY(ensure(ctx, ctx->sh_target, sizeof(uint32_t) * n));
+  TRY(ensure(ctx, ctx->sh_idx, sizeof(uint32_t) * m));
+  const unsigned long long n_ull = n;
+  uint64_t n_att = 0, accepted = 0;
+  uint32_t n_rejected = 0;
+  for (int round = 0;; ++round)
+  {
+    if (round >= 64)
+      return ctx->fail(-4, "internal: the random stream did not yield the %llu steps of the shuffle in 64 rounds", n_ull - 1);
+    n_att = rng::shuffle_attempt_budget(n_att, accepted, n);
+    const uint64_t n_groups = (n_att + PER_GROUP - 1) / PER_GROUP;
+    if (n_att > 0xffffffffull || n_groups > 0x7fffffffull)
+      return ctx->fail(-3, "a shuffle of %llu elements takes more attempts than the device path numbers in 32 bits", n_ull);
+    // counts[0 .. n_groups) | [n_groups] = 0, the total behind the scan | [n_groups + 1, + 2] = the resolve kernel's result
+    TRY(ensure(ctx, ctx->rng_counts, sizeof(uint32_t) * (n_groups + 3)));
+    TRY(ensure(ctx, ctx->rng_ws, sizeof(uint32_t) * (n_groups / 1023 + 8)));
+    uint32_t* d_counts = ctx->rng_counts.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(d_counts + n_groups, 0, sizeof(uint32_t) * 3, ctx->stream));
+    const dim3 grid(static_cast<unsigned>(n_groups)), block(rng::GROUP_THREADS);
+    hipLaunchKernelGGL(rng::shuffle_doubt_count_kernel, grid, block, 0, ctx->stream, state_in, d_table, n_ull,
+                       static_cast<unsigned long long>(n_att), d_counts);
+    HIP_TRY(hipGetLastError());
+    TRY(device_exclusive_scan_ws(ctx, d_counts, static_cast<long long>(n_groups) + 1, ctx->rng_ws.as<uint32_t>()));
+    uint32_t n_doubt = 0;
+    TRY(d2h(ctx, &n_doubt, d_counts + n_groups, sizeof(n_doubt)));
+    TRY(sync_stream(ctx));
+    n_rejected = 0;
+    if (n_doubt == 0)
+      break;  // every attempt is accepted wherever it arrives, and the budget is at least n - 1
+    TRY(ensure(ctx, ctx->sh_doubt_t, sizeof(uint32_t) * n_doubt));
+    TRY(ensure(ctx, ctx->sh_doubt_v, sizeof(uint32_t) * n_doubt));
+    TRY(ensure(ctx, ctx->sh_rejected, sizeof(uint32_t) * n_doubt));
+    hipLaunchKernelGGL(rng::shuffle_doubt_emit_kernel, grid, block, 0, ctx->stream, state_in, d_table, n_ull,
+                       static_cast<unsigned long long>(n_att), d_counts, n_doubt, ctx->sh_doubt_t.as<uint32_t>(),
+                       ctx->sh_doubt_v.as<uint32_t>());
+    hipLaunchKernelGGL(rng::shuffle_resolve_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->sh_doubt_t.as<uint32_t>(),
+                       ctx->sh_doubt_v.as<uint32_t>(), n_doubt, n_ull, static_cast<unsigned long long>(n_att),
+                       ctx->sh_rejected.as<uint32_t>(), d_counts + n_groups + 1);
+    HIP_TRY(hipGetLastError());
+    uint32_t home[2] = { 0u, 0u };  // {rejections among the steps, 1 = the attempts hold every step}
+    TRY(d2h(ctx, home, d_counts + n_groups + 1, sizeof(home)));
+    TRY(sync_stream(ctx));
+    if (home[0] > n_doubt)
+      return ctx->fail(-4, "internal: %u rejections among %u doubtful attempts", home[0], n_doubt);
+    n_rejected = home[0];
+    if (home[1])
+      break;
+    accepted = n_att - n_rejected;
+  }
+  const uint64_t n_used = (n - 1) + n_rejected;
+  hipLaunchKernelGGL(rng::shuffle_targets_kernel, dim3(static_cast<unsigned>((n_used + PER_GROUP - 1) / PER_GROUP)),
+                     dim3(rng::GROUP_THREADS), 0, ctx->stream, state_in, d_table, n_ull, static_cast<unsigned long long>(n_used),
+                     ctx->sh_rejected.as<uint32_t>(), n_rejected, ctx->sh_target.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  // (j_i, i - 1) by j_i: the keys are target[1 ..], the values the sort's own index; keys are at most n - 1
+  RsKeyGen kg{};
+  kg.keys = ctx->sh_target.as<uint32_t>() + 1;
+  TRY(radix_sort<RS_KEY_ARRAY>(ctx, kg, static_cast<long long>(n - 1), bits_for(n - 1), nullptr));
+  hipLaunchKernelGGL(rng::shuffle_chain_kernel, dim3(blocks_for(static_cast<long long>(m))), dim3(256), 0, ctx->stream,
+                     ctx->cl_key[1].as<uint32_t>(), ctx->cl_val[1].as<uint32_t>(), ctx->sh_target.as<uint32_t>(),
+                     static_cast<uint32_t>(n), static_cast<uint32_t>(m), ctx->sh_idx.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  *state_out = rng::minstd_jump(state_in, n_used, rng_host_table());
+  return 0;
+}
+}  // namespace

@@ -26,6 +26,8 @@
 //   rng_index_kernels.h   the uniform sampler's index draws from the same engine (rng_index.h: the restatement)
 //   rng_weighted_kernels.h  the normal-weighted sampler's draw: cumulative weights as the serial double recurrence (double_chain.h),
 //                         draws, lower_bound, duplicate rejection and the unordered_set's iteration order (rng_weighted.h)
+//   rng_shuffle_kernels.h  std::shuffle(iota(n), engine_) of the sampled covariance: doubtful attempts resolved by one wavefront, every
+//                         step's target, one chain walk per entry over the sorted (target, step) pairs (rng_shuffle.h: the restatement)
 //   stage_kernels.h       head and tail of a host-buffer update as one launch each: scan ordering + pose / weight take-over
 //                         from page-locked host memory; lik_finalize + pf::measure with the results written back there
 //
@@ -50,3 +52,4 @@
 #include "rng_kernels.h"
 #include "rng_index_kernels.h"
 #include "rng_weighted_kernels.h"
+#include "rng_shuffle_kernels.h"

@@ -34,6 +34,7 @@ using namespace mcl3dl;
 #include "host_rng.h"
 #include "host_cloud.h"
 #include "host_weighted.h"
+#include "host_shuffle.h"
 #include "host_grid_builders.h"
 #include "host_group.h"
 
@@ -53,4 +54,5 @@ extern "C"
 #include "api_global_loc.inl"
 #include "api_sampler.inl"
 #include "api_rng.inl"
+#include "api_shuffle.inl"
 }  // extern "C"

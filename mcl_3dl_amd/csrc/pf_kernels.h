@@ -737,12 +737,15 @@ __host__ __device__ inline Vec3f quat_get_rpy(Quat q)
 
 constexpr int COV_N = 22;  // 21 upper-triangular sums + p_sum
 
-// subset == nullptr: particles 0..n-1; else the n indices the caller drew (pf.h:322-336 shuffles them with its own RNG)
-__global__ __launch_bounds__(PF_BLOCK) void pf_covariance_kernel(const float* __restrict__ pose7,
-                                                                 const float* __restrict__ w,
-                                                                 const uint32_t* __restrict__ subset, int n,
-                                                                 float e0, float e1, float e2, Vec3f exp_rpy,
-                                                                 double* __restrict__ block_cov /*[grid][COV_N]*/)
+// subset == nullptr: particles 0..n-1; else the n indices the caller drew (pf.h:322-336 shuffles them with its own RNG).
+// WINDOW: pose7 / w hold the particles [window_lo, window_lo + window_n) of a sharded set and the list names particles of the
+// whole set: an entry outside the window contributes nothing and keeps its place in the list, so every entry is summed by the
+// lane and in the turn that the unwindowed kernel gives it.
+template <bool WINDOW>
+__device__ __forceinline__ void pf_covariance_body(const float* __restrict__ pose7, const float* __restrict__ w,
+                                                   const uint32_t* __restrict__ subset, int n, uint32_t window_lo,
+                                                   uint32_t window_n, float e0, float e1, float e2, Vec3f exp_rpy,
+                                                   double* __restrict__ block_cov /*[grid][COV_N]*/)
 {
   double acc[COV_N];
 #pragma unroll
@@ -750,7 +753,13 @@ __global__ __launch_bounds__(PF_BLOCK) void pf_covariance_kernel(const float* __
     acc[k] = 0.0;
   for (int t = blockIdx.x * PF_BLOCK + threadIdx.x; t < n; t += gridDim.x * PF_BLOCK)
   {
-    const size_t i = subset ? subset[t] : static_cast<size_t>(t);
+    size_t i = subset ? subset[t] : static_cast<size_t>(t);
+    if (WINDOW)
+    {
+      if (i < window_lo || i - window_lo >= window_n)
+        continue;
+      i -= window_lo;
+    }
     const float* ps = pose7 + 7 * i;
     const float prob = w[i];
     const Vec3f rpy = quat_get_rpy(Quat{ ps[3], ps[4], ps[5], ps[6] });
@@ -793,6 +802,26 @@ __global__ __launch_bounds__(PF_BLOCK) void pf_covariance_kernel(const float* __
       s += sh[threadIdx.x][q];
     block_cov[COV_N * blockIdx.x + threadIdx.x] = s;
   }
+}
+
+__global__ __launch_bounds__(PF_BLOCK) void pf_covariance_kernel(const float* __restrict__ pose7,
+                                                                 const float* __restrict__ w,
+                                                                 const uint32_t* __restrict__ subset, int n,
+                                                                 float e0, float e1, float e2, Vec3f exp_rpy,
+                                                                 double* __restrict__ block_cov /*[grid][COV_N]*/)
+{
+  pf_covariance_body<false>(pose7, w, subset, n, 0u, 0u, e0, e1, e2, exp_rpy, block_cov);
+}
+
+// the sampled covariance of a device group (api_shuffle.inl): one shard's share of a list over the whole particle set
+__global__ __launch_bounds__(PF_BLOCK) void pf_covariance_window_kernel(const float* __restrict__ pose7,
+                                                                        const float* __restrict__ w,
+                                                                        const uint32_t* __restrict__ subset, int n,
+                                                                        uint32_t window_lo, uint32_t window_n, float e0,
+                                                                        float e1, float e2, Vec3f exp_rpy,
+                                                                        double* __restrict__ block_cov /*[grid][COV_N]*/)
+{
+  pf_covariance_body<true>(pose7, w, subset, n, window_lo, window_n, e0, e1, e2, exp_rpy, block_cov);
 }
 
 __global__ __launch_bounds__(64) void pf_covariance_reduce_kernel(const double* __restrict__ block_cov, int n_blocks,
