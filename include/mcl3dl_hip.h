@@ -838,6 +838,10 @@ int mcl3dl_hip_memory_footprint(mcl3dl_hip_ctx* ctx, uint64_t* bytes8);
  *   "lik_coop"          1 = quad-cooperative record fetch + VALU-trimmed evaluation in the tiled kernel
  *   "lik_defer"         1 = overflow rounds queued per wavefront and run densely (packed 64-byte records); 0 = at once; 2 = only on
  *                       maps where enough voxels overflow. Read-only "lik_defer_active"
+ *   "lik_tiled_fast"    -1 = the tiled kernel's deferred form runs its pose loop specialised for the common map (records, overflow
+ *                       records and brick table below 4 GB, 24-bit table index, packed words, 64-byte records) when the parameters
+ *                       allow it (match_dist_flat <= match_dist_min); 0 = never. Same results: a switch for A/B runs and tests.
+ *                       Read-only "lik_tiled_fast_active"
  *   "update_small", "update_small_max"   the whole update as ONE launch up to that many particles (512) where the per-particle
  *                       kernels serve the scans; "update_small_conformant" = its arrival tickets as acq_rel RMWs (the memory
  *                       model's form; slower; a mitigation switch, tests/test_gpu_soak.py runs both)

@@ -45,11 +45,36 @@ int mcl3dl_hip_memory_footprint(mcl3dl_hip_ctx* ctx, uint64_t* bytes8)
   return 0;
 }
 
+// Switches between two forms of one kernel that compute the same bits: set and read through the same two calls as the options,
+// but no rows of host_options.h's table — nothing a caller tunes, they exist for A/B runs and for the tests that hold one form
+// against the other.
+namespace
+{
+struct Switch
+{
+  const char* name;
+  int Options::*field;
+  OptionRule rule;
+  const char* must;
+};
+const Switch kSwitches[] = {
+    { "lik_tiled_fast", &Options::lik_tiled_fast, one_of(-1, 0), "be -1 (where the map and the parameters allow it) or 0 (never)" },
+};
+}  // namespace
+
 // The keys, their rules and their effects are the table of host_options.h; here the effects meet the engine's state.
 int mcl3dl_hip_set_option(mcl3dl_hip_ctx* ctx, const char* name, double value)
 {
   if (!ctx || !name)
     return -1;
+  for (const Switch& s : kSwitches)
+    if (strcmp(s.name, name) == 0)
+    {
+      if (!option_accepts(s.rule, value))
+        return ctx->fail(-3, "%s must %s", s.name, s.must);
+      ctx->opt.*s.field = static_cast<int>(value);
+      return 0;
+    }
   const OptionSet set = option_set(ctx->opt, name, value);
   if (set.effects & EFFECT_CAND)
     ctx->cand_dirty = true;
@@ -90,6 +115,7 @@ const Diagnostic kDiagnostics[] = {
     { "dda_overlay_points", [](const mcl3dl_hip_ctx* c) -> double { return c->dda_dirty ? 0.0 : static_cast<double>(c->dg.ov_n); } },
     { "batch_slices_run", [](const mcl3dl_hip_ctx* c) -> double { return static_cast<double>(c->batch_slices_run); } },
     { "lik_defer_active", [](const mcl3dl_hip_ctx* c) -> double { return lik_defer_active(c) ? 1.0 : 0.0; } },
+    { "lik_tiled_fast_active", [](const mcl3dl_hip_ctx* c) -> double { return lik_tiled_fast_active(c, lik_params(c)) ? 1.0 : 0.0; } },
     { "cand_packed_active", [](const mcl3dl_hip_ctx* c) -> double { return c->rg.packed; } },
     { "cand_bound_active", [](const mcl3dl_hip_ctx* c) -> double { return c->rg.bound_step > 0.0f ? 1.0 : 0.0; } },
     { "lik_grid_build_ms", [](const mcl3dl_hip_ctx* c) -> double { return c->grid_build_ms[0]; } },
@@ -105,6 +131,12 @@ int mcl3dl_hip_get_option(mcl3dl_hip_ctx* ctx, const char* name, double* value)
     return -1;
   if (option_get(ctx->opt, name, value))
     return 0;
+  for (const Switch& s : kSwitches)
+    if (strcmp(s.name, name) == 0)
+    {
+      *value = ctx->opt.*s.field;
+      return 0;
+    }
   for (const Diagnostic& d : kDiagnostics)
     if (strcmp(d.name, name) == 0)
     {

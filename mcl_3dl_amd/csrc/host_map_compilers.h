@@ -724,6 +724,8 @@ int build_cand_grid_at(mcl3dl_hip_ctx* ctx, double voxel_ratio, uint32_t cap = 4
     ctx->cand_parts = cap;
     g.ovf_bytes32 = bytes32(64ull * (n_ovf ? n_ovf : 1));
     g.ti_empty = static_cast<uint32_t>(n_table);
+    g.table_bytes32 = bytes32(sizeof(int) * (static_cast<unsigned long long>(n_table) + 1));
+    g.common_map = rec_common_map(g);
     ctx->footprint[5] = sizeof(int) * n_table;
     ctx->footprint[6] = rec_bytes * static_cast<size_t>(n_vox);
     ctx->footprint[7] = 64ull * n_ovf;
@@ -911,6 +913,7 @@ int compact_overflow(mcl3dl_hip_ctx* ctx)
   ctx->cand_ovf_leaked = 0;
   ctx->rg.ovf = ctx->cand_ovf.as<float4>();
   ctx->rg.ovf_bytes32 = bytes32(64ull * (live ? live : 1));
+  ctx->rg.common_map = rec_common_map(ctx->rg);
   ctx->footprint[7] = 64ull * live;
   ctx->cand_stats[6] = live;
   ++ctx->cand_ovf_compactions;
@@ -1097,6 +1100,7 @@ int update_cand_grid(mcl3dl_hip_ctx* ctx, size_t n_base, const std::vector<float
   ctx->rg.off32_ok = (rec_bytes * 512 * n_bricks < (1ull << 32)) ? 1 : 0;
   ctx->rg.rec_bytes32 = bytes32(rec_bytes * 512 * n_bricks);
   ctx->rg.ovf_bytes32 = bytes32(64ull * (ctx->cand_n_ovf ? ctx->cand_n_ovf : 1));
+  ctx->rg.common_map = rec_common_map(ctx->rg);
   ctx->footprint[6] = rec_bytes * 512 * n_bricks;
   ctx->footprint[7] = 64ull * ctx->cand_n_ovf;
   ctx->cand_stats[0] = n_bricks;

@@ -313,6 +313,22 @@ bool lik_defer_active(const mcl3dl_hip_ctx* ctx)
   return with_cand > 0 && over4 / with_cand > LIK_DEFER_MIN_FRAC;
 }
 
+// the tiled kernel's pose loop specialised for the common map (RecGrid::common_map): taken by the deferred form when the map
+// is one, the parameters let `matched` follow from the radius test, and nobody switched it off
+bool lik_tiled_fast_active(const mcl3dl_hip_ctx* ctx, const LikParams& p)
+{
+  return ctx->opt.lik_tiled_fast != 0 && ctx->rg.common_map && lik_defer_active(ctx) && lik_coop_active(ctx) &&
+         lik_match_from_radius(p.match_dist_min, p.r2, p.match_dist_flat);
+}
+
+// the record grid as a launch of the tiled kernel gets it: common_map says which pose loop the launch runs
+RecGrid tiled_rec_grid(const mcl3dl_hip_ctx* ctx, const LikParams& p)
+{
+  RecGrid rg = ctx->rg;
+  rg.common_map = lik_tiled_fast_active(ctx, p) ? 1 : 0;
+  return rg;
+}
+
 // hand-off words + error word of the in-kernel chain for n_p particles and n_tiles tiles; *tag0 = tag of tile 0
 int ensure_chain(mcl3dl_hip_ctx* ctx, size_t n_p, int n_tiles, uint32_t* tag0)
 {
@@ -797,7 +813,7 @@ Interleave merged_args(const MeasureCall& c, long long n_beam, long long n_other
   a->pose7 = c.d_pose;
   a->n_p = c.np;
   a->g = ctx->lg;
-  a->rg = ctx->rg;
+  a->rg = tiled_rec_grid(ctx, c.lp);  // (the per-particle kernels ignore common_map)
   a->prm = c.lp;
   a->scan_beam = ctx->scan_beam.as<float4>();
   a->n_b = static_cast<int>(ctx->n_b);
@@ -888,8 +904,8 @@ void launch_tiled(const MeasureCall& c, const float4* t_scan, int t_ns, int t_ti
       constexpr int G = decltype(g)::value;
       constexpr int MINW = G == 32 ? 4 : 8;  // G = 32: 33 KB of LDS per work-group, 4 wavefronts per SIMD at most
       hipLaunchKernelGGL((likelihood_tiled_kernel<G, decltype(mode)::value, MINW, decltype(coop)::value, decltype(defer)::value>), dim3(static_cast<unsigned>(t_blocks)),
-                         dim3(256), 0, ctx->stream, c.d_pose, c.np, t_scan, t_ns, t_tiles, pl.n_groups, ctx->lg, ctx->rg, c.lp,
-                         t_psum, t_pcnt, t_perm, t_terms, STRICT_SKEW4);
+                         dim3(256), 0, ctx->stream, c.d_pose, c.np, t_scan, t_ns, t_tiles, pl.n_groups, ctx->lg, tiled_rec_grid(ctx, c.lp),
+                         c.lp, t_psum, t_pcnt, t_perm, t_terms, STRICT_SKEW4);
     });
   });
 }
@@ -1028,7 +1044,8 @@ int launch_chain(const MeasureCall& c)
     dispatch_int<4, 8, 16>(pl.group_size, [&](auto g) {
       dispatch_form(pl, [&](auto mode, auto coop, auto defer) {
         hipLaunchKernelGGL((likelihood_tiled_kernel<decltype(g)::value, decltype(mode)::value, 8, decltype(coop)::value, decltype(defer)::value, true>),
-                           grid, dim3(256), 0, ctx->stream, c.d_pose, c.np, c.scan, c.ns, pl.n_tiles, pl.n_groups, ctx->lg, ctx->rg, c.lp,
+                           grid, dim3(256), 0, ctx->stream, c.d_pose, c.np, c.scan, c.ns, pl.n_tiles, pl.n_groups, ctx->lg,
+                           tiled_rec_grid(ctx, c.lp), c.lp,
                            static_cast<double*>(nullptr), static_cast<unsigned*>(nullptr), static_cast<const uint32_t*>(nullptr),
                            static_cast<float*>(nullptr), 0, lc);
       });

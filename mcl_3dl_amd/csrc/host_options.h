@@ -5,6 +5,7 @@
 // flags, the counters) is state and stays in the context. The thresholds nobody needs to move are the constants below.
 #pragma once
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,6 +29,16 @@ constexpr long long BEAM_PREPARE_MIN_RAYS = 32768;  // launches of at least this
 // strict_order = 3: the four-tile form up to this many particles (profiles/r05r_chain_multi.txt: slower from 2048)
 constexpr int CHAIN_MULTI_MAX = 1536;
 
+// `matched` of a likelihood evaluation follows from the radius test alone — every d2 < r2 gives dist = r - max(RN(sqrt(d2)), flat)
+// >= 0 — when flat does not exceed r and the root of r2 = float(double(r) * r) rounds back to r: the root is monotone in d2, so
+// RN(sqrt(d2)) <= RN(sqrt(r2)) = r. A NaN among the three fails a comparison. The tiled kernel's specialised pose loop then takes
+// `matched` from the exec mask of its sqrt block instead of comparing dist with 0 (likelihood_kernels.h: eval_coop_first<true>);
+// tests/cpp/match_exec_check.cpp walks every float d2 below r2.
+inline bool lik_match_from_radius(float r, float r2, float flat)
+{
+  return flat <= r && sqrtf(r2) == r;
+}
+
 // ---- what the caller sets ------------------------------------------------------------------------------------------------
 struct Options
 {
@@ -42,6 +53,10 @@ struct Options
   int lik_tiled_min = 1024;  // scans of at least this many points take the tiled kernel
   int lik_group = 0;       // particles per work-group of the tiled kernel: 0 = chosen per launch, or 4 / 8 / 16 / 32
   int lik_coop = 1;        // tiled kernel: 1 = quad-cooperative record fetch + VALU-trimmed evaluation (same results)
+  // tiled kernel with deferred overflow rounds: -1 = the pose loop specialised for the common map where the map and the
+  // parameters allow it (host_measure.h:lik_tiled_fast_active), 0 = never. Same bits either way: a switch for A/B runs and for the
+  // tests that hold one loop against the other, kept beside the table (api_support.inl:kSwitches), not a row of it
+  int lik_tiled_fast = -1;
   int pf_fused = 1;        // 1 = pf::measure as ONE kernel up to PF_FUSED_MAX_PARTICLES particles on one GPU (same bits, two launches
                            // fewer)
   // 1 = add the likelihood terms AND the weights in the reference's float order (single GPU; bit-identical results);

@@ -141,12 +141,14 @@ __device__ inline int floor_to_int(float x)
 // the grid (a non-finite coordinate saturates to a voxel outside the grid, or for NaN lands in voxel 0 and yields NaN
 // distances: no match either way). 32-bit index arithmetic (the dense brick table has < 2^31 entries, there are <= 2^22
 // bricks: build_cand_grid) with 24-bit multiplies where build_cand_grid found every factor below 2^24.
+// FAST: the caller knows that it did (RecGrid::common_map) — no test of a launch constant per evaluation.
+template <bool FAST = false>
 __device__ inline bool rec_locate(const RecGrid& g, float qx, float qy, float qz, uint32_t& ti, uint32_t& sub)
 {
   const int vx = floor_to_int((qx - g.ox) * g.inv_ex);
   const int vy = floor_to_int((qy - g.oy) * g.inv_ey);
   const int vz = floor_to_int((qz - g.oz) * g.inv_ez);
-  if (g.mul24_ok)
+  if (FAST || g.mul24_ok)
     ti = __umul24(static_cast<uint32_t>(vz >> 3), static_cast<uint32_t>(g.nbx * g.nby)) +
          __umul24(static_cast<uint32_t>(vy >> 3), static_cast<uint32_t>(g.nbx)) + static_cast<uint32_t>(vx >> 3);
   else
@@ -284,11 +286,13 @@ constexpr unsigned long long QUAD_LANE0_MASK = 0x1111111111111111ull;
 // returns to every lane the minimum over the four candidates of ITS record. w[e] = the w word of the part this lane read
 // of record e (part 0's w = count, part 1's w = first overflow record). Every lane of the wavefront must be active (DPP
 // reads 0 from an inactive lane); a lane without a record passes any valid index and ignores the answer.
+// FAST: `recs` is known to be below 4 GB (RecGrid::common_map), the 64-bit path is not compiled in.
+template <bool FAST = false>
 __device__ inline float quad_round(const float4* recs, uint32_t bytes32, uint32_t rec_index, float qx, float qy, float qz,
                                    int j, uint32_t (&w)[4])
 {
   float4 R0, R1, R2, R3;
-  if (bytes32)
+  if (FAST || bytes32)
   {
     // array below 4 GB: buffer loads — the (uniform) base sits in a scalar resource descriptor and the lane supplies a
     // 32-bit byte offset: one v_add_u32 with a DPP operand per load, no 64-bit address arithmetic. An offset past
@@ -300,6 +304,10 @@ __device__ inline float quad_round(const float4* recs, uint32_t bytes32, uint32_
     R1 = buffer_load_f4(rs, quad_u<QUAD_BCAST1>(mine) + part);
     R2 = buffer_load_f4(rs, quad_u<QUAD_BCAST2>(mine) + part);
     R3 = buffer_load_f4(rs, quad_u<QUAD_BCAST3>(mine) + part);
+    // (the general form ends a basic block here, which keeps the four loads together; without one the scheduler moves the first
+    // subtractions — and the wait for the first record — in front of the last two loads: two memory latencies per round)
+    if constexpr (FAST)
+      __builtin_amdgcn_sched_barrier(0);
   }
   else
   {
@@ -817,6 +825,12 @@ __device__ inline unsigned long long chain_pack(uint32_t value, uint32_t tag)
   return (static_cast<unsigned long long>(tag) << 32) | value;
 }
 
+template <bool B>
+struct BoolConstant
+{
+  static constexpr bool value = B;
+};
+
 // ---- deferred overflow rounds (tiled kernel, packed 64-byte records) ------------------------------------------------
 // On a map of voxel-filter centroids a quarter of the voxels hold more than four candidates. A wavefront runs an overflow
 // round as soon as ONE of its 64 evaluations needs it — practically always — with a quarter of its lanes doing useful work
@@ -839,15 +853,37 @@ struct DeferQueue
 // record's packed word in `mine` instead of running the overflow rounds.
 // over_m = the wavefront's lanes with `over` as a 64-bit mask, built from compare MASKS with scalar operations: a ballot of a
 // combined boolean costs a v_cndmask + v_cmp round trip through a VGPR per use (two uses per evaluation: four of 159 instructions).
+// FAST (RecGrid::common_map as the launcher left it: host_measure.h:lik_tiled_fast_active): the properties of the map that the
+// general form tests per evaluation are constants — 24-bit multiplies, every array behind a buffer descriptor with a 32-bit
+// offset, the brick table included — and `matched` IS the set of lanes that pass the radius test (the host has checked that
+// their dist cannot be negative), so the term needs no compare with 0 and no select: what is returned for a lane with `over`
+// is its best-so-far, the value the tiled kernel parks in the lane's term slot, and matched_m is that set as a mask.
+template <bool FAST = false>
 __device__ inline float eval_coop_first(const RecGrid& rg, const LikParams& prm, const Vec3f pos, const Quat rot, const float4 v,
                                         bool have_point, int lane, bool& matched, bool& over, float& best, uint32_t& mine,
-                                        unsigned long long& over_m)
+                                        unsigned long long& over_m, unsigned long long* matched_m = nullptr)
 {
   const Vec3f tp = vadd(qrot_trim(rot, Vec3f{ v.x, v.y, v.z }), pos);
   const float qx = tp.x * prm.wx, qy = tp.y * prm.wy, qz = tp.z * prm.wz;
   uint32_t ti, sub;
-  const bool inside = rec_locate(rg, qx, qy, qz, ti, sub) && have_point;
-  const int b = rg.brick_table[inside ? ti : rg.ti_empty];
+  const bool inside = rec_locate<FAST>(rg, qx, qy, qz, ti, sub) && have_point;
+  int b;
+  if constexpr (FAST)
+  {
+    // (brick 0 is a brick: a lane without a voxel must read the table's extra entry, not rely on the zeros of a range miss)
+    // A descriptor with a stride of four bytes takes the entry's INDEX (idxen): no shift and no 64-bit address arithmetic per
+    // evaluation. The compiler has no builtin for an indexed load, hence the instruction itself with its own wait — the general
+    // form waits for the entry at the same place. Words of the descriptor: base, base >> 32 | stride << 16, size, flags as
+    // __builtin_amdgcn_make_buffer_rsrc sets them for the records. Every index a lane forms is inside the table (ti of a voxel
+    // inside the grid, or ti_empty); the size is the table's bytes, under either reading of a strided descriptor's size no
+    // narrower than the table, and what lies beyond it reads as zero instead of faulting.
+    const unsigned long long base = reinterpret_cast<unsigned long long>(rg.brick_table);
+    const u32x4 tb = { static_cast<uint32_t>(base), (static_cast<uint32_t>(base >> 32) & 0xffffu) | (4u << 16), rg.table_bytes32,
+                       0x00020000u };
+    asm volatile("buffer_load_dword %0, %1, %2, 0 idxen\n\ts_waitcnt vmcnt(0)" : "=v"(b) : "v"(inside ? ti : rg.ti_empty), "s"(tb) : "memory");
+  }
+  else
+    b = rg.brick_table[inside ? ti : rg.ti_empty];
   const bool valid = b >= 0;
   float dist = -1.0f;
   over = false;
@@ -857,10 +893,16 @@ __device__ inline float eval_coop_first(const RecGrid& rg, const LikParams& prm,
   const unsigned long long valid_m = __builtin_amdgcn_ballot_w64(valid);  // (straight from the compare)
   if (valid_m != 0ull)
   {
-    const uint32_t rec = (static_cast<uint32_t>(b) << 9) | sub;
-    const uint32_t vrec = rg.rec_bytes32 ? rec : (valid ? rec : 0u);
+    // (FAST: the empty asm statements keep `sub`, the index and quad_round's << 6 the seven instructions they are in the general
+    // form; left alone the compiler spreads the shifts over the fields and needs eight)
+    if constexpr (FAST)
+      asm("" : "+v"(sub));
+    uint32_t rec = (static_cast<uint32_t>(b) << 9) | sub;
+    if constexpr (FAST)
+      asm("" : "+v"(rec));
+    const uint32_t vrec = (FAST || rg.rec_bytes32) ? rec : (valid ? rec : 0u);
     uint32_t w[4];
-    best = quad_round(rg.rec, rg.rec_bytes32, vrec, qx, qy, qz, lane & 3, w);
+    best = quad_round<FAST>(rg.rec, rg.rec_bytes32, vrec, qx, qy, qz, lane & 3, w);
     mine = own_word(w, lane & 3);
     over_m = valid_m & lanes_gt_u32(mine, rg.over_thr);
     // bounded records (RecGrid::bound_step): no overflow candidate is nearer than the voxel's skip bound to ANY query inside
@@ -874,11 +916,27 @@ __device__ inline float eval_coop_first(const RecGrid& rg, const LikParams& prm,
       over_m &= __builtin_amdgcn_fcmpf(best, rec_bound2(rg, mine), 2 /* FCMP_OGT: false for a NaN, like `>` */);
     }
     over = __builtin_amdgcn_inverse_ballot_w64(over_m);
+    if constexpr (FAST)
+    {
+      const unsigned long long in_m = valid_m & ~over_m & __builtin_amdgcn_fcmpf(best, prm.r2, 4 /* FCMP_OLT */);
+      float out = over ? best : 0.0f * prm.match_weight;
+      if (__builtin_amdgcn_inverse_ballot_w64(in_m))
+        out = lik_dist(prm, sqrt_in_radius(best)) * prm.match_weight;
+      *matched_m = in_m;
+      matched = __builtin_amdgcn_inverse_ballot_w64(in_m);
+      return out;
+    }
     if (valid && !over && best < prm.r2)
     {
       const float s = sqrt_in_radius(best);
       dist = lik_dist(prm, s);
     }
+  }
+  if constexpr (FAST)
+  {
+    *matched_m = 0ull;
+    matched = false;
+    return 0.0f * prm.match_weight;
   }
   matched = !(dist < 0.0f);
   return lik_term(prm, dist, matched);
@@ -886,7 +944,9 @@ __device__ inline float eval_coop_first(const RecGrid& rg, const LikParams& prm,
 
 // One dense overflow round for entries [base, base + n) of this wavefront's queue, n <= 64 (all lanes arrive; lane l takes
 // entry base + l). s_term / s_cnt rows are the tiled kernel's: the parked best is replaced by the term, a match is counted.
-template <int G, int LD>
+// FAST: the arithmetic of eval_coop_first<true> (the overflow records behind their descriptor unconditionally, the match from
+// the radius test).
+template <bool FAST = false, int G, int LD>
 __device__ inline void defer_drain(const RecGrid& rg, const LikParams& prm, const float (&s_pose)[G][8], float (&s_term)[G][LD],
                                    unsigned (&s_cnt)[G][4], const DeferQueue& q, int wave, int lane, uint32_t base, uint32_t n,
                                    const float4 v)
@@ -910,8 +970,19 @@ __device__ inline void defer_drain(const RecGrid& rg, const LikParams& prm, cons
   {
     const bool more = r < rounds;
     uint32_t unused[4];
-    const float m = quad_round(rg.ovf, rg.ovf_bytes32, more ? ext + r : 0u, qx, qy, qz, lane & 3, unused);
+    const float m = quad_round<FAST>(rg.ovf, rg.ovf_bytes32, more ? ext + r : 0u, qx, qy, qz, lane & 3, unused);
     best = (more && m < best) ? m : best;
+  }
+  if constexpr (FAST)
+  {
+    if (act)
+    {
+      const bool in = best < prm.r2;
+      s_term[k][t_src] = in ? lik_dist(prm, sqrt_in_radius(best)) * prm.match_weight : 0.0f * prm.match_weight;
+      if (in)
+        atomicAdd(&s_cnt[k][wave], 1u);
+    }
+    return;
   }
   float dist = -1.0f;
   if (act && best < prm.r2)
@@ -960,7 +1031,7 @@ __device__ __forceinline__ void likelihood_tiled_body(const uint32_t block_index
   // (CHAIN: rows padded to 260 floats — the chain's lanes read DIFFERENT rows at the same column, 16 bytes at a time: with a
   // row length of 256 they would all hit the same LDS banks)
   constexpr int TERM_LD = CHAIN ? 260 : 256;
-  __shared__ float s_pose[G][8];        // px,py,pz, qx,qy,qz,qw (normalised), valid
+  __shared__ __attribute__((aligned(16))) float s_pose[G][8];  // px,py,pz, qx,qy,qz,qw (normalised), valid
   __shared__ __attribute__((aligned(16))) float s_term[G][TERM_LD];
   __shared__ unsigned s_cnt[G][4];
   // Work-groups are dispatched round-robin over the 8 XCDs (block b runs on XCD b % 8). The tiles of the largest
@@ -1031,54 +1102,88 @@ __device__ __forceinline__ void likelihood_tiled_body(const uint32_t block_index
   if constexpr (COOP && MODE == 2 && DEFER)
   {
     __shared__ DeferQueue s_q;
-    uint32_t qn = 0;  // entries queued by this wavefront (uniform)
-    for (int k = 0; k < n_valid; ++k)
-    {
-      const Vec3f pos = { s_pose[k][0], s_pose[k][1], s_pose[k][2] };
-      const Quat rot = { s_pose[k][3], s_pose[k][4], s_pose[k][5], s_pose[k][6] };
-      bool matched, over;
-      float best;
-      uint32_t mine;
-      unsigned long long om;
-      const float term = eval_coop_first(rg, prm, pos, rot, v, have_point, lane, matched, over, best, mine, om);
-      s_term[k][t] = over ? best : term;
-      const unsigned long long m = __builtin_amdgcn_ballot_w64(matched);
-      if (lane == 0)
-        s_cnt[k][wave] = static_cast<unsigned>(__popcll(m));
-      if (om != 0ull)
+    // the pose loop, in two forms picked ONCE per launch from a uniform flag of the map index: the general one, and the one
+    // in which the properties of the common map are constants (eval_coop_first<true>). Same bits.
+    const auto pose_loop = [&](auto fast) {
+      constexpr bool FAST = decltype(fast)::value;
+      uint32_t qn = 0;  // entries queued by this wavefront (uniform)
+      // FAST: the LDS addresses of the pose, the term slot and the count slot advance by one add per pose instead of being
+      // rebuilt from the loop counter (a move, a shift-or and a shift-add per evaluation)
+      typedef float f32x4 __attribute__((ext_vector_type(4)));
+      typedef __attribute__((address_space(3))) const f32x4 LdsPose;  // (a pose is two aligned 16-byte reads)
+      typedef __attribute__((address_space(3))) float LdsTerm;
+      typedef __attribute__((address_space(3))) unsigned LdsCount;
+      LdsPose* p_pose = (LdsPose*)&s_pose[0][0];
+      LdsTerm* p_term = (LdsTerm*)&s_term[0][t];
+      LdsCount* p_cnt = (LdsCount*)&s_cnt[0][wave];
+      for (int k = 0; k < n_valid; ++k)
       {
-        const uint32_t n_new = static_cast<uint32_t>(__popcll(om));
-        if (qn + n_new > static_cast<uint32_t>(DEFER_QCAP))
+        LdsPose* ps = FAST ? p_pose : (LdsPose*)&s_pose[k][0];
+        const f32x4 pa = ps[0], pb = ps[1];
+        const Vec3f pos = { pa.x, pa.y, pa.z };
+        const Quat rot = { pa.w, pb.x, pb.y, pb.z };
+        bool matched, over;
+        float best;
+        uint32_t mine;
+        unsigned long long om;
+        unsigned long long m;
+        if constexpr (FAST)
         {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          defer_drain(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, 0u, qn, v);
-          qn = 0;
+          *p_term = eval_coop_first<true>(rg, prm, pos, rot, v, have_point, lane, matched, over, best, mine, om, &m);
+          if (lane == 0)
+            *p_cnt = static_cast<unsigned>(__popcll(m));
+          asm volatile("" : "+v"(p_pose), "+v"(p_term), "+v"(p_cnt));
+          p_pose += 2;
+          p_term += TERM_LD;
+          p_cnt += 4;
         }
-        if (over)
+        else
         {
-          const uint32_t slot = qn + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(om >> 32),
-                                                               __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(om), 0u));
-          s_q.word[wave][slot] = mine;
-          s_q.who[wave][slot] = static_cast<uint16_t>((static_cast<uint32_t>(k) << 6) | static_cast<uint32_t>(lane));
+          const float term = eval_coop_first(rg, prm, pos, rot, v, have_point, lane, matched, over, best, mine, om);
+          s_term[k][t] = over ? best : term;
+          m = __builtin_amdgcn_ballot_w64(matched);
+          if (lane == 0)
+            s_cnt[k][wave] = static_cast<unsigned>(__popcll(m));
         }
-        qn += n_new;
-        if (qn >= 64u)
+        if (om != 0ull)
         {
-          // the LAST 64 entries: what stays queued keeps its place
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          defer_drain(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, qn - 64u, 64u, v);
-          qn -= 64u;
+          const uint32_t n_new = static_cast<uint32_t>(__popcll(om));
+          if (qn + n_new > static_cast<uint32_t>(DEFER_QCAP))
+          {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            defer_drain<FAST>(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, 0u, qn, v);
+            qn = 0;
+          }
+          if (over)
+          {
+            const uint32_t slot = qn + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(om >> 32),
+                                                                 __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(om), 0u));
+            s_q.word[wave][slot] = mine;
+            s_q.who[wave][slot] = static_cast<uint16_t>((static_cast<uint32_t>(k) << 6) | static_cast<uint32_t>(lane));
+          }
+          qn += n_new;
+          if (qn >= 64u)
+          {
+            // the LAST 64 entries: what stays queued keeps its place
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            defer_drain<FAST>(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, qn - 64u, 64u, v);
+            qn -= 64u;
+          }
         }
       }
-    }
-    if (qn != 0u)
-    {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      defer_drain(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, 0u, qn, v);
-    }
+      if (qn != 0u)
+      {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        defer_drain<FAST>(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, 0u, qn, v);
+      }
+    };
+    if (rg.common_map)
+      pose_loop(BoolConstant<true>{});
+    else
+      pose_loop(BoolConstant<false>{});
   }
   else if constexpr (COOP && MODE == 2)
   {

@@ -604,6 +604,12 @@ struct RecGrid
   float ox, oy, oz, inv_ex, inv_ey, inv_ez;
   int nvx, nvy, nvz, nbx, nby, nbz;
   int mul24_ok;  // nbx * nby and every brick coordinate < 2^24: the table index can use 24-bit multiplies
+  // the common map: records, overflow records and brick table each below 4 GB, mul24_ok, packed w words, 64-byte records
+  // (rec_common_map below, set wherever the index is built or grows). The tiled kernel then runs a pose loop in which all of
+  // these are compile-time constants (likelihood_kernels.h: FAST); the launcher clears it for a launch that must not take that
+  // loop (option lik_tiled_fast = 0, or parameters for which `matched` does not follow from the radius test: host_measure.h)
+  int common_map;
+  uint32_t table_bytes32;  // size of brick_table (its extra last entry included) in bytes when below 4 GB, else 0
   int off32_ok;  // the record array is smaller than 4 GB: byte offsets fit 32 bits
   uint32_t rec_bytes32, ovf_bytes32;  // size of rec / ovf in bytes when below 4 GB (buffer loads), else 0
   int rec_parts;                      // 16-byte parts (= inline candidates) per voxel record: 4 (64 bytes) or 8 (128 bytes)
@@ -622,6 +628,10 @@ struct RecGrid
   // requests, +39 % L2 misses, 0.2362 against 0.2314 ms; twice as slow at 32 768 particles: profiles/r06g_tiled_levers_ab.txt.)
 };
 
+__host__ __device__ inline int rec_common_map(const RecGrid& g)
+{
+  return (g.rec_bytes32 != 0u && g.ovf_bytes32 != 0u && g.table_bytes32 != 0u && g.mul24_ok && g.packed && g.rec_parts == 4) ? 1 : 0;
+}
 __host__ __device__ inline uint32_t rec_ext_mask(const RecGrid& g)
 {
   return (1u << g.ext_bits) - 1u;
