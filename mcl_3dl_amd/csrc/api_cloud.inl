@@ -145,7 +145,7 @@ int mcl3dl_hip_scan_finish_drawn(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b, co
     return -1;
   if (!ctx->sp_ready)
     return ctx->fail(-5, "no prepared scan: call mcl3dl_hip_scan_begin first");
-  TRY(rng_check_state_ctx(ctx, engine_state));
+  TRY(rng_check_state(ctx, engine_state));
   if (n_b && (!origins || n_o == 0))
     return ctx->fail(-3, "n_b = %zu beam points asked for but no origins given", n_b);
   // sample() returns an empty cloud, drawing nothing, from an empty cloud (point_cloud_uniform_sampler.h:63-64)

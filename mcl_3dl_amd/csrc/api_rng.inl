@@ -11,15 +11,6 @@
 //   mcl3dl_hip_group_resample_apply_drawn       pf::resample's generateNoise per duplicated slot, in slot order (pf.h:216)
 namespace
 {
-int rng_check_state(mcl3dl_hip_group* g, const uint32_t* engine_state)
-{
-  if (!engine_state)
-    return g->fail(-3, "null engine_state");
-  if (*engine_state < 1u || *engine_state > rng::MINSTD_M - 1u)
-    return g->fail(-3, "engine_state %u is outside [1, 2^31 - 2]", *engine_state);
-  return 0;
-}
-
 // DiagonalNoiseGenerator(mean, sigma) for State6DOF; mean6 == null: State6DOF()
 int rng_generator(mcl3dl_hip_group* g, const float* mean6, const float* sigma6, rng::NoiseGen6* gen)
 {
@@ -252,7 +243,7 @@ int mcl3dl_hip_rng_draw_indices(mcl3dl_hip_ctx* ctx, uint64_t range, size_t coun
     return -1;
   if (range < 1 || range > rng::INDEX_MAX_RANGE)
     return ctx->fail(-3, "range %llu is outside [1, 2147483646]", static_cast<unsigned long long>(range));
-  TRY(rng_check_state_ctx(ctx, engine_state));
+  TRY(rng_check_state(ctx, engine_state));
   if (count > 0x7fffffffu)
     return ctx->fail(-3, "count %zu is more than one call draws", count);
   if (count && !out_idx)

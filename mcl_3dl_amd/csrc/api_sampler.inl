@@ -245,7 +245,7 @@ int mcl3dl_hip_rng_draw_weighted(mcl3dl_hip_ctx* ctx, const double* weight, size
     return ctx->fail(-3, "too many points (%zu)", n);
   if (num)
   {
-    TRY(rng_check_state_ctx(ctx, engine_state));
+    TRY(rng_check_state(ctx, engine_state));
     if (!out_idx)
       return ctx->fail(-3, "null out_idx");
     if (n <= num)
@@ -314,7 +314,7 @@ int mcl3dl_hip_scan_finish_drawn_normal(mcl3dl_hip_ctx* ctx, size_t n_s, size_t 
     return -1;
   if (!ctx->sp_ready)
     return ctx->fail(-5, "no prepared scan: call mcl3dl_hip_scan_begin first");
-  TRY(rng_check_state_ctx(ctx, engine_state));
+  TRY(rng_check_state(ctx, engine_state));
   if (n_b && (!origins || n_o == 0))
     return ctx->fail(-3, "n_b = %zu beam points asked for but no origins given", n_b);
   TRY(scan_normal_weights_check(ctx, normal_search_range, fpc_local3, max_weight));

@@ -69,7 +69,7 @@ int mcl3dl_hip_rng_shuffle_prefix(mcl3dl_hip_ctx* ctx, size_t n, size_t m, uint3
     return ctx->fail(-3, "a shuffle of %zu elements is outside [1, 2147483646]", n);
   if (m > n)
     return ctx->fail(-3, "%zu entries of a shuffle of %zu elements asked for", m, n);
-  TRY(rng_check_state_ctx(ctx, engine_state));
+  TRY(rng_check_state(ctx, engine_state));
   if (m && !out_idx)
     return ctx->fail(-3, "null out_idx");
   uint32_t state = *engine_state;

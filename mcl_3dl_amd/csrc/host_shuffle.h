@@ -25,50 +25,41 @@ void shuffle_prefix_host(uint64_t n, uint64_t m, uint32_t state_in, std::vector<
 // the WHOLE shuffle. Nothing is synchronised behind the last launch.
 int shuffle_prefix_device(mcl3dl_hip_ctx* ctx, uint64_t n, uint64_t m, uint32_t state_in, uint32_t* state_out)
 {
-  constexpr uint64_t PER_GROUP = static_cast<uint64_t>(rng::GROUP_THREADS) * rng::ATTEMPTS_PER_LANE;
   TRY(rng_device_table(ctx));
   const uint32_t* d_table = ctx->rng_table.as<uint32_t>();
   TRY(ensure(ctx, ctx->sh_target, sizeof(uint32_t) * n));
   TRY(ensure(ctx, ctx->sh_idx, sizeof(uint32_t) * m));
   const unsigned long long n_ull = n;
+  const rng::DoubtPolicy policy{ n_ull };
   uint64_t n_att = 0, accepted = 0;
   uint32_t n_rejected = 0;
   for (int round = 0;; ++round)
   {
     if (round >= 64)
       return ctx->fail(-4, "internal: the random stream did not yield the %llu steps of the shuffle in 64 rounds", n_ull - 1);
-    n_att = rng::shuffle_attempt_budget(n_att, accepted, n);
-    const uint64_t n_groups = (n_att + PER_GROUP - 1) / PER_GROUP;
+    n_att = policy.budget(n_att, accepted);
+    const uint64_t n_groups = rng_groups(n_att);
     if (n_att > 0xffffffffull || n_groups > 0x7fffffffull)
       return ctx->fail(-3, "a shuffle of %llu elements takes more attempts than the device path numbers in 32 bits", n_ull);
-    // counts[0 .. n_groups) | [n_groups] = 0, the total behind the scan | [n_groups + 1, + 2] = the resolve kernel's result
-    TRY(ensure(ctx, ctx->rng_counts, sizeof(uint32_t) * (n_groups + 3)));
-    TRY(ensure(ctx, ctx->rng_ws, sizeof(uint32_t) * (n_groups / 1023 + 8)));
-    uint32_t* d_counts = ctx->rng_counts.as<uint32_t>();
-    HIP_TRY(hipMemsetAsync(d_counts + n_groups, 0, sizeof(uint32_t) * 3, ctx->stream));
-    const dim3 grid(static_cast<unsigned>(n_groups)), block(rng::GROUP_THREADS);
-    hipLaunchKernelGGL(rng::shuffle_doubt_count_kernel, grid, block, 0, ctx->stream, state_in, d_table, n_ull,
-                       static_cast<unsigned long long>(n_att), d_counts);
-    HIP_TRY(hipGetLastError());
-    TRY(device_exclusive_scan_ws(ctx, d_counts, static_cast<long long>(n_groups) + 1, ctx->rng_ws.as<uint32_t>()));
+    // two tail words behind the total: the resolve kernel's result
     uint32_t n_doubt = 0;
-    TRY(d2h(ctx, &n_doubt, d_counts + n_groups, sizeof(n_doubt)));
-    TRY(sync_stream(ctx));
+    TRY(rng_count_scan(ctx, state_in, policy, n_att, 2, &n_doubt));
+    uint32_t* d_result = ctx->rng_counts.as<uint32_t>() + n_groups + 1;
     n_rejected = 0;
     if (n_doubt == 0)
       break;  // every attempt is accepted wherever it arrives, and the budget is at least n - 1
     TRY(ensure(ctx, ctx->sh_doubt_t, sizeof(uint32_t) * n_doubt));
     TRY(ensure(ctx, ctx->sh_doubt_v, sizeof(uint32_t) * n_doubt));
     TRY(ensure(ctx, ctx->sh_rejected, sizeof(uint32_t) * n_doubt));
-    hipLaunchKernelGGL(rng::shuffle_doubt_emit_kernel, grid, block, 0, ctx->stream, state_in, d_table, n_ull,
-                       static_cast<unsigned long long>(n_att), d_counts, n_doubt, ctx->sh_doubt_t.as<uint32_t>(),
-                       ctx->sh_doubt_v.as<uint32_t>());
+    // (the emit kernel's result word is not used: the resolve kernel behind it overwrites it)
+    TRY(rng_emit(ctx, state_in, policy, n_att, 0, n_doubt,
+                 rng::DoubtSink{ ctx->sh_doubt_t.as<uint32_t>(), ctx->sh_doubt_v.as<uint32_t>() }, d_result));
     hipLaunchKernelGGL(rng::shuffle_resolve_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->sh_doubt_t.as<uint32_t>(),
                        ctx->sh_doubt_v.as<uint32_t>(), n_doubt, n_ull, static_cast<unsigned long long>(n_att),
-                       ctx->sh_rejected.as<uint32_t>(), d_counts + n_groups + 1);
+                       ctx->sh_rejected.as<uint32_t>(), d_result);
     HIP_TRY(hipGetLastError());
     uint32_t home[2] = { 0u, 0u };  // {rejections among the steps, 1 = the attempts hold every step}
-    TRY(d2h(ctx, home, d_counts + n_groups + 1, sizeof(home)));
+    TRY(d2h(ctx, home, d_result, sizeof(home)));
     TRY(sync_stream(ctx));
     if (home[0] > n_doubt)
       return ctx->fail(-4, "internal: %u rejections among %u doubtful attempts", home[0], n_doubt);
@@ -78,7 +69,7 @@ int shuffle_prefix_device(mcl3dl_hip_ctx* ctx, uint64_t n, uint64_t m, uint32_t 
     accepted = n_att - n_rejected;
   }
   const uint64_t n_used = (n - 1) + n_rejected;
-  hipLaunchKernelGGL(rng::shuffle_targets_kernel, dim3(static_cast<unsigned>((n_used + PER_GROUP - 1) / PER_GROUP)),
+  hipLaunchKernelGGL(rng::shuffle_targets_kernel, dim3(static_cast<unsigned>(rng_groups(n_used))),
                      dim3(rng::GROUP_THREADS), 0, ctx->stream, state_in, d_table, n_ull, static_cast<unsigned long long>(n_used),
                      ctx->sh_rejected.as<uint32_t>(), n_rejected, ctx->sh_target.as<uint32_t>());
   HIP_TRY(hipGetLastError());

@@ -21,13 +21,18 @@
 //   cloud_keys.h          the sort keys (VoxelGrid leaf index, Morton key, range key)
 //   global_loc_kernels.h  global localisation: the blocked-above test over the VoxelGrid centroids of the base map, and the seeding
 //                         of points x div_yaw particles into a shard of resident particles
-//   rng_kernels.h         the filter's noise from the reference's engine: polar-method attempts counted, scanned and emitted in
-//                         stream order (rng_polar.h: the restatement both the device and the CPU emulation compile)
-//   rng_index_kernels.h   the uniform sampler's index draws from the same engine (rng_index.h: the restatement)
+//   rng_stream_kernels.h  the attempt stream the polar, index and shuffle draws share (rng_stream.h: the lane walk and the
+//                         placement loop both the device and the CPU emulations compile): one count kernel and one emit kernel
+//                         over an attempt policy and a sink, wavefront and work-group ranks
+//   rng_kernels.h         the filter's noise from the reference's engine: the polar sink, the noise rows, the odometry noise
+//                         (rng_polar.h: the restatement and the polar policy)
+//   rng_index_kernels.h   the uniform sampler's index draws from the same engine: the one-work-group form and the index sink
+//                         (rng_index.h: the restatement and the index policy)
 //   rng_weighted_kernels.h  the normal-weighted sampler's draw: cumulative weights as the serial double recurrence (double_chain.h),
 //                         draws, lower_bound, duplicate rejection and the unordered_set's iteration order (rng_weighted.h)
-//   rng_shuffle_kernels.h  std::shuffle(iota(n), engine_) of the sampled covariance: doubtful attempts resolved by one wavefront, every
-//                         step's target, one chain walk per entry over the sorted (target, step) pairs (rng_shuffle.h: the restatement)
+//   rng_shuffle_kernels.h  std::shuffle(iota(n), engine_) of the sampled covariance: the doubt sink, doubtful attempts resolved by one
+//                         wavefront, every step's target, one chain walk per entry over the sorted (target, step) pairs
+//                         (rng_shuffle.h: the restatement and the doubt policy)
 //   stage_kernels.h       head and tail of a host-buffer update as one launch each: scan ordering + pose / weight take-over
 //                         from page-locked host memory; lik_finalize + pf::measure with the results written back there
 //
@@ -49,6 +54,7 @@
 #include "grid_kernels.h"
 #include "global_loc_kernels.h"
 #include "sampler_kernels.h"
+#include "rng_stream_kernels.h"
 #include "rng_kernels.h"
 #include "rng_index_kernels.h"
 #include "rng_weighted_kernels.h"

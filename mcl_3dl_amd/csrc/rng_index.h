@@ -1,5 +1,6 @@
 // rng_index.h — the reference's uniform sampler restated so that every position of its stream can be evaluated at once
-// (rng_index_kernels.h runs it on the device, tests/cpp/rng_index_emul.cpp on the CPU with g++: no HIP type appears here).
+// (rng_stream.h walks it, rng_index_kernels.h holds what the device adds, tests/cpp/rng_index_emul.cpp replays it on the CPU with
+// g++: no HIP type appears here).
 //
 // PINNED TO libstdc++, as rng_polar.h is. PointCloudUniformSampler::sample (point_cloud_uniform_sampler.h:66-71) draws
 // std::uniform_int_distribution<size_t>(0, n - 1)(engine) per point, the engine being std::default_random_engine = minstd_rand0:
@@ -72,5 +73,20 @@ inline uint64_t index_attempt_budget(uint64_t k_remaining, const IndexRange& r)
   const double k = static_cast<double>(k_remaining);
   return static_cast<uint64_t>(std::ceil(k / p)) + static_cast<uint64_t>(std::ceil(3.0 * std::sqrt(k * (1.0 - p)) / p));
 }
+
+// rng_stream.h's attempt policy of this stream: one engine call per attempt; the output is also the engine state behind it
+struct IndexPolicy
+{
+  IndexRange r;
+  static constexpr int CALLS = 1;
+  using Kept = uint32_t;
+  RNG_HD bool judge(const uint32_t* v, Kept* k) const
+  {
+    *k = v[0];
+    return index_accepted(r, v[0]);
+  }
+  RNG_HD static uint32_t state(const Kept& k) { return k; }
+  uint64_t budget(uint64_t k_remaining) const { return index_attempt_budget(k_remaining, r); }
+};
 }  // namespace rng
 }  // namespace mcl3dl

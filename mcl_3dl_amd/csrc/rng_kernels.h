@@ -1,20 +1,15 @@
-// rng_kernels.h — the reference's noise draws on the device (rng_polar.h holds the restatement; api_rng.inl the host rounds):
+// rng_kernels.h — the reference's noise draws on the device (rng_polar.h holds the restatement and the attempt policy;
+// rng_stream_kernels.h the count and emit kernels, instantiated with PolarPolicy and the sink below; host_rng.h the rounds):
 //
-//   rng_polar_count_kernel   one lane per run of E consecutive attempts (one jump, then 2E engine steps); accept flags by
-//                            ballot, ONE count per work-group
-//   (exclusive scan of the work-group counts: scan_tiles / scan_add_offsets of map_compiler.h, the cloud path's)
-//   rng_polar_emit_kernel    the attempts again; rank of an accepted attempt = work-group offset + wavefront offset + mbcnt of
-//                            the ballots; writes the values whose rank lies in the caller's window, and the engine state behind
-//                            the K-th accepted attempt
+//   PolarSink<PAIRS>         what stream_emit_kernel writes for an accepted polar attempt: the values whose rank lies in the
+//                            caller's window
 //   rng_noise_state_kernel   one lane per particle: DiagonalNoiseGenerator::operator() (value sigma + mean, zero sigmas skipped)
 //                            and State6DOF::generateNoise into the 13-float rows add_noise_kernel / resample_apply_kernel read
 //   rng_odom_noise_kernel    update_noise_func's four values per particle, scaled, in set_odom_noise's storage order
-//
-// No work-group waits on another: the unknown length of the stream is handled by rounds on the host.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "rng_polar.h"
+#include "rng_stream_kernels.h"
 
 #pragma clang fp contract(off)
 
@@ -22,122 +17,26 @@ namespace mcl3dl
 {
 namespace rng
 {
-// the E attempts of this lane, from the state 2 E lane engine calls behind x0; attempts at or beyond n_att are not accepted
-struct LaneAttempts
-{
-  float x[ATTEMPTS_PER_LANE], y[ATTEMPTS_PER_LANE], r2[ATTEMPTS_PER_LANE];
-  uint32_t state[ATTEMPTS_PER_LANE];  // the engine state behind each attempt's second draw
-  uint32_t accepted;                  // bit e: attempt e
-};
-
-__device__ inline uint32_t lane_accept_mask(uint32_t x0, const uint32_t* __restrict__ table, unsigned long long n_att,
-                                            unsigned long long lane, LaneAttempts* keep)
-{
-  constexpr int E = ATTEMPTS_PER_LANE;
-  const unsigned long long t0 = lane * E;
-  uint32_t mask = 0u;
-  if (t0 >= n_att)
-    return 0u;
-  uint32_t x = minstd_jump(x0, 2ull * t0, table);
-#pragma unroll
-  for (int e = 0; e < E; ++e)
-  {
-    const uint32_t v1 = minstd_next(x);
-    x = minstd_next(v1);
-    const Attempt a = polar_attempt(v1, x);
-    const bool ok = a.accepted && t0 + e < n_att;
-    mask |= ok ? (1u << e) : 0u;
-    if (keep)
-    {
-      keep->x[e] = a.x;
-      keep->y[e] = a.y;
-      keep->r2[e] = a.r2;
-      keep->state[e] = x;
-    }
-  }
-  return mask;
-}
-
-__global__ __launch_bounds__(GROUP_THREADS) void rng_polar_count_kernel(uint32_t x0, const uint32_t* __restrict__ table,
-                                                                        unsigned long long n_att,
-                                                                        uint32_t* __restrict__ group_count)
-{
-  constexpr int E = ATTEMPTS_PER_LANE;
-  __shared__ uint32_t s_wave[GROUP_THREADS / 64];
-  const unsigned long long lane = static_cast<unsigned long long>(blockIdx.x) * GROUP_THREADS + threadIdx.x;
-  const uint32_t mask = lane_accept_mask(x0, table, n_att, lane, nullptr);
-  uint32_t wave_total = 0u;
-#pragma unroll
-  for (int e = 0; e < E; ++e)
-    wave_total += static_cast<uint32_t>(__popcll(__ballot((mask >> e) & 1u)));
-  if ((threadIdx.x & 63) == 0)
-    s_wave[threadIdx.x >> 6] = wave_total;
-  __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    uint32_t s = 0u;
-#pragma unroll
-    for (int w = 0; w < GROUP_THREADS / 64; ++w)
-      s += s_wave[w];
-    group_count[blockIdx.x] = s;
-  }
-}
-
-// group_offset: the exclusive scan of group_count. rank_base: accepted attempts of earlier rounds. Ranks in [k_begin, k_end)
-// (and below k_total) are written to values[rank - k_begin] (PAIRS: values[2 (rank - k_begin)] = y mult, + 1 = x mult). The
-// lane holding rank k_total - 1 writes the engine state behind that attempt to *result (0 = not in this round: no state is 0).
+// Ranks in [k_begin, k_end) are written to values[rank - k_begin] (PAIRS: values[2 (rank - k_begin)] = y mult, + 1 = x mult).
 template <bool PAIRS>
-__global__ __launch_bounds__(GROUP_THREADS) void rng_polar_emit_kernel(uint32_t x0, const uint32_t* __restrict__ table,
-                                                                       unsigned long long n_att,
-                                                                       const uint32_t* __restrict__ group_offset,
-                                                                       unsigned long long rank_base, unsigned long long k_total,
-                                                                       unsigned long long k_begin, unsigned long long k_end,
-                                                                       float* __restrict__ values, uint32_t* __restrict__ result)
+struct PolarSink
 {
-  constexpr int E = ATTEMPTS_PER_LANE;
-  __shared__ uint32_t s_wave[GROUP_THREADS / 64];
-  const unsigned long long lane = static_cast<unsigned long long>(blockIdx.x) * GROUP_THREADS + threadIdx.x;
-  LaneAttempts at;
-  const uint32_t mask = lane_accept_mask(x0, table, n_att, lane, &at);
-  // accepted attempts of the lower lanes of this wavefront (all their E attempts come first), and of the whole wavefront
-  uint32_t before = 0u, wave_total = 0u;
-#pragma unroll
-  for (int e = 0; e < E; ++e)
+  unsigned long long k_begin, k_end;
+  float* __restrict__ values;
+  __device__ void operator()(unsigned long long rank, unsigned long long, const PolarPolicy::Kept& k) const
   {
-    const unsigned long long b = __ballot((mask >> e) & 1u);
-    before += __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(b >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(b), 0u));
-    wave_total += static_cast<uint32_t>(__popcll(b));
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0)
-    s_wave[wave] = wave_total;
-  __syncthreads();
-  uint32_t wave_offset = 0u;
-#pragma unroll
-  for (int w = 0; w < GROUP_THREADS / 64; ++w)
-    wave_offset += w < wave ? s_wave[w] : 0u;
-  unsigned long long rank = rank_base + group_offset[blockIdx.x] + wave_offset + before;
-#pragma unroll
-  for (int e = 0; e < E; ++e)
-  {
-    if (!((mask >> e) & 1u))
-      continue;
-    if (rank < k_total && rank >= k_begin && rank < k_end)
+    if (rank < k_begin || rank >= k_end)
+      return;
+    const float mult = polar_mult(k.r2, LogDouble());
+    if (PAIRS)
     {
-      const float mult = polar_mult(at.r2[e], LogDouble());
-      if (PAIRS)
-      {
-        values[2 * (rank - k_begin)] = at.y[e] * mult;
-        values[2 * (rank - k_begin) + 1] = at.x[e] * mult;
-      }
-      else
-        values[rank - k_begin] = at.y[e] * mult;
+      values[2 * (rank - k_begin)] = k.y * mult;
+      values[2 * (rank - k_begin) + 1] = k.x * mult;
     }
-    if (rank + 1 == k_total)
-      *result = at.state[e];
-    ++rank;
+    else
+      values[rank - k_begin] = k.y * mult;
   }
-}
+};
 
 struct NoiseGen6
 {

@@ -1,5 +1,6 @@
 // rng_polar.h — the reference's random stream restated so that every position of it can be evaluated at once
-// (rng_kernels.h runs it on the device, tests/cpp/rng_polar_emul.cpp on the CPU with g++: no HIP type appears here).
+// (rng_stream.h walks it, rng_kernels.h holds what the device adds, tests/cpp/rng_polar_emul.cpp replays it on the CPU with g++:
+// no HIP type appears here).
 //
 // PINNED TO libstdc++, as oracle/_ref is: std::default_random_engine is minstd_rand0 there, x <- 16807 x mod (2^31 - 1),
 // seeded with seed mod (2^31 - 1), 0 -> 1. Another standard library uses another engine; this header does not follow it.
@@ -34,7 +35,7 @@ namespace rng
 {
 constexpr uint32_t MINSTD_M = 2147483647u;  // 2^31 - 1
 constexpr uint32_t MINSTD_A = 16807u;
-constexpr int ATTEMPTS_PER_LANE = 8;        // E of rng_kernels.h: consecutive attempts one lane walks behind its jump
+constexpr int ATTEMPTS_PER_LANE = 8;        // E of rng_stream.h: consecutive attempts one lane walks behind its jump
 constexpr int GROUP_THREADS = 256;
 
 // a b mod (2^31 - 1) for a, b < 2^31 by the Mersenne identity 2^31 = 1: two folds (p < 2^62), one conditional subtract
@@ -139,6 +140,28 @@ inline uint64_t attempt_budget(uint64_t k_remaining)
   const double k = static_cast<double>(k_remaining);
   return static_cast<uint64_t>(std::ceil(k / p)) + static_cast<uint64_t>(std::ceil(3.0 * std::sqrt(k * (1.0 - p)) / p));
 }
+
+// rng_stream.h's attempt policy of this stream: two engine calls per attempt
+struct PolarPolicy
+{
+  static constexpr int CALLS = 2;
+  struct Kept
+  {
+    float x, y, r2;
+    uint32_t state;  // the engine state behind the attempt's second draw
+  };
+  RNG_HD bool judge(const uint32_t* v, Kept* k) const
+  {
+    const Attempt a = polar_attempt(v[0], v[1]);
+    k->x = a.x;
+    k->y = a.y;
+    k->r2 = a.r2;
+    k->state = v[1];
+    return a.accepted;
+  }
+  RNG_HD static uint32_t state(const Kept& k) { return k.state; }
+  uint64_t budget(uint64_t k_remaining) const { return attempt_budget(k_remaining); }
+};
 
 // Quat::setRPY (quat.h:202-215): cos / sin of the float half angles in double, rounded to float (the motion kernels' rule);
 // every product of :211-214 kept, in float, left to right

@@ -107,6 +107,21 @@ inline uint64_t shuffle_attempt_budget(uint64_t evaluated, uint64_t accepted, ui
   return evaluated + static_cast<uint64_t>(k) + static_cast<uint64_t>(std::ceil(d + SHUFFLE_BUDGET_SIGMAS * std::sqrt(d))) + 1u;
 }
 
+// rng_stream.h's attempt policy of the doubtful attempts: "accepted" means doubtful, to be compacted in stream order
+struct DoubtPolicy
+{
+  unsigned long long n;
+  static constexpr int CALLS = 1;
+  using Kept = uint32_t;
+  RNG_HD bool judge(const uint32_t* v, Kept* k) const
+  {
+    *k = v[0];
+    return shuffle_doubtful(v[0], n);
+  }
+  RNG_HD static uint32_t state(const Kept& k) { return k; }
+  uint64_t budget(uint64_t evaluated, uint64_t accepted) const { return shuffle_attempt_budget(evaluated, accepted, n); }
+};
+
 // Sorted pairs: keys[k] = j_i ascending, steps[k] = i - 1, ascending within one key (count = n - 1 of them).
 // The first position whose pair (j, i) is not below (q, L).
 RNG_HD inline uint32_t shuffle_lower_bound(const uint32_t* keys, const uint32_t* steps, uint32_t count, uint32_t q, uint32_t L)

@@ -1,10 +1,9 @@
 // rng_shuffle_kernels.h — the single path of std::shuffle(iota(n), engine_) on the device (rng_shuffle.h holds the restatement
 // and says why the pair path, n <= 46340, stays on the host; host_shuffle.h the rounds). Integers only; wave64; no scratch.
 //
-//   shuffle_doubt_count_kernel   the attempts in runs of E per lane behind one jump, as rng_index_count_kernel: ONE count of
-//                                doubtful attempts per work-group
-//   (exclusive scan of the work-group counts: the cloud path's)
-//   shuffle_doubt_emit_kernel    the attempts again: {attempt number, engine output} of every doubtful attempt, in stream order
+//   DoubtPolicy, DoubtSink       rng_stream_kernels.h's count and emit kernels with these: the attempts in runs of E per lane
+//                                behind one jump, ONE count of doubtful attempts per work-group, the exclusive scan (the cloud
+//                                path's), then {attempt number, engine output} of every doubtful attempt, in stream order
 //   shuffle_resolve_kernel       ONE wavefront walks the doubtful list in order, 64 entries speculated at a time: every lane judges
 //                                its entry as if no entry of the batch in front of it were rejected, the lowest lane that reports a
 //                                rejection (or the end of the shuffle) is right, the batch restarts behind it. Leaves the sorted
@@ -15,98 +14,24 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "rng_index_kernels.h"
 #include "rng_shuffle.h"
+#include "rng_stream_kernels.h"
 
 namespace mcl3dl
 {
 namespace rng
 {
-// the E attempts of this lane, as index_lane_mask; bit e: attempt lane E + e is below n_att and doubtful
-__device__ inline uint32_t shuffle_lane_mask(uint32_t x0, const uint32_t* __restrict__ table, unsigned long long n,
-                                             unsigned long long n_att, unsigned long long lane, uint32_t* v)
+// {attempt number, engine output} of a doubtful attempt at its rank; the two lists have room for the count pass's total
+struct DoubtSink
 {
-  constexpr int E = ATTEMPTS_PER_LANE;
-  const unsigned long long t0 = lane * E;
-  uint32_t mask = 0u;
-  if (t0 >= n_att)
+  uint32_t* __restrict__ doubt_t;
+  uint32_t* __restrict__ doubt_v;
+  __device__ void operator()(unsigned long long rank, unsigned long long t, uint32_t v) const
   {
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-      v[e] = 0u;
-    return 0u;
+    doubt_t[rank] = static_cast<uint32_t>(t);  // (the host refuses a stream of 2^32 attempts or more)
+    doubt_v[rank] = v;
   }
-  uint32_t x = minstd_jump(x0, t0, table);
-#pragma unroll
-  for (int e = 0; e < E; ++e)
-  {
-    x = minstd_next(x);
-    v[e] = x;
-    mask |= (shuffle_doubtful(x, n) && t0 + e < n_att) ? (1u << e) : 0u;
-  }
-  return mask;
-}
-
-__global__ __launch_bounds__(GROUP_THREADS) void shuffle_doubt_count_kernel(uint32_t x0, const uint32_t* __restrict__ table,
-                                                                            unsigned long long n, unsigned long long n_att,
-                                                                            uint32_t* __restrict__ group_count)
-{
-  constexpr int E = ATTEMPTS_PER_LANE;
-  __shared__ uint32_t s_wave[GROUP_THREADS / 64];
-  const unsigned long long lane = static_cast<unsigned long long>(blockIdx.x) * GROUP_THREADS + threadIdx.x;
-  uint32_t v[E];
-  const uint32_t mask = shuffle_lane_mask(x0, table, n, n_att, lane, v);
-  uint32_t before, wave_total;
-  index_wave_ranks(mask, &before, &wave_total);
-  if ((threadIdx.x & 63) == 0)
-    s_wave[threadIdx.x >> 6] = wave_total;
-  __syncthreads();
-  if (threadIdx.x == 0)
-  {
-    uint32_t s = 0u;
-#pragma unroll
-    for (int w = 0; w < GROUP_THREADS / 64; ++w)
-      s += s_wave[w];
-    group_count[blockIdx.x] = s;
-  }
-}
-
-// group_offset: the exclusive scan of group_count; n_doubt: its total (the capacity of the two lists)
-__global__ __launch_bounds__(GROUP_THREADS) void shuffle_doubt_emit_kernel(uint32_t x0, const uint32_t* __restrict__ table,
-                                                                           unsigned long long n, unsigned long long n_att,
-                                                                           const uint32_t* __restrict__ group_offset,
-                                                                           uint32_t n_doubt, uint32_t* __restrict__ doubt_t,
-                                                                           uint32_t* __restrict__ doubt_v)
-{
-  constexpr int E = ATTEMPTS_PER_LANE;
-  __shared__ uint32_t s_wave[GROUP_THREADS / 64];
-  const unsigned long long lane = static_cast<unsigned long long>(blockIdx.x) * GROUP_THREADS + threadIdx.x;
-  uint32_t v[E];
-  const uint32_t mask = shuffle_lane_mask(x0, table, n, n_att, lane, v);
-  uint32_t before, wave_total;
-  index_wave_ranks(mask, &before, &wave_total);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0)
-    s_wave[wave] = wave_total;
-  __syncthreads();
-  uint32_t wave_offset = 0u;
-#pragma unroll
-  for (int w = 0; w < GROUP_THREADS / 64; ++w)
-    wave_offset += w < wave ? s_wave[w] : 0u;
-  uint32_t rank = group_offset[blockIdx.x] + wave_offset + before;
-#pragma unroll
-  for (int e = 0; e < E; ++e)
-  {
-    if (!((mask >> e) & 1u))
-      continue;
-    if (rank < n_doubt)
-    {
-      doubt_t[rank] = static_cast<uint32_t>(lane * E + e);  // (the host refuses a stream of 2^32 attempts or more)
-      doubt_v[rank] = v[e];
-    }
-    ++rank;
-  }
-}
+};
 
 // result[0] = rejections among the steps of the shuffle, result[1] = 1 when the n_att attempts hold all n - 1 steps.
 // rejected_t has room for n_doubt entries.

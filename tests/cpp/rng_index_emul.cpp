@@ -1,6 +1,7 @@
-// rng_index_emul.cpp — rng_index_kernels.h's two decompositions of the uniform sampler's stream, replayed on the CPU from the
-// header the kernels compile (mcl_3dl_amd/csrc/rng_index.h): runs of E attempts per lane behind one jump, 64-lane ballots,
-// 256-thread passes / work-groups; the one-work-group form with its pass loop, its start state carried from pass to pass and its
+// rng_index_emul.cpp — the device's two decompositions of the uniform sampler's stream, replayed on the CPU from the headers
+// the kernels compile (mcl_3dl_amd/csrc/rng_stream.h: the lane walk and the placement loop; rng_index.h: the index policy): runs of
+// E attempts per lane behind one jump, and around them rng_emul_common.h's stand-in for 64-lane ballots and 256-thread passes /
+// work-groups; the one-work-group form with its pass loop, its start state carried from pass to pass and its
 // hand-over from the first segment to the second; the rounds form with one count per work-group, the exclusive scan, ranks from
 // group offset + wavefront offset + mbcnt, and the host's rounds with index_attempt_budget. Its yardstick is the standard library
 // itself: std::default_random_engine with std::uniform_int_distribution<size_t> (libstdc++), a fresh distribution per draw as
@@ -16,47 +17,21 @@
 #include <cstdlib>
 #include <cstring>
 #include <random>
-#include <sstream>
 #include <string>
 #include <vector>
 
 #include "../../mcl_3dl_amd/csrc/rng_index.h"
-
-using namespace mcl3dl::rng;
+#include "rng_emul_common.h"
 
 namespace
 {
-uint32_t g_table[64];
-constexpr int E = ATTEMPTS_PER_LANE;
-constexpr int WAVES = GROUP_THREADS / 64;
-
-void set_state(std::default_random_engine& e, uint32_t s)
-{
-  std::stringstream ss;
-  ss << s;
-  ss >> e;
-}
-uint32_t get_state(const std::default_random_engine& e)
-{
-  std::stringstream ss;
-  ss << e;
-  unsigned long v = 0;
-  ss >> v;
-  return static_cast<uint32_t>(v);
-}
-
 struct Segment
 {
   uint64_t range;
   uint64_t count;
 };
 
-struct Result
-{
-  uint32_t state;
-  int rounds;         // rounds form: the most rounds any segment took; one-work-group form: 0
-  uint64_t attempts;  // attempts evaluated
-};
+using Result = Rounds;  // rounds: the most rounds any segment took (rounds form); 0 (one-work-group form)
 
 // the yardstick: sample()'s loop per segment, an empty segment draws nothing
 Result std_draw(uint32_t state, const Segment* seg, int n_seg, std::vector<uint32_t>& out)
@@ -73,54 +48,6 @@ Result std_draw(uint32_t state, const Segment* seg, int n_seg, std::vector<uint3
   return Result{ get_state(eng), 0, 0 };
 }
 
-struct Lane
-{
-  uint32_t v[E];
-  uint32_t mask;
-};
-
-// rng_index_kernels.h: index_lane_mask
-Lane lane_attempts(uint32_t x0, const IndexRange& r, uint64_t n_att, uint64_t lane)
-{
-  Lane L{};
-  const uint64_t t0 = lane * E;
-  if (t0 >= n_att)
-    return L;
-  uint32_t x = minstd_jump(x0, t0, g_table);
-  for (int e = 0; e < E; ++e)
-  {
-    x = minstd_next(x);
-    L.v[e] = x;
-    if (index_accepted(r, x) && t0 + e < n_att)
-      L.mask |= 1u << e;
-  }
-  return L;
-}
-
-// one work-group's lanes with index_wave_ranks: `before` per thread, the total per wavefront
-void group_lanes(uint32_t x0, const IndexRange& r, uint64_t n_att, uint64_t first_lane, Lane* lanes, uint32_t* before,
-                 uint32_t* wave_total)
-{
-  for (int w = 0; w < WAVES; ++w)
-  {
-    uint64_t ballot[E] = { 0 };
-    wave_total[w] = 0;
-    for (int l = 0; l < 64; ++l)
-    {
-      lanes[w * 64 + l] = lane_attempts(x0, r, n_att, first_lane + w * 64 + l);
-      before[w * 64 + l] = 0;
-      for (int e = 0; e < E; ++e)
-        ballot[e] |= static_cast<uint64_t>((lanes[w * 64 + l].mask >> e) & 1u) << l;
-    }
-    for (int e = 0; e < E; ++e)
-    {
-      wave_total[w] += static_cast<uint32_t>(__builtin_popcountll(ballot[e]));
-      for (int l = 0; l < 64; ++l)  // mbcnt: set bits below lane l
-        before[w * 64 + l] += static_cast<uint32_t>(__builtin_popcountll(ballot[e] & ((1ull << l) - 1ull)));
-    }
-  }
-}
-
 // rng_index_single_kernel
 Result single_draw(uint32_t state, const Segment* seg, int n_seg, std::vector<uint32_t>& out)
 {
@@ -132,38 +59,33 @@ Result single_draw(uint32_t state, const Segment* seg, int n_seg, std::vector<ui
     const uint64_t count = seg[s].count;
     if (count == 0)
       continue;
-    const IndexRange r = index_range(seg[s].range);
+    const IndexPolicy policy{ index_range(seg[s].range) };
     const size_t base = out.size();
     out.resize(base + count);
     uint64_t accepted = 0;
     while (accepted < count)
     {
       const uint32_t start = s_start;
-      Lane lanes[GROUP_THREADS];
+      Lane<IndexPolicy> lanes[GROUP_THREADS];
       uint32_t before[GROUP_THREADS], wave_total[WAVES];
-      group_lanes(start, r, static_cast<uint64_t>(GROUP_THREADS) * E, 0, lanes, before, wave_total);
-      res.attempts += static_cast<uint64_t>(GROUP_THREADS) * E;
+      group_lanes(policy, start, PER_GROUP, 0, lanes, before, wave_total);
+      res.attempts += PER_GROUP;
       uint32_t pass_total = 0;
       for (int w = 0; w < WAVES; ++w)
         pass_total += wave_total[w];
       for (int t = 0; t < GROUP_THREADS; ++t)
       {
-        uint32_t wave_offset = 0;
-        for (int w = 0; w < (t >> 6); ++w)
-          wave_offset += wave_total[w];
-        uint64_t rank = accepted + wave_offset + before[t];
-        for (int e = 0; e < E; ++e)
-        {
-          if (!((lanes[t].mask >> e) & 1u))
-            continue;
-          if (rank < count)
-            out[base + rank] = index_value(r, lanes[t].v[e]);
-          if (rank + 1 == count)
-            s_start = lanes[t].v[e];
-          ++rank;
-        }
+        const uint32_t* v = lanes[t].kept;
+        place_accepted(lanes[t].mask, accepted + wave_offset_of(wave_total, t) + before[t],
+                       [&](uint64_t rank, int e)
+                       {
+                         if (rank < count)
+                           out[base + rank] = index_value(policy.r, v[e]);
+                         if (rank + 1 == count)
+                           s_start = v[e];
+                       });
         if (accepted + pass_total < count && t == GROUP_THREADS - 1)
-          s_start = lanes[t].v[E - 1];
+          s_start = v[E - 1];
       }
       accepted += pass_total;
     }
@@ -172,85 +94,26 @@ Result single_draw(uint32_t state, const Segment* seg, int n_seg, std::vector<ui
   return res;
 }
 
-// host_rng.h: rng_index_rounds per segment, the two kernels and the scan replayed work-group by work-group
+// host_rng.h: rng_index_rounds per segment, with rng_index_kernels.h's IndexSink
 Result rounds_draw(uint32_t state, const Segment* seg, int n_seg, std::vector<uint32_t>& out)
 {
   Result res{ state, 0, 0 };
   out.clear();
-  const uint64_t per_group = static_cast<uint64_t>(GROUP_THREADS) * E;
   for (int s = 0; s < n_seg; ++s)
   {
     const uint64_t count = seg[s].count;
     if (count == 0)
       continue;
-    const IndexRange r = index_range(seg[s].range);
+    const IndexPolicy policy{ index_range(seg[s].range) };
     const size_t base = out.size();
     out.resize(base + count);
-    uint32_t x0 = res.state;
-    uint64_t accepted = 0;
-    int rounds = 0;
-    while (accepted < count)
-    {
-      ++rounds;
-      const uint64_t n_att = index_attempt_budget(count - accepted, r);
-      res.attempts += n_att;
-      const uint64_t n_groups = (n_att + per_group - 1) / per_group;
-      std::vector<uint32_t> counts(n_groups + 1, 0u);
-      Lane lanes[GROUP_THREADS];
-      uint32_t before[GROUP_THREADS], wave_total[WAVES];
-      for (uint64_t g = 0; g < n_groups; ++g)  // count kernel
-      {
-        group_lanes(x0, r, n_att, g * GROUP_THREADS, lanes, before, wave_total);
-        for (int w = 0; w < WAVES; ++w)
-          counts[g] += wave_total[w];
-      }
-      uint32_t run = 0;  // exclusive scan (n_groups + 1 entries: the last one becomes the total)
-      for (uint64_t g = 0; g <= n_groups; ++g)
-      {
-        const uint32_t c = counts[g];
-        counts[g] = run;
-        run += c;
-      }
-      uint32_t result = 0;
-      for (uint64_t g = 0; g < n_groups; ++g)  // emit kernel
-      {
-        group_lanes(x0, r, n_att, g * GROUP_THREADS, lanes, before, wave_total);
-        for (int t = 0; t < GROUP_THREADS; ++t)
-        {
-          uint32_t wave_offset = 0;
-          for (int w = 0; w < (t >> 6); ++w)
-            wave_offset += wave_total[w];
-          uint64_t rank = accepted + counts[g] + wave_offset + before[t];
-          for (int e = 0; e < E; ++e)
-          {
-            if (!((lanes[t].mask >> e) & 1u))
-              continue;
-            if (rank < count)
-              out[base + rank] = index_value(r, lanes[t].v[e]);
-            if (rank + 1 == count)
-              result = lanes[t].v[e];
-            ++rank;
-          }
-        }
-      }
-      accepted += counts[n_groups];
-      if (accepted >= count)
-        res.state = result;
-      else
-        x0 = minstd_jump(x0, n_att, g_table);
-    }
-    res.rounds = std::max(res.rounds, rounds);
+    const Rounds r = replay_rounds(policy, res.state, count,
+                                   [&](uint64_t rank, uint64_t, uint32_t v) { out[base + rank] = index_value(policy.r, v); });
+    res.state = r.state;
+    res.attempts += r.attempts;
+    res.rounds = std::max(res.rounds, r.rounds);
   }
   return res;
-}
-
-uint32_t modpow(uint32_t a, uint64_t k)
-{
-  uint32_t r = 1;
-  for (; k; k >>= 1, a = minstd_mulmod(a, a))
-    if (k & 1)
-      r = minstd_mulmod(r, a);
-  return r;
 }
 
 int g_fail = 0;

@@ -1,7 +1,8 @@
-// rng_polar_emul.cpp — rng_kernels.h's decomposition of the reference's random stream, replayed on the CPU from the header the
-// kernels compile (mcl_3dl_amd/csrc/rng_polar.h): runs of E attempts per lane behind one jump, 64-lane ballots, 256-thread
-// work-groups, one count per work-group, the exclusive scan, ranks from group offset + wavefront offset + mbcnt, and the host's
-// rounds with attempt_budget. Its yardstick is the standard library itself: std::default_random_engine with
+// rng_polar_emul.cpp — the device's decomposition of the reference's random stream, replayed on the CPU from the headers the
+// kernels compile (mcl_3dl_amd/csrc/rng_stream.h: the lane walk and the placement loop; rng_polar.h: the polar policy): runs of E
+// attempts per lane behind one jump, and around them rng_emul_common.h's stand-in for 64-lane ballots, 256-thread work-groups,
+// one count per work-group, the exclusive scan, ranks from group offset + wavefront offset + mbcnt, and the host's rounds with
+// attempt_budget. Its yardstick is the standard library itself: std::default_random_engine with
 // std::normal_distribution<float> / std::uniform_real_distribution<float> (libstdc++).
 //
 //   rng_polar_emul selftest                                        every case of tests/test_rng_polar_cpu.py, "all equal" at the end
@@ -15,169 +16,36 @@
 #include <cstdlib>
 #include <cstring>
 #include <random>
-#include <sstream>
 #include <string>
 #include <vector>
 
-#include "../../mcl_3dl_amd/csrc/rng_polar.h"
-
-using namespace mcl3dl::rng;
+#include "rng_emul_common.h"
 
 namespace
 {
-uint32_t g_table[64];
+using Result = Rounds;
 
-void set_state(std::default_random_engine& e, uint32_t s)
-{
-  std::stringstream ss;
-  ss << s;
-  ss >> e;
-}
-uint32_t get_state(const std::default_random_engine& e)
-{
-  std::stringstream ss;
-  ss << e;
-  unsigned long v = 0;
-  ss >> v;
-  return static_cast<uint32_t>(v);
-}
-
-constexpr int E = ATTEMPTS_PER_LANE;
-struct Lane
-{
-  float x[E], y[E], r2[E];
-  uint32_t state[E];
-  uint32_t mask;
-};
-
-// rng_kernels.h: lane_accept_mask
-Lane lane_attempts(uint32_t x0, uint64_t n_att, uint64_t lane)
-{
-  Lane L{};
-  const uint64_t t0 = lane * E;
-  if (t0 >= n_att)
-    return L;
-  uint32_t x = minstd_jump(x0, 2 * t0, g_table);
-  for (int e = 0; e < E; ++e)
-  {
-    const uint32_t v1 = minstd_next(x);
-    x = minstd_next(v1);
-    const Attempt a = polar_attempt(v1, x);
-    if (a.accepted && t0 + e < n_att)
-      L.mask |= 1u << e;
-    L.x[e] = a.x;
-    L.y[e] = a.y;
-    L.r2[e] = a.r2;
-    L.state[e] = x;
-  }
-  return L;
-}
-
-struct Result
-{
-  uint32_t state;
-  int rounds;
-  uint64_t attempts;
-};
-
-// host_rng.h: rng_draw, with the two kernels and the scan replayed work-group by work-group
+// host_rng.h: rng_draw, with rng_kernels.h's PolarSink
 template <typename Log>
 Result draw(uint32_t state_in, uint64_t k_total, bool pairs, uint64_t k_begin, uint64_t k_end, std::vector<float>& values)
 {
-  Result res{ state_in, 0, 0 };
   k_end = std::min(k_end, k_total);
   k_begin = std::min(k_begin, k_end);
   values.assign((pairs ? 2 : 1) * (k_end - k_begin), 0.0f);
-  uint32_t x0 = state_in;
-  uint64_t accepted = 0;
-  while (accepted < k_total)
-  {
-    ++res.rounds;
-    const uint64_t n_att = attempt_budget(k_total - accepted);
-    res.attempts += n_att;
-    const uint64_t per_group = static_cast<uint64_t>(GROUP_THREADS) * E;
-    const uint64_t n_groups = (n_att + per_group - 1) / per_group;
-    // count kernel: one count per work-group, from the ballots
-    std::vector<uint32_t> counts(n_groups + 1, 0u);
-    for (uint64_t g = 0; g < n_groups; ++g)
-      for (int w = 0; w < GROUP_THREADS / 64; ++w)
-      {
-        uint64_t ballot[E] = { 0 };
-        for (int l = 0; l < 64; ++l)
-        {
-          const Lane L = lane_attempts(x0, n_att, g * GROUP_THREADS + w * 64 + l);
-          for (int e = 0; e < E; ++e)
-            ballot[e] |= static_cast<uint64_t>((L.mask >> e) & 1u) << l;
-        }
-        for (int e = 0; e < E; ++e)
-          counts[g] += static_cast<uint32_t>(__builtin_popcountll(ballot[e]));
-      }
-    // exclusive scan (n_groups + 1 entries: the last one becomes the total)
-    uint32_t run = 0;
-    for (uint64_t g = 0; g <= n_groups; ++g)
-    {
-      const uint32_t c = counts[g];
-      counts[g] = run;
-      run += c;
-    }
-    uint32_t result = 0;
-    // emit kernel
-    for (uint64_t g = 0; g < n_groups; ++g)
-    {
-      Lane lanes[GROUP_THREADS];
-      uint32_t wave_total[GROUP_THREADS / 64] = { 0 }, before[GROUP_THREADS] = { 0 };
-      for (int w = 0; w < GROUP_THREADS / 64; ++w)
-      {
-        uint64_t ballot[E] = { 0 };
-        for (int l = 0; l < 64; ++l)
-        {
-          lanes[w * 64 + l] = lane_attempts(x0, n_att, g * GROUP_THREADS + w * 64 + l);
-          for (int e = 0; e < E; ++e)
-            ballot[e] |= static_cast<uint64_t>((lanes[w * 64 + l].mask >> e) & 1u) << l;
-        }
-        for (int e = 0; e < E; ++e)
-        {
-          wave_total[w] += static_cast<uint32_t>(__builtin_popcountll(ballot[e]));
-          for (int l = 0; l < 64; ++l)  // mbcnt: set bits below lane l
-            before[w * 64 + l] += static_cast<uint32_t>(__builtin_popcountll(ballot[e] & ((1ull << l) - 1ull)));
-        }
-      }
-      for (int t = 0; t < GROUP_THREADS; ++t)
-      {
-        const int w = t >> 6;
-        uint32_t wave_offset = 0;
-        for (int v = 0; v < w; ++v)
-          wave_offset += wave_total[v];
-        uint64_t rank = accepted + counts[g] + wave_offset + before[t];
-        const Lane& L = lanes[t];
-        for (int e = 0; e < E; ++e)
-        {
-          if (!((L.mask >> e) & 1u))
-            continue;
-          if (rank < k_total && rank >= k_begin && rank < k_end)
-          {
-            const float mult = polar_mult(L.r2[e], Log());
-            if (pairs)
-            {
-              values[2 * (rank - k_begin)] = L.y[e] * mult;
-              values[2 * (rank - k_begin) + 1] = L.x[e] * mult;
-            }
-            else
-              values[rank - k_begin] = L.y[e] * mult;
-          }
-          if (rank + 1 == k_total)
-            result = L.state[e];
-          ++rank;
-        }
-      }
-    }
-    accepted += counts[n_groups];
-    if (accepted >= k_total)
-      res.state = result;
-    else
-      x0 = minstd_jump(x0, 2 * n_att, g_table);
-  }
-  return res;
+  return replay_rounds(PolarPolicy{}, state_in, k_total,
+                       [&](uint64_t rank, uint64_t, const PolarPolicy::Kept& k)
+                       {
+                         if (rank < k_begin || rank >= k_end)
+                           return;
+                         const float mult = polar_mult(k.r2, Log());
+                         if (pairs)
+                         {
+                           values[2 * (rank - k_begin)] = k.y * mult;
+                           values[2 * (rank - k_begin) + 1] = k.x * mult;
+                         }
+                         else
+                           values[rank - k_begin] = k.y * mult;
+                       });
 }
 
 // n values of normal_distribution<float>(0, 1): fresh = one distribution per value, shared = one for all
@@ -215,15 +83,6 @@ Result emul_stream(uint32_t state, bool shared, size_t n, std::vector<float>& va
 bool same_bits(const std::vector<float>& a, const std::vector<float>& b)
 {
   return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(float)) == 0);
-}
-
-uint32_t modpow(uint32_t a, uint64_t k)
-{
-  uint32_t r = 1;
-  for (; k; k >>= 1, a = minstd_mulmod(a, a))
-    if (k & 1)
-      r = minstd_mulmod(r, a);
-  return r;
 }
 
 int g_fail = 0;

@@ -1,5 +1,6 @@
-// rng_shuffle_emul.cpp — rng_shuffle_kernels.h's form of std::shuffle(iota(n), engine), replayed on the CPU from the header the
-// kernels compile (mcl_3dl_amd/csrc/rng_shuffle.h): runs of E attempts per lane behind one jump, 64-lane ballots and 256-thread
+// rng_shuffle_emul.cpp — rng_shuffle_kernels.h's form of std::shuffle(iota(n), engine), replayed on the CPU from the headers the
+// kernels compile (mcl_3dl_amd/csrc/rng_stream.h: the lane walk and the placement loop; rng_shuffle.h: the doubt policy and the
+// rest): runs of E attempts per lane behind one jump, rng_emul_common.h's stand-in for 64-lane ballots and 256-thread
 // work-groups for the doubtful attempts (count, exclusive scan, emit in stream order), the one-wavefront resolve that speculates 64
 // entries at a time, the step of every attempt from the sorted rejections, the sort's contract (stable, by j_i on the bits of
 // n - 1) and one chain walk per entry; around them the host's rounds with shuffle_attempt_budget. Its yardstick is the standard
@@ -19,36 +20,14 @@
 #include <cstring>
 #include <numeric>
 #include <random>
-#include <sstream>
 #include <string>
 #include <vector>
 
 #include "../../mcl_3dl_amd/csrc/rng_shuffle.h"
-
-using namespace mcl3dl::rng;
+#include "rng_emul_common.h"
 
 namespace
 {
-uint32_t g_table[64];
-constexpr int E = ATTEMPTS_PER_LANE;
-constexpr int WAVES = GROUP_THREADS / 64;
-constexpr uint64_t PER_GROUP = static_cast<uint64_t>(GROUP_THREADS) * E;
-
-void set_state(std::default_random_engine& e, uint32_t s)
-{
-  std::stringstream ss;
-  ss << s;
-  ss >> e;
-}
-uint32_t get_state(const std::default_random_engine& e)
-{
-  std::stringstream ss;
-  ss << e;
-  unsigned long v = 0;
-  ss >> v;
-  return static_cast<uint32_t>(v);
-}
-
 struct Result
 {
   uint32_t state = 0;
@@ -81,53 +60,6 @@ Result serial_shuffle(uint64_t n, uint32_t state, bool force_single, std::vector
   shuffle_serial(n, &r.state, out.data(), force_single, &r.attempts);
   r.rejected = r.attempts - (force_single || !shuffle_pair_path(n) ? n - 1 : n / 2);
   return r;
-}
-
-struct Lane
-{
-  uint32_t v[E];
-  uint32_t mask;
-};
-
-// rng_shuffle_kernels.h: shuffle_lane_mask
-Lane lane_attempts(uint32_t x0, uint64_t n, uint64_t n_att, uint64_t lane)
-{
-  Lane L{};
-  const uint64_t t0 = lane * E;
-  if (t0 >= n_att)
-    return L;
-  uint32_t x = minstd_jump(x0, t0, g_table);
-  for (int e = 0; e < E; ++e)
-  {
-    x = minstd_next(x);
-    L.v[e] = x;
-    if (shuffle_doubtful(x, n) && t0 + e < n_att)
-      L.mask |= 1u << e;
-  }
-  return L;
-}
-
-// one work-group's lanes with index_wave_ranks: `before` per thread, the total per wavefront
-void group_lanes(uint32_t x0, uint64_t n, uint64_t n_att, uint64_t first_lane, Lane* lanes, uint32_t* before, uint32_t* wave_total)
-{
-  for (int w = 0; w < WAVES; ++w)
-  {
-    uint64_t ballot[E] = { 0 };
-    wave_total[w] = 0;
-    for (int l = 0; l < 64; ++l)
-    {
-      lanes[w * 64 + l] = lane_attempts(x0, n, n_att, first_lane + w * 64 + l);
-      before[w * 64 + l] = 0;
-      for (int e = 0; e < E; ++e)
-        ballot[e] |= static_cast<uint64_t>((lanes[w * 64 + l].mask >> e) & 1u) << l;
-    }
-    for (int e = 0; e < E; ++e)
-    {
-      wave_total[w] += static_cast<uint32_t>(__builtin_popcountll(ballot[e]));
-      for (int l = 0; l < 64; ++l)  // mbcnt: set bits below lane l
-        before[w * 64 + l] += static_cast<uint32_t>(__builtin_popcountll(ballot[e] & ((1ull << l) - 1ull)));
-    }
-  }
 }
 
 // shuffle_resolve_kernel: one wavefront, 64 entries speculated at a time
@@ -175,28 +107,13 @@ Result device_shuffle(uint64_t n, uint64_t m, uint32_t x0, bool short_budget, st
   uint64_t n_att = 0, accepted = 0;
   uint32_t n_rejected = 0;
   std::vector<uint32_t> rejected_t;
-  Lane lanes[GROUP_THREADS];
-  uint32_t before[GROUP_THREADS], wave_total[WAVES];
+  const DoubtPolicy policy{ n };
   for (;;)
   {
     ++res.rounds;
-    n_att = short_budget && res.rounds == 1 ? n - 1 : shuffle_attempt_budget(n_att, accepted, n);
-    const uint64_t n_groups = (n_att + PER_GROUP - 1) / PER_GROUP;
-    std::vector<uint32_t> counts(n_groups + 1, 0u);
-    for (uint64_t g = 0; g < n_groups; ++g)  // count kernel
-    {
-      group_lanes(x0, n, n_att, g * GROUP_THREADS, lanes, before, wave_total);
-      for (int w = 0; w < WAVES; ++w)
-        counts[g] += wave_total[w];
-    }
-    uint32_t run = 0;  // exclusive scan (n_groups + 1 entries: the last one becomes the total)
-    for (uint64_t g = 0; g <= n_groups; ++g)
-    {
-      const uint32_t c = counts[g];
-      counts[g] = run;
-      run += c;
-    }
-    const uint32_t n_doubt = counts[n_groups];
+    n_att = short_budget && res.rounds == 1 ? n - 1 : policy.budget(n_att, accepted);
+    const std::vector<uint32_t> counts = count_and_scan(policy, x0, n_att);
+    const uint32_t n_doubt = counts.back();
     res.attempts = n_att;
     res.doubtful = n_doubt;
     n_rejected = 0;
@@ -204,25 +121,12 @@ Result device_shuffle(uint64_t n, uint64_t m, uint32_t x0, bool short_budget, st
     if (n_doubt == 0)
       break;
     std::vector<uint32_t> doubt_t(n_doubt, 0u), doubt_v(n_doubt, 0u);
-    for (uint64_t g = 0; g < n_groups; ++g)  // emit kernel
-    {
-      group_lanes(x0, n, n_att, g * GROUP_THREADS, lanes, before, wave_total);
-      for (int t = 0; t < GROUP_THREADS; ++t)
-      {
-        uint32_t wave_offset = 0;
-        for (int w = 0; w < (t >> 6); ++w)
-          wave_offset += wave_total[w];
-        uint32_t rank = counts[g] + wave_offset + before[t];
-        for (int e = 0; e < E; ++e)
-        {
-          if (!((lanes[t].mask >> e) & 1u))
-            continue;
-          doubt_t.at(rank) = static_cast<uint32_t>((g * GROUP_THREADS + t) * E + e);
-          doubt_v.at(rank) = lanes[t].v[e];
-          ++rank;
-        }
-      }
-    }
+    emit_groups(policy, x0, n_att, counts, 0, n_doubt,
+                [&](uint64_t rank, uint64_t t, uint32_t v)  // rng_shuffle_kernels.h: DoubtSink
+                {
+                  doubt_t.at(rank) = static_cast<uint32_t>(t);
+                  doubt_v.at(rank) = v;
+                });
     uint32_t home[2];
     resolve_wave(doubt_t, doubt_v, n, n_att, rejected_t, home);
     n_rejected = home[0];
@@ -293,15 +197,6 @@ Result device_shuffle(uint64_t n, uint64_t m, uint32_t x0, bool short_budget, st
   }
   res.state = minstd_jump(x0, n_used, g_table);
   return res;
-}
-
-uint32_t modpow(uint32_t a, uint64_t k)
-{
-  uint32_t r = 1;
-  for (; k; k >>= 1, a = minstd_mulmod(a, a))
-    if (k & 1)
-      r = minstd_mulmod(r, a);
-  return r;
 }
 
 int g_fail = 0;

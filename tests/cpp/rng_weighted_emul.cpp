@@ -22,36 +22,19 @@
 #include <cstring>
 #include <limits>
 #include <random>
-#include <sstream>
 #include <string>
 #include <unordered_set>
 #include <vector>
 
 #include "../../mcl_3dl_amd/csrc/double_chain.h"
 #include "../../mcl_3dl_amd/csrc/rng_weighted.h"
+#include "rng_emul_common.h"  // g_table, set_state, get_state
 
 using namespace mcl3dl;
 using namespace mcl3dl::rng;
 
 namespace
 {
-uint32_t g_table[64];
-
-void set_state(std::default_random_engine& e, uint32_t s)
-{
-  std::stringstream ss;
-  ss << s;
-  ss >> e;
-}
-uint32_t get_state(const std::default_random_engine& e)
-{
-  std::stringstream ss;
-  ss << e;
-  unsigned long v = 0;
-  ss >> v;
-  return static_cast<uint32_t>(v);
-}
-
 bool same_bits(const std::vector<double>& a, const std::vector<double>& b)
 {
   return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), sizeof(double) * a.size()) == 0);
