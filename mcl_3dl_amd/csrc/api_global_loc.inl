@@ -187,11 +187,7 @@ int mcl3dl_hip_group_global_localization(mcl3dl_hip_group* g, double grid, int d
   const int N = g->n();
   // ---- steps 1-3 on every rank (the map is replicated; deterministic, so no collective): nothing resident is touched yet
   std::vector<size_t> pts(N, 0);
-  int bad = 0;
-  int rc = g->pool.run_all(
-      [&](int r) -> int { return mcl3dl_hip_global_localization_points(g->ctx[r], grid, nullptr, 0, &pts[r], nullptr); }, &bad);
-  if (rc)
-    return g->fail_rank(rc, bad);
+  TRY(group_run(g, [&](int r) -> int { return mcl3dl_hip_global_localization_points(g->ctx[r], grid, nullptr, 0, &pts[r], nullptr); }));
   for (int r = 1; r < N; ++r)
     if (pts[r] != pts[0])
       return g->fail(-4, "the ranks disagree on the standable points (%zu and %zu): are their maps the same?", pts[0], pts[r]);
@@ -209,13 +205,12 @@ int mcl3dl_hip_group_global_localization(mcl3dl_hip_group* g, double grid, int d
   g->n_resident = 0;
   g->rs_begun = g->rs_planned = false;
   g->noise_on = false;  // fresh State6DOF: no odometry noise
-  rc = g->pool.run_all(
-      [&](int r) -> int
+  TRY(group_run_shards(
+      g, n_p,
+      [&](const Shard& s) -> int
       {
-        mcl3dl_hip_ctx* ctx = g->ctx[r];
-        size_t lo, hi;
-        shard_bounds(n_p, N, r, &lo, &hi);
-        const size_t n = hi - lo;
+        mcl3dl_hip_ctx* ctx = s.ctx;
+        const size_t lo = s.lo, n = s.n;
         HIP_TRY(hipSetDevice(ctx->device));
         ctx->gs_n = 0;
         ctx->gs_cur = 0;
@@ -232,10 +227,7 @@ int mcl3dl_hip_group_global_localization(mcl3dl_hip_group* g, double grid, int d
         ctx->pose_resident = true;
         ctx->gs_n = n;
         return 0;
-      },
-      &bad);
-  if (rc)
-    return g->fail_rank(rc, bad);
+      }));
   g->n_resident = n_p;
   g->n_pose_uploaded = n_p;
   return 0;

@@ -1,34 +1,10 @@
 // api_group.inl — included inside the extern "C" block of mcl3dl_hip.hip: the device group (host_group.h) behind the C ABI.
-namespace
-{
-int group_comms(mcl3dl_hip_group* g)
-{
-  if (g->collective == 1 || !g->comms.empty())
-    return 0;
-  if (!g->devices_distinct)
-    return g->fail(-3, "a device id is listed more than once: RCCL needs one GPU per rank — set option \"collective\" to 1 "
-                       "(host combine) for several contexts on one GPU");
-  const std::string why = g->rccl.load();
-  if (!why.empty())
-    return g->fail(-7, "%s; set option \"collective\" to 1 (host combine) or MCL3DL_HIP_RCCL_LIB", why.c_str());
-  g->comms.assign(g->n(), nullptr);
-  const ncclResult_t rc = g->rccl.CommInitAll(g->comms.data(), g->n(), g->devices.data());
-  if (rc != ncclSuccess)
-  {
-    g->comms.clear();
-    return g->fail(-7, "ncclCommInitAll over %d devices failed: %s", g->n(), g->rccl.GetErrorString(rc));
-  }
-  return 0;
-}
-
-}  // namespace
-
 int mcl3dl_hip_group_create(mcl3dl_hip_group** out, const int* device_ids, int n_devices)
 {
   if (!out)
     return -1;
   *out = nullptr;
-  if (!device_ids || n_devices < 1 || n_devices > 64)
+  if (!device_ids || n_devices < 1 || n_devices > ROUND_MAX_RANKS)
     return -3;
   mcl3dl_hip_group* g = new mcl3dl_hip_group;
   for (int r = 0; r < n_devices; ++r)
@@ -109,10 +85,7 @@ int mcl3dl_hip_group_set_map(mcl3dl_hip_group* g, const float* xyz, const uint32
 {
   if (!g)
     return -1;
-  int bad = 0;
-  const int rc = g->pool.run_all([&](int r) { return mcl3dl_hip_set_map(g->ctx[r], xyz, label, n_m, stamp, dist_weight); },
-                                 &bad);
-  return rc ? g->fail_rank(rc, bad) : 0;
+  return group_run(g, [&](int r) { return mcl3dl_hip_set_map(g->ctx[r], xyz, label, n_m, stamp, dist_weight); });
 }
 
 int mcl3dl_hip_group_set_likelihood_params(mcl3dl_hip_group* g, float match_dist_min, float match_dist_flat,
@@ -178,8 +151,8 @@ int mcl3dl_hip_group_set_option(mcl3dl_hip_group* g, const char* name, double va
   }
   if (std::string(name) == "inject_failure_rank")
   {
-    // test hook (only with MCL3DL_HIP_TEST_HOOKS=1 in the environment): the next sharded update fails on that rank after its
-    // kernels are enqueued and before the collective
+    // test hook (only with MCL3DL_HIP_TEST_HOOKS=1 in the environment): the next sharded call that enters a collective fails on
+    // that rank after its kernels are enqueued and before the collective (group_voted_call)
     if (!test_hooks_enabled())
       return g->fail(-3, "inject_failure_rank is a test hook: set MCL3DL_HIP_TEST_HOOKS=1 in the environment to enable it");
     g->inject_failure_rank = static_cast<int>(value);
@@ -212,22 +185,14 @@ int mcl3dl_hip_group_upload_poses(mcl3dl_hip_group* g, const float* pose, size_t
   if (!pose || n_p == 0 || n_p > 0x7fffffffu)
     return g->fail(-3, "bad pose array");
   g->n_pose_uploaded = 0;
-  int bad = 0;
-  const int N = g->n();
-  const int rc = g->pool.run_all(
-      [&](int r) -> int
-      {
-        mcl3dl_hip_ctx* ctx = g->ctx[r];
-        size_t lo, hi;
-        shard_bounds(n_p, N, r, &lo, &hi);
-        ctx->poses_set(0);
-        if (hi == lo)
-          return 0;
-        return mcl3dl_hip_upload_poses(ctx, pose + 7 * lo, hi - lo);
-      },
-      &bad);
-  if (rc)
-    return g->fail_rank(rc, bad);
+  TRY(group_run_shards(g, n_p,
+                       [&](const Shard& s) -> int
+                       {
+                         s.ctx->poses_set(0);
+                         if (s.n == 0)
+                           return 0;
+                         return mcl3dl_hip_upload_poses(s.ctx, pose + 7 * s.lo, s.n);
+                       }));
   g->n_pose_uploaded = n_p;
   return 0;
 }
@@ -258,15 +223,12 @@ int mcl3dl_hip_group_measure_batch(mcl3dl_hip_group* g, const float* pose, size_
     return g->fail(-3, "%s", err.c_str());
   if (pose)
     g->n_pose_uploaded = 0;
-  int bad = 0;
-  const int N = g->n();
-  const int rc = g->pool.run_all(
-      [&](int r) -> int
+  TRY(group_run_shards(
+      g, n_p,
+      [&](const Shard& s) -> int
       {
-        mcl3dl_hip_ctx* ctx = g->ctx[r];
-        size_t lo, hi;
-        shard_bounds(n_p, N, r, &lo, &hi);
-        const size_t n = hi - lo;
+        mcl3dl_hip_ctx* ctx = s.ctx;
+        const size_t lo = s.lo, n = s.n;
         if (device_order)
           TRY(upload_scan_impl(ctx, scan, false));
         else
@@ -295,10 +257,7 @@ int mcl3dl_hip_group_measure_batch(mcl3dl_hip_group* g, const float* pose, size_
         if (out_beam)
           TRY(d2h(ctx, out_beam + lo, ctx->beam.p, sizeof(float) * n));
         return sync_stream(ctx);
-      },
-      &bad);
-  if (rc)
-    return g->fail_rank(rc, bad);
+      }));
   if (pose)
     g->n_pose_uploaded = n_p;
   return 0;
@@ -339,14 +298,12 @@ int mcl3dl_hip_group_measure_batch_begin(mcl3dl_hip_group* g, const float* pose,
   const int N = g->n();
   if (pose)
     g->n_pose_uploaded = 0;
-  int bad = 0;
-  const int rc = g->pool.run_all(
-      [&](int r) -> int
+  const int rc = group_run_shards(
+      g, n_p,
+      [&](const Shard& s) -> int
       {
-        mcl3dl_hip_ctx* ctx = g->ctx[r];
-        size_t lo, hi;
-        shard_bounds(n_p, N, r, &lo, &hi);
-        const size_t n = hi - lo;
+        mcl3dl_hip_ctx* ctx = s.ctx;
+        const size_t lo = s.lo, n = s.n;
         HIP_TRY(hipSetDevice(ctx->device));
         if (n == 0)
           return 0;
@@ -356,8 +313,7 @@ int mcl3dl_hip_group_measure_batch_begin(mcl3dl_hip_group* g, const float* pose,
                                               scan_beam_origin, n_b, origins, n_o, out_lik ? out_lik + lo : nullptr,
                                               out_match_ratio ? out_match_ratio + lo : nullptr,
                                               out_beam ? out_beam + lo : nullptr, slice_particles);
-      },
-      &bad);
+      });
   g->prog_done.assign(static_cast<size_t>(N), false);
   if (rc)
   {
@@ -366,7 +322,7 @@ int mcl3dl_hip_group_measure_batch_begin(mcl3dl_hip_group* g, const float* pose,
       (void)hipSetDevice(g->ctx[r]->device);
       (void)mcl3dl_hip_measure_batch_end(g->ctx[r]);
     }
-    return g->fail_rank(rc, bad);
+    return rc;
   }
   if (pose)
     g->n_pose_uploaded = n_p;
@@ -395,11 +351,11 @@ int mcl3dl_hip_group_measure_batch_wait(mcl3dl_hip_group* g, size_t particle, si
   const int N = g->n();
   for (int r = 0; r < N; ++r)
   {
-    size_t lo, hi;
-    shard_bounds(g->prog_n_p, N, r, &lo, &hi);
-    if (hi == lo)
+    const Shard s = shard_of(g, g->prog_n_p, r);
+    if (s.n == 0)
       continue;
-    mcl3dl_hip_ctx* ctx = g->ctx[r];
+    mcl3dl_hip_ctx* ctx = s.ctx;
+    const size_t lo = s.lo, hi = s.lo + s.n;
     if (particle >= hi)
     {
       // a rank in front of the owner: all of it must have arrived for the particles up to `particle` to be a leading run
@@ -470,293 +426,215 @@ void normal_likelihood_constants(float sigma, float* a, float* sq2)
   *sq2 = static_cast<float>(sigma * sigma * 2.0);
 }
 
+// where an update's results go (null = not wanted). weight: for the non-resident update the prior weights on the way in
+struct UpdateOutputs
+{
+  float* weight;
+  float* lik;
+  float* match_ratio;
+  float* beam;
+  float* entropy;
+  float* match_ratio_min;
+  float* match_ratio_max;
+  int* restored;
+};
+
+// One update over the group's shards: its arguments and what its ranks share.
+struct GroupUpdate
+{
+  mcl3dl_hip_group* g;
+  bool resident, prepared;
+  const float* pose;
+  const float* extra;
+  size_t n_p;
+  HostScan scan;
+  UpdateOutputs out;
+  // Large scans are ordered by every device for itself (upload_scan_impl: raw points up, keys / stable radix sort / gather
+  // there — the same order as the host's, bit for bit): N redundant sorts of ~0.05 ms that run side by side, instead of
+  // 0.15 ms of one host core at 16 k points ahead of any GPU work. Small scans are ordered once on the host and pushed.
+  bool device_order;
+  // (a rank whose staging launch is not eligible and whose scan is small pushes a copy ordered ONCE on the host, by whichever
+  // rank needs it first)
+  std::once_flag host_order_once;
+  std::string host_order_error;
+  bool host_ordered = false;
+  // the node's odometry factor formed on the devices from the resident states (mcl3dl_hip_group_set_odom_error_sigma)
+  bool device_extra;
+  float nd_a = 0.f, nd_sq2 = 0.f;
+  std::vector<float*> rank_weights;  // where each rank's prior weights are on its device
+  std::vector<float> stats;          // the four scalars of every rank
+};
+
+// phase A of a rank (group_allreduce_record): the shard and the scans go up, measure, the rank's partial sums
+int update_phase_a(GroupUpdate& u, const Shard& s)
+{
+  mcl3dl_hip_group* g = u.g;
+  mcl3dl_hip_ctx* ctx = s.ctx;
+  const int N = g->n();
+  const size_t lo = s.lo, n = s.n, fb = sizeof(float) * n;
+  const bool resident = u.resident, prepared = u.prepared;
+  const float* extra = u.extra;
+  if (resident && n)
+  {
+    if (ctx->gs_n != n)
+      return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, n);
+    // ctx->pose is shared with the non-resident calls (uploads, mcl3dl_hip_group_measure_update, moments of explicit
+    // states): whoever wrote it last, the poses evaluated here are those of the resident states
+    TRY(resident_poses(ctx));
+  }
+  // ONE launch takes the rank's inputs over — the raw scans (every rank orders them for itself, side by side), its
+  // pose / weight / odometry-factor shard — out of page-locked memory (stage_kernels.h); where that form is not
+  // eligible: uploads + the ordering launches, or the scans ordered once on the host and pushed
+  bool staged = false;
+  if (n && !prepared)
+  {
+    const int st = stage_inputs(ctx, resident ? nullptr : u.pose + 7 * lo, extra ? extra + lo : nullptr,
+                                resident ? nullptr : u.out.weight + lo, n, u.scan);
+    if (st < 0)
+      return st;
+    staged = st != 0;
+  }
+  if (!staged && !prepared)
+  {
+    if (u.device_order)
+      TRY(upload_scan_impl(ctx, u.scan, false));
+    else
+    {
+      std::call_once(u.host_order_once,
+                     [&]
+                     {
+                       u.host_ordered = order_scan(u.host_order_error, u.scan.scan_lik_xyz, u.scan.n_s, u.scan.scan_beam_xyz,
+                                                   u.scan.scan_beam_origin, u.scan.n_b, u.scan.origins, u.scan.n_o, g->scan,
+                                                   g->ctx[0]->opt.scan_presorted != 0) == 0;
+                     });
+      if (!u.host_ordered)
+        return ctx->fail(-3, "%s", u.host_order_error.c_str());
+      TRY(push_scan(ctx, g->scan, false));
+    }
+  }
+  if (!resident && !staged)
+    ctx->poses_set(0);
+  if (n == 0)
+    return pf_first_half_empty(ctx, s.r, N, ctx->packed.as<double>());
+  TRY(ensure(ctx, ctx->lik, fb));
+  TRY(ensure(ctx, ctx->ratio, fb));
+  TRY(ensure(ctx, ctx->beam, fb));
+  TRY(ensure(ctx, ctx->extra, fb));
+  if (!resident && !staged)
+  {
+    TRY(ensure(ctx, ctx->pose, sizeof(float) * 7 * n));
+    TRY(ensure(ctx, ctx->weightb, fb));
+    TRY(h2d(ctx, ctx->pose.p, u.pose + 7 * lo, sizeof(float) * 7 * n));
+    ctx->poses_set(n);
+    TRY(h2d(ctx, ctx->weightb.p, u.out.weight + lo, fb));
+  }
+  float* d_w = resident ? ctx->gs_weight.as<float>() : (staged ? staged_weights(ctx, n) : ctx->weightb.as<float>());
+  u.rank_weights[s.r] = d_w;
+  if (extra && !staged)
+    TRY(h2d(ctx, ctx->extra.p, extra + lo, fb));
+  if (u.device_extra)
+  {
+    hipLaunchKernelGGL(odom_factor_kernel, dim3((static_cast<int>(n) + 255) / 256), dim3(256), 0, ctx->stream,
+                       ctx->gs_state[ctx->gs_cur].as<float>(), static_cast<int>(n), u.nd_a, u.nd_sq2, ctx->extra.as<float>());
+    HIP_TRY(hipGetLastError());
+  }
+  // (the sum over the tiled kernel's per-tile partials and the beam model's last step ride in the first pf::measure kernel,
+  // as on one GPU: one launch less per model and rank)
+  LikTail tail;
+  tail.want = pf_tiles_fit(n);
+  tail.want_beam = true;
+  TRY(launch_measure(ctx, ctx->pose.as<float>(), n, ctx->lik.as<float>(), ctx->ratio.as<float>(), ctx->beam.as<float>(), &tail));
+  PfCall c{ ctx, d_w, ctx->lik.as<float>(), ctx->beam.as<float>(), (extra || u.device_extra) ? ctx->extra.as<float>() : nullptr,
+            ctx->ratio.as<float>(), n, nullptr };
+  c.tail = &tail;
+  return pf_first_half(c, s.r, N, ctx->packed.as<double>());
+}
+
+// phase B of a rank: normalise with the total, the rank's results home
+int update_phase_b(GroupUpdate& u, const Shard& s)
+{
+  mcl3dl_hip_ctx* ctx = s.ctx;
+  const size_t lo = s.lo, n = s.n, fb = sizeof(float) * n;
+  const UpdateOutputs& out = u.out;
+  TRY(ensure(ctx, ctx->stats4, sizeof(float) * 4));
+  if (n == 0)
+    return sync_stream(ctx);
+  float* d_w = u.rank_weights[s.r];
+  // the normalising kernel writes the shard's results straight into page-locked memory (the caller's arrays where they
+  // are page-locked, a staging block otherwise) and the rank learns of its completion from a polled word — instead of up
+  // to five D2H copies and a hipStreamSynchronize per rank
+  void* blk = (ctx->zero_copy() && ctx->poll_mode() && UpdBlock::bytes(n) <= STAGE_MAX_COPY) ? stage_alloc(ctx, UpdBlock::bytes(n)) :
+                                                                                                nullptr;
+  PfCall c{ ctx, d_w, ctx->lik.as<float>(), ctx->beam.as<float>(), nullptr, ctx->ratio.as<float>(), n, ctx->stats4.as<float>() };
+  PfEmit e{};
+  if (blk)
+  {
+    const UpdBlock ub(blk, n);
+    e.stats4 = ub.stats4();
+    ctx->stage_out.push_back({ &u.stats[4 * s.r], e.stats4, sizeof(float) * 4 });
+    float* const user[4] = { out.weight, out.lik, out.match_ratio, out.beam };
+    float** const slot[4] = { &e.w, &e.lik, &e.ratio, &e.beam };
+    for (int k = 0; k < 4; ++k)
+      if (user[k])
+        *slot[k] = host_target(ctx, user[k] + lo, ub.part(k), fb, true);
+    c.emit = &e;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  TRY(pf_second_half(c, u.g->n(), ctx->packed.as<double>()));
+  if (blk)
+    return sync_stream(ctx, true);
+  if (out.weight)
+    TRY(d2h(ctx, out.weight + lo, d_w, fb));
+  TRY(d2h(ctx, &u.stats[4 * s.r], ctx->stats4.p, sizeof(float) * 4));
+  if (out.lik)
+    TRY(d2h(ctx, out.lik + lo, ctx->lik.p, fb));
+  if (out.match_ratio)
+    TRY(d2h(ctx, out.match_ratio + lo, ctx->ratio.p, fb));
+  if (out.beam)
+    TRY(d2h(ctx, out.beam + lo, ctx->beam.p, fb));
+  return sync_stream(ctx);
+}
+
 // One update over the group's shards. resident = false: mcl3dl_hip_group_measure_update (poses and prior weights come from the
 // host, the weights go back). resident = true: the particles mcl3dl_hip_group_upload_state / _resample_apply left on the
 // devices (pose = first 7 floats of each 13-float state, kept as ctx->pose; weights in ctx->gs_weight, updated in place);
-// weight_inout is then an optional OUTPUT (may be null: nothing but four scalars comes back). prepared (with resident): every
+// out.weight is then an optional OUTPUT (may be null: nothing but four scalars comes back). prepared (with resident): every
 // rank's scans are those mcl3dl_hip_group_scan_finish installed — nothing is taken over, the context's scan state is left alone
 // (stage_inputs would record the scan it is given), an `extra` shard goes up by a plain copy.
-int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, const float* extra, float* weight_inout,
-                      size_t n_p, const float* scan_lik_xyz, size_t n_s, const float* scan_beam_xyz,
-                      const uint32_t* scan_beam_origin, size_t n_b, const float* origins, size_t n_o, float* out_lik,
-                      float* out_match_ratio, float* out_beam, float* entropy, float* match_ratio_min, float* match_ratio_max,
-                      int* restored, bool prepared = false)
+int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, const float* extra, size_t n_p, const HostScan& scan,
+                      const UpdateOutputs& out, bool prepared = false)
 {
   if (resident && g->n_resident == 0)
     return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
   if (n_p == 0)
     return g->fail(-3, "no particles");
-  if (!resident && (!pose || !weight_inout))
+  if (!resident && (!pose || !out.weight))
     return g->fail(-3, "null pose / weight array");
   if (resident && g->n_resident != n_p)
     return g->fail(-5, "%zu particles are resident on the group's devices, not %zu (mcl3dl_hip_group_upload_state first)",
                    g->n_resident, n_p);
   if (!resident && g->n() == 1 && g->direct_single)
   {
-    const int rc = mcl3dl_hip_measure_update(g->ctx[0], pose, extra, weight_inout, n_p, scan_lik_xyz, n_s, scan_beam_xyz,
-                                             scan_beam_origin, n_b, origins, n_o, out_lik, out_match_ratio, out_beam,
-                                             entropy, match_ratio_min, match_ratio_max, restored);
+    const int rc = mcl3dl_hip_measure_update(g->ctx[0], pose, extra, out.weight, n_p, scan.scan_lik_xyz, scan.n_s, scan.scan_beam_xyz,
+                                             scan.scan_beam_origin, scan.n_b, scan.origins, scan.n_o, out.lik, out.match_ratio,
+                                             out.beam, out.entropy, out.match_ratio_min, out.match_ratio_max, out.restored);
     return rc ? g->fail_rank(rc, 0) : 0;
   }
-  // a group of one device that may call its context directly needs no collective (and never loads RCCL)
-  const bool no_collective = g->n() == 1 && g->direct_single;
-  if (!no_collective)
-    TRY(group_comms(g));
-  // Large scans are ordered by every device for itself (upload_scan_impl: raw points up, keys / stable radix sort / gather
-  // there — the same order as the host's, bit for bit): N redundant sorts of ~0.05 ms that run side by side, instead of
-  // 0.15 ms of one host core at 16 k points ahead of any GPU work. Small scans are ordered once on the host and pushed.
-  const bool device_order = g->ctx[0]->opt.scan_order_device > 0 && n_s + n_b >= static_cast<size_t>(g->ctx[0]->opt.scan_order_device);
-  const HostScan scan{ scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o };
-  // (a rank whose staging launch is not eligible and whose scan is small pushes a copy ordered ONCE on the host, by whichever
-  // rank needs it first)
-  std::string host_order_error;
-  std::once_flag host_order_once;
-  bool host_ordered = false;
-  const int N = g->n();
-  const size_t n_pack = 2 + 2 * static_cast<size_t>(N);
-  const bool host_combine = g->collective == 1 && !no_collective;
-  std::vector<float> stats(4 * static_cast<size_t>(N), 0.f);
-  std::vector<float*> rank_weights(static_cast<size_t>(N), nullptr);  // where each rank's prior weights are on its device
-  // the node's odometry factor formed on the devices from the resident states (mcl3dl_hip_group_set_odom_error_sigma)
-  const bool device_extra = resident && !extra && g->odom_sigma > 0.f;
-  float nd_a = 0.f, nd_sq2 = 0.f;
-  if (device_extra)
-    normal_likelihood_constants(g->odom_sigma, &nd_a, &nd_sq2);
+  const size_t N = static_cast<size_t>(g->n());
+  GroupUpdate u{ g, resident, prepared, pose, extra, n_p, scan, out };
+  u.device_order = g->ctx[0]->opt.scan_order_device > 0 && scan.n_s + scan.n_b >= static_cast<size_t>(g->ctx[0]->opt.scan_order_device);
+  u.device_extra = resident && !extra && g->odom_sigma > 0.f;
+  if (u.device_extra)
+    normal_likelihood_constants(g->odom_sigma, &u.nd_a, &u.nd_sq2);
+  u.rank_weights.assign(N, nullptr);
+  u.stats.assign(4 * N, 0.f);
   if (!resident)
     g->n_pose_uploaded = 0;
-
-  // phase A: upload the shard, measure, partial sums, (RCCL) all-reduce, and — with RCCL — straight on to phase B
-  const auto phase_b = [&](mcl3dl_hip_ctx* ctx, int r, size_t lo, size_t n) -> int
-  {
-    const size_t fb = sizeof(float) * n;
-    TRY(ensure(ctx, ctx->stats4, sizeof(float) * 4));
-    if (n)
-    {
-      float* d_w = rank_weights[r];
-      // the normalising kernel writes the shard's results straight into page-locked memory (the caller's arrays where they
-      // are page-locked, a staging block otherwise) and the rank learns of its completion from a polled word — instead of up
-      // to five D2H copies and a hipStreamSynchronize per rank
-      void* blk = (ctx->zero_copy() && ctx->poll_mode() && UpdBlock::bytes(n) <= STAGE_MAX_COPY) ?
-                      stage_alloc(ctx, UpdBlock::bytes(n)) : nullptr;
-      PfCall c{ ctx, d_w, ctx->lik.as<float>(), ctx->beam.as<float>(), nullptr, ctx->ratio.as<float>(), n, ctx->stats4.as<float>() };
-      PfEmit e{};
-      if (blk)
-      {
-        const UpdBlock out(blk, n);
-        e.stats4 = out.stats4();
-        ctx->stage_out.push_back({ &stats[4 * r], e.stats4, sizeof(float) * 4 });
-        float* const user[4] = { weight_inout, out_lik, out_match_ratio, out_beam };
-        float** const slot[4] = { &e.w, &e.lik, &e.ratio, &e.beam };
-        for (int k = 0; k < 4; ++k)
-          if (user[k])
-            *slot[k] = host_target(ctx, user[k] + lo, out.part(k), fb, true);
-        c.emit = &e;
-      }
-      HIP_TRY(hipSetDevice(ctx->device));
-      TRY(pf_second_half(c, N, ctx->packed.as<double>()));
-      if (blk)
-        return sync_stream(ctx, true);
-      if (weight_inout)
-        TRY(d2h(ctx, weight_inout + lo, d_w, fb));
-      TRY(d2h(ctx, &stats[4 * r], ctx->stats4.p, sizeof(float) * 4));
-      if (out_lik)
-        TRY(d2h(ctx, out_lik + lo, ctx->lik.p, fb));
-      if (out_match_ratio)
-        TRY(d2h(ctx, out_match_ratio + lo, ctx->ratio.p, fb));
-      if (out_beam)
-        TRY(d2h(ctx, out_beam + lo, ctx->beam.p, fb));
-    }
-    return sync_stream(ctx);
-  };
-  int bad = 0;
-  std::vector<int> rcs(N, 0);
-  const int inject = g->inject_failure_rank;
-  g->inject_failure_rank = -1;
-  constexpr int RC_ABANDONED = -8;
-  int rc = g->pool.run_all(
-      [&](int r) -> int
-      {
-        mcl3dl_hip_ctx* ctx = g->ctx[r];
-        size_t lo, hi;
-        shard_bounds(n_p, N, r, &lo, &hi);
-        const size_t n = hi - lo, fb = sizeof(float) * n;
-        // everything up to the collective; nothing in here waits for another rank
-        const auto phase_a = [&]() -> int
-        {
-          HIP_TRY(hipSetDevice(ctx->device));
-          if (resident && n)
-          {
-            if (ctx->gs_n != n)
-              return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, n);
-            // ctx->pose is shared with the non-resident calls (uploads, mcl3dl_hip_group_measure_update, moments of explicit
-            // states): whoever wrote it last, the poses evaluated here are those of the resident states
-            TRY(resident_poses(ctx));
-          }
-          // ONE launch takes the rank's inputs over — the raw scans (every rank orders them for itself, side by side), its
-          // pose / weight / odometry-factor shard — out of page-locked memory (stage_kernels.h); where that form is not
-          // eligible: uploads + the ordering launches, or the scans ordered once on the host and pushed
-          bool staged = false;
-          if (n && !prepared)
-          {
-            const int st = stage_inputs(ctx, resident ? nullptr : pose + 7 * lo, extra ? extra + lo : nullptr,
-                                        resident ? nullptr : weight_inout + lo, n, scan);
-            if (st < 0)
-              return st;
-            staged = st != 0;
-          }
-          if (!staged && !prepared)
-          {
-            if (device_order)
-              TRY(upload_scan_impl(ctx, scan, false));
-            else
-            {
-              std::call_once(host_order_once,
-                             [&]
-                             {
-                               host_ordered = order_scan(host_order_error, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b,
-                                                         origins, n_o, g->scan, g->ctx[0]->opt.scan_presorted != 0) == 0;
-                             });
-              if (!host_ordered)
-                return ctx->fail(-3, "%s", host_order_error.c_str());
-              TRY(push_scan(ctx, g->scan, false));
-            }
-          }
-          TRY(ensure(ctx, ctx->packed, sizeof(double) * n_pack));
-          if (!resident && !staged)
-            ctx->poses_set(0);
-          if (n)
-          {
-            TRY(ensure(ctx, ctx->lik, fb));
-            TRY(ensure(ctx, ctx->ratio, fb));
-            TRY(ensure(ctx, ctx->beam, fb));
-            TRY(ensure(ctx, ctx->extra, fb));
-            if (!resident && !staged)
-            {
-              TRY(ensure(ctx, ctx->pose, sizeof(float) * 7 * n));
-              TRY(ensure(ctx, ctx->weightb, fb));
-              TRY(h2d(ctx, ctx->pose.p, pose + 7 * lo, sizeof(float) * 7 * n));
-              ctx->poses_set(n);
-              TRY(h2d(ctx, ctx->weightb.p, weight_inout + lo, fb));
-            }
-            float* d_w = resident ? ctx->gs_weight.as<float>() : (staged ? staged_weights(ctx, n) : ctx->weightb.as<float>());
-            rank_weights[r] = d_w;
-            if (extra && !staged)
-              TRY(h2d(ctx, ctx->extra.p, extra + lo, fb));
-            if (device_extra)
-            {
-              hipLaunchKernelGGL(odom_factor_kernel, dim3((static_cast<int>(n) + 255) / 256), dim3(256), 0, ctx->stream,
-                                 ctx->gs_state[ctx->gs_cur].as<float>(), static_cast<int>(n), nd_a, nd_sq2, ctx->extra.as<float>());
-              HIP_TRY(hipGetLastError());
-            }
-            // (the sum over the tiled kernel's per-tile partials and the beam model's last step ride in the first pf::measure kernel,
-            // as on one GPU: one launch less per model and rank)
-            LikTail tail;
-            tail.want = pf_tiles_fit(n);
-            tail.want_beam = true;
-            TRY(launch_measure(ctx, ctx->pose.as<float>(), n, ctx->lik.as<float>(), ctx->ratio.as<float>(),
-                               ctx->beam.as<float>(), &tail));
-            PfCall c{ ctx, d_w, ctx->lik.as<float>(), ctx->beam.as<float>(), (extra || device_extra) ? ctx->extra.as<float>() : nullptr,
-                      ctx->ratio.as<float>(), n, nullptr };
-            c.tail = &tail;
-            TRY(pf_first_half(c, r, N, ctx->packed.as<double>()));
-          }
-          else
-            TRY(pf_first_half_empty(ctx, r, N, ctx->packed.as<double>()));
-          if (r == inject)
-            return ctx->fail(-9, "injected failure ahead of the collective (test hook)");
-          return 0;
-        };
-        int rc_a = phase_a();
-        // the vote: the collective is entered by all ranks or by none
-        const bool all_ok = g->vote.vote(rc_a == 0);
-        if (rc_a == 0 && !all_ok)
-          rc_a = ctx->fail(RC_ABANDONED, "update abandoned: another rank failed ahead of the collective");
-        if (rc_a != 0)
-        {
-          (void)hipStreamSynchronize(ctx->stream);  // drain what this rank enqueued; its results are discarded
-          ctx->stage_out.clear();
-          ctx->stage_cur = 0;
-          ctx->stage_off = 0;
-          ctx->stage_pending = 0;
-          return rcs[r] = rc_a;
-        }
-        if (no_collective)
-          return rcs[r] = phase_b(ctx, r, lo, n);
-        if (host_combine)
-        {
-          g->host_packed[r].resize(n_pack);
-          TRY(d2h(ctx, g->host_packed[r].data(), ctx->packed.p, sizeof(double) * n_pack));
-          return rcs[r] = sync_stream(ctx);
-        }
-        // the update's single collective: 16 + 16 N bytes over xGMI, on this device's stream
-        const ncclResult_t nrc = g->rccl.AllReduce(ctx->packed.p, ctx->packed.p, n_pack, ncclDouble, ncclSum, g->comms[r],
-                                                   ctx->stream);
-        // second vote: a collective that one rank could not enqueue never completes on the ranks that did — nobody may
-        // wait for its stream then; the communicators are aborted below
-        const bool enqueued = g->vote.vote(nrc == ncclSuccess);
-        if (nrc != ncclSuccess)
-          return rcs[r] = ctx->fail(-7, "ncclAllReduce failed: %s", g->rccl.GetErrorString(nrc));
-        if (!enqueued)
-        {
-          ctx->stage_out.clear();
-          return rcs[r] = ctx->fail(RC_ABANDONED, "update abandoned: another rank could not enqueue the all-reduce");
-        }
-        return rcs[r] = phase_b(ctx, r, lo, n);
-      },
-      &bad);
-  if (rc)
-  {
-    // report the rank that actually failed, not one that merely stood down
-    for (int r = 0; r < N; ++r)
-      if (rcs[r] != 0 && rcs[r] != RC_ABANDONED)
-      {
-        rc = rcs[r];
-        bad = r;
-        break;
-      }
-    // communicators that saw a failed or abandoned update are rebuilt on next use
-    if (!host_combine && !g->comms.empty())
-      g->drop_comms();
-    return g->fail_rank(rc, bad);
-  }
-  if (host_combine)
-  {
-    // sum the N records in rank order (deterministic) and hand the total back to every device
-    std::vector<double> total(n_pack, 0.0);
-    for (int r = 0; r < N; ++r)
-      for (size_t i = 0; i < n_pack; ++i)
-        total[i] += g->host_packed[r][i];
-    rc = g->pool.run_all(
-        [&](int r) -> int
-        {
-          mcl3dl_hip_ctx* ctx = g->ctx[r];
-          size_t lo, hi;
-          shard_bounds(n_p, N, r, &lo, &hi);
-          HIP_TRY(hipSetDevice(ctx->device));
-          TRY(h2d(ctx, ctx->packed.p, total.data(), sizeof(double) * n_pack));
-          return phase_b(ctx, r, lo, hi - lo);
-        },
-        &bad);
-    if (rc)
-      return g->fail_rank(rc, bad);
-    ++g->collectives_host;
-  }
-  else if (!no_collective)
-    ++g->collectives_rccl;
+  // the round of DESIGN.md, "One round for every collective"
+  TRY(group_allreduce_record(
+      g, "update", n_p, [&u](const Shard& s) { return update_phase_a(u, s); }, [&u](const Shard& s) { return update_phase_b(u, s); }));
   g->n_pose_uploaded = n_p;
-  // every rank computed the same four scalars from the same all-reduced record: take the first non-empty shard's
-  int src = 0;
-  for (int r = 0; r < N; ++r)
-  {
-    size_t lo, hi;
-    shard_bounds(n_p, N, r, &lo, &hi);
-    if (hi > lo)
-    {
-      src = r;
-      break;
-    }
-  }
-  unpack_stats4(&stats[4 * src], entropy, match_ratio_min, match_ratio_max, restored);
+  unpack_stats4(&u.stats[4 * first_nonempty_rank(n_p)], out.entropy, out.match_ratio_min, out.match_ratio_max, out.restored);
   return 0;
 }
 }  // namespace
@@ -769,7 +647,7 @@ int mcl3dl_hip_group_measure_update(mcl3dl_hip_group* g, const float* pose, cons
 {
   if (!g)
     return -1;
-  return group_update_impl(g, false, pose, extra, weight_inout, n_p, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b,
-                           origins, n_o, out_lik, out_match_ratio, out_beam, entropy, match_ratio_min, match_ratio_max,
-                           restored);
+  return group_update_impl(g, false, pose, extra, n_p, HostScan{ scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o },
+                           UpdateOutputs{ weight_inout, out_lik, out_match_ratio, out_beam, entropy, match_ratio_min, match_ratio_max,
+                                          restored });
 }

@@ -39,32 +39,6 @@ MotionStep motion_step(const float* prev7, const float* cur7, float time_diff, f
   return m;
 }
 
-// the shard-local calls: f(ctx, n) on every rank whose shard holds particles
-int group_each_shard(mcl3dl_hip_group* g, const std::function<int(mcl3dl_hip_ctx*, int, size_t, size_t)>& f)
-{
-  const size_t n_p = g->n_resident;
-  if (n_p == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
-  const int N = g->n();
-  int bad = 0;
-  const int rc = g->pool.run_all(
-      [&](int r) -> int
-      {
-        mcl3dl_hip_ctx* ctx = g->ctx[r];
-        size_t lo, hi;
-        shard_bounds(n_p, N, r, &lo, &hi);
-        const size_t n = hi - lo;
-        if (n == 0)
-          return 0;
-        HIP_TRY(hipSetDevice(ctx->device));
-        if (ctx->gs_n != n)
-          return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, n);
-        return f(ctx, r, lo, n);
-      },
-      &bad);
-  return rc ? g->fail_rank(rc, bad) : 0;
-}
-
 inline dim3 grid_of(size_t n)
 {
   return dim3(static_cast<unsigned>((n + 255) / 256));
@@ -80,26 +54,23 @@ int mcl3dl_hip_group_set_odom_noise(mcl3dl_hip_group* g, const float* noise4, si
   if (g->n_resident == 0 || g->n_resident != n_p)
     return g->fail(-5, "%zu particles are resident, %zu noise records given", g->n_resident, n_p);
   const int N = g->n();
-  int bad = 0;
-  const int rc = g->pool.run_all(
-      [&](int r) -> int
+  const int rc = group_run_shards(
+      g, n_p,
+      [&](const Shard& s) -> int
       {
-        mcl3dl_hip_ctx* ctx = g->ctx[r];
-        size_t lo, hi;
-        shard_bounds(n_p, N, r, &lo, &hi);
+        mcl3dl_hip_ctx* ctx = s.ctx;
         HIP_TRY(hipSetDevice(ctx->device));
         // (room for the LARGEST shard on every rank, an empty one included: the resampling step's all-gather sends that many)
         TRY(ensure(ctx, ctx->gs_noise[ctx->gs_cur], sizeof(float) * 4 * ((n_p + N - 1) / N)));
-        if (hi == lo)
+        if (s.n == 0)
           return 0;
-        TRY(h2d(ctx, ctx->gs_noise[ctx->gs_cur].p, noise4 + 4 * lo, sizeof(float) * 4 * (hi - lo)));
+        TRY(h2d(ctx, ctx->gs_noise[ctx->gs_cur].p, noise4 + 4 * s.lo, sizeof(float) * 4 * s.n));
         return sync_stream(ctx);
-      },
-      &bad);
+      });
   if (rc)
   {
     g->noise_on = false;  // (some shards may hold the new noise, others none: the caller sets it again)
-    return g->fail_rank(rc, bad);
+    return rc;
   }
   g->noise_on = true;
   return 0;
@@ -218,31 +189,26 @@ namespace
 using ShardModel = std::function<int(mcl3dl_hip_ctx*, size_t, const float**, ImuGravity*)>;
 
 // pf::measure (pf.h:252-279) over the resident particles with the likelihoods of `model`: one device — the fused work-group up
-// to PF_FUSED_MAX_PARTICLES particles, else partial + apply; N shards — vote, partial sums, the 2 + 2N-double record all-reduced (RCCL, or
-// through the host), apply: the steps of mcl3dl_hip_group_update_resident. `what` names the update in error texts.
+// to PF_FUSED_MAX_PARTICLES particles, else partial + apply; N shards — the round of mcl3dl_hip_group_update_resident
+// (group_allreduce_record: partial sums, the 2 + 2N-double record summed, apply). `what` names the update in error texts.
 int group_measure_resident(mcl3dl_hip_group* g, const char* what, const ShardModel& model, float* out_weight, float* out_lik,
                            float* entropy, int* restored)
 {
   const size_t n_p = g->n_resident;
   const int N = g->n();
-  const bool no_collective = N == 1 && g->direct_single;
-  const bool host_combine = g->collective == 1 && !no_collective;
-  if (!no_collective)
-    TRY(group_comms(g));
-  const size_t n_pack = 2 + 2 * static_cast<size_t>(N);
   std::vector<float> stats(4 * static_cast<size_t>(N), 0.f);
   // the results of a rank home
-  const auto fetch = [&](mcl3dl_hip_ctx* ctx, int r, size_t lo, size_t n) -> int
+  const auto fetch = [&](const Shard& s) -> int
   {
-    TRY(d2h(ctx, &stats[4 * r], ctx->stats4.p, sizeof(float) * 4));
+    mcl3dl_hip_ctx* ctx = s.ctx;
+    TRY(d2h(ctx, &stats[4 * s.r], ctx->stats4.p, sizeof(float) * 4));
     if (out_weight)
-      TRY(d2h(ctx, out_weight + lo, ctx->gs_weight.p, sizeof(float) * n));
+      TRY(d2h(ctx, out_weight + s.lo, ctx->gs_weight.p, sizeof(float) * s.n));
     if (out_lik)
-      TRY(d2h(ctx, out_lik + lo, ctx->lik.p, sizeof(float) * n));
+      TRY(d2h(ctx, out_lik + s.lo, ctx->lik.p, sizeof(float) * s.n));
     return sync_stream(ctx);
   };
-  int bad = 0;
-  if (no_collective)
+  if (N == 1 && g->direct_single)
   {
     // one device: pf::measure as mcl3dl_hip_group_update_resident's single-GPU form runs it (pf_one_gpu: the fused
     // work-group up to PF_FUSED_MAX_PARTICLES particles, else partial + apply), the likelihood formed inside — one or two launches
@@ -263,126 +229,42 @@ int group_measure_resident(mcl3dl_hip_group* g, const char* what, const ShardMod
       PfCall c{ ctx, ctx->gs_weight.as<float>(), const_cast<float*>(d_lik), nullptr, nullptr, nullptr, n, ctx->stats4.as<float>() };
       c.model = &m;
       TRY(pf_one_gpu(c));
-      return fetch(ctx, 0, 0, n);
+      return fetch(Shard{ ctx, 0, 0, n });
     }();
     if (rc)
       return g->fail_rank(rc, 0);
   }
   else
-  {
-    // N shards: partial sums, the record all-reduced (RCCL, or through the host), apply — the steps and the 2 + 2N-double
-    // record of mcl3dl_hip_group_update_resident
-    std::vector<int> rcs(N, 0);
-    constexpr int RC_ABANDONED = -8;
-    const auto phase_b = [&](mcl3dl_hip_ctx* ctx, int r, size_t lo, size_t n) -> int
-    {
-      if (n == 0)
-        return sync_stream(ctx);
-      PfCall c{ ctx, ctx->gs_weight.as<float>(), nullptr, nullptr, nullptr, nullptr, n, ctx->stats4.as<float>() };
-      c.timed = false;
-      TRY(pf_second_half(c, N, ctx->packed.as<double>()));
-      return fetch(ctx, r, lo, n);
-    };
-    int rc = g->pool.run_all(
-        [&](int r) -> int
+    TRY(group_allreduce_record(
+        g, what, n_p,
+        [&](const Shard& s) -> int
         {
-          mcl3dl_hip_ctx* ctx = g->ctx[r];
-          size_t lo, hi;
-          shard_bounds(n_p, N, r, &lo, &hi);
-          const size_t n = hi - lo;
-          const auto phase_a = [&]() -> int
-          {
-            HIP_TRY(hipSetDevice(ctx->device));
-            TRY(ensure(ctx, ctx->packed, sizeof(double) * n_pack));
-            TRY(ensure(ctx, ctx->stats4, sizeof(float) * 4));
-            if (n == 0)
-              return pf_first_half_empty(ctx, r, N, ctx->packed.as<double>());
-            if (ctx->gs_n != n)
-              return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, n);
-            TRY(ensure(ctx, ctx->lik, sizeof(float) * n));
-            ImuGravity m{};
-            const float* d_lik = nullptr;
-            TRY(model(ctx, n, &d_lik, &m));
-            PfCall c{ ctx, ctx->gs_weight.as<float>(), const_cast<float*>(d_lik), nullptr, nullptr, nullptr, n, nullptr };
-            c.model = &m;
-            c.timed = false;
-            return pf_first_half(c, r, N, ctx->packed.as<double>());
-          };
-          int rc_a = phase_a();
-          const bool all_ok = g->vote.vote(rc_a == 0);
-          if (rc_a == 0 && !all_ok)
-            rc_a = ctx->fail(RC_ABANDONED, "%s abandoned: another rank failed ahead of the collective", what);
-          if (rc_a != 0)
-          {
-            (void)hipStreamSynchronize(ctx->stream);
-            return rcs[r] = rc_a;
-          }
-          if (host_combine)
-          {
-            g->host_packed[r].resize(n_pack);
-            TRY(d2h(ctx, g->host_packed[r].data(), ctx->packed.p, sizeof(double) * n_pack));
-            return rcs[r] = sync_stream(ctx);
-          }
-          const ncclResult_t nrc = g->rccl.AllReduce(ctx->packed.p, ctx->packed.p, n_pack, ncclDouble, ncclSum, g->comms[r],
-                                                     ctx->stream);
-          const bool enqueued = g->vote.vote(nrc == ncclSuccess);
-          if (nrc != ncclSuccess)
-            return rcs[r] = ctx->fail(-7, "ncclAllReduce failed: %s", g->rccl.GetErrorString(nrc));
-          if (!enqueued)
-            return rcs[r] = ctx->fail(RC_ABANDONED, "%s abandoned: another rank could not enqueue the all-reduce", what);
-          return rcs[r] = phase_b(ctx, r, lo, n);
+          mcl3dl_hip_ctx* ctx = s.ctx;
+          TRY(ensure(ctx, ctx->stats4, sizeof(float) * 4));
+          if (s.n == 0)
+            return pf_first_half_empty(ctx, s.r, N, ctx->packed.as<double>());
+          if (ctx->gs_n != s.n)
+            return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, s.n);
+          TRY(ensure(ctx, ctx->lik, sizeof(float) * s.n));
+          ImuGravity m{};
+          const float* d_lik = nullptr;
+          TRY(model(ctx, s.n, &d_lik, &m));
+          PfCall c{ ctx, ctx->gs_weight.as<float>(), const_cast<float*>(d_lik), nullptr, nullptr, nullptr, s.n, nullptr };
+          c.model = &m;
+          c.timed = false;
+          return pf_first_half(c, s.r, N, ctx->packed.as<double>());
         },
-        &bad);
-    if (rc)
-    {
-      for (int r = 0; r < N; ++r)
-        if (rcs[r] != 0 && rcs[r] != RC_ABANDONED)
+        [&](const Shard& s) -> int
         {
-          rc = rcs[r];
-          bad = r;
-          break;
-        }
-      if (!host_combine && !g->comms.empty())
-        g->drop_comms();
-      return g->fail_rank(rc, bad);
-    }
-    if (host_combine)
-    {
-      std::vector<double> total(n_pack, 0.0);
-      for (int r = 0; r < N; ++r)  // rank order: deterministic
-        for (size_t i = 0; i < n_pack; ++i)
-          total[i] += g->host_packed[r][i];
-      rc = g->pool.run_all(
-          [&](int r) -> int
-          {
-            mcl3dl_hip_ctx* ctx = g->ctx[r];
-            size_t lo, hi;
-            shard_bounds(n_p, N, r, &lo, &hi);
-            HIP_TRY(hipSetDevice(ctx->device));
-            TRY(h2d(ctx, ctx->packed.p, total.data(), sizeof(double) * n_pack));
-            return phase_b(ctx, r, lo, hi - lo);
-          },
-          &bad);
-      if (rc)
-        return g->fail_rank(rc, bad);
-      ++g->collectives_host;
-    }
-    else
-      ++g->collectives_rccl;
-  }
-  // every rank computed the same scalars from the same record: the first non-empty shard's
-  int src = 0;
-  for (int r = 0; r < N; ++r)
-  {
-    size_t lo, hi;
-    shard_bounds(n_p, N, r, &lo, &hi);
-    if (hi > lo)
-    {
-      src = r;
-      break;
-    }
-  }
-  unpack_stats4(&stats[4 * src], entropy, nullptr, nullptr, restored);
+          if (s.n == 0)
+            return sync_stream(s.ctx);
+          PfCall c{ s.ctx, s.ctx->gs_weight.as<float>(), nullptr, nullptr, nullptr, nullptr, s.n, s.ctx->stats4.as<float>() };
+          c.timed = false;
+          TRY(pf_second_half(c, N, s.ctx->packed.as<double>()));
+          return fetch(s);
+        }));
+  // every rank computed the same scalars from the same record
+  unpack_stats4(&stats[4 * first_nonempty_rank(n_p)], entropy, nullptr, nullptr, restored);
   return 0;
 }
 }  // namespace

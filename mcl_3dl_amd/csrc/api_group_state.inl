@@ -72,15 +72,13 @@ int mcl3dl_hip_group_upload_state(mcl3dl_hip_group* g, const float* state13, con
   g->n_resident = 0;
   g->rs_begun = g->rs_planned = false;
   g->noise_on = false;  // State6DOF's constructors: no odometry noise until set_odom_noise
-  int bad = 0;
   const int N = g->n();
-  const int rc = g->pool.run_all(
-      [&](int r) -> int
+  TRY(group_run_shards(
+      g, n_p,
+      [&](const Shard& s) -> int
       {
-        mcl3dl_hip_ctx* ctx = g->ctx[r];
-        size_t lo, hi;
-        shard_bounds(n_p, N, r, &lo, &hi);
-        const size_t n = hi - lo;
+        mcl3dl_hip_ctx* ctx = s.ctx;
+        const size_t lo = s.lo, n = s.n;
         HIP_TRY(hipSetDevice(ctx->device));
         ctx->gs_n = 0;
         ctx->gs_cur = 0;
@@ -100,10 +98,7 @@ int mcl3dl_hip_group_upload_state(mcl3dl_hip_group* g, const float* state13, con
         TRY(rebuild_pose(ctx, n));
         ctx->gs_n = n;
         return sync_stream(ctx);
-      },
-      &bad);
-  if (rc)
-    return g->fail_rank(rc, bad);
+      }));
   g->n_resident = n_p;
   g->n_pose_uploaded = n_p;
   return 0;
@@ -115,15 +110,12 @@ int mcl3dl_hip_group_download_state(mcl3dl_hip_group* g, float* state13, float* 
     return -1;
   if (g->n_resident == 0 || g->n_resident != n_p)
     return g->fail(-5, "%zu particles are resident, %zu asked for", g->n_resident, n_p);
-  int bad = 0;
-  const int N = g->n();
-  const int rc = g->pool.run_all(
-      [&](int r) -> int
+  return group_run_shards(
+      g, n_p,
+      [&](const Shard& s) -> int
       {
-        mcl3dl_hip_ctx* ctx = g->ctx[r];
-        size_t lo, hi;
-        shard_bounds(n_p, N, r, &lo, &hi);
-        const size_t n = hi - lo;
+        mcl3dl_hip_ctx* ctx = s.ctx;
+        const size_t lo = s.lo, n = s.n;
         if (n == 0)
           return 0;
         HIP_TRY(hipSetDevice(ctx->device));
@@ -132,9 +124,7 @@ int mcl3dl_hip_group_download_state(mcl3dl_hip_group* g, float* state13, float* 
         if (weight)
           TRY(d2h(ctx, weight + lo, ctx->gs_weight.p, sizeof(float) * n));
         return sync_stream(ctx);
-      },
-      &bad);
-  return rc ? g->fail_rank(rc, bad) : 0;
+      });
 }
 
 size_t mcl3dl_hip_group_resident(const mcl3dl_hip_group* g)
@@ -150,9 +140,10 @@ int mcl3dl_hip_group_update_resident(mcl3dl_hip_group* g, const float* extra, co
 {
   if (!g)
     return -1;
-  return group_update_impl(g, true, nullptr, extra, out_weight, g->n_resident, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin,
-                           n_b, origins, n_o, out_lik, out_match_ratio, out_beam, entropy, match_ratio_min, match_ratio_max,
-                           restored);
+  return group_update_impl(g, true, nullptr, extra, g->n_resident,
+                           HostScan{ scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o },
+                           UpdateOutputs{ out_weight, out_lik, out_match_ratio, out_beam, entropy, match_ratio_min, match_ratio_max,
+                                          restored });
 }
 
 // ---- scan preparation on a group: every rank prepares its own replica of the cloud (deterministic, no collective, as the
@@ -167,9 +158,7 @@ int group_scan_each(mcl3dl_hip_group* g, const std::function<int(mcl3dl_hip_ctx*
     const int rc = f(g->ctx[0], 0);
     return rc ? g->fail_rank(rc, 0) : 0;
   }
-  int bad = 0;
-  const int rc = g->pool.run_all([&](int r) -> int { return f(g->ctx[r], r); }, &bad);
-  return rc ? g->fail_rank(rc, bad) : 0;
+  return group_run(g, [&](int r) -> int { return f(g->ctx[r], r); });
 }
 
 // three sizes per rank -> the caller's, when all ranks agree (rng_hand_back's rule for the engine state)
@@ -304,9 +293,11 @@ int mcl3dl_hip_group_update_resident_prepared(mcl3dl_hip_group* g, const float* 
       return g->fail(-5, "rank %d holds a scan of %zu + %zu points and %zu origins, rank 0 one of %zu + %zu and %zu", r, c->n_s,
                      c->n_b, c->n_o, c0->n_s, c0->n_b, c0->n_o);
   }
-  return group_update_impl(g, true, nullptr, extra, out_weight, g->n_resident, nullptr, g->ctx[0]->n_s, nullptr, nullptr,
-                           g->ctx[0]->n_b, nullptr, g->ctx[0]->n_o, out_lik, out_match_ratio, out_beam, entropy, match_ratio_min,
-                           match_ratio_max, restored, true);
+  return group_update_impl(g, true, nullptr, extra, g->n_resident,
+                           HostScan{ nullptr, g->ctx[0]->n_s, nullptr, nullptr, g->ctx[0]->n_b, nullptr, g->ctx[0]->n_o },
+                           UpdateOutputs{ out_weight, out_lik, out_match_ratio, out_beam, entropy, match_ratio_min, match_ratio_max,
+                                          restored },
+                           true);
 }
 
 namespace
@@ -322,14 +313,13 @@ int group_expectation_impl(mcl3dl_hip_group* g, const float* bias, const JumpBia
   const int N = g->n();
   g->h_parts.assign(16 * static_cast<size_t>(N), 0.0);
   std::vector<uint64_t> offsets(N, 0);
-  int bad = 0;
-  const int rc = g->pool.run_all(
-      [&](int r) -> int
+  TRY(group_run_shards(
+      g, n_p,
+      [&](const Shard& s) -> int
       {
-        mcl3dl_hip_ctx* ctx = g->ctx[r];
-        size_t lo, hi;
-        shard_bounds(n_p, N, r, &lo, &hi);
-        const size_t n = hi - lo;
+        mcl3dl_hip_ctx* ctx = s.ctx;
+        const int r = s.r;
+        const size_t lo = s.lo, n = s.n;
         offsets[r] = lo;
         double* rec = &g->h_parts[16 * static_cast<size_t>(r)];
         if (n == 0)
@@ -366,10 +356,7 @@ int group_expectation_impl(mcl3dl_hip_group* g, const float* bias, const JumpBia
         if (jump && out_bias)
           TRY(d2h(ctx, out_bias + lo, ctx->extra.p, sizeof(float) * n));
         return sync_stream(ctx);
-      },
-      &bad);
-  if (rc)
-    return g->fail_rank(rc, bad);
+      }));
   if (mcl3dl_hip_moments_finish(g->h_parts.data(), N, offsets.data(), out_mean7, out_total, out_max_index,
                                 out_max_biased_index) != 0)
     return g->fail(-3, "moments_finish rejected the records");
@@ -420,12 +407,12 @@ int mcl3dl_hip_group_download_particle(mcl3dl_hip_group* g, int64_t index, float
   const size_t i = static_cast<size_t>(index);
   for (int r = 0; r < N; ++r)
   {
-    size_t lo, hi;
-    shard_bounds(n_p, N, r, &lo, &hi);
+    const Shard s = shard_of(g, n_p, r);
+    const size_t lo = s.lo, hi = s.lo + s.n;
     if (i < lo || i >= hi)
       continue;
     // one rank, 52 + 4 bytes, no collective: on the calling thread
-    mcl3dl_hip_ctx* ctx = g->ctx[r];
+    mcl3dl_hip_ctx* ctx = s.ctx;
     const int rc = [&]() -> int
     {
       HIP_TRY(hipSetDevice(ctx->device));
@@ -453,27 +440,21 @@ int mcl3dl_hip_group_covariance(mcl3dl_hip_group* g, const float* mean7, float* 
     return g->fail(-3, "null mean / covariance array");
   const int N = g->n();
   g->h_parts.assign(22 * static_cast<size_t>(N), 0.0);
-  int bad = 0;
-  const int rc = g->pool.run_all(
-      [&](int r) -> int
+  TRY(group_run_shards(
+      g, n_p,
+      [&](const Shard& s) -> int
       {
-        mcl3dl_hip_ctx* ctx = g->ctx[r];
-        size_t lo, hi;
-        shard_bounds(n_p, N, r, &lo, &hi);
-        const size_t n = hi - lo;
-        if (n == 0)
+        mcl3dl_hip_ctx* ctx = s.ctx;
+        if (s.n == 0)
           return 0;
         HIP_TRY(hipSetDevice(ctx->device));
         TRY(ensure(ctx, ctx->gs_rec, sizeof(double) * 32));
         TRY(resident_poses(ctx));
-        TRY(mcl3dl_hip_covariance_partial_device(ctx, ctx->pose.as<float>(), ctx->gs_weight.as<float>(), n, nullptr, 0, mean7,
+        TRY(mcl3dl_hip_covariance_partial_device(ctx, ctx->pose.as<float>(), ctx->gs_weight.as<float>(), s.n, nullptr, 0, mean7,
                                                  ctx->gs_rec.as<double>()));
-        TRY(d2h(ctx, &g->h_parts[22 * static_cast<size_t>(r)], ctx->gs_rec.p, sizeof(double) * 22));
+        TRY(d2h(ctx, &g->h_parts[22 * static_cast<size_t>(s.r)], ctx->gs_rec.p, sizeof(double) * 22));
         return sync_stream(ctx);
-      },
-      &bad);
-  if (rc)
-    return g->fail_rank(rc, bad);
+      }));
   double total[22] = { 0 };
   for (int r = 0; r < N; ++r)  // rank order: deterministic
     for (int k = 0; k < 22; ++k)
@@ -496,11 +477,7 @@ int mcl3dl_hip_group_resample_begin(mcl3dl_hip_group* g, size_t n_out, float* ou
   TRY(mcl3dl_hip_group_download_state(g, nullptr, g->h_weight.data(), n_p));
   const int N = g->n();
   std::vector<float> pstep(N, 0.f);
-  int bad = 0;
-  const int rc = g->pool.run_all(
-      [&](int r) -> int { return mcl3dl_hip_resample_begin(g->ctx[r], g->h_weight.data(), n_p, n_out, &pstep[r]); }, &bad);
-  if (rc)
-    return g->fail_rank(rc, bad);
+  TRY(group_run(g, [&](int r) -> int { return mcl3dl_hip_resample_begin(g->ctx[r], g->h_weight.data(), n_p, n_out, &pstep[r]); }));
   g->rs_n_out = n_out;
   g->rs_begun = true;
   if (out_pstep)
@@ -517,16 +494,12 @@ int mcl3dl_hip_group_resample_plan(mcl3dl_hip_group* g, int mode, float initial_
     return g->fail(-5, "group_resample_plan before group_resample_begin");
   const int N = g->n();
   std::vector<size_t> n_dup(N, 0);
-  int bad = 0;
-  const int rc = g->pool.run_all(
-      [&](int r) -> int
-      {
-        return mcl3dl_hip_resample_plan(g->ctx[r], mode, initial_p, r == 0 ? out_source : nullptr,
-                                        r == 0 ? out_duplicate : nullptr, &n_dup[r]);
-      },
-      &bad);
-  if (rc)
-    return g->fail_rank(rc, bad);
+  TRY(group_run(g,
+                [&](int r) -> int
+                {
+                  return mcl3dl_hip_resample_plan(g->ctx[r], mode, initial_p, r == 0 ? out_source : nullptr,
+                                                  r == 0 ? out_duplicate : nullptr, &n_dup[r]);
+                }));
   for (int r = 1; r < N; ++r)
     if (n_dup[r] != n_dup[0])
       return g->fail(-4, "the ranks disagree on the resampling plan (%zu and %zu duplicated particles)", n_dup[0], n_dup[r]);
@@ -565,156 +538,120 @@ int group_resample_apply_impl(mcl3dl_hip_group* g, const float* noise13, size_t 
     }
   }
   const size_t base = n_p / N, rem = n_p % N, max_count = base + (rem ? 1 : 0);
-  int bad = 0;
-  std::vector<int> rcs(N, 0);
-  constexpr int RC_ABANDONED = -8;
-  int rc = g->pool.run_all(
-      [&](int r) -> int
+  const bool over_rccl = !single && !host_gather;
+  // everything ahead of the collective; the all-gather is entered by all ranks or by none (group_voted_call)
+  const auto prepare = [&](const Shard& s) -> int
+  {
+    mcl3dl_hip_ctx* ctx = s.ctx;
+    const int other = ctx->gs_cur ^ 1;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t cap_new = std::max<size_t>((n_out + N - 1) / N, 1);
+    TRY(ensure(ctx, ctx->gs_state[other], sizeof(float) * 13 * cap_new));
+    TRY(ensure(ctx, ctx->gs_weight, sizeof(float) * cap_new));
+    if (with_noise)
+      TRY(ensure(ctx, ctx->gs_noise[other], sizeof(float) * 4 * cap_new));
+    if (single)
+      return 0;
+    TRY(ensure(ctx, ctx->gs_all, sizeof(float) * 13 * n_p));
+    if (with_noise)
+      TRY(ensure(ctx, ctx->gs_noise_all, sizeof(float) * 4 * n_p));
+    if (host_gather)
+    {
+      if (with_noise)
+        TRY(h2d(ctx, ctx->gs_noise_all.p, g->h_noise.data(), sizeof(float) * 4 * n_p));
+      return h2d(ctx, ctx->gs_all.p, g->h_state.data(), sizeof(float) * 13 * n_p);
+    }
+    TRY(ensure(ctx, ctx->gs_pad, sizeof(float) * 13 * max_count * static_cast<size_t>(N)));
+    if (ctx->gs_state[ctx->gs_cur].cap < sizeof(float) * 13 * max_count)  // (every shard buffer holds the largest shard)
+      return ctx->fail(-4, "internal: shard buffer smaller than the all-gather's send count");
+    if (with_noise)
+    {
+      TRY(ensure(ctx, ctx->gs_noise_pad, sizeof(float) * 4 * max_count * static_cast<size_t>(N)));
+      if (ctx->gs_noise[ctx->gs_cur].cap < sizeof(float) * 4 * max_count)
+        return ctx->fail(-4, "internal: noise buffer smaller than the all-gather's send count");
+    }
+    return 0;
+  };
+  // the all-gather(s), then the rank's slice of the new generation
+  const auto apply = [&](const Shard& s, const VotedRank& voted) -> int
+  {
+    mcl3dl_hip_ctx* ctx = s.ctx;
+    const int r = s.r, other = ctx->gs_cur ^ 1;
+    size_t olo, ohi;
+    shard_bounds(n_out, N, r, &olo, &ohi);
+    const size_t n_new = ohi - olo;
+    const float* d_all = nullptr;
+    const float* d_noise_all = nullptr;
+    if (single)
+    {
+      d_all = ctx->gs_state[ctx->gs_cur].as<float>();
+      d_noise_all = ctx->gs_noise[ctx->gs_cur].as<float>();
+    }
+    else if (host_gather)
+    {
+      d_all = ctx->gs_all.as<float>();
+      d_noise_all = ctx->gs_noise_all.as<float>();
+    }
+    else
+    {
+      // 13 floats x max_count per rank over xGMI into the padded layout, then into particle order
+      TRY(voted.enqueued(g->rccl.AllGather(ctx->gs_state[ctx->gs_cur].p, ctx->gs_pad.p, 13 * max_count, ncclFloat, g->comms[r],
+                                           ctx->stream),
+                         "ncclAllGather"));
+      const size_t total = 13 * n_p;
+      hipLaunchKernelGGL(unpad_states_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, ctx->stream,
+                         ctx->gs_pad.as<float>(), max_count, base, rem, n_p, ctx->gs_all.as<float>());
+      HIP_TRY(hipGetLastError());
+      d_all = ctx->gs_all.as<float>();
+      if (with_noise)
       {
-        mcl3dl_hip_ctx* ctx = g->ctx[r];
-        size_t lo, hi, olo, ohi;
-        shard_bounds(n_p, N, r, &lo, &hi);
-        shard_bounds(n_out, N, r, &olo, &ohi);
-        const size_t n = hi - lo, n_new = ohi - olo;
-        const int other = ctx->gs_cur ^ 1;
-        const float* d_all = nullptr;
-        const float* d_noise_all = nullptr;
-        // everything ahead of the collective; the all-gather is entered by all ranks or by none
-        const auto prepare = [&]() -> int
-        {
-          HIP_TRY(hipSetDevice(ctx->device));
-          const size_t cap_new = std::max<size_t>((n_out + N - 1) / N, 1);
-          TRY(ensure(ctx, ctx->gs_state[other], sizeof(float) * 13 * cap_new));
-          TRY(ensure(ctx, ctx->gs_weight, sizeof(float) * cap_new));
-          if (with_noise)
-            TRY(ensure(ctx, ctx->gs_noise[other], sizeof(float) * 4 * cap_new));
-          if (single)
-            return 0;
-          TRY(ensure(ctx, ctx->gs_all, sizeof(float) * 13 * n_p));
-          if (with_noise)
-            TRY(ensure(ctx, ctx->gs_noise_all, sizeof(float) * 4 * n_p));
-          if (host_gather)
-          {
-            if (with_noise)
-              TRY(h2d(ctx, ctx->gs_noise_all.p, g->h_noise.data(), sizeof(float) * 4 * n_p));
-            return h2d(ctx, ctx->gs_all.p, g->h_state.data(), sizeof(float) * 13 * n_p);
-          }
-          TRY(ensure(ctx, ctx->gs_pad, sizeof(float) * 13 * max_count * static_cast<size_t>(N)));
-          if (ctx->gs_state[ctx->gs_cur].cap < sizeof(float) * 13 * max_count)  // (every shard buffer holds the largest shard)
-            return ctx->fail(-4, "internal: shard buffer smaller than the all-gather's send count");
-          if (with_noise)
-          {
-            TRY(ensure(ctx, ctx->gs_noise_pad, sizeof(float) * 4 * max_count * static_cast<size_t>(N)));
-            if (ctx->gs_noise[ctx->gs_cur].cap < sizeof(float) * 4 * max_count)
-              return ctx->fail(-4, "internal: noise buffer smaller than the all-gather's send count");
-          }
-          return 0;
-        };
-        int rc_p = prepare();
-        const bool all_ok = g->vote.vote(rc_p == 0);
-        if (rc_p == 0 && !all_ok)
-          rc_p = ctx->fail(RC_ABANDONED, "resampling abandoned: another rank failed ahead of the all-gather");
-        if (rc_p != 0)
-        {
-          (void)hipStreamSynchronize(ctx->stream);
-          ctx->stage_out.clear();
-          ctx->stage_cur = 0;
-          ctx->stage_off = 0;
-          ctx->stage_pending = 0;
-          return rcs[r] = rc_p;
-        }
-        if (single)
-        {
-          d_all = ctx->gs_state[ctx->gs_cur].as<float>();
-          d_noise_all = ctx->gs_noise[ctx->gs_cur].as<float>();
-        }
-        else if (host_gather)
-        {
-          d_all = ctx->gs_all.as<float>();
-          d_noise_all = ctx->gs_noise_all.as<float>();
-        }
-        else
-        {
-          // 13 floats x max_count per rank over xGMI into the padded layout, then into particle order
-          const ncclResult_t nrc = g->rccl.AllGather(ctx->gs_state[ctx->gs_cur].p, ctx->gs_pad.p, 13 * max_count, ncclFloat,
-                                                     g->comms[r], ctx->stream);
-          const bool enqueued = g->vote.vote(nrc == ncclSuccess);
-          if (nrc != ncclSuccess)
-            return rcs[r] = ctx->fail(-7, "ncclAllGather failed: %s", g->rccl.GetErrorString(nrc));
-          if (!enqueued)
-            return rcs[r] = ctx->fail(RC_ABANDONED, "resampling abandoned: another rank could not enqueue the all-gather");
-          const size_t total = 13 * n_p;
-          hipLaunchKernelGGL(unpad_states_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                             ctx->gs_pad.as<float>(), max_count, base, rem, n_p, ctx->gs_all.as<float>());
-          HIP_TRY(hipGetLastError());
-          d_all = ctx->gs_all.as<float>();
-          if (with_noise)
-          {
-            // the four noise floats of every particle the same way: a second all-gather, only while noise is installed
-            const ncclResult_t nrc2 = g->rccl.AllGather(ctx->gs_noise[ctx->gs_cur].p, ctx->gs_noise_pad.p, 4 * max_count,
-                                                        ncclFloat, g->comms[r], ctx->stream);
-            const bool enqueued2 = g->vote.vote(nrc2 == ncclSuccess);
-            if (nrc2 != ncclSuccess)
-              return rcs[r] = ctx->fail(-7, "ncclAllGather (odometry noise) failed: %s", g->rccl.GetErrorString(nrc2));
-            if (!enqueued2)
-              return rcs[r] = ctx->fail(RC_ABANDONED, "resampling abandoned: another rank could not enqueue the all-gather");
-            hipLaunchKernelGGL(unpad_states_kernel, dim3(static_cast<unsigned>((4 * n_p + 255) / 256)), dim3(256), 0, ctx->stream,
-                               ctx->gs_noise_pad.as<float>(), max_count, base, rem, n_p, ctx->gs_noise_all.as<float>(),
-                               static_cast<size_t>(4));
-            HIP_TRY(hipGetLastError());
-            d_noise_all = ctx->gs_noise_all.as<float>();
-          }
-        }
-        (void)n;
-        if (n_new)
-        {
-          if (drawn)
-          {
-            TRY(resample_slice_check(ctx, d_all, olo, n_new, ctx->gs_state[other].as<float>()));
-            TRY((*drawn)(ctx, r, olo, n_new));
-            TRY(resample_slice_launch(ctx, d_all, olo, n_new, ctx->gs_state[other].as<float>()));
-          }
-          else
-            TRY(mcl3dl_hip_resample_apply_slice_device(ctx, d_all, noise13, n_noise, olo, n_new, ctx->gs_state[other].as<float>()));
-          if (with_noise)
-          {
-            hipLaunchKernelGGL(resample_noise_kernel, dim3((static_cast<int>(n_new) + 255) / 256), dim3(256), 0, ctx->stream,
-                               d_noise_all, ctx->rs_d_source.as<uint32_t>() + olo, ctx->rs_d_slot.as<uint32_t>() + olo,
-                               static_cast<int>(n_new), ctx->gs_noise[other].as<float>());
-            HIP_TRY(hipGetLastError());
-          }
-          // pf.h:207 / 417: every particle of the new generation weighs 1 / n
-          hipLaunchKernelGGL(fill_kernel, dim3((static_cast<int>(n_new) + 255) / 256), dim3(256), 0, ctx->stream,
-                             ctx->gs_weight.as<float>(), 1.0f / static_cast<float>(n_out), static_cast<float*>(nullptr), 0.0f,
-                             static_cast<int>(n_new));
-          HIP_TRY(hipGetLastError());
-        }
-        ctx->gs_cur = other;
-        ctx->gs_n = n_new;
-        TRY(rebuild_pose(ctx, n_new));
-        return rcs[r] = sync_stream(ctx);
-      },
-      &bad);
+        // the four noise floats of every particle the same way: a second all-gather, only while noise is installed
+        TRY(voted.enqueued(g->rccl.AllGather(ctx->gs_noise[ctx->gs_cur].p, ctx->gs_noise_pad.p, 4 * max_count, ncclFloat,
+                                             g->comms[r], ctx->stream),
+                           "ncclAllGather (odometry noise)"));
+        hipLaunchKernelGGL(unpad_states_kernel, dim3(static_cast<unsigned>((4 * n_p + 255) / 256)), dim3(256), 0, ctx->stream,
+                           ctx->gs_noise_pad.as<float>(), max_count, base, rem, n_p, ctx->gs_noise_all.as<float>(),
+                           static_cast<size_t>(4));
+        HIP_TRY(hipGetLastError());
+        d_noise_all = ctx->gs_noise_all.as<float>();
+      }
+    }
+    if (n_new)
+    {
+      if (drawn)
+      {
+        TRY(resample_slice_check(ctx, d_all, olo, n_new, ctx->gs_state[other].as<float>()));
+        TRY((*drawn)(ctx, r, olo, n_new));
+        TRY(resample_slice_launch(ctx, d_all, olo, n_new, ctx->gs_state[other].as<float>()));
+      }
+      else
+        TRY(mcl3dl_hip_resample_apply_slice_device(ctx, d_all, noise13, n_noise, olo, n_new, ctx->gs_state[other].as<float>()));
+      if (with_noise)
+      {
+        hipLaunchKernelGGL(resample_noise_kernel, dim3((static_cast<int>(n_new) + 255) / 256), dim3(256), 0, ctx->stream,
+                           d_noise_all, ctx->rs_d_source.as<uint32_t>() + olo, ctx->rs_d_slot.as<uint32_t>() + olo,
+                           static_cast<int>(n_new), ctx->gs_noise[other].as<float>());
+        HIP_TRY(hipGetLastError());
+      }
+      // pf.h:207 / 417: every particle of the new generation weighs 1 / n
+      hipLaunchKernelGGL(fill_kernel, dim3((static_cast<int>(n_new) + 255) / 256), dim3(256), 0, ctx->stream,
+                         ctx->gs_weight.as<float>(), 1.0f / static_cast<float>(n_out), static_cast<float*>(nullptr), 0.0f,
+                         static_cast<int>(n_new));
+      HIP_TRY(hipGetLastError());
+    }
+    ctx->gs_cur = other;
+    ctx->gs_n = n_new;
+    TRY(rebuild_pose(ctx, n_new));
+    return sync_stream(ctx);
+  };
+  const int rc = group_voted_call(VotedCall{ g, "resampling", "all-gather" }, n_p, over_rccl, !single, prepare, apply);
   g->rs_begun = g->rs_planned = false;
   if (rc)
   {
-    for (int r = 0; r < N; ++r)
-      if (rcs[r] != 0 && rcs[r] != RC_ABANDONED)
-      {
-        rc = rcs[r];
-        bad = r;
-        break;
-      }
-    if (!single && !host_gather && !g->comms.empty())
-      g->drop_comms();
     g->n_resident = 0;  // the shards may be half way into the new generation
     g->noise_on = false;
-    return g->fail_rank(rc, bad);
+    return rc;
   }
-  if (!single && !host_gather)
-    ++g->collectives_rccl;
-  else if (host_gather)
-    ++g->collectives_host;
   g->n_resident = n_out;
   g->n_pose_uploaded = n_out;
   return 0;

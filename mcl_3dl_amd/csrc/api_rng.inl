@@ -161,14 +161,13 @@ int mcl3dl_hip_group_init_drawn(mcl3dl_hip_group* g, const float* mean7, const f
   std::vector<char> drew(N, 0);
   const uint32_t x0 = *engine_state;
   const float weight = static_cast<float>(1.0 / static_cast<double>(n_p));  // pf.h:179
-  int bad = 0;
-  const int rc = g->pool.run_all(
-      [&](int r) -> int
+  TRY(group_run_shards(
+      g, n_p,
+      [&](const Shard& s) -> int
       {
-        mcl3dl_hip_ctx* ctx = g->ctx[r];
-        size_t lo, hi;
-        shard_bounds(n_p, N, r, &lo, &hi);
-        const size_t n = hi - lo;
+        mcl3dl_hip_ctx* ctx = s.ctx;
+        const int r = s.r;
+        const size_t lo = s.lo, n = s.n;
         HIP_TRY(hipSetDevice(ctx->device));
         ctx->gs_n = 0;
         ctx->gs_cur = 0;
@@ -186,10 +185,7 @@ int mcl3dl_hip_group_init_drawn(mcl3dl_hip_group* g, const float* mean7, const f
         TRY(rebuild_pose(ctx, n));
         ctx->gs_n = n;
         return sync_stream(ctx);
-      },
-      &bad);
-  if (rc)
-    return g->fail_rank(rc, bad);
+      }));
   TRY(rng_hand_back(g, states, drew, engine_state));
   g->n_resident = n_p;
   g->n_pose_uploaded = n_p;

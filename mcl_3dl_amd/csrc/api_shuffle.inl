@@ -18,22 +18,13 @@ namespace
 int group_covariance_over(mcl3dl_hip_group* g, const float* mean7, const uint32_t* host_list, size_t m,
                           const std::function<int(mcl3dl_hip_ctx*, int, const uint32_t**)>* make, float* out_cov36)
 {
-  const size_t n_p = g->n_resident;
   const int N = g->n();
   g->h_parts.assign(22 * static_cast<size_t>(N), 0.0);
-  int bad = 0;
-  const int rc = g->pool.run_all(
-      [&](int r) -> int
+  // (an empty shard holds no entry of the list; rank 0 is never empty: the state behind a draw comes from it)
+  TRY(group_each_shard(
+      g,
+      [&](mcl3dl_hip_ctx* ctx, int r, size_t lo, size_t n) -> int
       {
-        mcl3dl_hip_ctx* ctx = g->ctx[r];
-        size_t lo, hi;
-        shard_bounds(n_p, N, r, &lo, &hi);
-        const size_t n = hi - lo;
-        if (n == 0)
-          return 0;  // an empty shard holds no entry of the list (rank 0 is never empty: the state behind a draw comes from it)
-        HIP_TRY(hipSetDevice(ctx->device));
-        if (ctx->gs_n != n)
-          return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, n);
         TRY(ensure(ctx, ctx->gs_rec, sizeof(double) * 32));
         TRY(resident_poses(ctx));
         const uint32_t* d_list = nullptr;
@@ -49,10 +40,7 @@ int group_covariance_over(mcl3dl_hip_group* g, const float* mean7, const uint32_
                                                         mean7, ctx->gs_rec.as<double>()));
         TRY(d2h(ctx, &g->h_parts[22 * static_cast<size_t>(r)], ctx->gs_rec.p, sizeof(double) * 22));
         return sync_stream(ctx);
-      },
-      &bad);
-  if (rc)
-    return g->fail_rank(rc, bad);
+      }));
   double total[22] = { 0 };
   for (int r = 0; r < N; ++r)  // rank order: deterministic
     for (int k = 0; k < 22; ++k)

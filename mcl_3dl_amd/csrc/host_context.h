@@ -3,6 +3,8 @@
 // helpers, hipEvent kernel timing.
 #pragma once
 
+#include "host_group_sync.h"  // cpu_relax
+
 namespace
 {
 // A device allocation owned by the context (grown by ensure(), released with the context: mcl3dl_hip_destroy selects the
@@ -329,6 +331,15 @@ struct mcl3dl_hip_ctx
     // mcl3dl_hip_measure_batch_end by contract, and _wait must never report results it has not delivered)
     return code;
   }
+  // nothing staged is delivered and the staging memory is handed out from its start again: only once the stream has drained
+  // (a copy still in flight reads or writes that memory)
+  void stage_reset()
+  {
+    stage_out.clear();
+    stage_cur = 0;
+    stage_off = 0;
+    stage_pending = 0;
+  }
 };
 
 namespace
@@ -585,15 +596,6 @@ bool ensure_done_flag(mcl3dl_hip_ctx* ctx)
   return true;
 }
 
-inline void cpu_relax()
-{
-#if defined(__x86_64__) || defined(__i386__)
-  __builtin_ia32_pause();
-#elif defined(__aarch64__)
-  __asm__ __volatile__("yield");
-#endif
-}
-
 inline double mono_us()
 {
   timespec ts;
@@ -678,10 +680,7 @@ int chain_check(mcl3dl_hip_ctx* ctx)
   if (!ctx->chain_err || !*ctx->chain_err)
     return 0;
   *ctx->chain_err = 0u;
-  ctx->stage_out.clear();
-  ctx->stage_cur = 0;
-  ctx->stage_off = 0;
-  ctx->stage_pending = 0;
+  ctx->stage_reset();
   ctx->prog = mcl3dl_hip_ctx::BatchProgress();
   return ctx->fail(-2, "strict_order = 3: a hand-off of the in-kernel float sum did not arrive (likelihoods of this update are invalid)");
 }
@@ -744,10 +743,7 @@ int sync_stream(mcl3dl_hip_ctx* ctx, bool polled = false)
   TRY(chain_check(ctx));
   for (const mcl3dl_hip_ctx::StagedResult& r : ctx->stage_out)
     memcpy(r.user, r.staged, r.bytes);
-  ctx->stage_out.clear();
-  ctx->stage_cur = 0;
-  ctx->stage_off = 0;
-  ctx->stage_pending = 0;
+  ctx->stage_reset();
   return 0;
 }
 

@@ -5,17 +5,14 @@
 // over RCCL (librccl is dlopen'ed the first time a group with more than one device needs it — a single-GPU user never
 // loads it), or a host-side combine of the same record (collective = "host": used when device ids repeat — several
 // contexts on one GPU, which RCCL refuses — and as a fallback when librccl is not installed).
+// The threads and the rules by which the ranks enter a collective are host_group_sync.h's (no HIP: tested on a CPU); below
+// them here: the shard view of a rank, the voted collective call and the all-reduce of the record.
 #pragma once
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and enum values only: every RCCL call goes through the dlopen'ed pointers below
 
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
-#include <thread>
+#include "host_group_sync.h"  // WorkerPool, VoteBarrier, run_round
 
 namespace
 {
@@ -60,166 +57,6 @@ struct RcclApi
   }
 };
 
-// One worker thread per device; run_all() hands every worker the same closure (argument = rank) and waits for all.
-// Hand-over and completion are SPUN on for a short while before anybody sleeps on a condition variable: updates follow
-// each other within a fraction of a millisecond while a filter runs, and a futex wake-up costs 20 - 50 us per hop — two hops
-// per update, a tenth of a C2 update. A worker that has seen no task for SPIN_US goes to sleep (an idle filter burns nothing);
-// the caller spins while the ranks work (that is its only job) and sleeps only behind a long update.
-class WorkerPool
-{
-public:
-  void start(int n)
-  {
-    rc_.assign(n, 0);
-    for (int r = 0; r < n; ++r)
-      threads_.emplace_back([this, r] { loop(r); });
-  }
-  void stop()
-  {
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      stop_.store(true, std::memory_order_release);
-    }
-    cv_task_.notify_all();
-    for (std::thread& t : threads_)
-      t.join();
-    threads_.clear();
-  }
-  // returns the first non-zero return code (by rank), 0 if every rank succeeded
-  int run_all(const std::function<int(int)>& f, int* failed_rank)
-  {
-    if (threads_.empty())
-    {
-      const int rc = f(0);
-      if (rc != 0 && failed_rank)
-        *failed_rank = 0;
-      return rc;
-    }
-    task_ = &f;
-    pending_.store(static_cast<int>(threads_.size()), std::memory_order_relaxed);
-    gen_.fetch_add(1);  // publishes task_ and pending_ (sequentially consistent: paired with the sleeper's count-then-look)
-    if (sleepers_.load() > 0)
-    {
-      std::lock_guard<std::mutex> lk(m_);  // (a worker between its last look at gen_ and its wait holds m_)
-      cv_task_.notify_all();
-    }
-    // completion: spin, then sleep
-    const auto t0 = std::chrono::steady_clock::now();
-    bool done = false;
-    for (long spin = 0; !(done = pending_.load(std::memory_order_acquire) == 0); ++spin)
-    {
-      cpu_relax();
-      if ((spin & 1023) == 1023 &&
-          std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > 2000.0)
-        break;
-    }
-    if (!done)
-    {
-      std::unique_lock<std::mutex> lk(m_);
-      waiter_.store(true);  // (sequentially consistent, like the worker's decrement-then-look: one of the two sees the other)
-      cv_done_.wait(lk, [this] { return pending_.load() == 0; });
-      waiter_.store(false);
-    }
-    task_ = nullptr;
-    for (size_t r = 0; r < rc_.size(); ++r)
-      if (rc_[r] != 0)
-      {
-        if (failed_rank)
-          *failed_rank = static_cast<int>(r);
-        return rc_[r];
-      }
-    return 0;
-  }
-
-private:
-  static constexpr double SPIN_US = 300.0;
-  void loop(int r)
-  {
-    uint64_t seen = 0;
-    for (;;)
-    {
-      // the next task: spin for a while, then sleep
-      const auto t0 = std::chrono::steady_clock::now();
-      bool have = false;
-      for (long spin = 0; !stop_.load(std::memory_order_acquire); ++spin)
-      {
-        if (gen_.load(std::memory_order_acquire) != seen)
-        {
-          have = true;
-          break;
-        }
-        cpu_relax();
-        if ((spin & 255) == 255 &&
-            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > SPIN_US)
-          break;
-      }
-      if (!have)
-      {
-        std::unique_lock<std::mutex> lk(m_);
-        sleepers_.fetch_add(1);
-        cv_task_.wait(lk, [&] { return stop_.load() || gen_.load() != seen; });
-        sleepers_.fetch_sub(1);
-      }
-      if (stop_.load(std::memory_order_acquire))
-        return;
-      seen = gen_.load(std::memory_order_acquire);
-      const std::function<int(int)>* f = task_;
-      rc_[r] = (*f)(r);
-      if (pending_.fetch_sub(1) == 1 && waiter_.load())
-      {
-        std::lock_guard<std::mutex> lk(m_);
-        cv_done_.notify_one();
-      }
-    }
-  }
-  std::vector<std::thread> threads_;
-  std::mutex m_;
-  std::condition_variable cv_task_, cv_done_;
-  const std::function<int(int)>* task_ = nullptr;
-  std::atomic<uint64_t> gen_{ 0 };
-  std::atomic<int> pending_{ 0 }, sleepers_{ 0 };
-  std::atomic<bool> stop_{ false }, waiter_{ false };
-  std::vector<int> rc_;
-};
-
-// Every worker of one run_all() casts one vote and gets the conjunction of all votes back. The update's collective is
-// enqueued only when every rank reached it: a rank whose upload / launch failed must not leave the others blocked inside
-// an all-reduce that can never complete (api_group.inl, the RCCL path).
-class VoteBarrier
-{
-public:
-  void resize(int n)
-  {
-    n_ = n;
-  }
-  bool vote(bool ok)
-  {
-    if (n_ <= 1)
-      return ok;
-    std::unique_lock<std::mutex> lk(m_);
-    const uint64_t gen = gen_;
-    if (count_ == 0)
-      all_ok_ = true;
-    all_ok_ = all_ok_ && ok;
-    if (++count_ == n_)
-    {
-      result_[gen & 1] = all_ok_;
-      count_ = 0;
-      ++gen_;
-      cv_.notify_all();
-      return result_[gen & 1];
-    }
-    cv_.wait(lk, [&] { return gen_ != gen; });
-    return result_[gen & 1];
-  }
-
-private:
-  std::mutex m_;
-  std::condition_variable cv_;
-  int n_ = 1, count_ = 0;
-  uint64_t gen_ = 0;
-  bool all_ok_ = true, result_[2] = { true, true };
-};
 }  // namespace
 
 struct mcl3dl_hip_group
@@ -275,6 +112,10 @@ struct mcl3dl_hip_group
       }
     comms.clear();
   }
+  void count_collective(bool over_rccl)
+  {
+    ++(over_rccl ? collectives_rccl : collectives_host);
+  }
 
   int n() const
   {
@@ -305,5 +146,206 @@ inline void shard_bounds(size_t n, int world, int r, size_t* lo, size_t* hi)
   const size_t base = n / world, rem = n % world;
   *lo = r * base + std::min<size_t>(r, rem);
   *hi = *lo + base + (static_cast<size_t>(r) < rem ? 1 : 0);
+}
+
+// rank r's view of n_p sharded particles: its context and its shard [lo, lo + n)
+struct Shard
+{
+  mcl3dl_hip_ctx* ctx;
+  int r;
+  size_t lo, n;
+};
+
+inline Shard shard_of(const mcl3dl_hip_group* g, size_t n_p, int r)
+{
+  size_t lo, hi;
+  shard_bounds(n_p, g->n(), r, &lo, &hi);
+  return Shard{ g->ctx[r], r, lo, hi - lo };
+}
+
+// Every rank computes the same scalars from the same combined record; they are taken from the first shard that holds a
+// particle. shard_bounds hands rank 0 a particle before any other rank, so that is rank 0 whenever there is a particle at all.
+inline int first_nonempty_rank(size_t)
+{
+  return 0;
+}
+
+// f(rank) on every rank's worker, the failing rank's error reported; no collective, nothing waits for another rank
+template <typename F>
+int group_run(mcl3dl_hip_group* g, const F& f)
+{
+  int bad = 0;
+  const int rc = g->pool.run_all(f, &bad);
+  return rc ? g->fail_rank(rc, bad) : 0;
+}
+
+// ... f(shard), over the shards of n_p particles
+template <typename F>
+int group_run_shards(mcl3dl_hip_group* g, size_t n_p, const F& f)
+{
+  return group_run(g, [&](int r) -> int { return f(shard_of(g, n_p, r)); });
+}
+
+// the shard-local calls on the resident particles: f(ctx, rank, lo, n) on every rank whose shard holds particles
+template <typename F>
+int group_each_shard(mcl3dl_hip_group* g, const F& f)
+{
+  if (g->n_resident == 0)
+    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  return group_run_shards(g, g->n_resident,
+                          [&](const Shard& s) -> int
+                          {
+                            mcl3dl_hip_ctx* ctx = s.ctx;
+                            if (s.n == 0)
+                              return 0;
+                            HIP_TRY(hipSetDevice(ctx->device));
+                            if (ctx->gs_n != s.n)
+                              return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, s.n);
+                            return f(ctx, s.r, s.lo, s.n);
+                          });
+}
+
+int group_comms(mcl3dl_hip_group* g)
+{
+  if (g->collective == 1 || !g->comms.empty())
+    return 0;
+  if (!g->devices_distinct)
+    return g->fail(-3, "a device id is listed more than once: RCCL needs one GPU per rank — set option \"collective\" to 1 "
+                       "(host combine) for several contexts on one GPU");
+  const std::string why = g->rccl.load();
+  if (!why.empty())
+    return g->fail(-7, "%s; set option \"collective\" to 1 (host combine) or MCL3DL_HIP_RCCL_LIB", why.c_str());
+  g->comms.assign(g->n(), nullptr);
+  const ncclResult_t rc = g->rccl.CommInitAll(g->comms.data(), g->n(), g->devices.data());
+  if (rc != ncclSuccess)
+  {
+    g->comms.clear();
+    return g->fail(-7, "ncclCommInitAll over %d devices failed: %s", g->n(), g->rccl.GetErrorString(rc));
+  }
+  return 0;
+}
+
+// ---- the voted collective call ("One round for every collective") --------------------------------------------
+// `what` names the call and `collective` what it enters ("all-reduce", "all-gather") in the error texts.
+struct VotedCall
+{
+  mcl3dl_hip_group* g;
+  const char* what;
+  const char* collective;
+};
+
+// What the part of a rank behind the first vote is handed: enqueued() behind each RCCL collective it enqueued (the second
+// vote). 0: go on; else the rank's code — its error text is set — to return at once.
+struct VotedRank
+{
+  const VotedCall& call;
+  const Shard& s;
+  RoundRank& round;
+  int enqueued(ncclResult_t nrc, const char* nccl_call) const
+  {
+    const int own = nrc == ncclSuccess ? 0 : s.ctx->fail(-7, "%s failed: %s", nccl_call, call.g->rccl.GetErrorString(nrc));
+    const int rc = round.enqueued(own);
+    // (its stream is NOT drained: the collective in it never completes; the communicators are aborted behind the round)
+    return rc != RC_ABANDONED ? rc : s.ctx->fail(RC_ABANDONED, "%s abandoned: another rank could not enqueue the %s", call.what,
+                                                 call.collective);
+  }
+};
+
+// One round (host_group_sync.h:run_round) over the shards of n_p particles: ahead(shard) is everything a rank does in front of
+// the collective and waits for no other rank; behind(shard, VotedRank) runs only when EVERY rank's `ahead` succeeded — the
+// collective(s), each followed by VotedRank::enqueued, and what follows them. A rank that may not proceed drains its stream,
+// drops what it staged and stands down. over_rccl: the communicators are dropped when a rank failed or stood down behind the
+// first vote. count: a successful call is one collective of that kind.
+template <typename Ahead, typename Behind>
+int group_voted_call(const VotedCall& call, size_t n_p, bool over_rccl, bool count, const Ahead& ahead, const Behind& behind)
+{
+  mcl3dl_hip_group* g = call.g;
+  const int inject = g->inject_failure_rank;  // (the test hook: that rank fails behind its `ahead`, once)
+  g->inject_failure_rank = -1;
+  const RoundVerdict v = run_round(
+      g->pool, g->vote, g->n(),
+      [&](int r, RoundRank& round) -> int
+      {
+        const Shard s = shard_of(g, n_p, r);
+        int rc = ahead(s);
+        if (rc == 0 && r == inject)
+          rc = s.ctx->fail(-9, "injected failure ahead of the collective (test hook)");
+        rc = round.enter(rc);
+        if (rc == 0)
+          return behind(s, VotedRank{ call, s, round });
+        if (rc == RC_ABANDONED)
+          s.ctx->fail(RC_ABANDONED, "%s abandoned: another rank failed ahead of the %s", call.what, call.collective);
+        (void)hipStreamSynchronize(s.ctx->stream);  // drain what this rank enqueued; its results are discarded
+        s.ctx->stage_reset();
+        return rc;
+      });
+  if (v.rc)
+  {
+    // communicators that saw a failed or abandoned collective are rebuilt on next use
+    if (over_rccl && v.behind_first_vote)
+      g->drop_comms();
+    return g->fail_rank(v.rc, v.rank);
+  }
+  if (count)
+    g->count_collective(over_rccl);
+  return 0;
+}
+
+// pf::measure's collective: the record of 2 + 2N doubles in ctx->packed, summed over the ranks. phase_a(shard) enqueues what
+// fills the rank's record (the rank's device is current, ctx->packed holds room), phase_b(shard) what reads the total and
+// brings the rank's results home. RCCL: ncclAllReduce on the rank's stream and phase B behind it on the same worker; host
+// combine (collective = 1): the records come home, are summed in rank order (deterministic) and go back up in a second pass
+// over the workers, which runs phase B; a group of one device that may call its context directly needs no collective (and
+// never loads RCCL): phase B follows phase A.
+template <typename PhaseA, typename PhaseB>
+int group_allreduce_record(mcl3dl_hip_group* g, const char* what, size_t n_p, const PhaseA& phase_a, const PhaseB& phase_b)
+{
+  const int N = g->n();
+  const bool no_collective = N == 1 && g->direct_single;
+  const bool host_combine = g->collective == 1 && !no_collective;
+  const bool over_rccl = !no_collective && !host_combine;
+  if (!no_collective)
+    TRY(group_comms(g));
+  const size_t n_pack = 2 + 2 * static_cast<size_t>(N);
+  TRY(group_voted_call(
+      VotedCall{ g, what, "all-reduce" }, n_p, over_rccl, over_rccl,
+      [&](const Shard& s) -> int
+      {
+        mcl3dl_hip_ctx* ctx = s.ctx;
+        HIP_TRY(hipSetDevice(ctx->device));
+        TRY(ensure(ctx, ctx->packed, sizeof(double) * n_pack));
+        return phase_a(s);
+      },
+      [&](const Shard& s, const VotedRank& voted) -> int
+      {
+        mcl3dl_hip_ctx* ctx = s.ctx;
+        if (host_combine)
+        {
+          g->host_packed[s.r].resize(n_pack);
+          TRY(d2h(ctx, g->host_packed[s.r].data(), ctx->packed.p, sizeof(double) * n_pack));
+          return sync_stream(ctx);
+        }
+        if (over_rccl)
+          // the call's single collective: 16 + 16 N bytes over xGMI, on this device's stream
+          TRY(voted.enqueued(g->rccl.AllReduce(ctx->packed.p, ctx->packed.p, n_pack, ncclDouble, ncclSum, g->comms[s.r], ctx->stream),
+                             "ncclAllReduce"));
+        return phase_b(s);
+      }));
+  if (!host_combine)
+    return 0;
+  double total[2 + 2 * ROUND_MAX_RANKS] = {};
+  for (int r = 0; r < N; ++r)
+    for (size_t i = 0; i < n_pack; ++i)
+      total[i] += g->host_packed[r][i];
+  TRY(group_run_shards(g, n_p,
+                       [&](const Shard& s) -> int
+                       {
+                         mcl3dl_hip_ctx* ctx = s.ctx;
+                         HIP_TRY(hipSetDevice(ctx->device));
+                         TRY(h2d(ctx, ctx->packed.p, total, sizeof(double) * n_pack));
+                         return phase_b(s);
+                       }));
+  g->count_collective(false);
+  return 0;
 }
 }  // namespace

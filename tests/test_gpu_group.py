@@ -155,8 +155,8 @@ def test_a_rank_that_fails_ahead_of_the_collective_does_not_strand_the_others(sc
 
 
 def test_injected_failure_on_the_rccl_path_rebuilds_the_communicator(scene, single, monkeypatch):
-    """One rank, RCCL all-reduce (the only RCCL shape one GPU allows): the failed update destroys the communicator, the next
-    one brings it up again and is correct."""
+    """One rank, RCCL all-reduce (the only RCCL shape one GPU allows): the update that failed ahead of the first vote enqueued
+    no collective (its communicator stays; one that failed behind the vote would be rebuilt), the next one is correct."""
     sc = scene
     w0, extra, want = single
     g = make_group([0], sc)
@@ -219,3 +219,110 @@ def test_node_call_site_on_a_device_group(tmp_path, oracle_kind):
     np.testing.assert_array_equal(beam, want["beam"])
     np.testing.assert_array_equal(quality, want["quality"])
     np.testing.assert_allclose(w, want["weights"], rtol=1e-5)
+
+
+# ---- the stand-down paths of the other calls that enter a collective (host_group.h:group_voted_call): the injected failure
+# is a host return code behind the rank's enqueued work; nothing resident may change, nothing is counted, the next call is right
+
+def resident_start(n_p, seed=41):
+    rng = np.random.default_rng(seed)
+    st = np.zeros((n_p, 13), np.float32)
+    st[:, :3] = rng.normal(0.0, 1.0, (n_p, 3))
+    q = rng.normal(0.0, 0.2, (n_p, 4))
+    q[:, 3] = 1.0
+    st[:, 3:7] = q / np.linalg.norm(q, axis=1, keepdims=True)
+    st[:, 7:] = rng.normal(0.0, 0.05, (n_p, 6))
+    w = rng.uniform(0.5, 1.5, n_p).astype(np.float32)
+    return st.astype(np.float32), (w / w.sum()).astype(np.float32)
+
+
+IMU = ((0.3, -0.2, 9.7), 0.8)
+LANDMARK = ((0.2, -0.1, 0.05, 0.0, 0.0, 0.0, 1.0), np.diag([0.5, 0.6, 0.7, 0.2, 0.25, 0.3]))
+
+
+def assert_same_measure(got, want):
+    np.testing.assert_array_equal(got["weights"], want["weights"])
+    np.testing.assert_array_equal(got["lik"], want["lik"])
+    assert got["entropy"] == want["entropy"] and got["restored"] == want["restored"]
+
+
+def injected_measure_case(monkeypatch, devices, collective, n_p, bad_rank, call):
+    st, w = resident_start(n_p)
+    monkeypatch.setenv("MCL3DL_HIP_TEST_HOOKS", "1")
+    g, fresh = capi.Group(devices, collective=collective), capi.Group(devices, collective=collective)
+    try:
+        g.upload_state(st, w)
+        before = g.collective_stats()
+        g.set_option("inject_failure_rank", bad_rank)
+        with pytest.raises(capi.EngineError, match=r"rank %d\): injected failure" % bad_rank):
+            call(g)
+        got_st, got_w = g.download_state()
+        np.testing.assert_array_equal(got_st, st)
+        np.testing.assert_array_equal(got_w, w)
+        assert g.collective_stats() == before
+        fresh.upload_state(st, w)
+        assert_same_measure(call(g), call(fresh))
+    finally:
+        g.close()
+        fresh.close()
+
+
+@pytest.mark.parametrize("n_p,bad_rank", [(7, 0), (7, 1), (7, 2), (2, 2)], ids=["rank0", "rank1", "rank2", "empty_rank2"])
+def test_injected_failure_in_the_imu_update_leaves_the_particles_alone(monkeypatch, n_p, bad_rank):
+    """7 particles on three contexts (shards 3 / 2 / 2), and 2 particles with the failing rank the one whose shard is empty."""
+    injected_measure_case(monkeypatch, [0, 0, 0], "host", n_p, bad_rank, lambda g: g.measure_imu(*IMU))
+
+
+def test_injected_failure_in_the_landmark_update_leaves_the_particles_alone(monkeypatch):
+    injected_measure_case(monkeypatch, [0, 0, 0], "host", 7, 1, lambda g: g.measure_landmark(*LANDMARK))
+
+
+def test_injected_failure_in_resample_apply_drops_the_resident_particles(monkeypatch):
+    st, w = resident_start(7)
+    monkeypatch.setenv("MCL3DL_HIP_TEST_HOOKS", "1")
+    g, fresh = capi.Group([0, 0, 0], collective="host"), capi.Group([0, 0, 0], collective="host")
+    try:
+        def resample(obj):
+            obj.upload_state(st, w)
+            pstep = obj.resample_begin(0)
+            src, dup, n_dup = obj.resample_plan(0, 0.37 * pstep)
+            nz = np.full((n_dup, 13), 0.01, np.float32)
+            nz[:, 3:7] = (0.0, 0.0, 0.0, 1.0)
+            return nz
+        nz = resample(g)
+        g.set_option("inject_failure_rank", 1)
+        with pytest.raises(capi.EngineError, match=r"rank 1\): injected failure"):
+            g.resample_apply(nz)
+        with pytest.raises(capi.EngineError, match=r"-5.*no resident particles"):
+            g.measure_imu(*IMU)
+        g.resample_apply(resample(g))
+        fresh.resample_apply(resample(fresh))
+        got, want = g.download_state(), fresh.download_state()
+        np.testing.assert_array_equal(got[0], want[0])
+        np.testing.assert_array_equal(got[1], want[1])
+        assert len(got[0]) == 7 and g.collective_stats() == fresh.collective_stats()
+    finally:
+        g.close()
+        fresh.close()
+
+
+def test_injected_failure_in_the_imu_update_on_the_rccl_path(monkeypatch):
+    """One rank, RCCL all-reduce (the only RCCL shape one GPU allows): update, injected failure, update."""
+    st, w = resident_start(7)
+    monkeypatch.setenv("MCL3DL_HIP_TEST_HOOKS", "1")
+    g, fresh = capi.Group([0]), capi.Group([0])
+    try:
+        for obj in (g, fresh):
+            obj.set_option("direct_single", 0)
+            obj.upload_state(st, w)
+        first = g.measure_imu(*IMU)
+        g.set_option("inject_failure_rank", 0)
+        with pytest.raises(capi.EngineError, match="injected failure"):
+            g.measure_imu(*IMU)
+        second = g.measure_imu(*IMU)
+        assert_same_measure(first, fresh.measure_imu(*IMU))
+        assert_same_measure(second, fresh.measure_imu(*IMU))
+        assert g.collective_stats() == dict(rccl=2, host=0)
+    finally:
+        g.close()
+        fresh.close()
