@@ -860,6 +860,9 @@ int mcl3dl_hip_memory_footprint(mcl3dl_hip_ctx* ctx, uint64_t* bytes8);
  *   "index_budget_bytes"  upper bound of the records: -1 (default) = a quarter of the device's memory, 0 = none; cubes, then boxes,
  *                       then coarser voxels (<= 1.5 r), then a clean error naming the bytes needed. Read-only "index_note" says
  *                       when the index differs from what was asked for; "index_record_bytes", "cand_edge_ratio_x/_y/_z"
+ *                       Read-only geometry of the candidate grid in place: "cand_origin_x/_y/_z" (floats), "cand_edge_x/_y/_z",
+ *                       "cand_voxels_x/_y/_z", "cand_grow" (the slack of a voxel's grown box: 1e-3 of the shortest edge, more on
+ *                       grids longer than ~5 000 voxels; a map that would need more than 1/16 of an edge is refused with -4)
  *   "cand_prune_coop"   1 = the compiler's pruning pass runs 16 lanes per voxel; 0 = one thread per voxel (the form it is checked against)
  *   "grid_build_host"   1 = cell grid and DDA grid built by sequential counting sorts on the host (the form the device builders are
  *                       checked against)

@@ -1281,6 +1281,14 @@ class Engine:
                     packed_words=int(self.get_option("cand_packed_active")),
                     deferred_overflow=int(self.get_option("lik_defer_active")))
 
+    def index_geometry(self):
+        """The candidate grid in place: float origin, fp64 voxel edges, voxel counts per axis and the slack `grow` of V+ (the
+        voxel of a float q along an axis is floor((q - origin) * float32(1 / float32(edge))) in float arithmetic)."""
+        get = self.get_option
+        return dict(origin=np.array([get("cand_origin_" + a) for a in "xyz"], np.float32),
+                    edge=np.array([get("cand_edge_" + a) for a in "xyz"], np.float64),
+                    voxels=np.array([int(get("cand_voxels_" + a)) for a in "xyz"], np.int64), grow=get("cand_grow"))
+
 
 def rng_seed(seed):
     """std::default_random_engine(seed)'s state (libstdc++: minstd_rand0)."""

@@ -100,6 +100,17 @@ const Diagnostic kDiagnostics[] = {
     { "cand_edge_ratio_x", [](const mcl3dl_hip_ctx* c) -> double { return c->cand_edge_ratio[0]; } },
     { "cand_edge_ratio_y", [](const mcl3dl_hip_ctx* c) -> double { return c->cand_edge_ratio[1]; } },
     { "cand_edge_ratio_z", [](const mcl3dl_hip_ctx* c) -> double { return c->cand_edge_ratio[2]; } },
+    // geometry of the candidate grid in place (zeros before the first build): float origin, fp64 edges, voxel counts, slack of V+
+    { "cand_origin_x", [](const mcl3dl_hip_ctx* c) -> double { return c->cand_cp.ox; } },
+    { "cand_origin_y", [](const mcl3dl_hip_ctx* c) -> double { return c->cand_cp.oy; } },
+    { "cand_origin_z", [](const mcl3dl_hip_ctx* c) -> double { return c->cand_cp.oz; } },
+    { "cand_edge_x", [](const mcl3dl_hip_ctx* c) -> double { return c->cand_cp.ex; } },
+    { "cand_edge_y", [](const mcl3dl_hip_ctx* c) -> double { return c->cand_cp.ey; } },
+    { "cand_edge_z", [](const mcl3dl_hip_ctx* c) -> double { return c->cand_cp.ez; } },
+    { "cand_voxels_x", [](const mcl3dl_hip_ctx* c) -> double { return c->cand_cp.nvx; } },
+    { "cand_voxels_y", [](const mcl3dl_hip_ctx* c) -> double { return c->cand_cp.nvy; } },
+    { "cand_voxels_z", [](const mcl3dl_hip_ctx* c) -> double { return c->cand_cp.nvz; } },
+    { "cand_grow", [](const mcl3dl_hip_ctx* c) -> double { return c->cand_cp.grow; } },
     { "index_record_bytes", [](const mcl3dl_hip_ctx* c) -> double { return static_cast<double>(c->footprint[6]); } },
     { "index_note", [](const mcl3dl_hip_ctx* c) -> double { return c->index_note.empty() ? 0.0 : 1.0; } },
     { "cand_record_parts_in_use", [](const mcl3dl_hip_ctx* c) -> double { return c->cand_parts; } },

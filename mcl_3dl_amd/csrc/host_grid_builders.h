@@ -98,15 +98,12 @@ int build_lik_grid_device(mcl3dl_hip_ctx* ctx)
     TRY(cloud_minmax(ctx, static_cast<const float4*>(sp.p), nn, mm, &n_finite));
     if (n_finite != n)
       return ctx->fail(-3, "%llu map point(s) are not finite", static_cast<unsigned long long>(n) - n_finite);
-    float o[3];
-    int dim[3];
+    const CellGridGeometry geom = cell_grid_geometry(mm, mm + 3, cell);  // index_geometry.h
+    const float* o = geom.o;
+    const int* dim = geom.dim;
     double total = 1;
     for (int a = 0; a < 3; ++a)
-    {
-      o[a] = mm[a] - 2.0f * cell;
-      dim[a] = static_cast<int>(floorf((mm[3 + a] - o[a]) * inv)) + 3;
       total *= dim[a];
-    }
     if (total > 3.0e9)
       return ctx->fail(-4, "likelihood grid would need %.3g cells (map extent too large for the dense index)", total);
     const size_t ncell = static_cast<size_t>(dim[0]) * dim[1] * dim[2];

@@ -67,15 +67,12 @@ int build_lik_grid_host(mcl3dl_hip_ctx* ctx)
       if (i == 0 || v > mx[a])
         mx[a] = v;
     }
-  float o[3];
-  int dim[3];
+  const CellGridGeometry geom = cell_grid_geometry(mn, mx, cell);  // index_geometry.h
+  const float* o = geom.o;
+  const int* dim = geom.dim;
   double total = 1;
   for (int a = 0; a < 3; ++a)
-  {
-    o[a] = mn[a] - 2.0f * cell;
-    dim[a] = static_cast<int>(floorf((mx[a] - o[a]) * inv)) + 3;
     total *= dim[a];
-  }
   if (total > 3.0e9)
     return ctx->fail(-4, "likelihood grid would need %.3g cells (map extent too large for the dense index)", total);
   const size_t ncell = static_cast<size_t>(dim[0]) * dim[1] * dim[2];
@@ -86,7 +83,7 @@ int build_lik_grid_host(mcl3dl_hip_ctx* ctx)
     int c[3];
     for (int a = 0; a < 3; ++a)
     {
-      c[a] = static_cast<int>(floorf((s[3 * i + a] - o[a]) * inv));  // same expression as the kernel's
+      c[a] = static_cast<int>(grid_coord(s[3 * i + a], o[a], inv));  // same expression as the kernel's
       c[a] = std::min(std::max(c[a], 0), dim[a] - 1);
     }
     cell_of[i] = static_cast<uint32_t>((static_cast<size_t>(c[2]) * dim[1] + c[1]) * dim[0] + c[0]);
@@ -373,59 +370,22 @@ void cand_axis_stretch(const mcl3dl_hip_ctx* ctx, double stretch[3])
 int cand_geometry(mcl3dl_hip_ctx* ctx, double voxel_ratio, const double stretch[3], const float mn[3], const float mx[3],
                   CompileParams* out, long long* n_table_out)
 {
-  const double r = static_cast<double>(ctx->match_dist_min);
-  float e_f[3];
-  for (int a = 0; a < 3; ++a)
+  // (the arithmetic: index_geometry.h, where a plain C++ program can reach it)
+  double detail = 0.0;
+  switch (cand_grid_geometry(static_cast<double>(ctx->match_dist_min), voxel_ratio, stretch, ctx->opt.cand_phase, mn, mx, out,
+                             n_table_out, &detail))
   {
-    e_f[a] = static_cast<float>(r * voxel_ratio * stretch[a]);
-    if (!(e_f[a] > 0.f) || !std::isfinite(e_f[a]))
+    case CAND_GEOM_OK:
+      return 0;
+    case CAND_GEOM_BAD_EDGE:
       return ctx->fail(-3, "bad candidate voxel edge");
+    case CAND_GEOM_SLACK:
+      return ctx->fail(-4, "candidate index: a map this long needs voxels grown by %.3g of their edge to absorb the rounding of a "
+                           "query's voxel index (at most 1/16 is supported): raise match_dist_min or cand_voxel_ratio, or split the map",
+                       detail);
+    default:
+      return ctx->fail(-4, "candidate index would need %.3g bricks in its dense table", detail);
   }
-  CompileParams cp{};
-  cp.ex = static_cast<double>(e_f[0]);
-  cp.ey = static_cast<double>(e_f[1]);
-  cp.ez = static_cast<double>(e_f[2]);
-  cp.inv_ex = 1.0f / e_f[0];
-  cp.inv_ey = 1.0f / e_f[1];
-  cp.inv_ez = 1.0f / e_f[2];
-  const double ed[3] = { cp.ex, cp.ey, cp.ez };
-  cp.grow = 1e-3 * std::min(cp.ex, std::min(cp.ey, cp.ez));
-  const double r_hi = r * (1.0 + 1e-5);
-  cp.r2_hi = r_hi * r_hi;
-  cp.margin = 1e-5 * r * r;
-  int reach[3];
-  for (int a = 0; a < 3; ++a)
-    reach[a] = static_cast<int>(std::floor((r_hi + cp.grow) / ed[a])) + 1;
-  cp.rx = reach[0];
-  cp.ry = reach[1];
-  cp.rz = reach[2];
-  float o[3];
-  int nv[3], nb[3];
-  double n_table_d = 1;
-  for (int a = 0; a < 3; ++a)
-  {
-    // Phase: maps that come out of a voxel filter sit on a lattice; with the origin ON that lattice every voxel face
-    // coincides with a Voronoi face of the map and each voxel keeps 3 candidates per axis instead of the 2 a generic
-    // position needs. Half a voxel of phase puts lattice maps in the generic position; arbitrary maps do not care.
-    o[a] = mn[a] - static_cast<float>((reach[a] + 1 + ctx->opt.cand_phase) * ed[a]);
-    nv[a] = static_cast<int>(std::floor((static_cast<double>(mx[a]) - o[a]) / ed[a])) + reach[a] + 2;
-    nb[a] = (nv[a] + 7) / 8;
-    n_table_d *= nb[a];
-  }
-  if (n_table_d > 2.0e9)
-    return ctx->fail(-4, "candidate index would need %.3g bricks in its dense table", n_table_d);
-  cp.ox = o[0];
-  cp.oy = o[1];
-  cp.oz = o[2];
-  cp.nvx = nv[0];
-  cp.nvy = nv[1];
-  cp.nvz = nv[2];
-  cp.nbx = nb[0];
-  cp.nby = nb[1];
-  cp.nbz = nb[2];
-  *out = cp;
-  *n_table_out = static_cast<long long>(n_table_d);
-  return 0;
 }
 
 // Rescaled map points (PointRepresentation::vectorize) in map order, w = original index; bounds on request.
@@ -947,8 +907,8 @@ int update_cand_grid(mcl3dl_hip_ctx* ctx, size_t n_base, const std::vector<float
   // every added point, with its reach, must lie inside the grid the index was laid out for
   for (const float4& p : fresh)
   {
-    const int v[3] = { static_cast<int>(floorf((p.x - cp.ox) * cp.inv_ex)), static_cast<int>(floorf((p.y - cp.oy) * cp.inv_ey)),
-                       static_cast<int>(floorf((p.z - cp.oz) * cp.inv_ez)) };
+    const int v[3] = { static_cast<int>(grid_coord(p.x, cp.ox, cp.inv_ex)), static_cast<int>(grid_coord(p.y, cp.oy, cp.inv_ey)),
+                       static_cast<int>(grid_coord(p.z, cp.oz, cp.inv_ez)) };
     const int nv[3] = { cp.nvx, cp.nvy, cp.nvz };
     const int reach[3] = { cp.rx, cp.ry, cp.rz };
     for (int a = 0; a < 3; ++a)

@@ -24,6 +24,15 @@ int ensure_structures(mcl3dl_hip_ctx* ctx, bool need_lik, bool need_dda, bool ne
     TRY(build_lik_grid(ctx));
     built = true;
   }
+  // the 27-cell scan rests on the cell edge's 1 % margin over the radius, which the float rounding of the cell coordinates
+  // uses up at LIK_SCAN_MAX_CELLS cells per axis (index_geometry.h); radius searches scan a cell more each way and go on
+  if (need_lik && ctx->opt.lik_index == 0 && !need_cells)
+  {
+    const int dim[3] = { ctx->lg.nx, ctx->lg.ny, ctx->lg.nz };
+    if (!lik_scan_provable(dim))
+      return ctx->fail(-4, "the map's cell grid has %d x %d x %d cells: the 27-cell scan (lik_index 0) is exact up to %d cells per "
+                           "axis; use lik_index 2", dim[0], dim[1], dim[2], LIK_SCAN_MAX_CELLS);
+  }
   if (need_lik && ctx->opt.lik_index >= 1 && !need_cells && ctx->cand_dirty)
   {
     TRY(build_cand_grid(ctx));

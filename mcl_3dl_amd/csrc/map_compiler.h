@@ -9,39 +9,35 @@
 //   sampled wall) instead of 18 delimiter loads + ~25 points of the 27-cell scan — ~6x fewer cache-line accesses, which is
 //   what bounds likelihood_kernel.
 //
-// Exactness argument (V+ = V grown by 1e-3*e on every side to absorb the float rounding of the query's voxel index):
+// Exactness argument (V+ = V grown by `grow` on every side to absorb the float rounding of the query's voxel index):
+//   (0) every float q lies in V+ of the voxel floor((q - o) * inv_e) names: per axis that float expression is off by at most
+//       3.0000008 * 2^-24 * (v + 1) voxels — half an ulp of q - o (relative to the difference, wherever q and o are), the
+//       rounding of inv_e = 1 / e, the rounding of the product — so grow = max(1e-3 * e_min, 3.25 * 2^-24 * L + 2^-50 * (|x| + L))
+//       with L the longest axis of the grid and |x| its largest coordinate: 1e-3 * e_min up to ~5 000 voxels per axis, derived
+//       beyond (a float past 2 048 m whose spacing exceeds 1e-3 * e is covered: the spacing is under two thirds of that slack),
+//       refused (-4) past e_min / 16. index_geometry.h has the derivation and the arithmetic; tests/cpp/voxel_slack_check.cpp
+//       sweeps it face by face out to 5 km.
 //   (1) p is the NN of q in V+ at distance < r  =>  dmin(p,V+) <= |q-p| < r.
 //   (2) for any q in V+, |q - NN(q)| <= |q - p'| <= dmax(p',V+) for every p'  =>  dmin(NN(q),V+) <= D(V) := min_p' dmax(p',V+).
 //   (3) if some p' is closer than p by more than a margin m at EVERY q of V+ (the difference of squared distances is
 //       linear in q, so its minimum over the box is attained at a corner and has a closed form) then p is never the NN.
-//   All three tests are evaluated in fp64 with relative slack 1e-5 / absolute margin m = 1e-5*r^2, orders of magnitude above
+//   Tests (1)-(3) are evaluated in fp64 with relative slack 1e-5 / absolute margin m = 1e-5*r^2, orders of magnitude above
 //   the ~2e-7 relative error of the kernel's float d^2, so the float-argmin point of the query kernel is never dropped and
-//   min d^2 over C(V) is bit-identical to min d^2 over the whole map (checked by every parity test).
+//   min d^2 over C(V) is bit-identical to min d^2 over the whole map (checked by every parity test; kilometres from the grid's
+//   origin by tests/test_gpu_long_map.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "index_geometry.h"  // CompileParams, grid_coord
+
 namespace mcl3dl
 {
-struct CompileParams
-{
-  float ox, oy, oz, inv_ex, inv_ey, inv_ez;
-  double ex, ey, ez;  // voxel edges (rescaled coordinates). Every step of the candidate proof is per axis (boxes V, V+), so a
-                      // voxel may be a box: dist_weight stretches the map along an axis and thins its points out there in the
-                      // metric — an edge stretched likewise keeps the candidates per voxel and divides the voxel count
-  double grow;    // V+ = V grown by this on every side
-  double r2_hi;   // (r*(1+1e-5))^2
-  double margin;  // domination margin m
-  int rx, ry, rz;  // voxels to visit around a point's own voxel, per axis
-  int nvx, nvy, nvz, nbx, nby, nbz;
-  int n_points;
-};
-
 __device__ inline int3 voxel_of(const CompileParams& c, const float4 p)
 {
   // the same float expression the query kernel evaluates
-  return make_int3(static_cast<int>(floorf((p.x - c.ox) * c.inv_ex)), static_cast<int>(floorf((p.y - c.oy) * c.inv_ey)),
-                   static_cast<int>(floorf((p.z - c.oz) * c.inv_ez)));
+  return make_int3(static_cast<int>(grid_coord(p.x, c.ox, c.inv_ex)), static_cast<int>(grid_coord(p.y, c.oy, c.inv_ey)),
+                   static_cast<int>(grid_coord(p.z, c.oz, c.inv_ez)));
 }
 
 __device__ inline long long brick_index(const CompileParams& c, int vx, int vy, int vz)
