@@ -1,5 +1,9 @@
 // likelihood_kernels.h — likelihood-field model (R3/R4/R5): nearest-neighbour queries against the three map indices, the
 // per-particle / small-scan / tile-major kernels, the strict-order sums and the stand-alone radius search.
+// Each of these exists once, for every kernel that runs it: the cooperative evaluations (eval_coop, eval_coop_first), the
+// deferred-overflow queue (defer_push / defer_flush around defer_drain), pose staging (stage_poses) and
+// the float chain's block mapping and link (xcd_row_map; chain_take / chain_add_row / chain_give) — the last four shared with
+// likelihood_chain_multi.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -839,8 +843,7 @@ struct BoolConstant
 // a per-wavefront LDS queue; whenever 64 are queued the wavefront runs ONE dense overflow round for them — each lane
 // rebuilds its query from the queued lane's scan point (ds_bpermute) and the particle's pose (LDS), exactly the arithmetic
 // of the first pass, so the minimum, the term and therefore every result are the same bits as without the queue.
-constexpr int CHAIN_POLL_MAX = 1 << 20;  // polls of a hand-off word before the lane gives up (~1 s)
-constexpr int DEFER_QCAP = 96;   // entries per wavefront: a push never finds more than 63 queued, and flushes first if it would not fit
+constexpr int DEFER_QCAP = 96;  // entries per wavefront: a push never finds more than 63 queued, and flushes first if it would not fit
 
 struct DeferQueue
 {
@@ -945,12 +948,14 @@ __device__ inline float eval_coop_first(const RecGrid& rg, const LikParams& prm,
 // One dense overflow round for entries [base, base + n) of this wavefront's queue, n <= 64 (all lanes arrive; lane l takes
 // entry base + l). s_term / s_cnt rows are the tiled kernel's: the parked best is replaced by the term, a match is counted.
 // FAST: the arithmetic of eval_coop_first<true> (the overflow records behind their descriptor unconditionally, the match from
-// the radius test).
+// the radius test). Starts by making the wavefront's own pushes and parked terms visible to all of its lanes.
 template <bool FAST = false, int G, int LD>
 __device__ inline void defer_drain(const RecGrid& rg, const LikParams& prm, const float (&s_pose)[G][8], float (&s_term)[G][LD],
                                    unsigned (&s_cnt)[G][4], const DeferQueue& q, int wave, int lane, uint32_t base, uint32_t n,
                                    const float4 v)
 {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
   const bool act = static_cast<uint32_t>(lane) < n;
   const uint32_t slot = act ? base + static_cast<uint32_t>(lane) : base;
   const uint32_t word = q.word[wave][slot];
@@ -995,6 +1000,159 @@ __device__ inline void defer_drain(const RecGrid& rg, const LikParams& prm, cons
     s_term[k][t_src] = lik_term(prm, dist, !(dist < 0.0f));
     if (!(dist < 0.0f))
       atomicAdd(&s_cnt[k][wave], 1u);
+  }
+}
+
+// The queue protocol, once for every kernel that defers. After the evaluation of particle slot k: over_m = the wavefront's
+// lanes whose record overflows (eval_coop_first), `over` this lane's bit of it, `mine` its record's packed word. qn = entries
+// this wavefront holds (uniform, 0 at the start; the new count is returned). Flush first if the new entries would not fit, push in lane order (the slot
+// is the count of set bits below the lane), and as soon as 64 are queued run the LAST 64: what stays queued keeps its place.
+template <bool FAST, int G, int LD>
+__device__ __forceinline__ uint32_t defer_push(const RecGrid& rg, const LikParams& prm, const float (&s_pose)[G][8],
+                                               float (&s_term)[G][LD], unsigned (&s_cnt)[G][4], DeferQueue& q, int wave, int lane,
+                                               const float4 v, uint32_t qn, unsigned long long over_m, bool over, uint32_t mine,
+                                               int k)
+{
+  if (over_m != 0ull)
+  {
+    const uint32_t n_new = static_cast<uint32_t>(__popcll(over_m));
+    if (qn + n_new > static_cast<uint32_t>(DEFER_QCAP))
+    {
+      defer_drain<FAST>(rg, prm, s_pose, s_term, s_cnt, q, wave, lane, 0u, qn, v);
+      qn = 0;
+    }
+    if (over)
+    {
+      const uint32_t slot = qn + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(over_m >> 32),
+                                                           __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(over_m), 0u));
+      q.word[wave][slot] = mine;
+      q.who[wave][slot] = static_cast<uint16_t>((static_cast<uint32_t>(k) << 6) | static_cast<uint32_t>(lane));
+    }
+    qn += n_new;
+    if (qn >= 64u)
+    {
+      defer_drain<FAST>(rg, prm, s_pose, s_term, s_cnt, q, wave, lane, qn - 64u, 64u, v);
+      qn -= 64u;
+    }
+  }
+  return qn;
+}
+
+// ... and when the pose loop ends with a queue that is not empty (the caller tests qn != 0: as a branch of the caller this
+// compiles to the parent's code), every entry left, before the lane's scan point `v` is replaced or the terms are read
+template <bool FAST, int G, int LD>
+__device__ __forceinline__ void defer_flush(const RecGrid& rg, const LikParams& prm, const float (&s_pose)[G][8],
+                                            float (&s_term)[G][LD], unsigned (&s_cnt)[G][4], const DeferQueue& q, int wave,
+                                            int lane, const float4 v, uint32_t qn)
+{
+  defer_drain<FAST>(rg, prm, s_pose, s_term, s_cnt, q, wave, lane, 0u, qn, v);
+}
+
+// ---- pieces shared by the tiled kernel and likelihood_chain_multi_kernel -------------------------------------------------
+// The G normalised poses of particle group `group` into LDS: px,py,pz, qx,qy,qz,qw, valid (0 past the last particle). The
+// caller's barrier follows.
+template <int G>
+__device__ __forceinline__ void stage_poses(float (&s_pose)[G][8], const float* __restrict__ pose7, int n_p, int group, int t)
+{
+  if (t < G)
+  {
+    const int p = group * G + t;
+    float valid = 0.f;
+    if (p < n_p)
+    {
+      const float* ps = pose7 + 7 * static_cast<size_t>(p);
+      const Quat r = qnormalized(Quat{ ps[3], ps[4], ps[5], ps[6] });  // state_6dof.h:217
+      s_pose[t][0] = ps[0];
+      s_pose[t][1] = ps[1];
+      s_pose[t][2] = ps[2];
+      s_pose[t][3] = r.x;
+      s_pose[t][4] = r.y;
+      s_pose[t][5] = r.z;
+      s_pose[t][6] = r.w;
+      valid = 1.f;
+    }
+    s_pose[t][7] = valid;
+  }
+}
+
+// Block index -> (link, particle group) in rows of eight links — tiles, or likelihood_chain_multi_kernel's super-tiles — one per
+// XCD (block b runs on XCD b % 8): XCD x takes link 8 row + x over all particle groups. False = past the last link: with the
+// float chain a last partial row leaves XCDs idle (sharing it out as the fp64 form does would break "the producer's block
+// index is lower").
+__device__ __forceinline__ bool xcd_row_map(uint32_t block_index, int n_groups, int n_links, int& link, int& group)
+{
+  const uint32_t xcd = block_index & 7u, seq = block_index >> 3, ng = static_cast<uint32_t>(n_groups);
+  const uint32_t row = seq / ng;
+  link = static_cast<int>(row * 8u + xcd);
+  group = static_cast<int>(seq - row * ng);
+  return link < n_links;
+}
+
+// One link of a particle's float chain (LikChain above), run by one lane. cw = the particle's two hand-off words.
+// chain_take: the running sum and match count the previous link handed on (0, 0 for the first link). Every lane polls its own
+// two words; lanes that have theirs idle through the others' iterations. The poll is bounded: a lane that gives up raises
+// *ch.err and goes on with what it read.
+constexpr int CHAIN_POLL_MAX = 1 << 20;  // polls of a hand-off word before the lane gives up (~1 s)
+__device__ __forceinline__ void chain_take(const LikChain& ch, const unsigned long long* cw, int link, float& s,
+                                           uint32_t& cnt)
+{
+  s = 0.0f;
+  cnt = 0;
+  if (link > 0)
+  {
+    const uint32_t want = ch.tag0 + static_cast<uint32_t>(link) - 1u;
+    unsigned long long a = 0, b = 0;
+#pragma nounroll
+    for (int polls = 0;; ++polls)
+    {
+      a = __hip_atomic_load(cw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      b = __hip_atomic_load(cw + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (static_cast<uint32_t>(a >> 32) == want && static_cast<uint32_t>(b >> 32) == want)
+        break;
+      if (polls >= CHAIN_POLL_MAX)
+      {
+        *ch.err = 1u;
+        break;
+      }
+      __builtin_amdgcn_s_sleep(8);
+    }
+    s = __uint_as_float(static_cast<uint32_t>(a));
+    cnt = static_cast<uint32_t>(b);
+  }
+}
+
+// chain_add_row: the 256 terms of one tile in array order, four per 16-byte LDS read — the reference's dependent float adds
+__device__ __forceinline__ void chain_add_row(const float* term_row, float& s)
+{
+  const float4* row = reinterpret_cast<const float4*>(term_row);
+#pragma unroll 8
+  for (int j = 0; j < 64; ++j)
+  {
+    const float4 t4 = row[j];
+    s = s + t4.x;
+    s = s + t4.y;
+    s = s + t4.z;
+    s = s + t4.w;
+  }
+}
+
+// chain_give: the last link writes particle p's likelihood and match ratio, every other one hands on under its own tag
+__device__ __forceinline__ void chain_give(const LikChain& ch, unsigned long long* cw, size_t p, int link, bool last, int n_s,
+                                           float s, uint32_t cnt)
+{
+  if (last)
+  {
+    ch.out_lik[p] = s;
+    if (ch.out_ratio)
+      ch.out_ratio[p] = static_cast<float>(cnt) / static_cast<float>(n_s);
+    if (ch.also_fill)
+      ch.also_fill[p] = 1.0f;
+  }
+  else
+  {
+    const uint32_t tag = ch.tag0 + static_cast<uint32_t>(link);
+    __hip_atomic_store(cw, chain_pack(__float_as_uint(s), tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(cw + 1, chain_pack(cnt, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -1048,12 +1206,8 @@ __device__ __forceinline__ void likelihood_tiled_body(const uint32_t block_index
   int tile, group;
   if constexpr (CHAIN)
   {
-    // rows of eight tiles, XCD x takes tile 8 row + x over all particle groups; a last partial row leaves XCDs idle (the
-    // shared-out remainder below would break "the producer's block index is lower")
-    const uint32_t row = seq / ng;
-    tile = static_cast<int>(row * 8u + xcd);
-    group = static_cast<int>(seq - row * ng);
-    if (tile >= n_tiles)
+    // rows only: a last partial row leaves XCDs idle (xcd_row_map)
+    if (!xcd_row_map(block_index, n_groups, n_tiles, tile, group))
       return;
   }
   else if (seq < per_xcd_full)
@@ -1075,25 +1229,7 @@ __device__ __forceinline__ void likelihood_tiled_body(const uint32_t block_index
     group = static_cast<int>(item - row * ng);
   }
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  if (t < G)
-  {
-    const int p = group * G + t;
-    float v = 0.f;
-    if (p < n_p)
-    {
-      const float* ps = pose7 + 7 * static_cast<size_t>(p);
-      const Quat r = qnormalized(Quat{ ps[3], ps[4], ps[5], ps[6] });
-      s_pose[t][0] = ps[0];
-      s_pose[t][1] = ps[1];
-      s_pose[t][2] = ps[2];
-      s_pose[t][3] = r.x;
-      s_pose[t][4] = r.y;
-      s_pose[t][5] = r.z;
-      s_pose[t][6] = r.w;
-      v = 1.f;
-    }
-    s_pose[t][7] = v;
-  }
+  stage_poses<G>(s_pose, pose7, n_p, group, t);
   const int i = tile * 256 + t;
   const bool have_point = i < n_s;
   const float4 v = have_point ? scan[i] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1145,40 +1281,10 @@ __device__ __forceinline__ void likelihood_tiled_body(const uint32_t block_index
           if (lane == 0)
             s_cnt[k][wave] = static_cast<unsigned>(__popcll(m));
         }
-        if (om != 0ull)
-        {
-          const uint32_t n_new = static_cast<uint32_t>(__popcll(om));
-          if (qn + n_new > static_cast<uint32_t>(DEFER_QCAP))
-          {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            defer_drain<FAST>(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, 0u, qn, v);
-            qn = 0;
-          }
-          if (over)
-          {
-            const uint32_t slot = qn + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(om >> 32),
-                                                                 __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(om), 0u));
-            s_q.word[wave][slot] = mine;
-            s_q.who[wave][slot] = static_cast<uint16_t>((static_cast<uint32_t>(k) << 6) | static_cast<uint32_t>(lane));
-          }
-          qn += n_new;
-          if (qn >= 64u)
-          {
-            // the LAST 64 entries: what stays queued keeps its place
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            defer_drain<FAST>(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, qn - 64u, 64u, v);
-            qn -= 64u;
-          }
-        }
+        qn = defer_push<FAST>(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, v, qn, om, over, mine, k);
       }
       if (qn != 0u)
-      {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        defer_drain<FAST>(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, 0u, qn, v);
-      }
+        defer_flush<FAST>(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, v, qn);
     };
     if (rg.common_map)
       pose_loop(BoolConstant<true>{});
@@ -1240,58 +1346,12 @@ __device__ __forceinline__ void likelihood_tiled_body(const uint32_t block_index
     const int k = lane;
     const size_t p = static_cast<size_t>(group) * G + k;
     unsigned long long* cw = ch.carry + 2 * p;
-    float s = 0.0f;
-    uint32_t cnt = 0;
-    if (tile > 0)
-    {
-      const uint32_t want = ch.tag0 + static_cast<uint32_t>(tile) - 1u;
-      unsigned long long a = 0, b = 0;
-      int polls = 0;
-      bool got = false;
-      // (every lane polls its own two words; lanes that have theirs idle through the others' iterations)
-      while (!got)
-      {
-        a = __hip_atomic_load(cw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        b = __hip_atomic_load(cw + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        got = static_cast<uint32_t>(a >> 32) == want && static_cast<uint32_t>(b >> 32) == want;
-        if (!got)
-        {
-          if (++polls > CHAIN_POLL_MAX)
-          {
-            *ch.err = 1u;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(8);
-        }
-      }
-      s = __uint_as_float(static_cast<uint32_t>(a));
-      cnt = static_cast<uint32_t>(b);
-    }
-    const float4* row = reinterpret_cast<const float4*>(&s_term[k][0]);
-#pragma unroll 8
-    for (int j = 0; j < 64; ++j)
-    {
-      const float4 t4 = row[j];
-      s = s + t4.x;
-      s = s + t4.y;
-      s = s + t4.z;
-      s = s + t4.w;
-    }
+    float s;
+    uint32_t cnt;
+    chain_take(ch, cw, tile, s, cnt);
+    chain_add_row(&s_term[k][0], s);
     cnt += s_cnt[k][0] + s_cnt[k][1] + s_cnt[k][2] + s_cnt[k][3];
-    if (tile == n_tiles - 1)
-    {
-      ch.out_lik[p] = s;
-      if (ch.out_ratio)
-        ch.out_ratio[p] = static_cast<float>(cnt) / static_cast<float>(n_s);
-      if (ch.also_fill)
-        ch.also_fill[p] = 1.0f;
-    }
-    else
-    {
-      const uint32_t tag = ch.tag0 + static_cast<uint32_t>(tile);
-      __hip_atomic_store(cw, chain_pack(__float_as_uint(s), tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(cw + 1, chain_pack(cnt, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    chain_give(ch, cw, p, tile, tile == n_tiles - 1, n_s, s, cnt);
     return;
   }
   if (strict_terms)
