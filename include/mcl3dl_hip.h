@@ -705,6 +705,59 @@ int mcl3dl_hip_group_scan_finish_drawn(mcl3dl_hip_group* g, size_t n_s, size_t n
 int mcl3dl_hip_group_update_resident_prepared(mcl3dl_hip_group* g, const float* extra /*n_p or NULL*/, float* out_weight,
                                               float* out_lik, float* out_match_ratio, float* out_beam, float* entropy,
                                               float* match_ratio_min, float* match_ratio_max, int* restored);
+/* ---- clouds accumulated on the device: accum_cloud > 1 and several sensors without a host cloud -----------
+ * Replaces: accumClear and accumCloud (src/mcl_3dl.cpp:267-302) and the head of measure() (:312-336) in front of what
+ * mcl3dl_hip_scan_begin replaces. The accumulation logic (src/cloud_accum.cpp), the tf lookups and the per-cloud origins
+ * (:343-359) stay the caller's.
+ *   scan_accum_clear           accumClear: the accumulation is empty again, the next push gets index 0.
+ *   scan_accum_push            accumCloud for one message: every point is transformed by affine12 — the rows of the 3x4 [R | t],
+ *                              odom <- sensor —, labelled with the number of clouds pushed since the last clear and appended.
+ *                              *out_cloud_index (may be NULL) = that label, *out_total_points (may be NULL) = the points held
+ *                              afterwards. Returns once `xyz` may be reused; the work is enqueued on the context's stream.
+ *   scan_accum_push_pointcloud2  the same from the wire format (layout rules: mcl3dl_hip_pointcloud2_layout_ok above). The
+ *                              message's own label field is not read — accumCloud overwrites it —, hence no off_label.
+ *   scan_accum_size            clouds pushed since the last clear, points held.
+ *   scan_accum_download        the accumulation as held: odom frame, push order, label = cloud index (xyz NULL: only *n).
+ *   scan_begin_accumulated     transforms the accumulation by affine12 (base_link <- odom at the last stamp) into the scan path's
+ *                              raw cloud, then VoxelGrid + both clips exactly as mcl3dl_hip_scan_begin on that cloud; whatever
+ *                              follows a scan_begin follows it unchanged. The accumulation is NOT consumed: a second call gives
+ *                              the same bits, a later push continues with the next index, clearing is the caller's accumClear.
+ *                              No point travels host to device in this call.
+ * The arithmetic of both transforms, per output row r, in float32, every product and sum rounded on its own (no fused
+ * multiply-add):  out[r] = ((m[r][0] x + m[r][1] y) + m[r][2] z) + m[r][3].  The two transforms are not composed: between them
+ * the points are floats in the odom frame, as pc_local_accum_ holds them. affine12 == NULL copies the coordinates' bits.
+ * Non-finite coordinates get no special treatment (VoxelGrid drops them). The reference has this arithmetic from
+ * tf2_sensor_msgs and PCL over an Eigen it neither vendors nor pins: parity is against this statement.
+ * The caller builds the matrix with its own Eigen:
+ *   Eigen::Matrix<float, 3, 4, Eigen::RowMajor> m = (Eigen::Translation3f(..) * Eigen::Quaternionf(w, x, y, z)).matrix().topRows<3>();
+ * -3 (every argument is checked before anything is modified; a refused push consumes no index and leaves the accumulation as it
+ * was): an empty cloud ("Given PointCloud2 is empty", point_conversion.h:54-58, where accumCloud returns false), a NULL array,
+ * a field offset that does not fit point_step, a non-finite entry of affine12, more than 2^31 - 1 points in total. -5:
+ * scan_begin_accumulated with nothing pushed ("MCL measure function is called without available pointcloud", :312-316); a
+ * scan prepared earlier stays usable.
+ * group_*: the context forms on every rank, each on its own replica (mcl3dl_hip_group_scan_begin's rules: the ranks must agree,
+ * else -4). The accumulation of rank r is read with mcl3dl_hip_scan_accum_download on mcl3dl_hip_group_context(g, r). */
+int mcl3dl_hip_scan_accum_clear(mcl3dl_hip_ctx* ctx);
+int mcl3dl_hip_scan_accum_push(mcl3dl_hip_ctx* ctx, const float* xyz /*n*3, sensor frame*/, size_t n,
+                               const float* affine12 /*or NULL*/, size_t* out_cloud_index, size_t* out_total_points);
+int mcl3dl_hip_scan_accum_push_pointcloud2(mcl3dl_hip_ctx* ctx, const uint8_t* data, size_t n_points, uint32_t point_step,
+                                           int off_x, int off_y, int off_z, const float* affine12 /*or NULL*/,
+                                           size_t* out_cloud_index, size_t* out_total_points);
+int mcl3dl_hip_scan_accum_size(mcl3dl_hip_ctx* ctx, size_t* n_clouds, size_t* n_points);
+int mcl3dl_hip_scan_accum_download(mcl3dl_hip_ctx* ctx, float* xyz, uint32_t* label, size_t capacity, size_t* n);
+int mcl3dl_hip_scan_begin_accumulated(mcl3dl_hip_ctx* ctx, const float* affine12 /*or NULL*/, const float* leaf3,
+                                      const float* clip_lik4, const float* clip_beam4, size_t* n_full, size_t* n_lik_clipped,
+                                      size_t* n_beam_clipped);
+int mcl3dl_hip_group_scan_accum_clear(mcl3dl_hip_group* g);
+int mcl3dl_hip_group_scan_accum_push(mcl3dl_hip_group* g, const float* xyz /*n*3*/, size_t n, const float* affine12 /*or NULL*/,
+                                     size_t* out_cloud_index, size_t* out_total_points);
+int mcl3dl_hip_group_scan_accum_push_pointcloud2(mcl3dl_hip_group* g, const uint8_t* data, size_t n_points, uint32_t point_step,
+                                                 int off_x, int off_y, int off_z, const float* affine12 /*or NULL*/,
+                                                 size_t* out_cloud_index, size_t* out_total_points);
+int mcl3dl_hip_group_scan_accum_size(mcl3dl_hip_group* g, size_t* n_clouds, size_t* n_points);
+int mcl3dl_hip_group_scan_begin_accumulated(mcl3dl_hip_group* g, const float* affine12 /*or NULL*/, const float* leaf3,
+                                            const float* clip_lik4, const float* clip_beam4, size_t* n_full,
+                                            size_t* n_lik_clipped, size_t* n_beam_clipped);
 /* ---- the normal-weighted sampler drawn on the device ------------------------------------------------------
  * Replaces: lines :139-177 of PointCloudSamplerWithNormal::sample — the cumulative weights (a sequential double recurrence), the
  * std::uniform_real_distribution<double>(0, total) draws, std::lower_bound, the duplicate rejection through a

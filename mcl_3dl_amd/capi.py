@@ -144,6 +144,17 @@ SIGNATURES = {
     "mcl3dl_hip_group_scan_finish": (_i, [_p, _p, _sz, _p, _sz, _p, _sz]),
     "mcl3dl_hip_group_scan_finish_drawn": (_i, [_p, _sz, _sz, _p, _sz, C.POINTER(_u32), C.POINTER(_sz), C.POINTER(_sz)]),
     "mcl3dl_hip_group_update_resident_prepared": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "mcl3dl_hip_scan_accum_clear": (_i, [_p]),
+    "mcl3dl_hip_scan_accum_push": (_i, [_p, _p, _sz, _p, C.POINTER(_sz), C.POINTER(_sz)]),
+    "mcl3dl_hip_scan_accum_push_pointcloud2": (_i, [_p, _p, _sz, _u32, _i, _i, _i, _p, C.POINTER(_sz), C.POINTER(_sz)]),
+    "mcl3dl_hip_scan_accum_size": (_i, [_p, C.POINTER(_sz), C.POINTER(_sz)]),
+    "mcl3dl_hip_scan_accum_download": (_i, [_p, _p, _p, _sz, C.POINTER(_sz)]),
+    "mcl3dl_hip_scan_begin_accumulated": (_i, [_p, _p, _p, _p, _p, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
+    "mcl3dl_hip_group_scan_accum_clear": (_i, [_p]),
+    "mcl3dl_hip_group_scan_accum_push": (_i, [_p, _p, _sz, _p, C.POINTER(_sz), C.POINTER(_sz)]),
+    "mcl3dl_hip_group_scan_accum_push_pointcloud2": (_i, [_p, _p, _sz, _u32, _i, _i, _i, _p, C.POINTER(_sz), C.POINTER(_sz)]),
+    "mcl3dl_hip_group_scan_accum_size": (_i, [_p, C.POINTER(_sz), C.POINTER(_sz)]),
+    "mcl3dl_hip_group_scan_begin_accumulated": (_i, [_p, _p, _p, _p, _p, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     "mcl3dl_hip_rng_draw_weighted": (_i, [_p, _p, _sz, _sz, C.POINTER(_u32), _p, _p, C.POINTER(_u64)]),
     "mcl3dl_hip_scan_finish_drawn_normal": (_i, [_p, _sz, _sz, _p, _sz, _d, _p, _d, C.POINTER(_u32), C.POINTER(_sz),
                                                 C.POINTER(_sz)]),
@@ -214,6 +225,19 @@ def _ptr(a):
     if isinstance(a, int):
         return C.c_void_p(a)
     return C.c_void_p(a.data_ptr())  # torch tensor (device memory)
+
+
+def _affine12(affine):
+    """None, or the rows of the 3x4 [R | t] as twelve float32 (a 3x4, a 4x4 whose top rows are taken, or twelve floats)."""
+    if affine is None:
+        return None
+    a = np.asarray(affine, dtype=np.float32)
+    if a.shape == (4, 4):
+        a = a[:3]
+    a = np.ascontiguousarray(a).reshape(-1)
+    if a.size != 12:
+        raise ValueError("affine must hold the 3x4 [R | t] (twelve floats)")
+    return a
 
 
 def scan_order_host(scan_lik):
@@ -443,6 +467,40 @@ class Group:
                                                                      off_label, label_override, _ptr(lf), _ptr(cl), _ptr(cb),
                                                                      C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
+
+    # ---- clouds accumulated on the devices, every rank its replica (accumClear / accumCloud and the head of measure()) ----------
+    def scan_accum_clear(self):
+        """accumClear on every rank: the accumulation is empty, the next push gets index 0."""
+        self._check(self.lib.mcl3dl_hip_group_scan_accum_clear(self.h))
+
+    def scan_accum_push(self, xyz, affine=None):
+        """Engine.scan_accum_push on every rank; returns (cloud index, points held)."""
+        pts = _np_f32(xyz, 3)
+        a, idx, tot = _affine12(affine), C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_group_scan_accum_push(self.h, _ptr(pts), len(pts), _ptr(a), C.byref(idx), C.byref(tot)))
+        return int(idx.value), int(tot.value)
+
+    def scan_accum_push_pointcloud2(self, data, n_points, point_step, off_x, off_y, off_z, affine=None):
+        """scan_accum_push from PointCloud2 bytes (the message's label field, if any, is not read)."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        a, idx, tot = _affine12(affine), C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_group_scan_accum_push_pointcloud2(self.h, _ptr(buf), n_points, point_step, off_x, off_y,
+                                                                          off_z, _ptr(a), C.byref(idx), C.byref(tot)))
+        return int(idx.value), int(tot.value)
+
+    def scan_accum_size(self):
+        """(clouds pushed since the last clear, points held)."""
+        c, n = C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_group_scan_accum_size(self.h, C.byref(c), C.byref(n)))
+        return int(c.value), int(n.value)
+
+    def scan_begin_accumulated(self, affine=None, leaf=None, clip_lik=(0.5, 10.0, -2.0, 2.0), clip_beam=(0.5, 4.0, -2.0, 2.0)):
+        """Engine.scan_begin_accumulated on every rank; returns (n_full, n_lik_clipped, n_beam_clipped)."""
+        a, lf, cl, cb = _affine12(affine), Engine._f3(leaf), Engine._f3(clip_lik), Engine._f3(clip_beam)
+        x, y, z = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_group_scan_begin_accumulated(self.h, _ptr(a), _ptr(lf), _ptr(cl), _ptr(cb), C.byref(x),
+                                                                     C.byref(y), C.byref(z)))
+        return int(x.value), int(y.value), int(z.value)
 
     def scan_finish(self, idx_lik, idx_beam=None, origins=None):
         il = np.ascontiguousarray(idx_lik if idx_lik is not None else [], dtype=np.uint32)
@@ -1034,6 +1092,52 @@ class Engine:
                                                                off_label, label_override, _ptr(lf), _ptr(cl), _ptr(cb),
                                                                C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
+
+    # ---- clouds accumulated on the device (accumClear / accumCloud and the head of measure(), src/mcl_3dl.cpp:267-336) ----------
+    def scan_accum_clear(self):
+        """accumClear: the accumulation is empty, the next push gets index 0."""
+        self._check(self.lib.mcl3dl_hip_scan_accum_clear(self.h))
+
+    def scan_accum_push(self, xyz, affine=None):
+        """accumCloud for one message: the points (sensor frame) are transformed by `affine` (odom <- sensor; None: taken as they
+        are), labelled with the cloud's index and appended. Returns (cloud index, points held)."""
+        pts = _np_f32(xyz, 3)
+        a, idx, tot = _affine12(affine), C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_scan_accum_push(self.h, _ptr(pts), len(pts), _ptr(a), C.byref(idx), C.byref(tot)))
+        return int(idx.value), int(tot.value)
+
+    def scan_accum_push_pointcloud2(self, data, n_points, point_step, off_x, off_y, off_z, affine=None):
+        """scan_accum_push from PointCloud2 bytes (the message's label field, if any, is not read)."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        a, idx, tot = _affine12(affine), C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_scan_accum_push_pointcloud2(self.h, _ptr(buf), n_points, point_step, off_x, off_y, off_z,
+                                                                    _ptr(a), C.byref(idx), C.byref(tot)))
+        return int(idx.value), int(tot.value)
+
+    def scan_accum_size(self):
+        """(clouds pushed since the last clear, points held)."""
+        c, n = C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_scan_accum_size(self.h, C.byref(c), C.byref(n)))
+        return int(c.value), int(n.value)
+
+    def scan_accum_download(self):
+        """(xyz, label) of the accumulation as held: odom frame, push order, label = cloud index."""
+        n = C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_scan_accum_download(self.h, None, None, 0, C.byref(n)))
+        xyz = np.zeros((n.value, 3), np.float32)
+        lab = np.zeros(n.value, np.uint32)
+        if n.value:
+            self._check(self.lib.mcl3dl_hip_scan_accum_download(self.h, _ptr(xyz), _ptr(lab), n.value, C.byref(n)))
+        return xyz, lab
+
+    def scan_begin_accumulated(self, affine=None, leaf=None, clip_lik=(0.5, 10.0, -2.0, 2.0), clip_beam=(0.5, 4.0, -2.0, 2.0)):
+        """scan_begin on the accumulation, transformed by `affine` (base_link <- odom; None: as it is) on the device; the
+        accumulation stays. Returns (n_full, n_lik_clipped, n_beam_clipped)."""
+        a, lf, cl, cb = _affine12(affine), Engine._f3(leaf), Engine._f3(clip_lik), Engine._f3(clip_beam)
+        x, y, z = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._check(self.lib.mcl3dl_hip_scan_begin_accumulated(self.h, _ptr(a), _ptr(lf), _ptr(cl), _ptr(cb), C.byref(x),
+                                                               C.byref(y), C.byref(z)))
+        return int(x.value), int(y.value), int(z.value)
 
     def scan_finish(self, idx_lik, idx_beam=None, origins=None):
         il = np.ascontiguousarray(idx_lik if idx_lik is not None else [], dtype=np.uint32)

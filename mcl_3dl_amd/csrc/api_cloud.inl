@@ -223,6 +223,106 @@ int mcl3dl_hip_scan_download(mcl3dl_hip_ctx* ctx, int which, float* xyz, uint32_
   return download_cloud(ctx, src, cnt, xyz, label);
 }
 
+// ---- the accumulation of clouds on the device (scan_accum.h, host_cloud.h) ---------------------------------------------------
+// Replaces: accumClear (src/mcl_3dl.cpp:267-272). The buffer stays: a steady stream of scans allocates nothing.
+int mcl3dl_hip_scan_accum_clear(mcl3dl_hip_ctx* ctx)
+{
+  if (!ctx)
+    return -1;
+  ctx->sa_n_points = 0;
+  ctx->sa_n_clouds = 0;
+  return 0;
+}
+
+// Replaces: accumCloud (src/mcl_3dl.cpp:274-302) for one message
+int mcl3dl_hip_scan_accum_push(mcl3dl_hip_ctx* ctx, const float* xyz, size_t n, const float* affine12, size_t* out_cloud_index,
+                               size_t* out_total_points)
+{
+  if (!ctx)
+    return -1;
+  AccumAffine a;
+  TRY(accum_push_check(ctx, xyz, n, affine12, &a));
+  bool staged = false;
+  TRY(accum_push_stage(ctx, xyz, sizeof(float) * 3 * n, n, &staged));
+  const long long nn = static_cast<long long>(n);
+  hipLaunchKernelGGL(scan_accum_push_kernel, dim3(accum_push_blocks(nn)), dim3(256), 0, ctx->stream, ctx->cl_in_xyz.as<float>(), nn,
+                     a, static_cast<uint32_t>(ctx->sa_n_clouds), ctx->sa_accum.as<float4>() + ctx->sa_n_points);
+  return accum_push_done(ctx, n, staged, out_cloud_index, out_total_points);
+}
+
+int mcl3dl_hip_scan_accum_push_pointcloud2(mcl3dl_hip_ctx* ctx, const uint8_t* data, size_t n_points, uint32_t point_step,
+                                           int off_x, int off_y, int off_z, const float* affine12, size_t* out_cloud_index,
+                                           size_t* out_total_points)
+{
+  if (!ctx)
+    return -1;
+  if (off_x < 0 || off_y < 0 || off_z < 0)
+    return ctx->fail(-3, "Given PointCloud2 doesn't have x, y, z fields");
+  const int offs[3] = { off_x, off_y, off_z };
+  for (int k = 0; k < 3; ++k)
+    if (static_cast<uint64_t>(offs[k]) + 4 > point_step)
+      return ctx->fail(-3, "field offset %d does not fit point_step %u", offs[k], point_step);
+  AccumAffine a;
+  TRY(accum_push_check(ctx, data, n_points, affine12, &a));
+  bool staged = false;
+  TRY(accum_push_stage(ctx, data, n_points * static_cast<size_t>(point_step), n_points, &staged));
+  const long long nn = static_cast<long long>(n_points);
+  hipLaunchKernelGGL(scan_accum_push_pc2_kernel, dim3(accum_push_blocks(nn)), dim3(256), 0, ctx->stream,
+                     ctx->cl_in_xyz.as<uint8_t>(), nn, point_step, off_x, off_y, off_z, a, static_cast<uint32_t>(ctx->sa_n_clouds),
+                     ctx->sa_accum.as<float4>() + ctx->sa_n_points);
+  return accum_push_done(ctx, n_points, staged, out_cloud_index, out_total_points);
+}
+
+int mcl3dl_hip_scan_accum_size(mcl3dl_hip_ctx* ctx, size_t* n_clouds, size_t* n_points)
+{
+  if (!ctx)
+    return -1;
+  if (n_clouds)
+    *n_clouds = ctx->sa_n_clouds;
+  if (n_points)
+    *n_points = ctx->sa_n_points;
+  return 0;
+}
+
+int mcl3dl_hip_scan_accum_download(mcl3dl_hip_ctx* ctx, float* xyz, uint32_t* label, size_t capacity, size_t* n)
+{
+  if (!ctx)
+    return -1;
+  const size_t cnt = ctx->sa_n_points;
+  if (n)
+    *n = cnt;
+  if (!xyz)
+    return 0;
+  if (capacity < cnt)
+    return ctx->fail(-3, "capacity %zu < %zu points", capacity, cnt);
+  HIP_TRY(hipSetDevice(ctx->device));
+  return download_cloud(ctx, ctx->sa_accum.as<float4>(), cnt, xyz, label);
+}
+
+// Replaces: the transform of pc_local_accum_ into base_link at the last stamp (src/mcl_3dl.cpp:319-336) + what
+// mcl3dl_hip_scan_begin replaces. The accumulation is read, not consumed: the transformed cloud goes to the scan path's raw buffer.
+int mcl3dl_hip_scan_begin_accumulated(mcl3dl_hip_ctx* ctx, const float* affine12, const float* leaf3, const float* clip_lik4,
+                                      const float* clip_beam4, size_t* n_full, size_t* n_lik_clipped, size_t* n_beam_clipped)
+{
+  if (!ctx)
+    return -1;
+  AccumAffine a;
+  TRY(accum_affine(ctx, affine12, &a));
+  const size_t n = ctx->sa_n_points;
+  if (n == 0)  // "MCL measure function is called without available pointcloud" (src/mcl_3dl.cpp:312-316)
+    return ctx->fail(-5, "no accumulated cloud: call mcl3dl_hip_scan_accum_push first");
+  HIP_TRY(hipSetDevice(ctx->device));
+  TRY(ensure(ctx, ctx->sp_raw, sizeof(float4) * n));
+  const long long nn = static_cast<long long>(n);
+  const unsigned nb = minmax_blocks(nn);
+  MinMaxOut mm;
+  TRY(minmax_out(ctx, nb, &mm));
+  hipLaunchKernelGGL(scan_accum_to_raw_minmax_kernel, dim3(nb), dim3(256), 0, ctx->stream, ctx->sa_accum.as<float4>(), nn, a,
+                     ctx->sp_raw.as<float4>(), mm);
+  HIP_TRY(hipGetLastError());
+  return scan_begin_common(ctx, n, leaf3, clip_lik4, clip_beam4, n_full, n_lik_clipped, n_beam_clipped, true);
+}
+
 int mcl3dl_hip_sort_pairs(mcl3dl_hip_ctx* ctx, const uint32_t* keys, const uint32_t* vals, size_t n, int end_bit,
                           uint32_t* out_keys, uint32_t* out_vals)
 {

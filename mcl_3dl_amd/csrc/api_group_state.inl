@@ -210,6 +210,68 @@ int mcl3dl_hip_group_scan_begin_pointcloud2(mcl3dl_hip_group* g, const uint8_t* 
   return group_scan_sizes(g, got, "the sizes of the prepared clouds", n_full, n_lik_clipped, n_beam_clipped);
 }
 
+// ---- the accumulation of clouds on a group: every rank holds its replica (accumClear / accumCloud, src/mcl_3dl.cpp:267-302).
+// There is no group download: mcl3dl_hip_scan_accum_download on mcl3dl_hip_group_context(g, r) serves that.
+int mcl3dl_hip_group_scan_accum_clear(mcl3dl_hip_group* g)
+{
+  if (!g)
+    return -1;
+  return group_scan_each(g, [&](mcl3dl_hip_ctx* ctx, int) -> int { return mcl3dl_hip_scan_accum_clear(ctx); });
+}
+
+int mcl3dl_hip_group_scan_accum_push(mcl3dl_hip_group* g, const float* xyz, size_t n, const float* affine12,
+                                     size_t* out_cloud_index, size_t* out_total_points)
+{
+  if (!g)
+    return -1;
+  std::vector<size_t> got(3 * static_cast<size_t>(g->n()), 0);  // {cloud index, total points, -}
+  TRY(group_scan_each(g, [&](mcl3dl_hip_ctx* ctx, int r) -> int
+                      { return mcl3dl_hip_scan_accum_push(ctx, xyz, n, affine12, &got[3 * r], &got[3 * r + 1]); }));
+  return group_scan_sizes(g, got, "the accumulated clouds", out_cloud_index, out_total_points, nullptr);
+}
+
+int mcl3dl_hip_group_scan_accum_push_pointcloud2(mcl3dl_hip_group* g, const uint8_t* data, size_t n_points, uint32_t point_step,
+                                                 int off_x, int off_y, int off_z, const float* affine12, size_t* out_cloud_index,
+                                                 size_t* out_total_points)
+{
+  if (!g)
+    return -1;
+  std::vector<size_t> got(3 * static_cast<size_t>(g->n()), 0);
+  TRY(group_scan_each(g,
+                      [&](mcl3dl_hip_ctx* ctx, int r) -> int
+                      {
+                        return mcl3dl_hip_scan_accum_push_pointcloud2(ctx, data, n_points, point_step, off_x, off_y, off_z, affine12,
+                                                                      &got[3 * r], &got[3 * r + 1]);
+                      }));
+  return group_scan_sizes(g, got, "the accumulated clouds", out_cloud_index, out_total_points, nullptr);
+}
+
+int mcl3dl_hip_group_scan_accum_size(mcl3dl_hip_group* g, size_t* n_clouds, size_t* n_points)
+{
+  if (!g)
+    return -1;
+  std::vector<size_t> got(3 * static_cast<size_t>(g->n()), 0);
+  TRY(group_scan_each(g, [&](mcl3dl_hip_ctx* ctx, int r) -> int
+                      { return mcl3dl_hip_scan_accum_size(ctx, &got[3 * r], &got[3 * r + 1]); }));
+  return group_scan_sizes(g, got, "the accumulated clouds", n_clouds, n_points, nullptr);
+}
+
+// Replaces: what mcl3dl_hip_scan_begin_accumulated replaces, for the measurement of a device group
+int mcl3dl_hip_group_scan_begin_accumulated(mcl3dl_hip_group* g, const float* affine12, const float* leaf3, const float* clip_lik4,
+                                            const float* clip_beam4, size_t* n_full, size_t* n_lik_clipped, size_t* n_beam_clipped)
+{
+  if (!g)
+    return -1;
+  std::vector<size_t> got(3 * static_cast<size_t>(g->n()), 0);
+  TRY(group_scan_each(g,
+                      [&](mcl3dl_hip_ctx* ctx, int r) -> int
+                      {
+                        return mcl3dl_hip_scan_begin_accumulated(ctx, affine12, leaf3, clip_lik4, clip_beam4, &got[3 * r],
+                                                                 &got[3 * r + 1], &got[3 * r + 2]);
+                      }));
+  return group_scan_sizes(g, got, "the sizes of the prepared clouds", n_full, n_lik_clipped, n_beam_clipped);
+}
+
 // Replaces: what mcl3dl_hip_scan_finish replaces, on every rank: the sampler's push_back loop (point_cloud_uniform_sampler.h:
 // 66-71, or sampler_with_normal's) with caller-drawn indices, and the scans installed where the group's update reads them
 int mcl3dl_hip_group_scan_finish(mcl3dl_hip_group* g, const uint32_t* idx_lik, size_t n_s, const uint32_t* idx_beam, size_t n_b,

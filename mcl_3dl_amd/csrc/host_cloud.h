@@ -490,4 +490,94 @@ int device_order_scans(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b, const float*
   HIP_TRY(hipGetLastError());
   return 0;
 }
+
+// ---- the accumulation of clouds (scan_accum.h) ----------------------------------------------------------------------------
+// ensure() that keeps the first `keep` bytes: allocate, device-to-device copy on the stream, free. Grows geometrically (ten
+// pushes do not reallocate ten times). A failed allocation leaves the buffer as it was.
+int grow_keep(mcl3dl_hip_ctx* ctx, DevBuf& b, size_t keep, size_t bytes)
+{
+  if (b.cap >= bytes)
+    return 0;
+  if (b.view)
+    return ctx->fail(-2, "internal: grow_keep() on a view buffer");
+  const size_t cap = std::max(bytes + bytes / 4, 2 * b.cap);
+  void* p = nullptr;
+  HIP_TRY(hipMalloc(&p, cap));
+  if (b.p)
+  {
+    hipError_t e = keep ? hipMemcpyAsync(p, b.p, keep, hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
+    if (e == hipSuccess)
+      e = hipStreamSynchronize(ctx->stream);  // the copy, and every kernel that still reads the old allocation
+    if (e != hipSuccess)
+    {
+      (void)hipFree(p);
+      return ctx->fail(-2, "growing the accumulated cloud failed: %s", hipGetErrorString(e));
+    }
+    HIP_TRY(hipFree(b.p));
+  }
+  b.p = p;
+  b.cap = cap;
+  return 0;
+}
+
+// nullptr -> the bits are copied; else the twelve floats, all finite
+int accum_affine(mcl3dl_hip_ctx* ctx, const float* affine12, AccumAffine* a)
+{
+  *a = AccumAffine{};
+  if (!affine12)
+    return 0;
+  for (int k = 0; k < 12; ++k)
+  {
+    if (!std::isfinite(affine12[k]))
+      return ctx->fail(-3, "affine12[%d] is not finite", k);
+    a->m[k] = affine12[k];
+  }
+  a->on = 1;
+  return 0;
+}
+
+// what every push checks before anything is touched (the reference's accumCloud returns false on an empty message,
+// point_conversion.h:54-58)
+int accum_push_check(mcl3dl_hip_ctx* ctx, const void* data, size_t n, const float* affine12, AccumAffine* a)
+{
+  if (n == 0)
+    return ctx->fail(-3, "Given PointCloud2 is empty");
+  if (!data)
+    return ctx->fail(-3, "null cloud");
+  if (n > 0x7fffffffu || ctx->sa_n_points + n > 0x7fffffffu)
+    return ctx->fail(-3, "the accumulated cloud would hold %zu + %zu points: more than 2147483647", ctx->sa_n_points, n);
+  return accum_affine(ctx, affine12, a);
+}
+
+unsigned accum_push_blocks(long long n)
+{
+  return std::min(blocks_for(n), 2048u);
+}
+
+// `bytes` of the caller's cloud -> ctx->cl_in_xyz, and room for n more points in the accumulation. *staged: the caller's
+// array has been copied already
+int accum_push_stage(mcl3dl_hip_ctx* ctx, const void* data, size_t bytes, size_t n, bool* staged)
+{
+  HIP_TRY(hipSetDevice(ctx->device));
+  TRY(ensure(ctx, ctx->cl_in_xyz, bytes));
+  TRY(grow_keep(ctx, ctx->sa_accum, sizeof(float4) * ctx->sa_n_points, sizeof(float4) * (ctx->sa_n_points + n)));
+  return h2d(ctx, ctx->cl_in_xyz.p, data, bytes, staged);
+}
+
+// behind the push's launch: the push is counted, and the call returns once the caller's array may be reused — at once when it
+// went through the staging memory (which a run of pushes without any other call must not pile up: beyond one staging block's
+// worth the stream is drained and the memory recycled)
+int accum_push_done(mcl3dl_hip_ctx* ctx, size_t n, bool staged, size_t* out_cloud_index, size_t* out_total_points)
+{
+  HIP_TRY(hipGetLastError());
+  if (!staged || ctx->stage_pending > STAGE_MAX_COPY)
+    TRY(sync_stream(ctx));
+  if (out_cloud_index)
+    *out_cloud_index = ctx->sa_n_clouds;
+  ctx->sa_n_clouds += 1;
+  ctx->sa_n_points += n;
+  if (out_total_points)
+    *out_total_points = ctx->sa_n_points;
+  return 0;
+}
 }  // namespace

@@ -238,6 +238,10 @@ struct mcl3dl_hip_ctx
   uint32_t sp_kept32[2] = { 0, 0 };                 // their counts, delivered by one synchronisation
   size_t sp_n_full = 0, sp_n_clip[2] = { 0, 0 }, sp_n_samp[2] = { 0, 0 };
   bool sp_ready = false;
+  // pc_local_accum_ on the device (scan_accum.h): the clouds pushed since the last clear, odom frame, label = cloud index. A
+  // buffer of its own: sp_raw and cl_in_xyz are overwritten between two pushes by scan_begin, the map entry points and match_split
+  DevBuf sa_accum;
+  size_t sa_n_points = 0, sa_n_clouds = 0;
   size_t n_base = 0;  // points of the base map; anything behind them in map_xyz is the current map update
   DevBuf ms_xyz, ms_out, ms_flag[2];
   // global localisation (api_global_loc.inl): VoxelGrid centroids of the base map, their private cell grid (rescaled points

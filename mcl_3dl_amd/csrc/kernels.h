@@ -17,6 +17,8 @@
 //   grid_kernels.h        the cell-sorted exact-NN grid and the DDA occupancy / voxel index, built on the device
 //   cloud_kernels.h       scan / map preparation: PointCloud2 decode, VoxelGrid, clip + compaction, sampling gather,
 //                         matched / unmatched output (each with the min / max or the count the next step needs fused in)
+//   scan_accum.h          the head of measure(): accumCloud (sensor -> odom, label = cloud index, append) and the accumulation's
+//                         odom -> base_link pass with VoxelGrid's min / max fused in
 //   sort_kernels.h        stable radix sort of the cloud path: keys made in the first pass, points written by the last
 //   cloud_keys.h          the sort keys (VoxelGrid leaf index, Morton key, range key)
 //   global_loc_kernels.h  global localisation: the blocked-above test over the VoxelGrid centroids of the base map, and the seeding
@@ -49,6 +51,7 @@
 #include "landmark_kernels.h"
 #include "update_kernels.h"
 #include "cloud_kernels.h"
+#include "scan_accum.h"
 #include "sort_kernels.h"
 #include "stage_kernels.h"
 #include "grid_kernels.h"
