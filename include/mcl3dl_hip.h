@@ -582,6 +582,37 @@ int mcl3dl_hip_group_add_noise_drawn(mcl3dl_hip_group* g, const float* sigma6, u
 int mcl3dl_hip_group_init_drawn(mcl3dl_hip_group* g, const float* mean7, const float* sigma6, size_t n_p, uint32_t* engine_state);
 int mcl3dl_hip_group_draw_odom_noise(mcl3dl_hip_group* g, const float* odom_err4, uint32_t* engine_state);
 int mcl3dl_hip_group_resample_apply_drawn(mcl3dl_hip_group* g, const float* sigma6, uint32_t* engine_state);
+/* ---- resampling the resident particles in ONE call: the prefix sums on the device ---------------------------------------------
+ * pf_->resample(sigma) (src/mcl_3dl.cpp:809, pf.h:187-225) and pf_->resizeParticle(n) (:875-885, pf.h:399-436) without the
+ * weights, pstep or initial_p crossing the bus: one wavefront runs `accum += p.probability_` with the serial loop's bits and
+ * writes every prefix, forms pstep = accum / (float)n_out, draws initial_p = uniform_real_distribution<float>(0, pstep)(engine_)
+ * from the engine state handed in, and the searches read both from a device record.
+ *   float_prefix           out_prefix[i] = fl(out_prefix[i - 1] + term[i]) on its own, for introspection and tests; term == NULL:
+ *                          every term is `constant` (resizeParticle's pscan += pstep).
+ *   resample_plan_device   begin_device + the caller's uniform draw + plan on one context, weights in device memory. Leaves the
+ *                          context where mcl3dl_hip_resample_plan does: resample_apply_device / _apply_slice_device follow.
+ *                          mode 0: *engine_state in / out; mode 1: ignored, may be NULL. d_weight needs a float's alignment
+ *                          only (16-byte aligned arrays are read four floats at a time).
+ *   group_resample_drawn   group_resample_begin(0), rng_uniform(state, 0, pstep), group_resample_plan(0, initial_p),
+ *                          group_resample_apply_drawn(sigma6, state) in one call: the same particles, weights 1 / n, odometry
+ *                          noise, engine state and residency, bit for bit.
+ *   group_resize_resident  group_resample_begin(n_out), _plan(1, .), _apply without noise in one call.
+ * *out_route: 0 = no tie among the accumulated probabilities: on a group of one device nothing proportional to the particle
+ * count crossed the bus (two fixed-size read-backs: the record, and the duplicate count that sizes the noise draw). 1 = some
+ * i > 0 has !(accum[i - 1] < accum[i]) (weight-0 particles, weights below half an ulp of the running sum): libstdc++'s
+ * std::sort decides who leads each tie group, so the keys come to the host, are sorted there and the order goes up, as in
+ * mcl3dl_hip_resample_begin; the result is the same, only slower. On N devices every rank needs all weights in particle order:
+ * one ncclAllGather of the weight shards, or through the host with "collective" 1. Measured on one MI355X the one-call forms
+ * are the faster ones up to 65 536 particles without ties and the slower ones at 262 144 and on route 1.
+ * -3: NULL d_weight, n or n_out outside its range, bad mode, sigma6 / engine_state as above. -5: no resident particles. */
+int mcl3dl_hip_float_prefix(mcl3dl_hip_ctx* ctx, const float* term /*n, host; NULL = constant*/, float constant, size_t n,
+                            float* out_prefix /*n, host*/);
+int mcl3dl_hip_resample_plan_device(mcl3dl_hip_ctx* ctx, const float* d_weight /*n*/, size_t n, size_t n_out, int mode,
+                                    uint32_t* engine_state, float* out_pstep, float* out_initial_p, size_t* out_n_duplicates,
+                                    int* out_route);
+int mcl3dl_hip_group_resample_drawn(mcl3dl_hip_group* g, const float* sigma6, uint32_t* engine_state, float* out_pstep,
+                                    float* out_initial_p, size_t* out_n_duplicates, int* out_route);
+int mcl3dl_hip_group_resize_resident(mcl3dl_hip_group* g, size_t n_out, int* out_route);
 int mcl3dl_hip_group_measure_landmark(mcl3dl_hip_group* g, const float* measured7, const double* cov36,
                                       float* out_weight /*n_p or NULL*/, float* out_lik /*n_p or NULL*/, float* entropy,
                                       int* restored);

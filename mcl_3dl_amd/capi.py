@@ -137,6 +137,12 @@ SIGNATURES = {
     "mcl3dl_hip_group_draw_odom_noise": (_i, [_p, _p, C.POINTER(_u32)]),
     "mcl3dl_hip_group_resample_apply_drawn": (_i, [_p, _p, C.POINTER(_u32)]),
     "mcl3dl_hip_rng_draw_indices": (_i, [_p, _u64, _sz, C.POINTER(_u32), _p]),
+    "mcl3dl_hip_float_prefix": (_i, [_p, _p, _f, _sz, _p]),
+    "mcl3dl_hip_resample_plan_device": (_i, [_p, _p, _sz, _sz, _i, C.POINTER(_u32), C.POINTER(_f), C.POINTER(_f),
+                                             C.POINTER(_sz), C.POINTER(_i)]),
+    "mcl3dl_hip_group_resample_drawn": (_i, [_p, _p, C.POINTER(_u32), C.POINTER(_f), C.POINTER(_f), C.POINTER(_sz),
+                                             C.POINTER(_i)]),
+    "mcl3dl_hip_group_resize_resident": (_i, [_p, _sz, C.POINTER(_i)]),
     "mcl3dl_hip_scan_finish_drawn": (_i, [_p, _sz, _sz, _p, _sz, C.POINTER(_u32), C.POINTER(_sz), C.POINTER(_sz)]),
     "mcl3dl_hip_group_scan_begin": (_i, [_p, _p, _p, _sz, _p, _p, _p, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     "mcl3dl_hip_group_scan_begin_pointcloud2": (_i, [_p, _p, _sz, _u32, _i, _i, _i, _i, _u32, _p, _p, _p, C.POINTER(_sz),
@@ -664,6 +670,23 @@ class Group:
         self._check(self.lib.mcl3dl_hip_group_resample_apply_drawn(self.h, _ptr(_np_f32(sigma6)), C.byref(st)))
         return int(st.value)
 
+    def resample_drawn(self, sigma6, engine_state):
+        """All of pf::resample(sigma) on the resident particles in one call, prefix sums, pstep and initial_p formed on the
+        devices: (pstep, initial_p, duplicated particles, engine state behind the call, route). route 0: nothing proportional to
+        the particle count crossed the bus on a group of one; 1: tie groups were ordered by std::sort on the host."""
+        st, pstep, ip, nd, route = _u32(int(engine_state)), C.c_float(0), C.c_float(0), C.c_size_t(0), C.c_int(-1)
+        self._check(self.lib.mcl3dl_hip_group_resample_drawn(self.h, _ptr(_np_f32(sigma6)), C.byref(st), C.byref(pstep),
+                                                             C.byref(ip), C.byref(nd), C.byref(route)))
+        self._rs_n_out = 0   # (no plan is pending: a later resample_plan starts from resample_begin)
+        return float(pstep.value), float(ip.value), int(nd.value), int(st.value), int(route.value)
+
+    def resize_resident(self, n_out):
+        """pf::resizeParticle(n_out) on the resident particles in one call. Returns the route (as resample_drawn)."""
+        route = C.c_int(-1)
+        self._check(self.lib.mcl3dl_hip_group_resize_resident(self.h, int(n_out), C.byref(route)))
+        self._rs_n_out = 0
+        return int(route.value)
+
     def measure_imu(self, acc, acc_var, fetch=True):
         """cbImu's pf_->measure with ImuMeasurementModelGravity(acc_var) after setAccMeasure(acc)."""
         n_p = self.resident()
@@ -1026,6 +1049,27 @@ class Engine:
         self._check(self.lib.mcl3dl_hip_resample_begin_device(self.h, _ptr(d_weight), n, self._rs_n_out,
                                                               C.byref(pstep)))
         return float(pstep.value)
+
+    def resample_plan_device(self, d_weight, n, n_out=None, mode=0, engine_state=None):
+        """begin_device + the uniform draw + plan with the weights left on the device: (pstep, initial_p, duplicated particles,
+        engine state behind the draw or None for mode 1, route)."""
+        self._rs_n_out = n if n_out is None else n_out
+        st = _u32(0 if engine_state is None else int(engine_state))
+        pstep, ip, nd, route = C.c_float(0), C.c_float(0), C.c_size_t(0), C.c_int(-1)
+        self._check(self.lib.mcl3dl_hip_resample_plan_device(self.h, _ptr(d_weight), int(n), int(self._rs_n_out), int(mode),
+                                                             None if engine_state is None else C.byref(st), C.byref(pstep),
+                                                             C.byref(ip), C.byref(nd), C.byref(route)))
+        return (float(pstep.value), float(ip.value), int(nd.value), None if engine_state is None or mode else int(st.value),
+                int(route.value))
+
+    def float_prefix(self, term=None, constant=0.0, n=None):
+        """The serial float recurrence out[i] = fl(out[i - 1] + term[i]) by one wavefront, every prefix; term None: n terms, all
+        `constant`."""
+        t = None if term is None else _np_f32(term)
+        n = len(t) if t is not None else int(n)
+        out = np.zeros(n, np.float32)
+        self._check(self.lib.mcl3dl_hip_float_prefix(self.h, _ptr(t), float(constant), n, _ptr(out)))
+        return out
 
     def resample_apply_device(self, d_state13_in, noise13, d_state13_out, out_begin=0, out_count=None):
         """Gather (+ noise on duplicated slots) into d_state13_out; a slice of the planned slots when out_count is set."""

@@ -730,3 +730,99 @@ int mcl3dl_hip_group_resample_apply(mcl3dl_hip_group* g, const float* noise13, s
     return g->fail(-3, "group_resample_apply: %zu duplicated particles need noise, %zu given", g->rs_n_dup, n_noise);
   return group_resample_apply_impl(g, noise13, n_noise, nullptr);
 }
+
+namespace
+{
+// what every rank's resample_plan_device handed back, and whether the ranks agree
+struct GroupPlan
+{
+  float pstep = 0.f, initial_p = 0.f;
+  uint32_t state = 0u;
+  size_t n_dup = 0;
+  int route = 0;
+};
+
+// begin + [uniform draw] + plan over the resident particles in one pass over the ranks: every rank needs ALL weights in
+// particle order (the prefix recurrence is not associative) — its own buffer on a group of one, else gathered through the host
+// ("collective" 1: as the states) or by one ncclAllGather of the padded weight shards + unpad_states_kernel with width 1 —
+// and runs mcl3dl_hip_resample_plan_device over them. Leaves the group where group_resample_plan does.
+int group_plan_device(mcl3dl_hip_group* g, size_t n_out, int mode, uint32_t state_in, GroupPlan* out)
+{
+  const size_t n_p = g->n_resident;
+  const int N = g->n();
+  const bool single = N == 1 && g->direct_single;
+  const bool host_gather = g->collective == 1 && !single;
+  const bool over_rccl = !single && !host_gather;
+  g->rs_begun = g->rs_planned = false;
+  if (over_rccl)
+    TRY(group_comms(g));
+  if (host_gather)
+  {
+    g->h_weight.resize(n_p);
+    TRY(mcl3dl_hip_group_download_state(g, nullptr, g->h_weight.data(), n_p));
+  }
+  const size_t base = n_p / N, rem = n_p % N, max_count = base + (rem ? 1 : 0);
+  std::vector<GroupPlan> plan(N);
+  const auto prepare = [&](const Shard& s) -> int
+  {
+    mcl3dl_hip_ctx* ctx = s.ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->gs_n != s.n)
+      return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, s.n);
+    if (single)
+      return 0;
+    TRY(ensure(ctx, ctx->rs_d_w, sizeof(float) * n_p));
+    if (host_gather)
+      return h2d(ctx, ctx->rs_d_w.p, g->h_weight.data(), sizeof(float) * n_p);
+    TRY(ensure(ctx, ctx->rs_d_wpad, sizeof(float) * max_count * static_cast<size_t>(N)));
+    if (ctx->gs_weight.cap < sizeof(float) * max_count)  // (every shard buffer holds the largest shard)
+      return ctx->fail(-4, "internal: weight buffer smaller than the all-gather's send count");
+    return 0;
+  };
+  const auto behind = [&](const Shard& s, const VotedRank& voted) -> int
+  {
+    mcl3dl_hip_ctx* ctx = s.ctx;
+    const float* d_w = single ? ctx->gs_weight.as<float>() : ctx->rs_d_w.as<float>();
+    if (over_rccl)
+    {
+      TRY(voted.enqueued(g->rccl.AllGather(ctx->gs_weight.p, ctx->rs_d_wpad.p, max_count, ncclFloat, g->comms[s.r], ctx->stream),
+                         "ncclAllGather (weights)"));
+      hipLaunchKernelGGL(unpad_states_kernel, dim3(static_cast<unsigned>((n_p + 255) / 256)), dim3(256), 0, ctx->stream,
+                         ctx->rs_d_wpad.as<float>(), max_count, base, rem, n_p, ctx->rs_d_w.as<float>(), static_cast<size_t>(1));
+      HIP_TRY(hipGetLastError());
+    }
+    GroupPlan& p = plan[s.r];
+    p.state = state_in;
+    return mcl3dl_hip_resample_plan_device(ctx, d_w, n_p, n_out, mode, mode == 0 ? &p.state : nullptr, &p.pstep, &p.initial_p,
+                                           &p.n_dup, &p.route);
+  };
+  TRY(group_voted_call(VotedCall{ g, "resampling", "all-gather of the weights" }, n_p, over_rccl, !single, prepare, behind));
+  for (int r = 1; r < N; ++r)
+    if (plan[r].n_dup != plan[0].n_dup || plan[r].state != plan[0].state || plan[r].route != plan[0].route)
+      return g->fail(-4, "the ranks disagree on the resampling plan (%zu and %zu duplicated particles, engine states %u and %u)",
+                     plan[0].n_dup, plan[r].n_dup, plan[0].state, plan[r].state);
+  g->rs_n_out = n_out;
+  g->rs_n_dup = plan[0].n_dup;
+  g->rs_begun = g->rs_planned = true;
+  *out = plan[0];
+  return 0;
+}
+}  // namespace
+
+// Replaces: pf::resizeParticle(n_out) (pf.h:399-436) on the resident particles, in one call — group_resample_begin(n_out),
+// _plan(1, ·), _apply without noise, with the prefixes and `pscan += pstep` formed on the devices.
+int mcl3dl_hip_group_resize_resident(mcl3dl_hip_group* g, size_t n_out, int* out_route)
+{
+  if (!g)
+    return -1;
+  if (g->n_resident == 0)
+    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  if (n_out == 0 || n_out > 0x7fffffffu / 16)
+    return g->fail(-3, "group_resize_resident: n_out = %zu is outside [1, %u]", n_out, 0x7fffffffu / 16);
+  GroupPlan plan;
+  TRY(group_plan_device(g, n_out, 1, 0u, &plan));
+  TRY(group_resample_apply_impl(g, nullptr, 0, nullptr));
+  if (out_route)
+    *out_route = plan.route;
+  return 0;
+}

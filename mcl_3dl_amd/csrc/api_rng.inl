@@ -230,6 +230,35 @@ int mcl3dl_hip_group_resample_apply_drawn(mcl3dl_hip_group* g, const float* sigm
   return rng_hand_back(g, states, drew, engine_state);
 }
 
+// Replaces: all of pf::resample(sigma) (pf.h:187-225) on the resident particles — group_resample_begin(0), rng_uniform(state, 0,
+// pstep), group_resample_plan(0, initial_p), group_resample_apply_drawn(sigma6, state) — with nothing but the engine state going
+// in and coming out: prefixes, pstep and initial_p are formed on the devices (api_group_state.inl: group_plan_device).
+int mcl3dl_hip_group_resample_drawn(mcl3dl_hip_group* g, const float* sigma6, uint32_t* engine_state, float* out_pstep,
+                                    float* out_initial_p, size_t* out_n_duplicates, int* out_route)
+{
+  if (!g)
+    return -1;
+  rng::NoiseGen6 gen;
+  TRY(rng_generator(g, nullptr, sigma6, &gen));
+  TRY(rng_check_state(g, engine_state));
+  if (g->n_resident == 0)
+    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  GroupPlan plan;
+  TRY(group_plan_device(g, g->n_resident, 0, *engine_state, &plan));
+  uint32_t state = plan.state;  // behind initial_p's engine call
+  TRY(mcl3dl_hip_group_resample_apply_drawn(g, sigma6, &state));
+  *engine_state = state;
+  if (out_pstep)
+    *out_pstep = plan.pstep;
+  if (out_initial_p)
+    *out_initial_p = plan.initial_p;
+  if (out_n_duplicates)
+    *out_n_duplicates = plan.n_dup;
+  if (out_route)
+    *out_route = plan.route;
+  return 0;
+}
+
 // Replaces: `count` calls of std::uniform_int_distribution<size_t>(0, range - 1)(engine_) — PointCloudUniformSampler::sample's
 // draws (point_cloud_uniform_sampler.h:66-71) on their own, for introspection and general use. The rounds form of
 // rng_index_kernels.h; the indices come home.

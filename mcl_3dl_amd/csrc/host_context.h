@@ -272,6 +272,9 @@ struct mcl3dl_hip_ctx
   DevBuf rs_d_keys, rs_d_pscan, rs_d_it, rs_d_source, rs_d_slot, rs_d_noise, rs_d_in, rs_d_out, rs_d_order, rs_d_flag,
       rs_d_ws, rs_d_dup8;
   bool rs_sorted = false;  // std::sort had ties to order: rs_order is not the identity
+  // resample_plan_device: the record behind the prefix kernel; all weights in particle order on a rank of a group of
+  // several (and the padded all-gather in front of them); the terms / prefixes of mcl3dl_hip_float_prefix
+  DevBuf rs_d_rec, rs_d_w, rs_d_wpad, rs_d_prefix;
   // api_rng.inl: jump table, work-group counts (+ total + result word), scan workspace, this rank's window of the values
   DevBuf rng_table, rng_counts, rng_ws, rng_values;
   // the shuffle of the sampled covariance (host_shuffle.h): j_i per step, the doubtful attempts {number, engine output}, the

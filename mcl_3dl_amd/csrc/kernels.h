@@ -35,6 +35,9 @@
 //   rng_shuffle_kernels.h  std::shuffle(iota(n), engine_) of the sampled covariance: the doubt sink, doubtful attempts resolved by one
 //                         wavefront, every step's target, one chain walk per entry over the sorted (target, step) pairs
 //                         (rng_shuffle.h: the restatement and the doubt policy)
+//   resample_prefix_kernels.h  pf::resample / resizeParticle without the host between weights and plan: the accumulated
+//                         probabilities and `pscan += pstep` as the serial float recurrence by one wavefront, every prefix
+//                         written (float_prefix.h), pstep / initial_p / tie flag in a device record, the search fed from it
 //   stage_kernels.h       head and tail of a host-buffer update as one launch each: scan ordering + pose / weight take-over
 //                         from page-locked host memory; lik_finalize + pf::measure with the results written back there
 //
@@ -62,3 +65,4 @@
 #include "rng_index_kernels.h"
 #include "rng_weighted_kernels.h"
 #include "rng_shuffle_kernels.h"
+#include "resample_prefix_kernels.h"

@@ -838,9 +838,10 @@ __global__ __launch_bounds__(64) void pf_covariance_reduce_kernel(const double* 
 
 // ---------------------------------------------------------------------------------------------------------
 // "Next" row: pf::ParticleFilter::resample / resizeParticle (include/mcl_3dl/pf.h:187-225, 399-436).
-// The serial, order-defining parts (float prefix sums, libstdc++'s std::sort of the tie groups, the it/it_prev walk)
-// stay on the host in mcl3dl_hip.hip; the device does the n_out independent std::lower_bound searches and the
-// gather of the 13-dof states with State6DOF::operator+ / normalize() for the duplicated ones.
+// libstdc++'s std::sort of the tie groups stays on the host (api_resample.inl), and so do the float prefix sums of the
+// three-call form (resample_prefix_kernels.h runs them on a wavefront); the device does the n_out independent
+// std::lower_bound searches, the it/it_prev walk as a neighbour comparison + scan, and the gather of the 13-dof states with
+// State6DOF::operator+ / normalize() for the duplicated ones.
 // ---------------------------------------------------------------------------------------------------------
 __global__ void resample_lower_bound_kernel(const float* __restrict__ keys, int n, const float* __restrict__ pscan,
                                             float pstep, float initial_p, int n_out, uint32_t* __restrict__ it_out,
