@@ -119,6 +119,7 @@ LikParams lik_params(const mcl3dl_hip_ctx* ctx)
   p.wy = ctx->weight[1];
   p.wz = ctx->weight[2];
   p.has_weight = ctx->has_weight ? 1 : 0;
+  p.unit_form = lik_unit_form(p.wx, p.wy, p.wz);
   p.match_dist_min = ctx->match_dist_min;
   // pcl::KdTreeFLANN::radiusSearch: (float)(radius * radius) with radius widened to double
   p.r2 = static_cast<float>(static_cast<double>(ctx->match_dist_min) * static_cast<double>(ctx->match_dist_min));

@@ -11,6 +11,7 @@
 #include "device_math.h"
 #include "float_chain.h"
 #include "map_structs.h"
+#include "term_slots.h"
 #pragma clang fp contract(off)
 
 namespace mcl3dl
@@ -835,6 +836,12 @@ struct BoolConstant
   static constexpr bool value = B;
 };
 
+template <int I>
+struct IntConstant
+{
+  static constexpr int value = I;
+};
+
 // ---- deferred overflow rounds (tiled kernel, packed 64-byte records) ------------------------------------------------
 // On a map of voxel-filter centroids a quarter of the voxels hold more than four candidates. A wavefront runs an overflow
 // round as soon as ONE of its 64 evaluations needs it — practically always — with a quarter of its lanes doing useful work
@@ -861,13 +868,13 @@ struct DeferQueue
 // offset, the brick table included — and `matched` IS the set of lanes that pass the radius test (the host has checked that
 // their dist cannot be negative), so the term needs no compare with 0 and no select: what is returned for a lane with `over`
 // is its best-so-far, the value the tiled kernel parks in the lane's term slot, and matched_m is that set as a mask.
-template <bool FAST = false>
+template <bool FAST = false, int WFORM = 0>
 __device__ inline float eval_coop_first(const RecGrid& rg, const LikParams& prm, const Vec3f pos, const Quat rot, const float4 v,
                                         bool have_point, int lane, bool& matched, bool& over, float& best, uint32_t& mine,
                                         unsigned long long& over_m, unsigned long long* matched_m = nullptr)
 {
   const Vec3f tp = vadd(qrot_trim(rot, Vec3f{ v.x, v.y, v.z }), pos);
-  const float qx = tp.x * prm.wx, qy = tp.y * prm.wy, qz = tp.z * prm.wz;
+  const float qx = WFORM >= 1 ? tp.x : tp.x * prm.wx, qy = WFORM >= 1 ? tp.y : tp.y * prm.wy, qz = WFORM >= 2 ? tp.z : tp.z * prm.wz;
   uint32_t ti, sub;
   const bool inside = rec_locate<FAST>(rg, qx, qy, qz, ti, sub) && have_point;
   int b;
@@ -949,7 +956,7 @@ __device__ inline float eval_coop_first(const RecGrid& rg, const LikParams& prm,
 // entry base + l). s_term / s_cnt rows are the tiled kernel's: the parked best is replaced by the term, a match is counted.
 // FAST: the arithmetic of eval_coop_first<true> (the overflow records behind their descriptor unconditionally, the match from
 // the radius test). Starts by making the wavefront's own pushes and parked terms visible to all of its lanes.
-template <bool FAST = false, int G, int LD>
+template <bool FAST = false, int WFORM = 0, int G, int LD>
 __device__ inline void defer_drain(const RecGrid& rg, const LikParams& prm, const float (&s_pose)[G][8], float (&s_term)[G][LD],
                                    unsigned (&s_cnt)[G][4], const DeferQueue& q, int wave, int lane, uint32_t base, uint32_t n,
                                    const float4 v)
@@ -966,8 +973,10 @@ __device__ inline void defer_drain(const RecGrid& rg, const LikParams& prm, cons
   const Vec3f pos = { s_pose[k][0], s_pose[k][1], s_pose[k][2] };
   const Quat rot = { s_pose[k][3], s_pose[k][4], s_pose[k][5], s_pose[k][6] };
   const Vec3f tp = vadd(qrot_trim(rot, pt), pos);
-  const float qx = tp.x * prm.wx, qy = tp.y * prm.wy, qz = tp.z * prm.wz;
-  const int t_src = wave * 64 + src;
+  const float qx = WFORM >= 1 ? tp.x : tp.x * prm.wx, qy = WFORM >= 1 ? tp.y : tp.y * prm.wy, qz = WFORM >= 2 ? tp.z : tp.z * prm.wz;
+  // (the queued lane's term slot: rows of 256 floats are the fp64 sum's, in its reader's order — term_slots.h; the chain's padded
+  // rows are in array order)
+  const int t_src = term_slot<G, LD != 256>(wave * 64 + src);
   float best = s_term[k][t_src];
   const uint32_t ext = word & rec_ext_mask(rg);
   const uint32_t rounds = act ? rec_overflow_records(word >> rg.count_shift, 4u, rg.count_is_records) : 0u;
@@ -1007,7 +1016,7 @@ __device__ inline void defer_drain(const RecGrid& rg, const LikParams& prm, cons
 // lanes whose record overflows (eval_coop_first), `over` this lane's bit of it, `mine` its record's packed word. qn = entries
 // this wavefront holds (uniform, 0 at the start; the new count is returned). Flush first if the new entries would not fit, push in lane order (the slot
 // is the count of set bits below the lane), and as soon as 64 are queued run the LAST 64: what stays queued keeps its place.
-template <bool FAST, int G, int LD>
+template <bool FAST, int WFORM = 0, int G, int LD>
 __device__ __forceinline__ uint32_t defer_push(const RecGrid& rg, const LikParams& prm, const float (&s_pose)[G][8],
                                                float (&s_term)[G][LD], unsigned (&s_cnt)[G][4], DeferQueue& q, int wave, int lane,
                                                const float4 v, uint32_t qn, unsigned long long over_m, bool over, uint32_t mine,
@@ -1018,7 +1027,7 @@ __device__ __forceinline__ uint32_t defer_push(const RecGrid& rg, const LikParam
     const uint32_t n_new = static_cast<uint32_t>(__popcll(over_m));
     if (qn + n_new > static_cast<uint32_t>(DEFER_QCAP))
     {
-      defer_drain<FAST>(rg, prm, s_pose, s_term, s_cnt, q, wave, lane, 0u, qn, v);
+      defer_drain<FAST, WFORM>(rg, prm, s_pose, s_term, s_cnt, q, wave, lane, 0u, qn, v);
       qn = 0;
     }
     if (over)
@@ -1031,7 +1040,7 @@ __device__ __forceinline__ uint32_t defer_push(const RecGrid& rg, const LikParam
     qn += n_new;
     if (qn >= 64u)
     {
-      defer_drain<FAST>(rg, prm, s_pose, s_term, s_cnt, q, wave, lane, qn - 64u, 64u, v);
+      defer_drain<FAST, WFORM>(rg, prm, s_pose, s_term, s_cnt, q, wave, lane, qn - 64u, 64u, v);
       qn -= 64u;
     }
   }
@@ -1040,12 +1049,12 @@ __device__ __forceinline__ uint32_t defer_push(const RecGrid& rg, const LikParam
 
 // ... and when the pose loop ends with a queue that is not empty (the caller tests qn != 0: as a branch of the caller this
 // compiles to the parent's code), every entry left, before the lane's scan point `v` is replaced or the terms are read
-template <bool FAST, int G, int LD>
+template <bool FAST, int WFORM = 0, int G, int LD>
 __device__ __forceinline__ void defer_flush(const RecGrid& rg, const LikParams& prm, const float (&s_pose)[G][8],
                                             float (&s_term)[G][LD], unsigned (&s_cnt)[G][4], const DeferQueue& q, int wave,
                                             int lane, const float4 v, uint32_t qn)
 {
-  defer_drain<FAST>(rg, prm, s_pose, s_term, s_cnt, q, wave, lane, 0u, qn, v);
+  defer_drain<FAST, WFORM>(rg, prm, s_pose, s_term, s_cnt, q, wave, lane, 0u, qn, v);
 }
 
 // ---- pieces shared by the tiled kernel and likelihood_chain_multi_kernel -------------------------------------------------
@@ -1229,6 +1238,7 @@ __device__ __forceinline__ void likelihood_tiled_body(const uint32_t block_index
     group = static_cast<int>(item - row * ng);
   }
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int tslot = term_slot<G, CHAIN>(t);  // where this lane's term goes in a particle's row (term_slots.h)
   stage_poses<G>(s_pose, pose7, n_p, group, t);
   const int i = tile * 256 + t;
   const bool have_point = i < n_s;
@@ -1240,8 +1250,12 @@ __device__ __forceinline__ void likelihood_tiled_body(const uint32_t block_index
     __shared__ DeferQueue s_q;
     // the pose loop, in two forms picked ONCE per launch from a uniform flag of the map index: the general one, and the one
     // in which the properties of the common map are constants (eval_coop_first<true>). Same bits.
-    const auto pose_loop = [&](auto fast) {
+    // The common-map loop comes in three forms of the dist_weight (LikParams::unit_form), picked once per launch as well: a
+    // weight the host has seen to be exactly 1.0f is not multiplied by (x * 1.0f == x bit for bit: f32 denormals are kept, and a
+    // NaN ends as "no neighbour" whatever its payload).
+    const auto pose_loop = [&](auto fast, auto wform) {
       constexpr bool FAST = decltype(fast)::value;
+      constexpr int WFORM = decltype(wform)::value;
       uint32_t qn = 0;  // entries queued by this wavefront (uniform)
       // FAST: the LDS addresses of the pose, the term slot and the count slot advance by one add per pose instead of being
       // rebuilt from the loop counter (a move, a shift-or and a shift-add per evaluation)
@@ -1250,7 +1264,7 @@ __device__ __forceinline__ void likelihood_tiled_body(const uint32_t block_index
       typedef __attribute__((address_space(3))) float LdsTerm;
       typedef __attribute__((address_space(3))) unsigned LdsCount;
       LdsPose* p_pose = (LdsPose*)&s_pose[0][0];
-      LdsTerm* p_term = (LdsTerm*)&s_term[0][t];
+      LdsTerm* p_term = (LdsTerm*)&s_term[0][tslot];
       LdsCount* p_cnt = (LdsCount*)&s_cnt[0][wave];
       for (int k = 0; k < n_valid; ++k)
       {
@@ -1265,7 +1279,7 @@ __device__ __forceinline__ void likelihood_tiled_body(const uint32_t block_index
         unsigned long long m;
         if constexpr (FAST)
         {
-          *p_term = eval_coop_first<true>(rg, prm, pos, rot, v, have_point, lane, matched, over, best, mine, om, &m);
+          *p_term = eval_coop_first<true, WFORM>(rg, prm, pos, rot, v, have_point, lane, matched, over, best, mine, om, &m);
           if (lane == 0)
             *p_cnt = static_cast<unsigned>(__popcll(m));
           asm volatile("" : "+v"(p_pose), "+v"(p_term), "+v"(p_cnt));
@@ -1276,20 +1290,24 @@ __device__ __forceinline__ void likelihood_tiled_body(const uint32_t block_index
         else
         {
           const float term = eval_coop_first(rg, prm, pos, rot, v, have_point, lane, matched, over, best, mine, om);
-          s_term[k][t] = over ? best : term;
+          s_term[k][tslot] = over ? best : term;
           m = __builtin_amdgcn_ballot_w64(matched);
           if (lane == 0)
             s_cnt[k][wave] = static_cast<unsigned>(__popcll(m));
         }
-        qn = defer_push<FAST>(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, v, qn, om, over, mine, k);
+        qn = defer_push<FAST, WFORM>(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, v, qn, om, over, mine, k);
       }
       if (qn != 0u)
-        defer_flush<FAST>(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, v, qn);
+        defer_flush<FAST, WFORM>(rg, prm, s_pose, s_term, s_cnt, s_q, wave, lane, v, qn);
     };
-    if (rg.common_map)
-      pose_loop(BoolConstant<true>{});
+    if (!rg.common_map)
+      pose_loop(BoolConstant<false>{}, IntConstant<0>{});
+    else if (prm.unit_form == 2)
+      pose_loop(BoolConstant<true>{}, IntConstant<2>{});
+    else if (prm.unit_form == 1)
+      pose_loop(BoolConstant<true>{}, IntConstant<1>{});
     else
-      pose_loop(BoolConstant<false>{});
+      pose_loop(BoolConstant<true>{}, IntConstant<0>{});
   }
   else if constexpr (COOP && MODE == 2)
   {
@@ -1301,7 +1319,7 @@ __device__ __forceinline__ void likelihood_tiled_body(const uint32_t block_index
       const Quat rot = { s_pose[k][3], s_pose[k][4], s_pose[k][5], s_pose[k][6] };
       bool matched;
       const float term = eval_coop(rg, prm, pos, rot, v, have_point, lane, matched);
-      s_term[k][t] = term;
+      s_term[k][tslot] = term;
       const unsigned long long m = __builtin_amdgcn_ballot_w64(matched);
       if (lane == 0)
         s_cnt[k][wave] = static_cast<unsigned>(__popcll(m));
@@ -1333,7 +1351,7 @@ __device__ __forceinline__ void likelihood_tiled_body(const uint32_t block_index
         }
       }
     }
-    s_term[k][t] = term;
+    s_term[k][tslot] = term;
     const unsigned long long m = __ballot(matched);
     if (lane == 0)
       s_cnt[k][wave] = static_cast<unsigned>(__popcll(m));
@@ -1364,18 +1382,37 @@ __device__ __forceinline__ void likelihood_tiled_body(const uint32_t block_index
     for (int j = 0; j < Q; ++j)
     {
       const int e = t + 256 * j, pt = e / Q, k4 = (e % Q) * 4;
-      const int src = tile * 256 + pt;
+      const int src = tile * 256 + pt, sl = term_slot<G, CHAIN>(pt);
       if (src < n_s)
         rows[static_cast<size_t>(scan_perm[src]) * Q + (e % Q)] =
-            make_float4(s_term[k4][pt], s_term[k4 + 1][pt], s_term[k4 + 2][pt], s_term[k4 + 3][pt]);
+            make_float4(s_term[k4][sl], s_term[k4 + 1][sl], s_term[k4 + 2][sl], s_term[k4 + 3][sl]);
     }
   }
-  // fixed-order fp64 reduction: 256 / G lanes per particle, each sums a contiguous segment (bank-rotated reads)
+  // fixed-order fp64 reduction: 256 / G lanes per particle, each sums a contiguous segment in the order (j + t) % SEG. Where
+  // the writers stored the terms in that order (term_slots.h) the segment is read front to back, 16 bytes at a time, its
+  // chunks in the swizzled order that keeps the lanes of a read off each other's banks; else term by term (bank-rotated reads)
   constexpr int LPP = 256 / G;        // lanes per particle
   constexpr int SEG = 256 / LPP;      // = G terms per lane
   const int pk = t / LPP, seg = t % LPP;
   double acc = 0.0;
-  if (pk < n_valid)
+  if constexpr (TermSlots<G, CHAIN>::permuted)
+  {
+    if (pk < n_valid)
+    {
+      const float4* row = reinterpret_cast<const float4*>(&s_term[pk][0]);
+      const int first = (seg * (SEG / 4)) ^ term_chunk_xor<G>(seg);
+#pragma unroll
+      for (int c = 0; c < SEG / 4; ++c)
+      {
+        const float4 q = row[first ^ c];
+        acc += static_cast<double>(q.x);
+        acc += static_cast<double>(q.y);
+        acc += static_cast<double>(q.z);
+        acc += static_cast<double>(q.w);
+      }
+    }
+  }
+  else if (pk < n_valid)
   {
 #pragma unroll 8
     for (int j = 0; j < SEG; ++j)

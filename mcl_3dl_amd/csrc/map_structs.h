@@ -29,11 +29,18 @@ struct LikParams
 {
   float wx, wy, wz;  // dist_weight (1,1,1 when unset)
   int has_weight;
+  int unit_form;  // weights that are exactly 1.0f (launch constant, lik_unit_form): 0 none known, 1 wx and wy, 2 all three
   float match_dist_min;
   float r2;  // (float)((double)r*(double)r), pcl::KdTreeFLANN::radiusSearch
   float match_dist_flat;
   float match_weight;
 };
+
+// LikParams::unit_form of a dist_weight. The reference ships (1, 1, 5) (parameters.cpp:108-110): form 1.
+__host__ __device__ inline int lik_unit_form(float wx, float wy, float wz)
+{
+  return (wx == 1.0f && wy == 1.0f) ? (wz == 1.0f ? 2 : 1) : 0;
+}
 
 // DDA occupancy (replaces RaycastUsingDDA::point_exists_ / points_, raycast_using_dda.h:280-281).
 struct DdaGrid

@@ -131,6 +131,7 @@ struct LikTiles
   float* beam_fill;      // [n] set to 1 (an update without beam points), or null
   BeamCounts bc;         // the beam model's last step as well (penalty != null)
 };
+constexpr int LIK_TAIL_UNROLL = 16;  // tiles per wavefront of the unrolled form: up to 64 tiles (16 384 scan points)
 __global__ __launch_bounds__(256) void lik_pf_partial_kernel(LikTiles lt, const float* __restrict__ w,
                                                              const float* __restrict__ beam, const float* __restrict__ extra,
                                                              int n, float* __restrict__ w_new,
@@ -140,26 +141,64 @@ __global__ __launch_bounds__(256) void lik_pf_partial_kernel(LikTiles lt, const 
   __shared__ unsigned s_n[8][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int p = blockIdx.x * 64 + lane;
+  // Every load a lane needs is issued before the first add that depends on one: the partials were written by other XCDs a moment
+  // ago, so each wait is a round trip to memory, and a dozen of them one behind the other were most of this launch.
+  const bool read_beam = !lt.bc.penalty && beam && !lt.beam_fill;
+  float w_p = 0.0f, beam_p = 1.0f, extra_p = 1.0f;
+  if (wave == 0 && p < n)
+  {
+    w_p = w[p];
+    if (read_beam)
+      beam_p = beam[p];
+    if (extra)
+      extra_p = extra[p];
+  }
   double a0 = 0.0, a1 = 0.0;
   unsigned n0 = 0, n1 = 0;
   if (p < n)
   {
     const double* ps = lt.psum + p;
     const unsigned* pc = lt.pcnt + p;
-    int tl = wave;
-    for (; tl + 4 < lt.n_tiles; tl += 8)  // slice `wave` and slice `wave + 4` side by side: two independent chains of loads
+    if (lt.n_tiles > 0 && lt.n_tiles <= 4 * LIK_TAIL_UNROLL)
     {
-      const double x0 = ps[static_cast<size_t>(tl) * n], x1 = ps[static_cast<size_t>(tl + 4) * n];
-      const unsigned c0 = pc[static_cast<size_t>(tl) * n], c1 = pc[static_cast<size_t>(tl + 4) * n];
-      a0 += x0;
-      a1 += x1;
-      n0 += c0;
-      n1 += c1;
+      // unrolled: tile wave + 4 j for every j, a tile past the end read as the last one (a line this lane has anyway) and not added
+      double x[LIK_TAIL_UNROLL];
+      unsigned c[LIK_TAIL_UNROLL];
+#pragma unroll
+      for (int j = 0; j < LIK_TAIL_UNROLL; ++j)
+      {
+        const int tl = min(wave + 4 * j, lt.n_tiles - 1);
+        x[j] = ps[static_cast<size_t>(tl) * n];
+        c[j] = pc[static_cast<size_t>(tl) * n];
+      }
+      // the loop's order: slice `wave` (even j) into a0 and slice `wave + 4` (odd j) into a1, tiles ascending
+#pragma unroll
+      for (int j = 0; j < LIK_TAIL_UNROLL; j += 2)
+      {
+        const bool h0 = wave + 4 * j < lt.n_tiles, h1 = wave + 4 * j + 4 < lt.n_tiles;
+        a0 = h0 ? a0 + x[j] : a0;
+        n0 = h0 ? n0 + c[j] : n0;
+        a1 = h1 ? a1 + x[j + 1] : a1;
+        n1 = h1 ? n1 + c[j + 1] : n1;
+      }
     }
-    if (tl < lt.n_tiles)
+    else
     {
-      a0 += ps[static_cast<size_t>(tl) * n];
-      n0 += pc[static_cast<size_t>(tl) * n];
+      int tl = wave;
+      for (; tl + 4 < lt.n_tiles; tl += 8)  // slice `wave` and slice `wave + 4` side by side: two independent chains of loads
+      {
+        const double x0 = ps[static_cast<size_t>(tl) * n], x1 = ps[static_cast<size_t>(tl + 4) * n];
+        const unsigned c0 = pc[static_cast<size_t>(tl) * n], c1 = pc[static_cast<size_t>(tl + 4) * n];
+        a0 += x0;
+        a1 += x1;
+        n0 += c0;
+        n1 += c1;
+      }
+      if (tl < lt.n_tiles)
+      {
+        a0 += ps[static_cast<size_t>(tl) * n];
+        n0 += pc[static_cast<size_t>(tl) * n];
+      }
     }
   }
   s_a[wave][lane] = a0;
@@ -190,11 +229,11 @@ __global__ __launch_bounds__(256) void lik_pf_partial_kernel(LikTiles lt, const 
     if (lt.bc.penalty)
       l *= beam_score_from_count(lt.bc, p);
     else if (beam)  // (1 * 1 for an update without beam points: what pf_partial_kernel reads back from the array filled with ones)
-      l *= lt.beam_fill ? 1.0f : beam[p];
+      l *= beam_p;
     l *= lk;
     if (extra)
-      l = l * extra[p];
-    const float wn = w[p] * l;  // pf.h:258
+      l = l * extra_p;
+    const float wn = w_p * l;  // pf.h:258
     w_new[p] = wn;
     s += static_cast<double>(wn);  // (0.0 + x, as pf_partial_kernel's loop forms it: the sign of a zero included)
     if (wn > 0.0f)
@@ -306,6 +345,20 @@ __global__ __launch_bounds__(PF_BLOCK) void pf_apply_kernel(float* __restrict__ 
 {
   __shared__ double s_tot[4];
   const double* packed = packed_in;
+  // a thread's first element (its only one when the grid covers n): read before the reduction and its barrier, not behind them
+  const int i0 = blockIdx.x * PF_BLOCK + threadIdx.x;
+  const bool emits = emit.lik || emit.ratio || emit.beam;
+  float wn0 = 0.0f, lik0 = 0.0f, ratio0 = 0.0f, beam0 = 0.0f;
+  if (i0 < n)
+  {
+    wn0 = w_new[i0];
+    if (emit.lik)
+      lik0 = lik[i0];
+    if (emit.ratio)
+      ratio0 = ratio[i0];
+    if (emit.beam)
+      beam0 = beam[i0];
+  }
   if (partials)
   {
     if (threadIdx.x < 64)
@@ -335,9 +388,9 @@ __global__ __launch_bounds__(PF_BLOCK) void pf_apply_kernel(float* __restrict__ 
   const bool alive = sum_f > 0.0f;
   if (alive)
   {
-    for (int i = blockIdx.x * PF_BLOCK + threadIdx.x; i < n; i += gridDim.x * PF_BLOCK)
+    for (int i = i0; i < n; i += gridDim.x * PF_BLOCK)
     {
-      const float wv = w_new[i] / sum_f;
+      const float wv = (i == i0 ? wn0 : w_new[i]) / sum_f;
       w[i] = wv;
       if (emit.w)
         emit.w[i] = wv;
@@ -348,15 +401,15 @@ __global__ __launch_bounds__(PF_BLOCK) void pf_apply_kernel(float* __restrict__ 
     for (int i = blockIdx.x * PF_BLOCK + threadIdx.x; i < n; i += gridDim.x * PF_BLOCK)
       emit.w[i] = w[i];
   }
-  if (emit.lik || emit.ratio || emit.beam)
-    for (int i = blockIdx.x * PF_BLOCK + threadIdx.x; i < n; i += gridDim.x * PF_BLOCK)
+  if (emits)
+    for (int i = i0; i < n; i += gridDim.x * PF_BLOCK)
     {
       if (emit.lik)
-        emit.lik[i] = lik[i];
+        emit.lik[i] = i == i0 ? lik0 : lik[i];
       if (emit.ratio)
-        emit.ratio[i] = ratio[i];
+        emit.ratio[i] = i == i0 ? ratio0 : ratio[i];
       if (emit.beam)
-        emit.beam[i] = beam[i];
+        emit.beam[i] = i == i0 ? beam0 : beam[i];
     }
   if (blockIdx.x == 0 && threadIdx.x == 0 && (stats4 || emit.stats4))
   {
