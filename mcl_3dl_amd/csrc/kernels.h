@@ -6,13 +6,16 @@
 //   beam_kernels.h        beam model: one lane per ray, DDA walk through 4x4x4 occupancy bricks, point tests, penalty count
 //   beam_kd_kernels.h     beam model with the reference's default caster (RaycastUsingKDTree): fixed-step march, exact nearest-
 //                         within-radius over the cell-sorted map at every step
-//   pf_kernels.h          pf::measure (weights, deterministic fp64 reductions, normalisation, entropy) and the "next" rows
-//                         (expectation / max / covariance, resampling)
+//   pf_sums.h             pf::measure's arithmetic, once: the weight product, a particle's terms, the wavefront / block / 64-lane
+//                         reductions of {sum w, sum w ln w, max ratio, -min ratio}, the four statistics
+//   pf_kernels.h          pf::measure's kernels over pf_sums.h (split, behind the tiled kernel, fused; the float-order weight sum;
+//                         normalisation) and the "next" rows (expectation / max / covariance, resampling)
 //   motion_kernels.h      between two scans, on resident particles: motion prediction, odometry-error reset, pf::noise, the
 //                         scan update's odometry factor, the IMU gravity likelihood (inside pf::measure's partial-sum pass)
 //   landmark_kernels.h    on resident particles: the pose-jump bias formed inside the moments pass, the landmark likelihood
 //                         (NormalLikelihoodNd<float, 6> over s - measured)
-//   update_kernels.h      likelihood + beam + pf::measure in ONE launch for the reference's operating range (launch-bound sizes)
+//   update_kernels.h      likelihood + beam + pf::measure (pf_sums.h) in ONE launch for the reference's operating range
+//                         (launch-bound sizes)
 //   map_compiler.h        device-side compiler of the candidate-voxel index (whole map, or the bricks a map update touches)
 //   grid_kernels.h        the cell-sorted exact-NN grid and the DDA occupancy / voxel index, built on the device
 //   cloud_kernels.h       scan / map preparation: PointCloud2 decode, VoxelGrid, clip + compaction, sampling gather,

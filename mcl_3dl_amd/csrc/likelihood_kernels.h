@@ -1641,31 +1641,6 @@ __global__ __launch_bounds__(1024) void lik_strict_sum_rows_kernel(const float* 
     out_lik[p] = score;
 }
 
-// pf::measure's `sum += p.probability_` (pf.h:255-260) as the reference runs it — a float recurrence in particle order — behind
-// pf_partial / pf_reduce: the result replaces the fp64 tree sum in packed[0] so that pf_apply_kernel divides by exactly the
-// reference's float. One work-group: 256 lanes stage 4096 weights at a time in LDS (coalesced), the first wavefront runs
-// the recurrence over them (float_chain.h: 256 terms a pass instead of one), carrying the sum from chunk to chunk.
-__global__ __launch_bounds__(256) void pf_strict_sum_kernel(const float* __restrict__ w_new, int n,
-                                                            double* __restrict__ packed)
-{
-  __shared__ __attribute__((aligned(16))) float buf[4096 + 4];
-  if (blockIdx.x != 0)
-    return;
-  float sum = 0.0f;
-  for (int base = 0; base < n; base += 4096)
-  {
-    const int m = min(4096, n - base), m4 = chain_row_floats(m);
-    for (int j = threadIdx.x; j < m4; j += 256)
-      buf[j] = j < m ? w_new[base + j] : 0.0f;
-    __syncthreads();
-    if (threadIdx.x < 64)
-      sum = seq_sum_wave(buf, m, static_cast<int>(threadIdx.x), sum);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0)
-    packed[0] = static_cast<double>(sum);
-}
-
 // n_s == 0: (likelihood 1, quality 0), src/lidar_measurement_model_likelihood.cpp:111-114
 __global__ void fill_kernel(float* a, float va, float* b, float vb, int n)
 {

@@ -6,6 +6,7 @@
 #include "device_math.h"
 #include "float_chain.h"
 #include "motion_kernels.h"
+#include "pf_sums.h"
 
 #pragma clang fp contract(off)
 
@@ -49,7 +50,7 @@ __device__ inline float beam_score_from_count(const BeamCounts& bc, int i)
   return sb;
 }
 
-// w_new = w * (((1 * beam) * lik) * extra); per-block partials {sum w, sum w ln w, max ratio, -min ratio}.
+// w_new = pf_weight(...); per-block partials (PfSums, pf_sums.h).
 __global__ __launch_bounds__(PF_BLOCK) void pf_partial_kernel(const float* __restrict__ w, const float* __restrict__ lik,
                                                               const float* __restrict__ beam,
                                                               const float* __restrict__ extra,
@@ -58,69 +59,35 @@ __global__ __launch_bounds__(PF_BLOCK) void pf_partial_kernel(const float* __res
                                                               double* __restrict__ block_partials, BeamCounts bc = BeamCounts{},
                                                               ImuGravity imu = ImuGravity{})
 {
-  double s = 0.0, t = 0.0, rmax = 0.0, rneg = -1.0;  // match_ratio_max = 0, match_ratio_min = 1 (mcl_3dl.cpp:398-399)
+  PfSums a = pf_no_sums();
   for (int i = blockIdx.x * PF_BLOCK + threadIdx.x; i < n; i += gridDim.x * PF_BLOCK)
   {
-    float l = 1.0f;
-    if (bc.penalty)
-      l *= beam_score_from_count(bc, i);
-    else if (beam)
-      l *= beam[i];
-    l *= imu.state13 ? imu_gravity_likelihood(imu, i) : lik[i];  // (the IMU update: the likelihood formed here, lik == null)
-    if (extra)
-      l = l * extra[i];
-    const float wn = w[i] * l;  // pf.h:258
+    const float b = bc.penalty ? beam_score_from_count(bc, i) : beam ? beam[i] : 1.0f;
+    const float lk = imu.state13 ? imu_gravity_likelihood(imu, i) : lik[i];  // (the IMU update: the likelihood formed here, lik == null)
+    const float wn = pf_weight(w[i], b, lk, extra ? extra[i] : 1.0f);
     w_new[i] = wn;
-    s += static_cast<double>(wn);
-    if (wn > 0.0f)
-      t += static_cast<double>(wn) * log(static_cast<double>(wn));
+    pf_add_weight(a, wn);
     if (ratio)
-    {
-      const double r = static_cast<double>(ratio[i]);
-      rmax = r > rmax ? r : rmax;
-      rneg = -r > rneg ? -r : rneg;
-    }
+      pf_add_ratio(a, ratio[i]);
   }
-  __shared__ double sh[4][PF_BLOCK / 64];
-  s = wave_sum(s);
-  t = wave_sum(t);
-  rmax = wave_max(rmax);
-  rneg = wave_max(rneg);
+  __shared__ PfSums sh[PF_BLOCK / 64];
+  a = pf_wave_reduce(a);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0)
-  {
-    sh[0][wave] = s;
-    sh[1][wave] = t;
-    sh[2][wave] = rmax;
-    sh[3][wave] = rneg;
-  }
+    sh[wave] = a;
   __syncthreads();
   if (threadIdx.x == 0)
-  {
-    double a = 0, b = 0, c = sh[2][0], d = sh[3][0];
-    for (int k = 0; k < PF_BLOCK / 64; ++k)
-    {
-      a += sh[0][k];
-      b += sh[1][k];
-      c = sh[2][k] > c ? sh[2][k] : c;
-      d = sh[3][k] > d ? sh[3][k] : d;
-    }
-    block_partials[4 * blockIdx.x + 0] = a;
-    block_partials[4 * blockIdx.x + 1] = b;
-    block_partials[4 * blockIdx.x + 2] = c;
-    block_partials[4 * blockIdx.x + 3] = d;
-  }
+    pf_store(block_partials + 4 * blockIdx.x, pf_block_combine(sh));
 }
 
 // lik_finalize_kernel + pf_partial_kernel as ONE launch (round 6; one GPU, the tiled likelihood kernel in front, at most
 // 1024 x 256 particles — one per thread of pf_partial_kernel's grid). A work-group owns 64 consecutive particles (one wavefront
 // of pf_partial_kernel's 256-thread blocks) with lik_finalize_kernel's own parallelism: its four wavefronts add up the eight
 // tile slices of the per-tile partials (wavefront v: slices v and v + 4, every eighth tile in increasing order), the first one
-// combines them in order — lik_finalize_kernel's association — and goes on with pf_partial_kernel's product, fp64 terms and
-// wavefront reductions. What leaves is the WAVEFRONT partial {sum w, sum w ln w, max ratio, -min ratio} of the 64 particles;
-// pf_reduce_kernel (waves = 1) forms pf_partial_kernel's block partials from four of them in that kernel's order (0 + w0 + w1 +
-// w2 + w3; a missing wavefront counts {0, 0, 0, -1}, what a wavefront without particles reduces to). Same arithmetic in the same
-// association as the two launches: the same bits (tests/test_gpu_pf_fused.py).
+// combines them in order — lik_finalize_kernel's association — and goes on with pf_sums.h's product, terms and wavefront
+// reduction. What leaves is the WAVEFRONT partial of the 64 particles; pf_reduce_lanes (n_waves > 0) forms pf_partial_kernel's block
+// partials from four of them with the same pf_block_combine. Same arithmetic in the same association as the two launches: the
+// same bits (tests/test_gpu_pf_fused.py).
 struct LikTiles
 {
   const double* psum;    // [n_tiles][n]
@@ -208,7 +175,7 @@ __global__ __launch_bounds__(256) void lik_pf_partial_kernel(LikTiles lt, const 
   __syncthreads();
   if (wave != 0)
     return;
-  double s = 0.0, t = 0.0, rmax = 0.0, rneg = -1.0;
+  PfSums sums = pf_no_sums();
   if (p < n)
   {
     double a = a0;
@@ -225,34 +192,15 @@ __global__ __launch_bounds__(256) void lik_pf_partial_kernel(LikTiles lt, const 
     lt.ratio_out[p] = r32;
     if (lt.beam_fill)
       lt.beam_fill[p] = 1.0f;
-    float l = 1.0f;
-    if (lt.bc.penalty)
-      l *= beam_score_from_count(lt.bc, p);
-    else if (beam)  // (1 * 1 for an update without beam points: what pf_partial_kernel reads back from the array filled with ones)
-      l *= beam_p;
-    l *= lk;
-    if (extra)
-      l = l * extra_p;
-    const float wn = w_p * l;  // pf.h:258
+    // (beam_p is 1 for an update without beam points: what pf_partial_kernel reads back from the array filled with ones)
+    const float wn = pf_weight(w_p, lt.bc.penalty ? beam_score_from_count(lt.bc, p) : beam_p, lk, extra_p);
     w_new[p] = wn;
-    s += static_cast<double>(wn);  // (0.0 + x, as pf_partial_kernel's loop forms it: the sign of a zero included)
-    if (wn > 0.0f)
-      t += static_cast<double>(wn) * log(static_cast<double>(wn));
-    const double r = static_cast<double>(r32);
-    rmax = r > rmax ? r : rmax;
-    rneg = -r > rneg ? -r : rneg;
+    pf_add_weight(sums, wn);
+    pf_add_ratio(sums, r32);
   }
-  s = wave_sum(s);
-  t = wave_sum(t);
-  rmax = wave_max(rmax);
-  rneg = wave_max(rneg);
+  sums = pf_wave_reduce(sums);
   if (lane == 0)
-  {
-    wave_partials[4 * blockIdx.x + 0] = s;
-    wave_partials[4 * blockIdx.x + 1] = t;
-    wave_partials[4 * blockIdx.x + 2] = rmax;
-    wave_partials[4 * blockIdx.x + 3] = rneg;
-  }
+    pf_store(wave_partials + 4 * blockIdx.x, sums);
 }
 
 // Fixed-order reduction of the block partials (deterministic run to run). The result is written in the layout the
@@ -260,80 +208,68 @@ __global__ __launch_bounds__(256) void lik_pf_partial_kernel(LikTiles lt, const 
 // [2+2r] max ratio, [3+2r] -min ratio — this rank fills its own pair and zeroes the others, so that after the SUM every
 // rank holds every rank's pair. world == 1 degenerates to the plain 4 doubles.
 // n_waves > 0: `block_partials` holds lik_pf_partial_kernel's n_waves WAVEFRONT partials instead (block k = wavefronts 4 k .. 4 k + 3,
-// added up here the way pf_partial_kernel's thread 0 does).
-__device__ inline void pf_reduce_lanes(const double* __restrict__ block_partials, int n_blocks, int n_waves, int lane, double& a,
-                                       double& b, double& c, double& d)
+// every one of them loaded before pf_block_combine's first add).
+__device__ inline PfSums pf_reduce_lanes(const double* __restrict__ block_partials, int n_blocks, int n_waves, int lane)
 {
-  a = 0;
-  b = 0;
-  c = 0.0;
-  d = -1.0;
-  if (n_waves > 0)
-  {
-    for (int k = lane; k < n_blocks; k += 64)
-    {
-      const double* wp = block_partials + 16 * static_cast<size_t>(k);
-      const bool h1 = 4 * k + 1 < n_waves, h2 = 4 * k + 2 < n_waves, h3 = 4 * k + 3 < n_waves;
-      double ba = 0, bb = 0, bc = wp[2], bd = wp[3];
-      ba += wp[0];
-      bb += wp[1];
-      const double a1 = h1 ? wp[4] : 0.0, b1 = h1 ? wp[5] : 0.0, c1 = h1 ? wp[6] : 0.0, d1 = h1 ? wp[7] : -1.0;
-      const double a2 = h2 ? wp[8] : 0.0, b2 = h2 ? wp[9] : 0.0, c2 = h2 ? wp[10] : 0.0, d2 = h2 ? wp[11] : -1.0;
-      const double a3 = h3 ? wp[12] : 0.0, b3 = h3 ? wp[13] : 0.0, c3 = h3 ? wp[14] : 0.0, d3 = h3 ? wp[15] : -1.0;
-      ba += a1;
-      bb += b1;
-      bc = c1 > bc ? c1 : bc;
-      bd = d1 > bd ? d1 : bd;
-      ba += a2;
-      bb += b2;
-      bc = c2 > bc ? c2 : bc;
-      bd = d2 > bd ? d2 : bd;
-      ba += a3;
-      bb += b3;
-      bc = c3 > bc ? c3 : bc;
-      bd = d3 > bd ? d3 : bd;
-      a += ba;
-      b += bb;
-      c = bc > c ? bc : c;
-      d = bd > d ? bd : d;
-    }
-  }
-  else
-  for (int k = lane; k < n_blocks; k += 64)
-  {
-    a += block_partials[4 * k + 0];
-    b += block_partials[4 * k + 1];
-    c = block_partials[4 * k + 2] > c ? block_partials[4 * k + 2] : c;
-    d = block_partials[4 * k + 3] > d ? block_partials[4 * k + 3] : d;
-  }
-  a = wave_sum(a);
-  b = wave_sum(b);
-  c = wave_max(c);
-  d = wave_max(d);
+  return pf_reduce_blocks(n_blocks, lane, [&](int k) {
+    if (n_waves <= 0)
+      return pf_load(block_partials + 4 * k);
+    const double* wp = block_partials + 16 * static_cast<size_t>(k);
+    PfSums wv[4] = { pf_load(wp), pf_no_sums(), pf_no_sums(), pf_no_sums() };
+#pragma unroll
+    for (int j = 1; j < 4; ++j)
+      if (4 * k + j < n_waves)
+        wv[j] = pf_load(wp + 4 * j);
+    return pf_block_combine(wv);
+  });
 }
 
 __global__ __launch_bounds__(64) void pf_reduce_kernel(const double* __restrict__ block_partials, int n_blocks, int rank,
                                                        int world, double* __restrict__ packed, int n_waves = 0)
 {
-  double a, b, c, d;
-  pf_reduce_lanes(block_partials, n_blocks, n_waves, threadIdx.x, a, b, c, d);
+  const PfSums a = pf_reduce_lanes(block_partials, n_blocks, n_waves, threadIdx.x);
   if (threadIdx.x == 0)
   {
-    packed[0] = a;
-    packed[1] = b;
+    packed[0] = a.s;
+    packed[1] = a.t;
     for (int r = 0; r < world; ++r)
     {
-      packed[2 + 2 * r] = (r == rank) ? c : 0.0;
-      packed[3 + 2 * r] = (r == rank) ? d : 0.0;
+      packed[2 + 2 * r] = (r == rank) ? a.rmax : 0.0;
+      packed[3 + 2 * r] = (r == rank) ? a.rneg : 0.0;
     }
   }
 }
 
-// Normalise (pf.h:262-272) or restore (pf.h:274-278); entropy = ln S - T/S == -sum (w/S) ln (w/S).
+// pf::measure's `sum += p.probability_` (pf.h:255-260) as the reference runs it — a float recurrence in particle order — behind
+// pf_partial / pf_reduce: the result replaces the fp64 tree sum in packed[0] so that pf_apply_kernel divides by exactly the
+// reference's float. One work-group: 256 lanes stage 4096 weights at a time in LDS (coalesced), the first wavefront runs
+// the recurrence over them (float_chain.h: 256 terms a pass instead of one), carrying the sum from chunk to chunk.
+__global__ __launch_bounds__(256) void pf_strict_sum_kernel(const float* __restrict__ w_new, int n,
+                                                            double* __restrict__ packed)
+{
+  __shared__ __attribute__((aligned(16))) float buf[4096 + 4];
+  if (blockIdx.x != 0)
+    return;
+  float sum = 0.0f;
+  for (int base = 0; base < n; base += 4096)
+  {
+    const int m = min(4096, n - base), m4 = chain_row_floats(m);
+    for (int j = threadIdx.x; j < m4; j += 256)
+      buf[j] = j < m ? w_new[base + j] : 0.0f;
+    __syncthreads();
+    if (threadIdx.x < 64)
+      sum = seq_sum_wave(buf, m, static_cast<int>(threadIdx.x), sum);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0)
+    packed[0] = static_cast<double>(sum);
+}
+
+// Normalise (pf.h:262-272) or restore (pf.h:274-278); the statistics: pf_write_stats.
 // `packed` is the (all-reduced) vector described above.
 // emit (+ the device arrays its lik / ratio / beam copies come from): see PfEmit.
-// partials != null (one GPU, world == 1): EVERY work-group runs pf_reduce_kernel's reduction itself (first wavefront, the same
-// association) instead of reading `packed` behind a launch of its own; work-group 0 also leaves the four sums in packed_w.
+// partials != null (one GPU, world == 1): EVERY work-group runs pf_reduce_lanes itself (first wavefront) instead of reading
+// `packed` behind a launch of its own; work-group 0 also leaves the four sums in packed_w.
 __global__ __launch_bounds__(PF_BLOCK) void pf_apply_kernel(float* __restrict__ w, const float* __restrict__ w_new,
                                                             int n, int world, const double* __restrict__ packed_in,
                                                             float* __restrict__ stats4, PfEmit emit = PfEmit{},
@@ -363,21 +299,12 @@ __global__ __launch_bounds__(PF_BLOCK) void pf_apply_kernel(float* __restrict__ 
   {
     if (threadIdx.x < 64)
     {
-      double a, b, c, d;
-      pf_reduce_lanes(partials, n_blocks, n_waves, threadIdx.x, a, b, c, d);
+      const PfSums a = pf_reduce_lanes(partials, n_blocks, n_waves, threadIdx.x);
       if (threadIdx.x == 0)
       {
-        s_tot[0] = a;
-        s_tot[1] = b;
-        s_tot[2] = c;
-        s_tot[3] = d;
+        pf_store(s_tot, a);
         if (blockIdx.x == 0 && packed_w)
-        {
-          packed_w[0] = a;
-          packed_w[1] = b;
-          packed_w[2] = c;
-          packed_w[3] = d;
-        }
+          pf_store(packed_w, a);
       }
     }
     __syncthreads();
@@ -421,23 +348,15 @@ __global__ __launch_bounds__(PF_BLOCK) void pf_apply_kernel(float* __restrict__ 
       rmax = packed[2 + 2 * r] > rmax ? packed[2 + 2 * r] : rmax;
       rneg = packed[3 + 2 * r] > rneg ? packed[3 + 2 * r] : rneg;
     }
-    const float st[4] = { alive ? static_cast<float>(log(S) - packed[1] / S) : __builtin_nanf(""), static_cast<float>(-rneg),
-                          static_cast<float>(rmax), alive ? 0.0f : 1.0f };
-    for (int k = 0; k < 4; ++k)
-    {
-      if (stats4)
-        stats4[k] = st[k];
-      if (emit.stats4)
-        emit.stats4[k] = st[k];
-    }
+    pf_write_stats(PfSums{ S, packed[1], rmax, rneg }, alive, stats4, emit.stats4);
   }
 }
 
 // pf_partial_kernel -> pf_reduce_kernel -> pf_apply_kernel for ONE GPU and at most PF_FUSED_MAX particles, as a single
 // work-group: the reference's real operating range (64 .. a few thousand particles) is launch-bound — three launches of
-// a few microseconds each around ~1 us of work. The arithmetic is the three kernels' own, in the same association (the
-// 256-thread "blocks" of pf_partial_kernel become quarters of this 1024-thread group that walk the same elements, the
-// 64-lane reduce runs in the first wavefront), so weights, entropy and ratio bounds are bit-identical to the split form.
+// a few microseconds each around ~1 us of work. The arithmetic is pf_sums.h's, called in the three kernels' association (the
+// 256-thread "blocks" of pf_partial_kernel become quarters of this 1024-thread group that walk the same elements,
+// pf_reduce_blocks runs in the first wavefront), so weights, entropy and ratio bounds are bit-identical to the split form.
 // Measured and NOT kept (round 3, commit 5b571a1): pf_partial_kernel's grid with the reduce and the apply run by the last
 // work-group behind an arrival-ticket tree, for 1024 < n <= 16 384 — bit-identical, and the group cost 24 us instead of
 // 12.5 us at 4096 particles (49 at 16 384): three launches enqueued back to back cost 4.2 us each, less than two ticket
@@ -454,84 +373,40 @@ __global__ __launch_bounds__(1024) void pf_fused_kernel(float* __restrict__ w, c
   // float_order: pf::measure's `sum += p.probability_` (pf.h:255-260) as the reference runs it — float, sequentially, in
   // particle order (float_chain.h) — instead of the fp64 tree: the weights are divided by exactly the reference's float
   __shared__ __attribute__((aligned(16))) float s_w[PF_FUSED_MAX + 4];
-  __shared__ double sh[4][16];          // per wavefront of the group
-  __shared__ double part[4][16];        // per virtual block (n <= 4096 -> at most 16 of them)
-  __shared__ double tot[4];
+  __shared__ PfSums sh[16];             // per wavefront of the group
+  __shared__ PfSums part[16];           // per virtual block (n <= 4096 -> at most 16 of them)
+  __shared__ PfSums tot;
   const int nb = (n + PF_BLOCK - 1) / PF_BLOCK;  // pf_blocks(n) for n <= 4096
   const int q = threadIdx.x >> 8, tid = threadIdx.x & 255, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int vb0 = 0; vb0 < nb; vb0 += 4)
   {
     const int vb = vb0 + q;  // this quarter's virtual block
-    double s = 0.0, t = 0.0, rmax = 0.0, rneg = -1.0;
+    PfSums a = pf_no_sums();
     const int i = vb * PF_BLOCK + tid;  // stride nb * PF_BLOCK >= n: one element per thread, like pf_partial_kernel
     if (vb < nb && i < n)
     {
-      float l = 1.0f;
-      if (bc.penalty)  // (beam == bc.beam_out: the apply loop below re-reads what THIS thread writes here)
-        l *= beam_score_from_count(bc, i);
-      else if (beam)
-        l *= beam[i];
-      l *= imu.state13 ? imu_gravity_likelihood(imu, i) : lik[i];  // (as in pf_partial_kernel; no emit.lik then)
-      if (extra)
-        l = l * extra[i];
-      const float wn = w[i] * l;
+      // (beam == bc.beam_out: the apply loop below re-reads what THIS thread writes here; the IMU update: no emit.lik)
+      const float b = bc.penalty ? beam_score_from_count(bc, i) : beam ? beam[i] : 1.0f;
+      const float lk = imu.state13 ? imu_gravity_likelihood(imu, i) : lik[i];
+      const float wn = pf_weight(w[i], b, lk, extra ? extra[i] : 1.0f);
       w_new[i] = wn;
       if (float_order)
         s_w[i] = wn;
-      s += static_cast<double>(wn);
-      if (wn > 0.0f)
-        t += static_cast<double>(wn) * log(static_cast<double>(wn));
+      pf_add_weight(a, wn);
       if (ratio)
-      {
-        const double r = static_cast<double>(ratio[i]);
-        rmax = r > rmax ? r : rmax;
-        rneg = -r > rneg ? -r : rneg;
-      }
+        pf_add_ratio(a, ratio[i]);
     }
-    s = wave_sum(s);
-    t = wave_sum(t);
-    rmax = wave_max(rmax);
-    rneg = wave_max(rneg);
+    a = pf_wave_reduce(a);
     if (lane == 0)
-    {
-      sh[0][wave] = s;
-      sh[1][wave] = t;
-      sh[2][wave] = rmax;
-      sh[3][wave] = rneg;
-    }
+      sh[wave] = a;
     __syncthreads();
     if (tid == 0 && vb < nb)
-    {
-      double a = 0, b = 0, c = sh[2][4 * q], d = sh[3][4 * q];
-      for (int k = 0; k < PF_BLOCK / 64; ++k)
-      {
-        a += sh[0][4 * q + k];
-        b += sh[1][4 * q + k];
-        c = sh[2][4 * q + k] > c ? sh[2][4 * q + k] : c;
-        d = sh[3][4 * q + k] > d ? sh[3][4 * q + k] : d;
-      }
-      part[0][vb] = a;
-      part[1][vb] = b;
-      part[2][vb] = c;
-      part[3][vb] = d;
-    }
+      part[vb] = pf_block_combine(sh + 4 * q);
     __syncthreads();
   }
   if (wave == 0)
   {
-    // pf_reduce_kernel: 64 lanes stride the block partials, wavefront reduction
-    double a = 0, b = 0, c = 0.0, d = -1.0;
-    for (int k = lane; k < nb; k += 64)
-    {
-      a += part[0][k];
-      b += part[1][k];
-      c = part[2][k] > c ? part[2][k] : c;
-      d = part[3][k] > d ? part[3][k] : d;
-    }
-    a = wave_sum(a);
-    b = wave_sum(b);
-    c = wave_max(c);
-    d = wave_max(d);
+    PfSums a = pf_reduce_blocks(nb, lane, [&](int k) { return part[k]; });
     if (float_order)
     {
       // (s_w[0 .. n) was written before the loop's last barrier; the padding of the last float4 here, by this wavefront)
@@ -539,23 +414,17 @@ __global__ __launch_bounds__(1024) void pf_fused_kernel(float* __restrict__ w, c
         s_w[n + lane] = 0.0f;
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      a = static_cast<double>(seq_sum_wave(s_w, n, lane));
+      a.s = static_cast<double>(seq_sum_wave(s_w, n, lane));
     }
     if (lane == 0)
     {
-      tot[0] = a;
-      tot[1] = b;
-      tot[2] = c;
-      tot[3] = d;
-      packed[0] = a;
-      packed[1] = b;
-      packed[2] = c;
-      packed[3] = d;
+      tot = a;
+      pf_store(packed, a);
     }
   }
   __syncthreads();
   // pf_apply_kernel
-  const double S = tot[0];
+  const double S = tot.s;
   const float sum_f = static_cast<float>(S);
   const bool alive = sum_f > 0.0f;
   for (int i = threadIdx.x; i < n; i += 1024)
@@ -577,18 +446,8 @@ __global__ __launch_bounds__(1024) void pf_fused_kernel(float* __restrict__ w, c
     if (emit.beam)
       emit.beam[i] = beam ? beam[i] : 1.f;
   }
-  if (threadIdx.x == 0 && (stats4 || emit.stats4))
-  {
-    const float st[4] = { alive ? static_cast<float>(log(S) - tot[1] / S) : __builtin_nanf(""), static_cast<float>(-tot[3]),
-                          static_cast<float>(tot[2]), alive ? 0.0f : 1.0f };
-    for (int k = 0; k < 4; ++k)
-    {
-      if (stats4)
-        stats4[k] = st[k];
-      if (emit.stats4)
-        emit.stats4[k] = st[k];
-    }
-  }
+  if (threadIdx.x == 0)
+    pf_write_stats(tot, alive, stats4, emit.stats4);
 }
 
 // per-particle results of the two models -> page-locked host memory (mcl3dl_hip_measure_batch without a D2H copy)
@@ -604,19 +463,6 @@ __global__ __launch_bounds__(PF_BLOCK) void emit3_kernel(PfEmit emit, const floa
     if (emit.beam)
       emit.beam[i] = beam[i];
   }
-}
-
-
-__device__ __forceinline__ float pf_weight_product(float w, float lik, float beam, bool has_beam, const float* __restrict__ extra,
-                                                   int i)
-{
-  float l = 1.0f;
-  if (has_beam)
-    l *= beam;
-  l *= lik;
-  if (extra)
-    l = l * extra[i];
-  return w * l;  // pf.h:258
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -5,9 +5,9 @@
 //   work-group p  = particle p: likelihood score (lik_particle — the code of likelihood_kernel), beam score (cast_ray —
 //                   the code of beam_kernel; penalty count -> power table -> clamp), results written to out_lik / _ratio / _beam
 //   256 particles = one "virtual block" of pf::measure's split form (pf_partial_kernel's 256-thread blocks): the LAST of
-//                   its work-groups to finish (an arrival ticket) computes that block's partial {sum w, sum w ln w, max
-//                   ratio, -min ratio} with the split form's association
-//   the LAST virtual block to finish runs pf_reduce_kernel's 64-lane reduction and pf_apply_kernel's normalisation
+//                   its work-groups to finish (an arrival ticket) computes that block's partial (pf_sums.h: the terms, the
+//                   wavefront reduction and pf_block_combine, as pf_partial_kernel calls them)
+//   the LAST virtual block to finish runs pf_reduce_blocks over the partials and pf_apply_kernel's normalisation
 //
 // Nobody waits for anybody: a ticket is an atomic counter, the work-group that draws the last number does the next stage.
 // Arrivals are counted through an 8-ary TREE of tickets: atomics on one address from many CUs are served one after the
@@ -228,86 +228,46 @@ __global__ __launch_bounds__(BLOCK) void update_small_kernel(UpdateSmallArgs a)
   constexpr int VB_TREE = 32 + 4 + 1;  // ticket_tree_size(256)
   if (!last_of_tree(a.tickets + vb * VB_TREE, p - vb * PF_BLOCK, in_vb, a.conformant))
     return;
-  __shared__ double sh[4][4];
+  __shared__ PfSums sh[4];
   for (int chunk = wave; chunk < 4; chunk += NW)  // pf_partial_kernel: wavefront `chunk` of the block, one element per lane
   {
-    double s = 0.0, t = 0.0, rmax = 0.0, rneg = -1.0;  // match_ratio_max = 0, match_ratio_min = 1 (mcl_3dl.cpp:398-399)
+    PfSums sums = pf_no_sums();
     const int i = vb * PF_BLOCK + chunk * 64 + lane;
     if (i < a.n_p)
     {
-      float l = 1.0f;
-      if (a.use_beam)
-        l *= load_agent(a.out_beam + i);
-      l *= load_agent(a.out_lik + i);
-      if (a.extra)
-        l = l * a.extra[i];
-      const float wn = a.w[i] * l;  // pf.h:258
+      const float wn = pf_weight(a.w[i], a.use_beam ? load_agent(a.out_beam + i) : 1.0f, load_agent(a.out_lik + i),
+                                 a.extra ? a.extra[i] : 1.0f);
       store_agent(a.w_new + i, wn);
-      s += static_cast<double>(wn);
-      if (wn > 0.0f)
-        t += static_cast<double>(wn) * log(static_cast<double>(wn));
-      const double r = static_cast<double>(load_agent(a.out_ratio + i));
-      rmax = r > rmax ? r : rmax;
-      rneg = -r > rneg ? -r : rneg;
+      pf_add_weight(sums, wn);
+      pf_add_ratio(sums, load_agent(a.out_ratio + i));
     }
-    s = wave_sum(s);
-    t = wave_sum(t);
-    rmax = wave_max(rmax);
-    rneg = wave_max(rneg);
+    sums = pf_wave_reduce(sums);
     if (lane == 0)
-    {
-      sh[0][chunk] = s;
-      sh[1][chunk] = t;
-      sh[2][chunk] = rmax;
-      sh[3][chunk] = rneg;
-    }
+      sh[chunk] = sums;
   }
   __syncthreads();
   if (threadIdx.x == 0)
   {
-    double x = 0, y = 0, c = sh[2][0], d = sh[3][0];
-    for (int k = 0; k < 4; ++k)
-    {
-      x += sh[0][k];
-      y += sh[1][k];
-      c = sh[2][k] > c ? sh[2][k] : c;
-      d = sh[3][k] > d ? sh[3][k] : d;
-    }
-    store_agent(a.vb_partials + 4 * vb + 0, x);
-    store_agent(a.vb_partials + 4 * vb + 1, y);
-    store_agent(a.vb_partials + 4 * vb + 2, c);
-    store_agent(a.vb_partials + 4 * vb + 3, d);
+    const PfSums b = pf_block_combine(sh);
+    store_agent(a.vb_partials + 4 * vb + 0, b.s);
+    store_agent(a.vb_partials + 4 * vb + 1, b.t);
+    store_agent(a.vb_partials + 4 * vb + 2, b.rmax);
+    store_agent(a.vb_partials + 4 * vb + 3, b.rneg);
   }
   // ---- Stage 2: the last virtual block to finish
   if (!last_of_tree(a.tickets + nvb * VB_TREE, vb, nvb, a.conformant))
     return;
-  __shared__ double tot[4];
+  __shared__ PfSums tot;
   if (wave == 0)
   {
-    // pf_reduce_kernel: 64 lanes stride the block partials, wavefront reduction
-    double x = 0, y = 0, c = 0.0, d = -1.0;
-    for (int k = lane; k < nvb; k += 64)
-    {
-      x += load_agent(a.vb_partials + 4 * k + 0);
-      y += load_agent(a.vb_partials + 4 * k + 1);
-      const double ck = load_agent(a.vb_partials + 4 * k + 2), dk = load_agent(a.vb_partials + 4 * k + 3);
-      c = ck > c ? ck : c;
-      d = dk > d ? dk : d;
-    }
-    x = wave_sum(x);
-    y = wave_sum(y);
-    c = wave_max(c);
-    d = wave_max(d);
+    const PfSums all = pf_reduce_blocks(nvb, lane, [&](int k) {
+      const double* vp = a.vb_partials + 4 * k;
+      return PfSums{ load_agent(vp), load_agent(vp + 1), load_agent(vp + 2), load_agent(vp + 3) };
+    });
     if (lane == 0)
     {
-      tot[0] = x;
-      tot[1] = y;
-      tot[2] = c;
-      tot[3] = d;
-      a.packed[0] = x;
-      a.packed[1] = y;
-      a.packed[2] = c;
-      a.packed[3] = d;
+      tot = all;
+      pf_store(a.packed, all);
     }
   }
   __syncthreads();
@@ -325,14 +285,14 @@ __global__ __launch_bounds__(BLOCK) void update_small_kernel(UpdateSmallArgs a)
       const float sum_w = seq_sum_wave(dyn_row, a.n_p, lane);
       if (lane == 0)
       {
-        tot[0] = static_cast<double>(sum_w);
+        tot.s = static_cast<double>(sum_w);
         a.packed[0] = static_cast<double>(sum_w);
       }
     }
     __syncthreads();
   }
   // pf_apply_kernel
-  const double S = tot[0];
+  const double S = tot.s;
   const float sum_f = static_cast<float>(S);
   const bool alive = sum_f > 0.0f;
   if (alive)
@@ -347,17 +307,7 @@ __global__ __launch_bounds__(BLOCK) void update_small_kernel(UpdateSmallArgs a)
     for (int i = threadIdx.x; i < a.n_p; i += BLOCK)
       a.emit.w[i] = a.w[i];
   if (threadIdx.x == 0)
-  {
-    const float st[4] = { alive ? static_cast<float>(log(S) - tot[1] / S) : __builtin_nanf(""), static_cast<float>(-tot[3]),
-                          static_cast<float>(tot[2]), alive ? 0.0f : 1.0f };
-    for (int k = 0; k < 4; ++k)
-    {
-      if (a.stats4)
-        a.stats4[k] = st[k];
-      if (a.emit.stats4)
-        a.emit.stats4[k] = st[k];
-    }
-  }
+    pf_write_stats(tot, alive, a.stats4, a.emit.stats4);
   for (int k = threadIdx.x; k < nvb * VB_TREE + ticket_tree_size(nvb); k += BLOCK)
     a.tickets[k] = 0u;  // ready for the next launch
 }
