@@ -1,13 +1,13 @@
 // beam_kd_kernels.h — beam model with the reference's DEFAULT raycaster (beam/use_raycast_using_dda = false):
 // RaycastUsingKDTree marches along the ray in steps of the smallest map grid edge and asks the map's kd-tree for the
 // nearest point around every position; here every such search is the exact nearest-within-radius over the cell-sorted
-// map (LikGrid, cloud_kernels.h:cell_grid_nearest — the definition of mcl3dl_hip_radius_search).
+// map (LikGrid, cell_grid.h:cell_grid_nearest — the definition of mcl3dl_hip_radius_search).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "beam_kernels.h"
-#include "cloud_kernels.h"
+#include "cell_grid.h"
 #include "device_math.h"
 #include "map_structs.h"
 #pragma clang fp contract(off)
@@ -45,14 +45,15 @@ __global__ __launch_bounds__(256) void kd_occupancy_kernel(LikGrid g, int reach,
     const int cx = static_cast<int>(c % static_cast<unsigned>(g.nx));
     const unsigned long long r = c / static_cast<unsigned>(g.nx);
     const int cy = static_cast<int>(r % static_cast<unsigned>(g.ny)), cz = static_cast<int>(r / static_cast<unsigned>(g.ny));
-    const int x0 = max(cx - reach, 0), x1 = min(cx + reach, g.nx - 1);
-    const int y0 = max(cy - reach, 0), y1 = min(cy + reach, g.ny - 1);
-    const int z0 = max(cz - reach, 0), z1 = min(cz + reach, g.nz - 1);
-    for (int z = z0; z <= z1; ++z)
-      for (int y = y0; y <= y1; ++y)
+    const CellBlock b = cell_block(g, cx, cy, cz, reach);
+    for (int z = b.z0; z <= b.z1; ++z)
+      for (int y = b.y0; y <= b.y1; ++y)
       {
-        const size_t row = (static_cast<size_t>(z) * g.ny + y) * g.nx;
-        any = any || g.cell_start[row + x1 + 1] != g.cell_start[row + x0];
+        if (any)
+          continue;  // (a lane that has found a point loads no more delimiters)
+        uint32_t s, e;
+        cell_row_run(g, z, y, b.y1, b.x0, b.x1, s, e);
+        any = e != s;
       }
   }
   const unsigned long long word = __ballot(any);
@@ -60,26 +61,12 @@ __global__ __launch_bounds__(256) void kd_occupancy_kernel(LikGrid g, int reach,
     out[c >> 6] = word;
 }
 
-// The searches. cell_grid_nearest (cloud_kernels.h) defines the result — min d2 below `best` over the cells within `reach` of
+// The searches. cell_grid_nearest (cell_grid.h) defines the result — min d2 below `best` over the cells within `reach` of
 // the query's, flann::L2_Simple float order, ties to the lowest map index — and reads one row's run delimiters, then that
 // run's points one by one: every load waits for the one before it, and a ray near a wall pays dozens of memory latencies per
 // search. The forms below compute the same minimum over the same candidates with the loads batched: the delimiters of
 // several rows together, four points per round (a round's indices are clamped to the run: a point looked at twice changes
 // neither the minimum nor the tie).
-__device__ inline void kd_consider(const float4 p, float qx, float qy, float qz, float& best, int& best_idx)
-{
-  const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-  float d2 = dx * dx;
-  d2 = d2 + dy * dy;
-  d2 = d2 + dz * dz;
-  const int idx = static_cast<int>(__float_as_uint(p.w));
-  if (d2 < best || (d2 == best && best_idx >= 0 && idx < best_idx))
-  {
-    best = d2;
-    best_idx = idx;
-  }
-}
-
 __device__ inline void kd_scan_run(const float4* __restrict__ pts, uint32_t s, uint32_t e, float qx, float qy, float qz,
                                    float& best, int& best_idx)
 {
@@ -87,10 +74,10 @@ __device__ inline void kd_scan_run(const float4* __restrict__ pts, uint32_t s, u
   {
     const uint32_t last = e - 1;
     const float4 p0 = pts[k], p1 = pts[min(k + 1, last)], p2 = pts[min(k + 2, last)], p3 = pts[min(k + 3, last)];
-    kd_consider(p0, qx, qy, qz, best, best_idx);
-    kd_consider(p1, qx, qy, qz, best, best_idx);
-    kd_consider(p2, qx, qy, qz, best, best_idx);
-    kd_consider(p3, qx, qy, qz, best, best_idx);
+    nearest_consider(p0, qx, qy, qz, best, best_idx);
+    nearest_consider(p1, qx, qy, qz, best, best_idx);
+    nearest_consider(p2, qx, qy, qz, best, best_idx);
+    nearest_consider(p3, qx, qy, qz, best, best_idx);
   }
 }
 
@@ -99,47 +86,26 @@ __device__ inline float kd_nearest_27(const LikGrid& g, float qx, float qy, floa
                                       int& best_idx)
 {
   uint32_t rs[9], re[9];
-#pragma unroll
-  for (int r = 0; r < 9; ++r)
-  {
-    const int dz = r / 3 - 1, dy = r % 3 - 1;
-    const size_t row = (static_cast<size_t>(cz + dz) * g.ny + (cy + dy)) * g.nx + cx;
-    rs[r] = g.cell_start[row - 1];
-    re[r] = g.cell_start[row + 2];
-  }
+  cell_rows_27(g, cx, cy, cz, rs, re);
 #pragma unroll
   for (int r = 0; r < 9; ++r)
     kd_scan_run(g.pts, rs[r], re[r], qx, qy, qz, best, best_idx);
   return best;
 }
 
-// any reach, any query (cell_grid_nearest's range test and clamping): the rows of a z layer five at a time
+// any reach, any query: the rows of a z layer five at a time
 __device__ inline float kd_nearest(const LikGrid& g, float qx, float qy, float qz, int reach, float best, int& best_idx)
 {
-  const float fx = floorf((qx - g.ox) * g.inv_cell), fy = floorf((qy - g.oy) * g.inv_cell),
-              fz = floorf((qz - g.oz) * g.inv_cell);
-  if (!(fx >= -static_cast<float>(reach) && fy >= -static_cast<float>(reach) && fz >= -static_cast<float>(reach) &&
-        fx <= static_cast<float>(g.nx - 1 + reach) && fy <= static_cast<float>(g.ny - 1 + reach) &&
-        fz <= static_cast<float>(g.nz - 1 + reach)))
+  CellBlock b;
+  if (!cell_block_of(g, qx, qy, qz, reach, b))
     return best;
-  const int cx = static_cast<int>(fx), cy = static_cast<int>(fy), cz = static_cast<int>(fz);
-  const int x0 = max(cx - reach, 0), x1 = min(cx + reach, g.nx - 1);
-  const int y0 = max(cy - reach, 0), y1 = min(cy + reach, g.ny - 1);
-  const int z0 = max(cz - reach, 0), z1 = min(cz + reach, g.nz - 1);
-  if (x0 > x1)
-    return best;
-  for (int z = z0; z <= z1; ++z)
-    for (int yb = y0; yb <= y1; yb += 5)
+  for (int z = b.z0; z <= b.z1; ++z)
+    for (int yb = b.y0; yb <= b.y1; yb += 5)
     {
       uint32_t rs[5], re[5];
 #pragma unroll
       for (int j = 0; j < 5; ++j)
-      {
-        const bool in = yb + j <= y1;
-        const size_t row = (static_cast<size_t>(z) * g.ny + (in ? yb + j : yb)) * g.nx;
-        rs[j] = g.cell_start[row + x0];
-        re[j] = in ? g.cell_start[row + x1 + 1] : rs[j];  // (a row past y1: an empty run)
-      }
+        cell_row_run(g, z, yb + j, b.y1, b.x0, b.x1, rs[j], re[j]);
 #pragma unroll
       for (int j = 0; j < 5; ++j)
         kd_scan_run(g.pts, rs[j], re[j], qx, qy, qz, best, best_idx);
@@ -194,9 +160,9 @@ __device__ inline int cast_ray_kd(const LikGrid& g, const KdRayParams& k, const 
         qz = qz * k.wz;
       }
       // Past the cell grid by more than the search's reach on an axis the ray is moving away on: this search and every later
-      // one finds nothing (cell_grid_nearest's own range test, on a coordinate that only moves further out) — LONG
-      const float fx = floorf((qx - g.ox) * g.inv_cell), fy = floorf((qy - g.oy) * g.inv_cell),
-                  fz = floorf((qz - g.oz) * g.inv_cell);
+      // one finds nothing (cell_block_of's own range test, on a coordinate that only moves further out) — LONG
+      const Vec3f f = cell_of(g, qx, qy, qz);
+      const float fx = f.x, fy = f.y, fz = f.z;
       if ((mx >= 0.f && fx > hx) || (mx <= 0.f && fx < lo) || (my >= 0.f && fy > hy) || (my <= 0.f && fy < lo) ||
           (mz >= 0.f && fz > hz) || (mz <= 0.f && fz < lo))
       {
@@ -254,12 +220,7 @@ __device__ inline int cast_ray_kd(const LikGrid& g, const KdRayParams& k, const 
       *hit = id;
       status = 3;
       if (sin_ang > bp.sin_total_ref)
-      {
-        const double ddx = static_cast<double>(e.x - m.x), ddy = static_cast<double>(e.y - m.y),
-                     ddz = static_cast<double>(e.z - m.z);
-        const float distance_from_point_sq = static_cast<float>(ddx * ddx + ddy * ddy + ddz * ddz);
-        status = distance_from_point_sq < bp.hit_range_sq ? 1 : 0;
-      }
+        status = beam_hit_or_short(bp, e, Vec3f{ m.x, m.y, m.z });
       break;
     }
     ++count;
@@ -268,8 +229,8 @@ __device__ inline int cast_ray_kd(const LikGrid& g, const KdRayParams& k, const 
   return status;
 }
 
-// One lane per (particle, beam point), rays of a particle next to each other — beam_kernel's layout and its penalty counters
-// (beam_kernels.h:beam_body): the kernels behind it (beam_finalize_kernel or pf::measure's first) do not know which caster ran.
+// One lane per (particle, beam point), rays of a particle next to each other: beam_kernel's frame (beam_kernels.h:beam_body)
+// around this caster — the kernels behind it (beam_finalize_kernel or pf::measure's first) do not know which caster ran.
 __global__ __launch_bounds__(256) void beam_kd_kernel(const float* __restrict__ pose7, const float4* __restrict__ scan, int n_b,
                                                       const float4* __restrict__ origins, long long n_rays, LikGrid g,
                                                       KdRayParams k, BeamParams bp, unsigned* __restrict__ penalty_count)
@@ -291,28 +252,13 @@ __global__ __launch_bounds__(256) void beam_kd_kernel(const float* __restrict__ 
     const float* ps = pose7 + 7 * p;
     const Vec3f pos = { ps[0], ps[1], ps[2] };
     const Quat raw = { ps[3], ps[4], ps[5], ps[6] };
-    const Quat rot = qnormalized(raw);
-    const Vec3f end = vadd(qrot(rot, Vec3f{ v.x, v.y, v.z }), pos);  // beam.cpp:139 (transform)
+    const Vec3f end = beam_ray_end(pos, qnormalized(raw), Vec3f{ v.x, v.y, v.z });
     const float4 og = origins[__float_as_uint(v.w)];
-    const Vec3f begin = vadd(pos, qrot(raw, Vec3f{ og.x, og.y, og.z }));  // beam.cpp:145: s.pos_ + s.rot_ * origin
+    const Vec3f begin = beam_ray_begin(pos, raw, Vec3f{ og.x, og.y, og.z });
     int hit;
-    const int status = cast_ray_kd(g, k, bp, begin, end, &hit);
-    penalised = (status == 0) || (!bp.short_only && (status == 2));  // beam.cpp:146
+    penalised = beam_penalised(bp, cast_ray_kd(g, k, bp, begin, end, &hit));
   }
-  // per work-group counts in LDS for the first two particles of its rays, one global atomic each (see beam_body)
-  const int rel = static_cast<int>(p - p0);
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-  {
-    const unsigned long long m = __ballot(penalised && rel == s);
-    if (m != 0ull && (threadIdx.x & 63) == 0)
-      atomicAdd(&block_count[s], static_cast<unsigned>(__popcll(m)));
-  }
-  if (penalised && rel >= 2)
-    atomicAdd(&penalty_count[p], 1u);
-  __syncthreads();
-  if (threadIdx.x < 2 && block_count[threadIdx.x] != 0u)
-    atomicAdd(&penalty_count[p0 + threadIdx.x], block_count[threadIdx.x]);
+  beam_count_penalised(penalised, p, p0, block_count, penalty_count);
 }
 
 // LidarMeasurementModelBeam::getBeamStatus for explicit rays with the kd-tree caster (debug-marker path, src/mcl_3dl.cpp:471-478).

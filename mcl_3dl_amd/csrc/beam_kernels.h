@@ -1,4 +1,7 @@
-// beam_kernels.h — beam model (R6/R7/R8): the DDA ray walk and its kernels.
+// beam_kernels.h — beam model (R6/R7/R8): the DDA ray walk and its kernels, and the steps of the model around a caster's walk,
+// each stated once for every kernel that runs it (beam_kd_kernels.h, update_kernels.h, pf_kernels.h): a ray's ends (beam_ray_begin, beam_ray_end),
+// HIT / SHORT, the penalty rule, the per-work-group penalty count behind the
+// casts (beam_count_penalised) and the score of a count (beam_score).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,6 +68,15 @@ __device__ inline void to_index(const DdaGrid& g, const Vec3f p, int& ix, int& i
   ix = static_cast<int>(static_cast<double>(p.x - g.min_x) / g.grid);
   iy = static_cast<int>(static_cast<double>(p.y - g.min_y) / g.grid);
   iz = static_cast<int>(static_cast<double>(p.z - g.min_z) / g.grid);
+}
+
+// getBeamStatus, beam.cpp:176-186: HIT (1) when the measured end point e lies within hit_range of the collided map point m,
+// SHORT (0) otherwise
+__device__ inline int beam_hit_or_short(const BeamParams& bp, const Vec3f e, const Vec3f m)
+{
+  const double ddx = static_cast<double>(e.x - m.x), ddy = static_cast<double>(e.y - m.y), ddz = static_cast<double>(e.z - m.z);
+  const float distance_from_point_sq = static_cast<float>(ddx * ddx + ddy * ddy + ddz * ddz);
+  return distance_from_point_sq < bp.hit_range_sq ? 1 : 0;
 }
 
 // The walk from a begin point that lies within the map and whose voxel (bx, by, bz) = toIndex(begin) is known.
@@ -262,12 +274,7 @@ __device__ inline int cast_ray_from(const DdaGrid& g, const BeamParams& bp, Vec3
       continue;
     *hit = hit_index;
     if (1.0f > bp.sin_total_ref)  // DDA always reports sin_angle_ = 1.0 (raycast_using_dda.h:152)
-    {
-      const double ddx = static_cast<double>(e_org.x - cp.x), ddy = static_cast<double>(e_org.y - cp.y),
-                   ddz = static_cast<double>(e_org.z - cp.z);
-      const float distance_from_point_sq = static_cast<float>(ddx * ddx + ddy * ddy + ddz * ddz);
-      return distance_from_point_sq < bp.hit_range_sq ? 1 : 0;
-    }
+      return beam_hit_or_short(bp, e_org, Vec3f{ cp.x, cp.y, cp.z });
     return 3;
   }
   return 2;
@@ -286,6 +293,32 @@ __device__ inline int cast_ray(const DdaGrid& g, const BeamParams& bp, Vec3f b, 
   return cast_ray_from<STATS, TRACE, OVERLAY>(g, bp, b, bx, by, bz, e_org, hit, st_steps, st_occ, st_tested, tr);
 }
 
+// A ray's ends. The measured point v is transformed by the particle's pose with the NORMALISED quaternion (beam.cpp:139,
+// State6DOF::transform); the ray begins at s.pos_ + s.rot_ * origin with the RAW one (beam.cpp:145).
+__device__ inline Vec3f beam_ray_end(const Vec3f pos, const Quat rot_normalised, const Vec3f v)
+{
+  return vadd(qrot(rot_normalised, v), pos);
+}
+__device__ inline Vec3f beam_ray_begin(const Vec3f pos, const Quat raw, const Vec3f origin)
+{
+  return vadd(pos, qrot(raw, origin));
+}
+// beam.cpp:146: the statuses that cost a particle a factor of beam_likelihood_
+__device__ inline bool beam_penalised(const BeamParams& bp, int status)
+{
+  return (status == 0) || (!bp.short_only && (status == 2));
+}
+
+// score_beam = beam_likelihood_^count by `count` float multiplications (pow_table, built on the host the same way: beam.cpp:148),
+// then the clamp of :151-152
+__device__ inline float beam_score(const float* __restrict__ pow_table, unsigned count, float beam_likelihood_min)
+{
+  float s = pow_table[count];
+  if (s < beam_likelihood_min)
+    s = beam_likelihood_min;
+  return s;
+}
+
 // Everything about a ray that depends only on (particle, origin): all N_b rays of a particle share it, so a small
 // kernel computes it once instead of every ray repeating a quaternion normalisation, a rotation and three
 // double-precision divisions. Same expressions, same order: same bits.
@@ -297,14 +330,14 @@ struct BeamOrigin
   float4 pos;    // particle position
 };
 
-// what depends only on (particle, origin): beam.cpp:139 / :145 and the begin voxel
+// what depends only on (particle, origin): the normalised rotation, the begin point and its voxel
 __device__ inline BeamOrigin make_beam_origin(const float* __restrict__ pose7, long long p, const float4 og, const DdaGrid& g)
 {
   const float* ps = pose7 + 7 * p;
   const Vec3f pos = { ps[0], ps[1], ps[2] };
   const Quat raw = { ps[3], ps[4], ps[5], ps[6] };
   const Quat rot = qnormalized(raw);
-  const Vec3f begin = vadd(pos, qrot(raw, Vec3f{ og.x, og.y, og.z }));
+  const Vec3f begin = beam_ray_begin(pos, raw, Vec3f{ og.x, og.y, og.z });
   BeamOrigin r;
   r.rot = make_float4(rot.x, rot.y, rot.z, rot.w);
   const bool within = point_within_map(g, begin);
@@ -331,14 +364,41 @@ __global__ void beam_origin_kernel(const float* __restrict__ pose7, int n_p, con
   out[t] = make_beam_origin(pose7, p, origins[o], g);
 }
 
-// One lane per (particle, beam point).  scan_beam.w = origin index (PointXYZIL::label of the scan point).
+// Penalised rays are counted per particle. Thousands of rays of one particle bumping one global counter serialise in
+// L2 (same cache line), so a work-group first counts in LDS (block_count, zeroed behind a barrier before the rays were cast) for
+// the (at most two, when N_b >= 256) particles its rays start with — one ballot + popcount per wavefront — and issues one global
+// atomic per particle at the end. p = the lane's particle, p0 = the work-group's first.
+__device__ __forceinline__ void beam_count_penalised(bool penalised, long long p, long long p0, unsigned* block_count,
+                                                     unsigned* __restrict__ penalty_count)
+{
+  const int rel = static_cast<int>(p - p0);  // >= 0; small N_b puts many particles in one work-group
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+  {
+    const unsigned long long m = __ballot(penalised && rel == s);
+    if (m != 0ull && (threadIdx.x & 63) == 0)
+      atomicAdd(&block_count[s], static_cast<unsigned>(__popcll(m)));
+  }
+  if (penalised && rel >= 2)
+    atomicAdd(&penalty_count[p], 1u);
+  __syncthreads();
+  if (threadIdx.x < 2 && block_count[threadIdx.x] != 0u)
+    atomicAdd(&penalty_count[p0 + threadIdx.x], block_count[threadIdx.x]);
+}
+
+// The frame of every beam kernel: one lane per (particle, beam point), rays of a particle next to each other, BLOCK rays per
+// work-group (its thread count); the work-group's two LDS counters are zeroed behind a barrier in front of the cast and
+// beam_count_penalised is the frame's tail. (The head stands in beam_body and in beam_kd_kernel, not in a function of its own:
+// as one, the DDA kernels' instruction order changed and C3's beam group measured 0.2 - 0.3 us slower,
+// profiles/beam_cell_once_ab.txt.)
+// The DDA caster in that frame. scan_beam.w = origin index (PointXYZIL::label of the scan point).
 // prepared != nullptr: the per-(particle, origin) table of beam_origin_kernel ([n_p][n_o]); nullptr: every ray computes
 // its own begin point (small launches, where one more kernel launch costs more than it saves). (Round 6 measured a third form —
 // every work-group prepares the entries of ITS particles in LDS, no launch, no trip through memory — level at C3 and 4.6 % slower
 // at the C5 shard: one or two lanes computing while four wavefronts wait cost more than a 64-byte load: profiles/r06q_beam_tail_ab.txt.)
 // (the body as a device function of the work-group's index: beam_kernel is it with blockIdx.x; lik_beam_kernel, update_kernels.h,
 // interleaves it with the tiled likelihood kernel's work-groups in one launch)
-// (BLOCK: rays per work-group = its thread count; 256 for beam_kernel, 64 where the launch it rides in has 64-thread work-groups)
+// (BLOCK: 256 for beam_kernel, 64 where the launch it rides in has 64-thread work-groups)
 template <bool STATS, bool OVERLAY = true, int BLOCK = 256>
 __device__ __forceinline__ void beam_body(const long long block_index, const float* __restrict__ pose7,
                                           const float4* __restrict__ scan, int n_b, const float4* __restrict__ origins,
@@ -346,12 +406,9 @@ __device__ __forceinline__ void beam_body(const long long block_index, const flo
                                           unsigned* __restrict__ penalty_count, RayStats* __restrict__ stats,
                                           const BeamOrigin* __restrict__ prepared, int n_o)
 {
+  unsigned st_steps = 0, st_occ = 0, st_tested = 0;
   const long long ray0 = block_index * BLOCK;
   const long long ray = ray0 + threadIdx.x;
-  unsigned st_steps = 0, st_occ = 0, st_tested = 0;
-  // Penalised rays are counted per particle. Thousands of rays of one particle bumping one global counter serialise in
-  // L2 (same cache line), so a work-group first counts in LDS for the (at most two, when N_b >= 256) particles its 256
-  // rays start with — one ballot + popcount per wavefront — and issues one global atomic per particle at the end.
   __shared__ unsigned block_count[2];
   if (threadIdx.x < 2)
     block_count[threadIdx.x] = 0u;
@@ -368,39 +425,26 @@ __device__ __forceinline__ void beam_body(const long long block_index, const flo
     if (prepared)
     {
       const BeamOrigin bo = prepared[p * n_o + __float_as_uint(v.w)];
-      const Vec3f end = vadd(qrot(Quat{ bo.rot.x, bo.rot.y, bo.rot.z, bo.rot.w }, Vec3f{ v.x, v.y, v.z }),
-                             Vec3f{ bo.pos.x, bo.pos.y, bo.pos.z });  // beam.cpp:139 (transform)
-      status = 2;
+      const Vec3f end = beam_ray_end(Vec3f{ bo.pos.x, bo.pos.y, bo.pos.z }, Quat{ bo.rot.x, bo.rot.y, bo.rot.z, bo.rot.w },
+                                     Vec3f{ v.x, v.y, v.z });
+      status = 2;  // a begin outside the map: LONG
       if (bo.begin.w != 0.0f)
-        status = cast_ray_from<STATS, false, OVERLAY>(g, bp, Vec3f{ bo.begin.x, bo.begin.y, bo.begin.z }, bo.voxel.x, bo.voxel.y, bo.voxel.z,
-                                      end, &hit, st_steps, st_occ, st_tested);
+        status = cast_ray_from<STATS, false, OVERLAY>(g, bp, Vec3f{ bo.begin.x, bo.begin.y, bo.begin.z }, bo.voxel.x, bo.voxel.y,
+                                                      bo.voxel.z, end, &hit, st_steps, st_occ, st_tested);
     }
     else
     {
       const float* ps = pose7 + 7 * p;
       const Vec3f pos = { ps[0], ps[1], ps[2] };
       const Quat raw = { ps[3], ps[4], ps[5], ps[6] };
-      const Quat rot = qnormalized(raw);
-      const Vec3f end = vadd(qrot(rot, Vec3f{ v.x, v.y, v.z }), pos);  // beam.cpp:139 (transform)
+      const Vec3f end = beam_ray_end(pos, qnormalized(raw), Vec3f{ v.x, v.y, v.z });
       const float4 og = origins[__float_as_uint(v.w)];
-      const Vec3f begin = vadd(pos, qrot(raw, Vec3f{ og.x, og.y, og.z }));  // beam.cpp:145: s.pos_ + s.rot_ * origin
+      const Vec3f begin = beam_ray_begin(pos, raw, Vec3f{ og.x, og.y, og.z });
       status = cast_ray<STATS, false, OVERLAY>(g, bp, begin, end, &hit, st_steps, st_occ, st_tested);
     }
-    penalised = (status == 0) || (!bp.short_only && (status == 2));  // beam.cpp:146
+    penalised = beam_penalised(bp, status);
   }
-  const int rel = static_cast<int>(p - p0);  // >= 0; small N_b puts many particles in one work-group
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-  {
-    const unsigned long long m = __ballot(penalised && rel == s);
-    if (m != 0ull && (threadIdx.x & 63) == 0)
-      atomicAdd(&block_count[s], static_cast<unsigned>(__popcll(m)));
-  }
-  if (penalised && rel >= 2)
-    atomicAdd(&penalty_count[p], 1u);
-  __syncthreads();
-  if (threadIdx.x < 2 && block_count[threadIdx.x] != 0u)
-    atomicAdd(&penalty_count[p0 + threadIdx.x], block_count[threadIdx.x]);
+  beam_count_penalised(penalised, p, p0, block_count, penalty_count);
   if (STATS)
   {
     atomicAdd(&stats->steps, static_cast<unsigned long long>(st_steps));
@@ -420,19 +464,12 @@ __global__ __launch_bounds__(256) void beam_kernel(const float* __restrict__ pos
                             n_o);
 }
 
-// score_beam = beam_likelihood_^k by k float multiplications (table built on the host the same way), then the
-// clamp of beam.cpp:151-152.
 __global__ void beam_finalize_kernel(const unsigned* __restrict__ penalty_count, const float* __restrict__ pow_table,
                                      float beam_likelihood_min, float* __restrict__ out_beam, int n_p)
 {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p < n_p)
-  {
-    float s = pow_table[penalty_count[p]];
-    if (s < beam_likelihood_min)
-      s = beam_likelihood_min;
-    out_beam[p] = s;
-  }
+    out_beam[p] = beam_score(pow_table, penalty_count[p], beam_likelihood_min);
 }
 
 // LidarMeasurementModelBeam::getBeamStatus for explicit rays (debug-marker path, src/mcl_3dl.cpp:471-478).

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cell_grid.h"
 #include "cloud_keys.h"
 #include "device_math.h"
 #include "map_structs.h"
@@ -556,46 +557,6 @@ __global__ __launch_bounds__(256) void gather2_minmax_kernel(const float4* __res
 }
 
 // ---- matched / unmatched output (src/mcl_3dl.cpp:761-805) --------------------------------------------------------------
-// Nearest map point to the (already rescaled) query within `reach` cells of the cell-sorted map: min d2 below `best`
-// (initialised by the caller with r2), ties to the lowest map index. Shared with radius_search_kernel's logic.
-__device__ inline float cell_grid_nearest(const LikGrid& g, float qx, float qy, float qz, int reach, float best,
-                                          int& best_idx)
-{
-  const float fx = floorf((qx - g.ox) * g.inv_cell), fy = floorf((qy - g.oy) * g.inv_cell),
-              fz = floorf((qz - g.oz) * g.inv_cell);
-  if (!(fx >= -static_cast<float>(reach) && fy >= -static_cast<float>(reach) && fz >= -static_cast<float>(reach) &&
-        fx <= static_cast<float>(g.nx - 1 + reach) && fy <= static_cast<float>(g.ny - 1 + reach) &&
-        fz <= static_cast<float>(g.nz - 1 + reach)))
-    return best;
-  const int cx = static_cast<int>(fx), cy = static_cast<int>(fy), cz = static_cast<int>(fz);
-  const int x0 = max(cx - reach, 0), x1 = min(cx + reach, g.nx - 1);
-  const int y0 = max(cy - reach, 0), y1 = min(cy + reach, g.ny - 1);
-  const int z0 = max(cz - reach, 0), z1 = min(cz + reach, g.nz - 1);
-  if (x0 > x1)
-    return best;
-  for (int z = z0; z <= z1; ++z)
-    for (int y = y0; y <= y1; ++y)
-    {
-      const size_t row = (static_cast<size_t>(z) * g.ny + y) * g.nx;
-      const uint32_t s = g.cell_start[row + x0], e = g.cell_start[row + x1 + 1];
-      for (uint32_t k = s; k < e; ++k)
-      {
-        const float4 p = g.pts[k];
-        const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-        float d2 = dx * dx;
-        d2 = d2 + dy * dy;
-        d2 = d2 + dz * dz;
-        const int idx = static_cast<int>(__float_as_uint(p.w));
-        if (d2 < best || (d2 == best && best_idx >= 0 && idx < best_idx))
-        {
-          best = d2;
-          best_idx = idx;
-        }
-      }
-    }
-  return best;
-}
-
 // One thread per point of the down-sampled scan: transform by the expectation pose (State6DOF::transform), search with
 // unmatch_output_dist, classify: cls = 2 unmatched (no neighbour), 1 matched (sqdist < match_output_dist^2, compared in
 // double like the reference), 0 neither. The transformed point is written to out_xyz4.

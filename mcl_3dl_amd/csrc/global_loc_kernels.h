@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cell_grid.h"
 #include "cloud_kernels.h"
 #include "device_math.h"
 #include "map_structs.h"

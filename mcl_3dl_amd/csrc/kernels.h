@@ -3,9 +3,13 @@
 //   likelihood_kernels.h  likelihood-field model: per-particle / small-scan / tile-major (XCD-aware) kernels over the
 //                         candidate-voxel index (map_compiler.h) or the cell-sorted map; strict-order sums; radius search
 //   likelihood_chain_multi.h  strict_order = 3 for few particles on long scans: several tiles per work-group, a quarter of the hand-offs
-//   beam_kernels.h        beam model: one lane per ray, DDA walk through 4x4x4 occupancy bricks, point tests, penalty count
+//   cell_grid.h           the walk over the cell-sorted map, once: a query's cell, the block of cells within a reach, a row's run,
+//                         the nine rows around an interior cell, L2_Simple's distance with the tie rule, cell_grid_nearest (the
+//                         definition of the radius search)
+//   beam_kernels.h        beam model: one lane per ray, DDA walk through 4x4x4 occupancy bricks, point tests, penalty count; the
+//                         model's steps around a caster's walk, once (ray ends, penalty rule and count, HIT / SHORT, score)
 //   beam_kd_kernels.h     beam model with the reference's default caster (RaycastUsingKDTree): fixed-step march, exact nearest-
-//                         within-radius over the cell-sorted map at every step
+//                         within-radius over the cell-sorted map at every step (cell_grid.h's pieces, loads batched)
 //   pf_sums.h             pf::measure's arithmetic, once: the weight product, a particle's terms, the wavefront / block / 64-lane
 //                         reductions of {sum w, sum w ln w, max ratio, -min ratio}, the four statistics
 //   pf_kernels.h          pf::measure's kernels over pf_sums.h (split, behind the tiled kernel, fused; the float-order weight sum;
@@ -48,6 +52,7 @@
 // there is no dense contraction anywhere on this path, so no matrix-core code.
 #pragma once
 #include "map_structs.h"
+#include "cell_grid.h"
 #include "likelihood_kernels.h"
 #include "likelihood_chain_multi.h"
 #include "beam_kernels.h"

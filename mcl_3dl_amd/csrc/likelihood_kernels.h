@@ -1,5 +1,6 @@
 // likelihood_kernels.h — likelihood-field model (R3/R4/R5): nearest-neighbour queries against the three map indices, the
-// per-particle / small-scan / tile-major kernels, the strict-order sums and the stand-alone radius search.
+// per-particle / small-scan / tile-major kernels, the strict-order sums and the stand-alone radius search (the cell-sorted map's
+// walk and L2_Simple's distance: cell_grid.h).
 // Each of these exists once, for every kernel that runs it: the cooperative evaluations (eval_coop, eval_coop_first), the
 // deferred-overflow queue (defer_push / defer_flush around defer_drain), pose staging (stage_poses) and
 // the float chain's block mapping and link (xcd_row_map; chain_take / chain_add_row / chain_give) — the last four shared with
@@ -8,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cell_grid.h"
 #include "device_math.h"
 #include "float_chain.h"
 #include "map_structs.h"
@@ -23,36 +25,21 @@ namespace mcl3dl
 template <bool STATS>
 __device__ inline float nearest_d2(const LikGrid& g, float qx, float qy, float qz, unsigned& n_tested)
 {
-  // cell of the query; (q - o) * inv is the same float expression the host used to bin the map points
-  const float fx = floorf((qx - g.ox) * g.inv_cell);
-  const float fy = floorf((qy - g.oy) * g.inv_cell);
-  const float fz = floorf((qz - g.oz) * g.inv_cell);
+  const Vec3f f = cell_of(g, qx, qy, qz);
   float best = 3.0e38f;
   // written so that NaN coordinates fall through to "not found"
-  if (!(fx >= 1.0f && fy >= 1.0f && fz >= 1.0f && fx <= static_cast<float>(g.nx - 2) &&
-        fy <= static_cast<float>(g.ny - 2) && fz <= static_cast<float>(g.nz - 2)))
+  if (!(f.x >= 1.0f && f.y >= 1.0f && f.z >= 1.0f && f.x <= static_cast<float>(g.nx - 2) &&
+        f.y <= static_cast<float>(g.ny - 2) && f.z <= static_cast<float>(g.nz - 2)))
     return best;
-  const int cx = static_cast<int>(fx), cy = static_cast<int>(fy), cz = static_cast<int>(fz);
   uint32_t rs[9], re[9];
-#pragma unroll
-  for (int r = 0; r < 9; ++r)
-  {
-    const int dz = r / 3 - 1, dy = r % 3 - 1;
-    const size_t row = (static_cast<size_t>(cz + dz) * g.ny + (cy + dy)) * g.nx + cx;
-    rs[r] = g.cell_start[row - 1];
-    re[r] = g.cell_start[row + 2];
-  }
+  cell_rows_27(g, static_cast<int>(f.x), static_cast<int>(f.y), static_cast<int>(f.z), rs, re);
 #pragma unroll
   for (int r = 0; r < 9; ++r)
   {
     for (uint32_t k = rs[r]; k < re[r]; ++k)
     {
       const float4 p = g.pts[k];
-      // flann::L2_Simple<float>: ((0 + dx*dx) + dy*dy) + dz*dz
-      const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-      float d2 = dx * dx;
-      d2 = d2 + dy * dy;
-      d2 = d2 + dz * dz;
+      const float d2 = d2_simple(qx, qy, qz, p.x, p.y, p.z);
       best = d2 < best ? d2 : best;
       if (STATS)
         ++n_tested;
@@ -61,20 +48,8 @@ __device__ inline float nearest_d2(const LikGrid& g, float qx, float qy, float q
   return best;
 }
 
-// flann::L2_Simple<float>: ((0 + dx*dx) + dy*dy) + dz*dz, float, no contraction
-__device__ inline float d2_simple(float qx, float qy, float qz, float px, float py, float pz)
-{
-  const float dx = qx - px, dy = qy - py, dz = qz - pz;
-  float d2 = dx * dx;
-  d2 = d2 + dy * dy;
-  d2 = d2 + dz * dz;
-  return d2;
-}
-
-// ChunkedKdtree::radiusSearch(p, radius, id, sqdist, 1) as a stand-alone query (include/mcl_3dl/chunked_kdtree.h:217-237):
-// nearest map point with d2 < (float)(radius*radius) in the rescaled metric, ANY radius (the node also searches with
-// unmatch_output_dist, src/mcl_3dl.cpp:780, and global_localization_grid, :1058-1070). Walks the cell-sorted map over
-// ceil(radius / cell) cells each way: one contiguous run per (y,z) row. Ties in d2 resolve to the lowest map index.
+// mcl3dl_hip_radius_search: cell_grid_nearest (cell_grid.h) in the rescaled metric, for ANY radius (the node also searches with
+// unmatch_output_dist, src/mcl_3dl.cpp:780, and global_localization_grid, :1058-1070).
 __global__ void radius_search_kernel(const float* __restrict__ query_xyz, int n, LikGrid g, LikParams prm, float radius,
                                      float r2, int reach, int* __restrict__ out_index, float* __restrict__ out_sqdist)
 {
@@ -89,38 +64,8 @@ __global__ void radius_search_kernel(const float* __restrict__ query_xyz, int n,
     qz = qz * prm.wz;
   }
   (void)radius;
-  float best = r2;
   int best_idx = -1;
-  const float fx = floorf((qx - g.ox) * g.inv_cell), fy = floorf((qy - g.oy) * g.inv_cell),
-              fz = floorf((qz - g.oz) * g.inv_cell);
-  // NaN / far-away queries: comparisons fail -> no neighbour
-  if (fx >= -static_cast<float>(reach) && fy >= -static_cast<float>(reach) && fz >= -static_cast<float>(reach) &&
-      fx <= static_cast<float>(g.nx - 1 + reach) && fy <= static_cast<float>(g.ny - 1 + reach) &&
-      fz <= static_cast<float>(g.nz - 1 + reach))
-  {
-    const int cx = static_cast<int>(fx), cy = static_cast<int>(fy), cz = static_cast<int>(fz);
-    const int x0 = max(cx - reach, 0), x1 = min(cx + reach, g.nx - 1);
-    const int y0 = max(cy - reach, 0), y1 = min(cy + reach, g.ny - 1);
-    const int z0 = max(cz - reach, 0), z1 = min(cz + reach, g.nz - 1);
-    if (x0 <= x1)
-      for (int z = z0; z <= z1; ++z)
-        for (int y = y0; y <= y1; ++y)
-        {
-          const size_t row = (static_cast<size_t>(z) * g.ny + y) * g.nx;
-          const uint32_t s = g.cell_start[row + x0], e = g.cell_start[row + x1 + 1];
-          for (uint32_t k = s; k < e; ++k)
-          {
-            const float4 p = g.pts[k];
-            const float d2 = d2_simple(qx, qy, qz, p.x, p.y, p.z);
-            const int idx = static_cast<int>(__float_as_uint(p.w));
-            if (d2 < best || (d2 == best && best_idx >= 0 && idx < best_idx))
-            {
-              best = d2;
-              best_idx = idx;
-            }
-          }
-        }
-  }
+  const float best = cell_grid_nearest(g, qx, qy, qz, reach, r2, best_idx);
   out_index[i] = best_idx;
   if (out_sqdist)
     out_sqdist[i] = best_idx >= 0 ? best : -1.0f;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "beam_kernels.h"
 #include "device_math.h"
 #include "float_chain.h"
 #include "motion_kernels.h"
@@ -29,10 +30,10 @@ struct PfEmit
   float* beam;
 };
 
-// The beam model's last step (beam_kernels.h: beam_finalize_kernel — score = table[penalised rays], clamped from below, beam.cpp:
-// 146-152) for the kernel that needs the score next, instead of a launch of its own in front of it (round 6): penalty != null —
-// the score is formed from the count, written to beam_out, and the counter is ZEROED behind the read (the next update's beam kernel
-// counts from 0 without a launch that clears: mcl3dl_hip_ctx::penalty_clean_n).
+// The beam model's last step (beam_kernels.h: beam_score, as beam_finalize_kernel calls it) for the kernel that needs the score
+// next, instead of a launch of its own in front of it (round 6): penalty != null — the score is formed from the count, written
+// to beam_out, and the counter is ZEROED behind the read (the next update's beam kernel counts from 0 without a launch that
+// clears: mcl3dl_hip_ctx::penalty_clean_n).
 struct BeamCounts
 {
   unsigned* penalty;     // [n] penalised rays per particle
@@ -42,10 +43,8 @@ struct BeamCounts
 };
 __device__ inline float beam_score_from_count(const BeamCounts& bc, int i)
 {
-  float sb = bc.pow_table[bc.penalty[i]];
+  const float sb = beam_score(bc.pow_table, bc.penalty[i], bc.beam_likelihood_min);
   bc.penalty[i] = 0u;
-  if (sb < bc.beam_likelihood_min)
-    sb = bc.beam_likelihood_min;
   bc.beam_out[i] = sb;
   return sb;
 }

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cell_grid.h"
 #include "grid_kernels.h"
 #include "map_structs.h"
 #pragma clang fp contract(off)
@@ -103,11 +104,8 @@ __device__ inline void sn_accumulate_run(const float4* __restrict__ pts, uint32_
   for (uint32_t i = s; i < e; ++i)
   {
     const float4 p = pts[i];
-    const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-    float d2 = dx * dx;
-    d2 = d2 + dy * dy;
-    d2 = d2 + dz * dz;
-    if (d2 < r2)
+    // (neighbour minus query, where the searches subtract the other way round: the squares are the same floats)
+    if (d2_simple(p.x, p.y, p.z, q.x, q.y, q.z) < r2)
     {
       // q_j = (double)p_j - (double)p_i: exact
       const double ux = static_cast<double>(p.x) - qx, uy = static_cast<double>(p.y) - qy, uz = static_cast<double>(p.z) - qz;
@@ -123,15 +121,6 @@ __device__ inline void sn_accumulate_run(const float4* __restrict__ pts, uint32_
       ++m.cnt;
     }
   }
-}
-
-// run delimiters of the cells [x0, x1] of row (z, y); a row past y1 is an empty run
-__device__ inline void sn_row_run(const LikGrid& g, int z, int y, int y1, int x0, int x1, uint32_t& s, uint32_t& e)
-{
-  const bool in = y <= y1;
-  const size_t row = (static_cast<size_t>(z) * g.ny + (in ? y : y1)) * g.nx;
-  s = g.cell_start[row + x0];
-  e = in ? g.cell_start[row + x1 + 1] : s;
 }
 
 // One lane per point, taken in CELL-SORTED order k (the lanes of a wavefront sit in the same few cells and walk the same
@@ -152,25 +141,20 @@ __global__ void __launch_bounds__(256) sampler_normal_weight_kernel(LikGrid g, l
     if (isfinite(q.x) && isfinite(q.y) && isfinite(q.z))
     {
       // the cell the grid's key kernel put this point into (the same expression), and the block of cells around it
-      int cx = static_cast<int>(floorf((q.x - g.ox) * g.inv_cell));
-      int cy = static_cast<int>(floorf((q.y - g.oy) * g.inv_cell));
-      int cz = static_cast<int>(floorf((q.z - g.oz) * g.inv_cell));
-      cx = min(max(cx, 0), g.nx - 1);
-      cy = min(max(cy, 0), g.ny - 1);
-      cz = min(max(cz, 0), g.nz - 1);
-      const int x0 = max(cx - prm.reach, 0), x1 = min(cx + prm.reach, g.nx - 1);
-      const int y0 = max(cy - prm.reach, 0), y1 = min(cy + prm.reach, g.ny - 1);
-      const int z0 = max(cz - prm.reach, 0), z1 = min(cz + prm.reach, g.nz - 1);
-      for (int z = z0; z <= z1; ++z)
-        for (int yb = y0; yb <= y1; yb += 5)
+      // (clamped like the key kernel's, in front of the block's own clamping)
+      const Vec3f f = cell_of(g, q.x, q.y, q.z);
+      const CellBlock b = cell_block(g, min(max(static_cast<int>(f.x), 0), g.nx - 1), min(max(static_cast<int>(f.y), 0), g.ny - 1),
+                                     min(max(static_cast<int>(f.z), 0), g.nz - 1), prm.reach);
+      for (int z = b.z0; z <= b.z1; ++z)
+        for (int yb = b.y0; yb <= b.y1; yb += 5)
         {
           // the run delimiters of up to five rows of this layer together (reach 1: three rows, reach 2: five), then their points
           uint32_t s0, e0, s1, e1, s2, e2, s3, e3, s4, e4;
-          sn_row_run(g, z, yb, y1, x0, x1, s0, e0);
-          sn_row_run(g, z, yb + 1, y1, x0, x1, s1, e1);
-          sn_row_run(g, z, yb + 2, y1, x0, x1, s2, e2);
-          sn_row_run(g, z, yb + 3, y1, x0, x1, s3, e3);
-          sn_row_run(g, z, yb + 4, y1, x0, x1, s4, e4);
+          cell_row_run(g, z, yb, b.y1, b.x0, b.x1, s0, e0);
+          cell_row_run(g, z, yb + 1, b.y1, b.x0, b.x1, s1, e1);
+          cell_row_run(g, z, yb + 2, b.y1, b.x0, b.x1, s2, e2);
+          cell_row_run(g, z, yb + 3, b.y1, b.x0, b.x1, s3, e3);
+          cell_row_run(g, z, yb + 4, b.y1, b.x0, b.x1, s4, e4);
           sn_accumulate_run(g.pts, s0, e0, q, prm.r2, m);
           sn_accumulate_run(g.pts, s1, e1, q, prm.r2, m);
           sn_accumulate_run(g.pts, s2, e2, q, prm.r2, m);

@@ -2,8 +2,8 @@
 // thousand particles, N_s <= 2048 likelihood points, N_b <= 256 beam points; parameters.h:68,98 default to 64 x 96 + 3):
 // there the update is launch-bound — three to five launches of ~4 us around ~10 us of work.
 //
-//   work-group p  = particle p: likelihood score (lik_particle — the code of likelihood_kernel), beam score (cast_ray —
-//                   the code of beam_kernel; penalty count -> power table -> clamp), results written to out_lik / _ratio / _beam
+//   work-group p  = particle p: likelihood score (lik_particle, as likelihood_kernel calls it), beam score (beam_kernels.h:
+//                   beam_ray_*, cast_ray, beam_penalised, beam_score), results written to out_lik / _ratio / _beam
 //   256 particles = one "virtual block" of pf::measure's split form (pf_partial_kernel's 256-thread blocks): the LAST of
 //                   its work-groups to finish (an arrival ticket) computes that block's partial (pf_sums.h: the terms, the
 //                   wavefront reduction and pf_block_combine, as pf_partial_kernel calls them)
@@ -188,13 +188,12 @@ __global__ __launch_bounds__(BLOCK) void update_small_kernel(UpdateSmallArgs a)
       if (i < a.n_b)
       {
         const float4 v = a.scan_beam[i];
-        const Vec3f end = vadd(qrot(rot, Vec3f{ v.x, v.y, v.z }), pos);  // beam.cpp:139 (transform)
         const float4 og = a.origins[__float_as_uint(v.w)];
-        const Vec3f begin = vadd(pos, qrot(raw, Vec3f{ og.x, og.y, og.z }));  // beam.cpp:145: s.pos_ + s.rot_ * origin
+        const Vec3f end = beam_ray_end(pos, rot, Vec3f{ v.x, v.y, v.z });
+        const Vec3f begin = beam_ray_begin(pos, raw, Vec3f{ og.x, og.y, og.z });
         int hit;
         unsigned s0 = 0, s1 = 0, s2 = 0;
-        const int status = cast_ray<false, false, false>(a.dg, a.bp, begin, end, &hit, s0, s1, s2);
-        penalised = (status == 0) || (!a.bp.short_only && (status == 2));  // beam.cpp:146
+        penalised = beam_penalised(a.bp, cast_ray<false, false, false>(a.dg, a.bp, begin, end, &hit, s0, s1, s2));
       }
       const unsigned long long m = __ballot(penalised);
       if (m != 0ull && lane == 0)
@@ -202,12 +201,7 @@ __global__ __launch_bounds__(BLOCK) void update_small_kernel(UpdateSmallArgs a)
     }
     __syncthreads();
     if (threadIdx.x == 0)
-    {
-      float s = a.pow_table[s_pen];  // beam_likelihood_^k by k float multiplications (beam.cpp:148)
-      if (s < a.bp.beam_likelihood_min)
-        s = a.bp.beam_likelihood_min;  // :151-152
-      beam = s;
-    }
+      beam = beam_score(a.pow_table, s_pen, a.bp.beam_likelihood_min);
   }
   if (threadIdx.x == 0)
   {
@@ -318,7 +312,7 @@ __global__ __launch_bounds__(BLOCK) void update_small_kernel(UpdateSmallArgs a)
 // traversal waits on dependent loads (VALU issue 0.52 alone), the tiled kernel on the L2's request rate (0.61 alone), and what one
 // leaves idle the other uses. (Two streams do not give this: the second kernel's work-groups only get the slots the first one's
 // free at its end.) Rounds are multiples of eight blocks, so a tiled work-group keeps the XCD its index is congruent to
-// (likelihood_tiled_body's tile -> XCD mapping). Each work-group runs exactly the code of its own kernel: same bits.
+// (likelihood_tiled_body's tile -> XCD mapping). Each work-group runs its own kernel's body: same bits.
 struct LikBeamArgs
 {
   // tiled likelihood kernel (likelihood_tiled_body<16, 2, 8, true, DEFER, false>)
