@@ -41,8 +41,8 @@ namespace
 // the checks and the device buffers ahead of scan_finish's index buffer: [error, pad x3][idx_lik n_s][idx_beam n_b]
 int scan_finish_prepare(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b)
 {
-  if (n_s > 0x7fffffffu || n_b > 0x7fffffffu)
-    return ctx->fail(-3, "scan too large");
+  if (const char* e = scan_size_error(n_s, n_b))
+    return ctx->fail(-3, "%s", e);
   HIP_TRY(hipSetDevice(ctx->device));
   TRY(ensure(ctx, ctx->sp_samp[0], sizeof(float4) * std::max<size_t>(n_s, 1)));
   TRY(ensure(ctx, ctx->sp_samp[1], sizeof(float4) * std::max<size_t>(n_b, 1)));
@@ -81,14 +81,7 @@ int scan_finish_launch(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b, const float*
     return ctx->fail(-3, "a beam point names an origin that was not given");
   if (state_home)
     *state_home = home[1];
-  ctx->sp_n_samp[0] = n_s;
-  ctx->sp_n_samp[1] = n_b;
-  if (n_b > ctx->pow_table_len)
-    ctx->pow_table_dirty = true;
-  ctx->n_s = n_s;
-  ctx->n_b = n_b;
-  ctx->n_o = n_o;
-  ctx->has_scan = true;
+  scan_installed(ctx, n_s, n_b, n_o, true);
   return 0;
 }
 }  // namespace
@@ -102,8 +95,8 @@ int mcl3dl_hip_scan_finish(mcl3dl_hip_ctx* ctx, const uint32_t* idx_lik, size_t 
     return ctx->fail(-5, "no prepared scan: call mcl3dl_hip_scan_begin first");
   if ((n_s && !idx_lik) || (n_b && (!idx_beam || !origins || n_o == 0)))
     return ctx->fail(-3, "null index / origin array");
-  if (n_s > 0x7fffffffu || n_b > 0x7fffffffu)
-    return ctx->fail(-3, "scan too large");
+  if (const char* e = scan_size_error(n_s, n_b))
+    return ctx->fail(-3, "%s", e);
   // the sampler draws from a non-empty cloud only (point_cloud_uniform_sampler.h:63-64 returns an empty cloud otherwise)
   if ((n_s && ctx->sp_n_clip[0] == 0) || (n_b && ctx->sp_n_clip[1] == 0))
     return ctx->fail(-3, "indices given for an empty clipped cloud");

@@ -265,22 +265,64 @@ int mcl3dl_hip_get_beam_raycast(mcl3dl_hip_ctx* ctx, int* mode)
   return 0;
 }
 
-// Host-side ordering of one update's scans (no device work): shared by the single-context upload and by a device group,
-// which orders once and pushes the same arrays to every GPU. Returns 0, or -3 with `err` filled.
-static int order_scan(std::string& err, const float* scan_lik_xyz, size_t n_s, const float* scan_beam_xyz,
-                      const uint32_t* scan_beam_origin, size_t n_b, const float* origins, size_t n_o, OrderedScan& o,
-                      bool presorted = false)
+// the raw scan of a host-buffer call, as the caller handed it over
+struct HostScan
 {
-  if ((n_s && !scan_lik_xyz) || (n_b && (!scan_beam_xyz || !origins || n_o == 0)))
+  const float* scan_lik_xyz;
+  size_t n_s;
+  const float* scan_beam_xyz;
+  const uint32_t* scan_beam_origin;
+  size_t n_b;
+  const float* origins;
+  size_t n_o;
+};
+
+// (point counts are 32-bit signed kernel arguments) null, or the error text
+static const char* scan_size_error(size_t n_s, size_t n_b)
+{
+  return (n_s > 0x7fffffffu || n_b > 0x7fffffffu) ? "scan too large" : nullptr;
+}
+
+// The argument checks of every route that takes a raw scan ("Scan intake"). Returns 0, or -3 with `err` filled.
+static int check_host_scan(std::string& err, const HostScan& s)
+{
+  if ((s.n_s && !s.scan_lik_xyz) || (s.n_b && (!s.scan_beam_xyz || !s.origins || s.n_o == 0)))
   {
     err = "null scan array";
     return -3;
   }
-  if (n_s > 0x7fffffffu || n_b > 0x7fffffffu)
+  if (const char* e = scan_size_error(s.n_s, s.n_b))
   {
-    err = "scan too large";
+    err = e;
     return -3;
   }
+  if (s.scan_beam_origin)
+    for (size_t i = 0; i < s.n_b; ++i)
+      if (s.scan_beam_origin[i] >= s.n_o)
+      {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "beam point %zu names origin %u but only %zu origins were given", i, s.scan_beam_origin[i], s.n_o);
+        err = buf;
+        return -3;
+      }
+  return 0;
+}
+
+// Large scans are ordered on the device (host_cloud.h:device_order_scans: raw points up, min / key / stable radix sort /
+// gather there — same keys, same order, same bits as the host ordering, which costs ~0.1 ms of one core at 16 k points);
+// small ones on the host, where a dozen launches would cost more than the sort. (A device group asks rank 0's options.)
+static bool scan_ordered_on_device(const Options& opt, size_t n_s, size_t n_b)
+{
+  return opt.scan_order_device > 0 && n_s + n_b >= static_cast<size_t>(opt.scan_order_device);
+}
+
+// Host-side ordering of one update's scans (no device work): shared by the single-context upload and by a device group,
+// which orders once and pushes the same arrays to every GPU. The keys are those of the device (cloud_keys.h). Returns 0, or -3
+// with `err` filled.
+static int order_scan(std::string& err, const HostScan& s, OrderedScan& o, bool presorted)
+{
+  TRY(check_host_scan(err, s));
+  const auto& [scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o] = s;
   // likelihood scan: spatial (Morton) order. The score is a sum, so the order only changes which lanes work together.
   std::vector<float4>& lik = o.lik;
   lik.resize(n_s);
@@ -309,18 +351,8 @@ static int order_scan(std::string& err, const float* scan_lik_xyz, size_t n_s, c
         mx[a] = std::max(mx[a], q[a]);
       }
     }
-    // Morton key (10 bits per axis, 0.25 m cells; the MCL3DL_MORTON_BITS most significant bits the extent can set: cloud_keys.h) + LSD radix sort
-    uint32_t cells = 0;
-    for (int a = 0; a < 3; ++a)
-    {
-      const float e = (mx[a] - mn[a]) * 4.0f;
-      const uint32_t c = (e >= 0.f) ? (e < 1023.f ? static_cast<uint32_t>(e) : 1023u) : 0u;
-      cells = std::max(cells, c);
-    }
-    uint32_t bits = 0;
-    while (bits < 32 && (cells >> bits) != 0)
-      ++bits;
-    const uint32_t drop = 3u * bits > MCL3DL_MORTON_BITS ? 3u * bits - MCL3DL_MORTON_BITS : 0u;
+    // Morton key + LSD radix sort
+    const uint32_t drop = morton_drop_bits(mn, mx);
     std::vector<uint32_t>& idx = o.perm;
     std::vector<uint32_t>&key = o.key, &key2 = o.key2, &idx2 = o.idx2;
     key.resize(n_s);
@@ -328,13 +360,7 @@ static int order_scan(std::string& err, const float* scan_lik_xyz, size_t n_s, c
     idx2.resize(n_s);
     for (size_t i = 0; i < n_s; ++i)
     {
-      uint32_t c[3];
-      for (int a = 0; a < 3; ++a)
-      {
-        const float f = (scan_lik_xyz[3 * i + a] - mn[a]) * 4.0f;
-        c[a] = (f >= 0.f) ? (f < 1023.f ? static_cast<uint32_t>(f) : 1023u) : 0u;
-      }
-      key[i] = static_cast<uint32_t>(morton3(c[0], c[1], c[2])) >> drop;
+      key[i] = morton_key(scan_lik_xyz[3 * i], scan_lik_xyz[3 * i + 1], scan_lik_xyz[3 * i + 2], mn) >> drop;
       idx[i] = static_cast<uint32_t>(i);
     }
     for (int pass = 0; pass < 3; ++pass)
@@ -367,21 +393,15 @@ static int order_scan(std::string& err, const float* scan_lik_xyz, size_t n_s, c
   beam.resize(n_b);
   if (n_b)
   {
-    std::vector<std::pair<float, uint32_t>>& keys = o.beam_keys;
+    // (key, index) pairs sorted as unsigned integers: a total order whatever the points hold — a NaN range goes behind every
+    // other, as on the device — with ties in the caller's order
+    std::vector<std::pair<uint32_t, uint32_t>>& keys = o.beam_keys;
     keys.resize(n_b);
     for (size_t i = 0; i < n_b; ++i)
     {
-      const uint32_t og = scan_beam_origin ? scan_beam_origin[i] : 0u;
-      if (og >= n_o)
-      {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "beam point %zu names origin %u but only %zu origins were given", i, og, n_o);
-        err = buf;
-        return -3;
-      }
-      const float dx = scan_beam_xyz[3 * i] - origins[3 * og], dy = scan_beam_xyz[3 * i + 1] - origins[3 * og + 1],
-                  dz = scan_beam_xyz[3 * i + 2] - origins[3 * og + 2];
-      keys[i] = { dx * dx + dy * dy + dz * dz, static_cast<uint32_t>(i) };
+      const float* og = origins + 3 * (scan_beam_origin ? scan_beam_origin[i] : 0u);
+      keys[i] = { range_key(scan_beam_xyz[3 * i], scan_beam_xyz[3 * i + 1], scan_beam_xyz[3 * i + 2], og[0], og[1], og[2]),
+                  static_cast<uint32_t>(i) };
     }
     std::sort(keys.begin(), keys.end());
     for (size_t k = 0; k < n_b; ++k)
@@ -427,64 +447,31 @@ static int push_scan(mcl3dl_hip_ctx* ctx, const OrderedScan& o, bool sync_at_end
   }
   if (sync_at_end)
     TRY(sync_stream(ctx));
-  if (n_b > ctx->pow_table_len)
-    ctx->pow_table_dirty = true;  // table[k] = beam_likelihood^k is a prefix property: a shorter scan reuses it
-  ctx->n_s = n_s;
-  ctx->n_b = n_b;
-  ctx->n_o = n_o;
-  ctx->has_scan = true;
+  scan_installed(ctx, n_s, n_b, n_o, false);
   return 0;
 }
-
-// the raw scan of a host-buffer call, as the caller handed it over
-struct HostScan
-{
-  const float* scan_lik_xyz;
-  size_t n_s;
-  const float* scan_beam_xyz;
-  const uint32_t* scan_beam_origin;
-  size_t n_b;
-  const float* origins;
-  size_t n_o;
-};
 
 static int upload_scan_impl(mcl3dl_hip_ctx* ctx, const HostScan& scan, bool sync_at_end)
 {
   if (!ctx)
     return -1;
-  const auto& [scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o] = scan;
-  // Large scans are ordered on the device (host_cloud.h:device_order_scans: raw points up, min / key / stable radix sort /
-  // gather there — same keys, same order, same bits as the host ordering, which costs ~0.1 ms of one core at 16 k points);
-  // small ones on the host, where a dozen launches would cost more than the sort.
-  if (ctx->opt.scan_order_device > 0 && n_s + n_b >= static_cast<size_t>(ctx->opt.scan_order_device))
+  std::string err;
+  if (scan_ordered_on_device(ctx->opt, scan.n_s, scan.n_b))
   {
-    if ((n_s && !scan_lik_xyz) || (n_b && (!scan_beam_xyz || !origins || n_o == 0)))
-      return ctx->fail(-3, "null scan array");
-    if (n_s > 0x7fffffffu || n_b > 0x7fffffffu)
-      return ctx->fail(-3, "scan too large");
-    if (scan_beam_origin)
-      for (size_t i = 0; i < n_b; ++i)
-        if (scan_beam_origin[i] >= n_o)
-          return ctx->fail(-3, "beam point %zu names origin %u but only %zu origins were given", i, scan_beam_origin[i], n_o);
+    if (check_host_scan(err, scan) != 0)
+      return ctx->fail(-3, "%s", err.c_str());
+    const size_t n_s = scan.n_s, n_b = scan.n_b;
     HIP_TRY(hipSetDevice(ctx->device));
     TRY(ensure(ctx, ctx->cl_err, sizeof(int)));
-    TRY(upload_cloud(ctx, scan_lik_xyz, nullptr, n_s, ctx->sp_samp[0], true));  // + the min corner of the Morton keys
-    TRY(upload_cloud(ctx, scan_beam_xyz, scan_beam_origin, n_b, ctx->sp_samp[1]));
-    TRY(device_order_scans(ctx, n_s, n_b, origins, n_o, n_s != 0, ctx->cl_err.as<int>()));
+    TRY(upload_cloud(ctx, scan.scan_lik_xyz, nullptr, n_s, ctx->sp_samp[0], true));  // + the min corner of the Morton keys
+    TRY(upload_cloud(ctx, scan.scan_beam_xyz, scan.scan_beam_origin, n_b, ctx->sp_samp[1]));
+    TRY(device_order_scans(ctx, n_s, n_b, scan.origins, scan.n_o, n_s != 0, ctx->cl_err.as<int>()));
     if (sync_at_end)
       TRY(sync_stream(ctx));
-    if (n_b > ctx->pow_table_len)
-      ctx->pow_table_dirty = true;
-    ctx->n_s = n_s;
-    ctx->n_b = n_b;
-    ctx->n_o = n_o;
-    ctx->has_scan = true;
-    ctx->sp_n_samp[0] = n_s;
-    ctx->sp_n_samp[1] = n_b;
+    scan_installed(ctx, n_s, n_b, scan.n_o, true);
     return 0;
   }
-  std::string err;
-  if (order_scan(err, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o, ctx->h_scan, ctx->opt.scan_presorted != 0) != 0)
+  if (order_scan(err, scan, ctx->h_scan, ctx->opt.scan_presorted != 0) != 0)
     return ctx->fail(-3, "%s", err.c_str());
   return push_scan(ctx, ctx->h_scan, sync_at_end);
 }
@@ -503,7 +490,7 @@ int mcl3dl_hip_scan_order_host(const float* scan_lik_xyz, size_t n_s, uint32_t* 
     return -3;
   std::string err;
   OrderedScan o;
-  if (order_scan(err, scan_lik_xyz, n_s, nullptr, nullptr, 0, nullptr, 0, o) != 0)
+  if (order_scan(err, HostScan{ scan_lik_xyz, n_s, nullptr, nullptr, 0, nullptr, 0 }, o, false) != 0)
     return -3;
   memcpy(order, o.perm.data(), sizeof(uint32_t) * n_s);
   return 0;
@@ -739,12 +726,9 @@ int stage_inputs(mcl3dl_hip_ctx* ctx, const float* pose, const float* extra, con
   auto& [scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o] = scan;
   if (!ctx->opt.update_stage || n_s > 0x0fffffffu || n_b > 0x0fffffffu || n_o > 4096 || n_p > 0x7fffffffu / 8)
     return 0;
-  if ((n_s && !scan_lik_xyz) || (n_b && (!scan_beam_xyz || !origins || n_o == 0)))
-    return ctx->fail(-3, "null scan array");
-  if (scan_beam_origin)
-    for (size_t i = 0; i < n_b; ++i)
-      if (scan_beam_origin[i] >= n_o)
-        return ctx->fail(-3, "beam point %zu names origin %u but only %zu origins were given", i, scan_beam_origin[i], n_o);
+  std::string err;
+  if (check_host_scan(err, scan) != 0)
+    return ctx->fail(-3, "%s", err.c_str());
   if (!origins)
     n_o = 0;
   // Whatever has to be (re)built lazily — the index after a map change, the DDA grid, the penalty table — is built NOW: a
@@ -871,18 +855,31 @@ int stage_inputs(mcl3dl_hip_ctx* ctx, const float* pose, const float* extra, con
     TRY(device_order_scans(ctx, n_s, n_b, nullptr, n_o, true, ctx->cl_err.as<int>()));
   }
   TRY(timing_end(ctx, ep));
-  // the context's scan state, as upload_scan_impl leaves it
-  if (n_b > ctx->pow_table_len)
-    ctx->pow_table_dirty = true;
-  ctx->n_s = n_s;
-  ctx->n_b = n_b;
-  ctx->n_o = n_o;
-  ctx->has_scan = true;
-  ctx->sp_n_samp[0] = n_s;
-  ctx->sp_n_samp[1] = n_b;
+  scan_installed(ctx, n_s, n_b, n_o, true);
   if (pose)
     ctx->poses_set(n_p);
   return 1;
+}
+
+// n poses of a host array into ctx->pose. The mark is withdrawn BEFORE the buffer changes and set once it holds the new poses
+// (host_context.h:poses_set).
+int poses_upload(mcl3dl_hip_ctx* ctx, const float* pose, size_t n)
+{
+  ctx->poses_set(0);
+  TRY(ensure(ctx, ctx->pose, sizeof(float) * 7 * n));
+  TRY(h2d(ctx, ctx->pose.p, pose, sizeof(float) * 7 * n));
+  ctx->poses_set(n);
+  return 0;
+}
+
+// the models' three result arrays { lik, match ratio, beam }, n floats each, home to `off` of the caller's arrays (null: not
+// wanted); in the caller's memory after sync_stream()
+int models_home(mcl3dl_hip_ctx* ctx, float* const user[3], const float* const dev[3], size_t off, size_t n)
+{
+  for (int k = 0; k < 3; ++k)
+    if (user[k])
+      TRY(d2h(ctx, user[k] + off, dev[k], sizeof(float) * n));
+  return 0;
 }
 
 // page-locked room for the two models' three result arrays (null: no zero-copy, or the staging memory is used up)
@@ -912,9 +909,27 @@ int deliver_models(mcl3dl_hip_ctx* ctx, size_t n_p, float* out_lik, float* out_m
     HIP_TRY(hipGetLastError());
     return sync_stream(ctx, true);
   }
-  for (int k = 0; k < 3; ++k)
-    if (user[k])
-      TRY(d2h(ctx, user[k], dev.part(1 + k), dev.fb));
+  const float* const parts[3] = { dev.part(1), dev.part(2), dev.part(3) };
+  TRY(models_home(ctx, user, parts, 0, n_p));
+  return sync_stream(ctx);
+}
+
+// The general body of measure_batch behind the scan's installation: n poses (null: those an upload left in ctx->pose) through
+// both models with plain copies, the results to `off` of the caller's arrays — a context's whole batch, or a device group's shard.
+int measure_batch_general(mcl3dl_hip_ctx* ctx, const float* pose, size_t n, size_t off, float* out_lik, float* out_match_ratio,
+                          float* out_beam)
+{
+  TRY(ensure(ctx, ctx->lik, sizeof(float) * n));
+  TRY(ensure(ctx, ctx->ratio, sizeof(float) * n));
+  TRY(ensure(ctx, ctx->beam, sizeof(float) * n));
+  if (pose)
+    TRY(poses_upload(ctx, pose, n));
+  const bool lik_wanted = out_lik || out_match_ratio;
+  TRY(launch_measure(ctx, ctx->pose.as<float>(), n, lik_wanted ? ctx->lik.as<float>() : nullptr,
+                     lik_wanted ? ctx->ratio.as<float>() : nullptr, out_beam ? ctx->beam.as<float>() : nullptr));
+  float* const user[3] = { out_lik, out_match_ratio, out_beam };
+  const float* const dev[3] = { ctx->lik.as<float>(), ctx->ratio.as<float>(), ctx->beam.as<float>() };
+  TRY(models_home(ctx, user, dev, off, n));
   return sync_stream(ctx);
 }
 
@@ -1030,27 +1045,7 @@ int mcl3dl_hip_measure_batch(mcl3dl_hip_ctx* ctx, const float* pose, size_t n_p,
   if (staged)
     return deliver_models(ctx, n_p, out_lik, out_match_ratio, out_beam, models_block(ctx, n_p));
   TRY(upload_scan_impl(ctx, scan, false));
-  TRY(ensure(ctx, ctx->lik, sizeof(float) * n_p));
-  TRY(ensure(ctx, ctx->ratio, sizeof(float) * n_p));
-  TRY(ensure(ctx, ctx->beam, sizeof(float) * n_p));
-  if (pose)
-  {
-    ctx->poses_set(0);
-    TRY(ensure(ctx, ctx->pose, sizeof(float) * 7 * n_p));
-    TRY(h2d(ctx, ctx->pose.p, pose, sizeof(float) * 7 * n_p));
-    ctx->poses_set(n_p);
-  }
-  const bool lik_wanted = out_lik || out_match_ratio;
-  TRY(launch_measure(ctx, ctx->pose.as<float>(), n_p, lik_wanted ? ctx->lik.as<float>() : nullptr,
-                     lik_wanted ? ctx->ratio.as<float>() : nullptr, out_beam ? ctx->beam.as<float>() : nullptr));
-  if (out_lik)
-    TRY(d2h(ctx, out_lik, ctx->lik.p, sizeof(float) * n_p));
-  if (out_match_ratio)
-    TRY(d2h(ctx, out_match_ratio, ctx->ratio.p, sizeof(float) * n_p));
-  if (out_beam)
-    TRY(d2h(ctx, out_beam, ctx->beam.p, sizeof(float) * n_p));
-  TRY(sync_stream(ctx));
-  return 0;
+  return measure_batch_general(ctx, pose, n_p, 0, out_lik, out_match_ratio, out_beam);
 }
 
 // ---- the same batch, delivered in particle slices ------------------------------------------------------------------------
@@ -1196,14 +1191,11 @@ int mcl3dl_hip_measure_update(mcl3dl_hip_ctx* ctx, const float* pose, const floa
     return 0;
   }
   TRY(upload_scan_impl(ctx, scan, false));
-  TRY(ensure(ctx, ctx->pose, sizeof(float) * 7 * n_p));
   TRY(ensure(ctx, ctx->upd_block, UpdBlock::bytes(n_p)));
   TRY(ensure(ctx, ctx->extra, fb));
   TRY(ensure(ctx, ctx->partial4, sizeof(double) * 4));
   const UpdBlock dev(ctx->upd_block.p, n_p);
-  ctx->poses_set(0);
-  TRY(h2d(ctx, ctx->pose.p, pose, sizeof(float) * 7 * n_p));
-  ctx->poses_set(n_p);
+  TRY(poses_upload(ctx, pose, n_p));
   TRY(h2d(ctx, dev.part(0), weight_inout, fb));
   if (extra)
     TRY(h2d(ctx, ctx->extra.p, extra, fb));

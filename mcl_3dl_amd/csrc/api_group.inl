@@ -215,11 +215,10 @@ int mcl3dl_hip_group_measure_batch(mcl3dl_hip_group* g, const float* pose, size_
                                             origins, n_o, out_lik, out_match_ratio, out_beam);
     return rc ? g->fail_rank(rc, 0) : 0;
   }
-  const bool device_order = g->ctx[0]->opt.scan_order_device > 0 && n_s + n_b >= static_cast<size_t>(g->ctx[0]->opt.scan_order_device);
+  const bool device_order = scan_ordered_on_device(g->ctx[0]->opt, n_s, n_b);
   const HostScan scan{ scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o };
   std::string err;
-  if (!device_order &&
-      order_scan(err, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o, g->scan, g->ctx[0]->opt.scan_presorted != 0) != 0)
+  if (!device_order && order_scan(err, scan, g->scan, g->ctx[0]->opt.scan_presorted != 0) != 0)
     return g->fail(-3, "%s", err.c_str());
   if (pose)
     g->n_pose_uploaded = 0;
@@ -228,35 +227,15 @@ int mcl3dl_hip_group_measure_batch(mcl3dl_hip_group* g, const float* pose, size_
       [&](const Shard& s) -> int
       {
         mcl3dl_hip_ctx* ctx = s.ctx;
-        const size_t lo = s.lo, n = s.n;
         if (device_order)
           TRY(upload_scan_impl(ctx, scan, false));
         else
           TRY(push_scan(ctx, g->scan, false));
-        if (n == 0)
+        if (s.n == 0)
           return sync_stream(ctx);
-        if (pose)
-        {
-          ctx->poses_set(0);
-          TRY(ensure(ctx, ctx->pose, sizeof(float) * 7 * n));
-          TRY(h2d(ctx, ctx->pose.p, pose + 7 * lo, sizeof(float) * 7 * n));
-          ctx->poses_set(n);
-        }
-        else if (ctx->n_pose_uploaded != n)
-          return ctx->fail(-3, "uploaded pose shard holds %zu poses, not %zu", ctx->n_pose_uploaded, n);
-        TRY(ensure(ctx, ctx->lik, sizeof(float) * n));
-        TRY(ensure(ctx, ctx->ratio, sizeof(float) * n));
-        TRY(ensure(ctx, ctx->beam, sizeof(float) * n));
-        const bool lik_wanted = out_lik || out_match_ratio;
-        TRY(launch_measure(ctx, ctx->pose.as<float>(), n, lik_wanted ? ctx->lik.as<float>() : nullptr,
-                           lik_wanted ? ctx->ratio.as<float>() : nullptr, out_beam ? ctx->beam.as<float>() : nullptr));
-        if (out_lik)
-          TRY(d2h(ctx, out_lik + lo, ctx->lik.p, sizeof(float) * n));
-        if (out_match_ratio)
-          TRY(d2h(ctx, out_match_ratio + lo, ctx->ratio.p, sizeof(float) * n));
-        if (out_beam)
-          TRY(d2h(ctx, out_beam + lo, ctx->beam.p, sizeof(float) * n));
-        return sync_stream(ctx);
+        if (!pose && ctx->n_pose_uploaded != s.n)
+          return ctx->fail(-3, "uploaded pose shard holds %zu poses, not %zu", ctx->n_pose_uploaded, s.n);
+        return measure_batch_general(ctx, pose ? pose + 7 * s.lo : nullptr, s.n, s.lo, out_lik, out_match_ratio, out_beam);
       }));
   if (pose)
     g->n_pose_uploaded = n_p;
@@ -503,9 +482,7 @@ int update_phase_a(GroupUpdate& u, const Shard& s)
       std::call_once(u.host_order_once,
                      [&]
                      {
-                       u.host_ordered = order_scan(u.host_order_error, u.scan.scan_lik_xyz, u.scan.n_s, u.scan.scan_beam_xyz,
-                                                   u.scan.scan_beam_origin, u.scan.n_b, u.scan.origins, u.scan.n_o, g->scan,
-                                                   g->ctx[0]->opt.scan_presorted != 0) == 0;
+                       u.host_ordered = order_scan(u.host_order_error, u.scan, g->scan, g->ctx[0]->opt.scan_presorted != 0) == 0;
                      });
       if (!u.host_ordered)
         return ctx->fail(-3, "%s", u.host_order_error.c_str());
@@ -522,10 +499,8 @@ int update_phase_a(GroupUpdate& u, const Shard& s)
   TRY(ensure(ctx, ctx->extra, fb));
   if (!resident && !staged)
   {
-    TRY(ensure(ctx, ctx->pose, sizeof(float) * 7 * n));
     TRY(ensure(ctx, ctx->weightb, fb));
-    TRY(h2d(ctx, ctx->pose.p, u.pose + 7 * lo, sizeof(float) * 7 * n));
-    ctx->poses_set(n);
+    TRY(poses_upload(ctx, u.pose + 7 * lo, n));
     TRY(h2d(ctx, ctx->weightb.p, u.out.weight + lo, fb));
   }
   float* d_w = resident ? ctx->gs_weight.as<float>() : (staged ? staged_weights(ctx, n) : ctx->weightb.as<float>());
@@ -586,12 +561,9 @@ int update_phase_b(GroupUpdate& u, const Shard& s)
   if (out.weight)
     TRY(d2h(ctx, out.weight + lo, d_w, fb));
   TRY(d2h(ctx, &u.stats[4 * s.r], ctx->stats4.p, sizeof(float) * 4));
-  if (out.lik)
-    TRY(d2h(ctx, out.lik + lo, ctx->lik.p, fb));
-  if (out.match_ratio)
-    TRY(d2h(ctx, out.match_ratio + lo, ctx->ratio.p, fb));
-  if (out.beam)
-    TRY(d2h(ctx, out.beam + lo, ctx->beam.p, fb));
+  float* const user[3] = { out.lik, out.match_ratio, out.beam };
+  const float* const dev[3] = { ctx->lik.as<float>(), ctx->ratio.as<float>(), ctx->beam.as<float>() };
+  TRY(models_home(ctx, user, dev, lo, n));
   return sync_stream(ctx);
 }
 
@@ -622,7 +594,7 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
   }
   const size_t N = static_cast<size_t>(g->n());
   GroupUpdate u{ g, resident, prepared, pose, extra, n_p, scan, out };
-  u.device_order = g->ctx[0]->opt.scan_order_device > 0 && scan.n_s + scan.n_b >= static_cast<size_t>(g->ctx[0]->opt.scan_order_device);
+  u.device_order = scan_ordered_on_device(g->ctx[0]->opt, scan.n_s, scan.n_b);
   u.device_extra = resident && !extra && g->odom_sigma > 0.f;
   if (u.device_extra)
     normal_likelihood_constants(g->odom_sigma, &u.nd_a, &u.nd_sq2);

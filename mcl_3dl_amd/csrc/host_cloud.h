@@ -415,8 +415,8 @@ int scan_begin_common(mcl3dl_hip_ctx* ctx, size_t n, const float* leaf3, const f
 }
 
 // The two sampled clouds in ctx->sp_samp[0] (likelihood, n_s points) and ctx->sp_samp[1] (beam, n_b points, w = origin id)
-// -> the context's ordered scan buffers, on the device: the ordering api_core.inl:order_scan does on the host — 30-bit
-// Morton key from the cloud's minimum corner resp. squared range from the scan origin, stable sort — so both entry paths
+// -> the context's ordered scan buffers, on the device: the ordering api_core.inl:order_scan does on the host — the Morton
+// key from the cloud's minimum corner resp. the range key from the scan origin (cloud_keys.h, one statement for both sides), stable sort — so both entry paths
 // produce the same order and with it bit-identical results. Keys are made inside the sort's first pass and the points are
 // written by its last one. have_minmax: ctx->cl_minmax holds the min corner of sp_samp[0] already. Raises error flag 2
 // (*d_err, device memory) for a bad origin id.

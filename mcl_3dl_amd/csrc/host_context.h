@@ -37,7 +37,7 @@ struct OrderedScan
   std::vector<float4> lik, beam, origins;
   std::vector<uint32_t> perm;
   std::vector<uint32_t> key, key2, idx2;
-  std::vector<std::pair<float, uint32_t>> beam_keys;
+  std::vector<std::pair<uint32_t, uint32_t>> beam_keys;  // (range key's bits, index)
 };
 
 struct EventPair
@@ -456,6 +456,23 @@ int ensure_scan_block(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b, size_t n_o, s
     off += part[k];
   }
   return 0;
+}
+
+// The context now holds this update's ordered scans — the last step of every intake route ("Scan intake").
+// raw_in_samp: the route ordered them on the device, out of the raw points it left in sp_samp[].
+void scan_installed(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b, size_t n_o, bool raw_in_samp)
+{
+  if (n_b > ctx->pow_table_len)
+    ctx->pow_table_dirty = true;  // table[k] = beam_likelihood^k is a prefix property: a shorter scan reuses it
+  ctx->n_s = n_s;
+  ctx->n_b = n_b;
+  ctx->n_o = n_o;
+  ctx->has_scan = true;
+  if (raw_in_samp)
+  {
+    ctx->sp_n_samp[0] = n_s;
+    ctx->sp_n_samp[1] = n_b;
+  }
 }
 
 constexpr size_t STAGE_MAX_COPY = 4u << 20;  // larger copies go straight from / to the caller's (pageable) memory

@@ -149,23 +149,6 @@ void beam_refresh(mcl3dl_hip_ctx* ctx)
   ctx->pow_table_dirty = true;
 }
 
-// 3-D Morton key of a scan point (robot frame), 0.25 m cells: neighbouring lanes of a wavefront then gather from
-// neighbouring map cells.
-uint64_t morton3(uint32_t x, uint32_t y, uint32_t z)
-{
-  auto spread = [](uint64_t v)
-  {
-    v &= 0x1fffff;
-    v = (v | v << 32) & 0x1f00000000ffffULL;
-    v = (v | v << 16) & 0x1f0000ff0000ffULL;
-    v = (v | v << 8) & 0x100f00f00f00f00fULL;
-    v = (v | v << 4) & 0x10c30c30c30c30c3ULL;
-    v = (v | v << 2) & 0x1249249249249249ULL;
-    return v;
-  };
-  return spread(x) | (spread(y) << 1) | (spread(z) << 2);
-}
-
 // table[k] = score_beam after k penalised rays: `score_beam *= beam_likelihood_` repeated k times (beam.cpp:148), float. Built
 // for at least 1024 counts so that alternating scan sizes (the adapter launches the two models separately) do not rebuild it
 // every update.

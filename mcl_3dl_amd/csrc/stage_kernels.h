@@ -6,8 +6,8 @@
 //                       block after one copy) and leaves everything the update kernels need in device memory:
 //                         work-group 0   the likelihood scan: xyz -> float4, min corner, Morton keys (cloud_keys.h), stable LSD radix
 //                                        sort of (key, index) with the pairs exchanged through LDS, ordered points + the
-//                                        permutation written by the last pass                 (api_core.inl:order_scan)
-//                         work-group 1   the beam scan the same way, keyed by squared range from its origin
+//                                        permutation written by the last pass
+//                         work-group 1   the beam scan the same way, keyed by squared range from its origin (cloud_keys.h)
 //                         work-groups 2+ poses, prior weights and the odometry factor copied to their device arrays
 //                       Same keys, same stable order as host_cloud.h:device_order_scans (pack + min / max, key + count, three
 //                       count / scatter pairs: seven launches) and as the host ordering: bit-identical results on every path.

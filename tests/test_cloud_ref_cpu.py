@@ -2,7 +2,13 @@
 test_gpu_cloud_edges.py (tests/cloud_cases.py), so that the GPU tests do not rest on an unchecked reference:
   * voxel_grid and clip equal the compiled reference-backed oracle (pcl::VoxelGrid restated in oracle/shims, the reference's own
     filter() lambdas), array for array;
-  * morton_order equals mcl3dl_hip_scan_order_host (host library only), range_order a plain lexicographic sort."""
+  * morton_order equals mcl3dl_hip_scan_order_host (host library only), range_order a plain lexicographic sort;
+  * the Morton keys and the range keys equal, bit for bit, those of mcl_3dl_amd/csrc/cloud_keys.h compiled for the host
+    (tests/cpp/scan_keys_check.cpp): the one statement the sort kernels and the host ordering share."""
+import os
+import shutil
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -119,3 +125,86 @@ def test_range_order_is_the_lexicographic_order_of_range_and_index(n):
     same = r2[first][1:] == r2[first][:-1]
     assert np.count_nonzero(same & (og[first][1:] != og[first][:-1])) > n // 16
     assert n - len(np.unique(np.c_[xyz, og], axis=0)) >= n // 8 - 1
+
+
+# ---- the keys of cloud_keys.h, compiled for the host ----------------------------------------------------------------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def scan_keys(tmp_path_factory):
+    """keys(lik xyz, beam xyz, origin ids, origins) -> (dropped bits, Morton keys, range keys' bits) from scan_keys_check."""
+    gxx = shutil.which("g++")
+    if not gxx:
+        pytest.skip("no g++")
+    tmp = tmp_path_factory.mktemp("scan_keys")
+    exe = str(tmp / "scan_keys_check")
+    subprocess.run([gxx, "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-I",
+                    os.path.join(ROOT, "mcl_3dl_amd", "csrc"), "-o", exe,
+                    os.path.join(ROOT, "tests", "cpp", "scan_keys_check.cpp")], check=True)
+
+    def keys(lik=None, beam=None, og=None, origins=None):
+        lik = np.zeros((0, 3), np.float32) if lik is None else np.ascontiguousarray(lik, np.float32).reshape(-1, 3)
+        beam = np.zeros((0, 3), np.float32) if beam is None else np.ascontiguousarray(beam, np.float32).reshape(-1, 3)
+        og = np.zeros(len(beam), np.uint32) if og is None else np.ascontiguousarray(og, np.uint32)
+        origins = np.zeros((0, 3), np.float32) if origins is None else np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        src, dst = str(tmp / "in.bin"), str(tmp / "out.bin")
+        with open(src, "wb") as f:
+            np.array([len(lik), len(beam), len(origins)], np.uint32).tofile(f)
+            for a in (lik, beam, og, origins):
+                a.tofile(f)
+        subprocess.run([exe, src, dst], check=True, timeout=120)
+        out = np.fromfile(dst, np.uint32)
+        assert len(out) == 1 + len(lik) + len(beam)
+        return int(out[0]), out[1:1 + len(lik)], out[1 + len(lik):]
+    return keys
+
+
+def range_key_bits(xyz, og, origins):
+    """The float32 expression of cloud_ref.range_order, viewed as uint32."""
+    xyz, origins = np.asarray(xyz, np.float32).reshape(-1, 3), np.asarray(origins, np.float32).reshape(-1, 3)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = xyz - origins[np.asarray(og, np.int64)]
+        key = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    return key.view(np.uint32)
+
+
+ALL_NON_FINITE_3 = np.array([[np.nan, 0.0, 0.0], [1.0, np.inf, 2.0], [np.nan, -np.inf, np.inf]], np.float32)
+
+
+@pytest.mark.parametrize("n", cases.LIK_SIZES + ["all_non_finite_3"])
+def test_morton_keys_equal_the_header_compiled_for_the_host(scan_keys, n):
+    scan = ALL_NON_FINITE_3 if n == "all_non_finite_3" else cases.lik_scan(n)
+    drop, got, _ = scan_keys(lik=scan)
+    want = cloud_ref.morton_keys(scan)
+    np.testing.assert_array_equal(got, want)
+    fin = cloud_ref.finite_rows(scan)
+    if fin.any():
+        with np.errstate(over="ignore"):
+            cells = int(cloud_ref._cell((scan[fin].max(0) - scan[fin].min(0)) * np.float32(4)).max())
+        assert drop == max(0, 3 * cells.bit_length() - cloud_ref.MORTON_BITS)
+    else:
+        assert drop == 0                            # the corners stay at +-FLT_MAX: an extent of -inf, no cell, no bit to drop
+    if n == cases.LIK_WIDE:
+        assert drop == 30 - cloud_ref.MORTON_BITS   # cells clamp at 1023: all ten bits per axis in use
+    if n in cases.LIK_NONFINITE:
+        assert np.count_nonzero(~fin) == 4
+
+
+@pytest.mark.parametrize("n", cases.BEAM_SIZES)
+def test_range_keys_equal_the_header_compiled_for_the_host(scan_keys, n):
+    xyz, og, origins = cases.beam_scan(n)
+    _, _, got = scan_keys(beam=xyz, og=og, origins=origins)
+    np.testing.assert_array_equal(got, range_key_bits(xyz, og, origins))
+    # sorting the bits as unsigned integers is sorting the ranges
+    np.testing.assert_array_equal(np.argsort(got, kind="stable"), cloud_ref.range_order(xyz, og, origins))
+
+
+def test_range_keys_of_non_finite_points_sort_last(scan_keys):
+    origins = np.array([[0.5, -1.0, 0.25]], np.float32)
+    xyz = np.array([[np.nan, 1.0, 2.0], [np.inf, 1.0, 2.0], [3.0, -np.inf, 2.0], [3.0, 1.0, 2.0]], np.float32)
+    _, _, got = scan_keys(beam=xyz, og=np.zeros(4, np.uint32), origins=origins)
+    np.testing.assert_array_equal(got, range_key_bits(xyz, np.zeros(4, np.int64), origins))
+    assert got[0] > 0x7f800000                      # NaN: above +inf's bits, behind every other range
+    assert got[1] == 0x7f800000 and got[2] == 0x7f800000
+    assert got[3] < 0x7f800000
