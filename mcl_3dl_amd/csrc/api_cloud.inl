@@ -327,11 +327,7 @@ int mcl3dl_hip_sort_pairs(mcl3dl_hip_ctx* ctx, const uint32_t* keys, const uint3
     return ctx->fail(-3, "bad arguments to sort_pairs");
   HIP_TRY(hipSetDevice(ctx->device));
   const size_t bytes = sizeof(uint32_t) * n;
-  for (int k = 0; k < 2; ++k)
-  {
-    TRY(ensure(ctx, ctx->cl_key[k], bytes + 4));
-    TRY(ensure(ctx, ctx->cl_val[k], bytes + 4));
-  }
+  TRY(ensure_sort_pairs(ctx, n));
   HIP_TRY(hipMemcpyAsync(ctx->cl_key[0].p, keys, bytes, hipMemcpyHostToDevice, ctx->stream));
   if (vals)
   {

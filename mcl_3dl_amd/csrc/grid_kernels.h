@@ -3,11 +3,14 @@
 // are counting sorts of the map by a cell id: key per point -> stable radix sort of (key, map index) -> gather; the run
 // delimiters come from a histogram (one atomic per point) and an exclusive scan. Same keys, same order inside a cell
 // (ascending map index) as a sequential counting sort on the host: the structures are bit-identical to what
-// host_map_compilers.h:build_*_grid_host lays out (tests/test_gpu_map_path.py compares results under both builders).
+// host_grid_builders.h:build_*_grid_host lays out, and the keys are the same functions there and here (index_geometry.h:
+// cell_index, dda_voxel_coord / dda_voxel_index, dda_brick_of / dda_brick_bit). tests/test_gpu_grid_builders.py and
+// tests/test_gpu_map_path.py compare results under both forms.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "index_geometry.h"
 #include "map_structs.h"
 #pragma clang fp contract(off)
 
@@ -25,27 +28,17 @@ __global__ void grid_rescale_kernel(const float4* __restrict__ map, long long n,
                        __uint_as_float(static_cast<uint32_t>(i)));
 }
 
-struct CellGeom
-{
-  float ox, oy, oz, inv;
-  int nx, ny, nz;
-};
-
-// cell of every rescaled point — floorf((s - o) * inv), the expression nearest_d2 uses for its queries — clamped into the grid
-__global__ void lik_cell_key_kernel(const float4* __restrict__ sp, long long n, CellGeom g, uint32_t* __restrict__ key,
+// cell of every rescaled point (index_geometry.h:cell_index) + the cells' histogram. ANY: the cloud may hold non-finite
+// points (a scan, build_transient_cell_grid), which go to cell 0 by decree (cell_index_any)
+template <bool ANY>
+__global__ void lik_cell_key_kernel(const float4* __restrict__ sp, long long n, CellGridGeometry g, uint32_t* __restrict__ key,
                                     uint32_t* __restrict__ val, uint32_t* __restrict__ count)
 {
   const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (i >= n)
     return;
   const float4 p = sp[i];
-  int cx = static_cast<int>(floorf((p.x - g.ox) * g.inv));
-  int cy = static_cast<int>(floorf((p.y - g.oy) * g.inv));
-  int cz = static_cast<int>(floorf((p.z - g.oz) * g.inv));
-  cx = min(max(cx, 0), g.nx - 1);
-  cy = min(max(cy, 0), g.ny - 1);
-  cz = min(max(cz, 0), g.nz - 1);
-  const uint32_t k = static_cast<uint32_t>((static_cast<size_t>(cz) * g.ny + cy) * g.nx + cx);
+  const uint32_t k = ANY ? cell_index_any(g, p.x, p.y, p.z) : cell_index(g, p.x, p.y, p.z);
   key[i] = k;
   val[i] = static_cast<uint32_t>(i);
   atomicAdd(&count[k], 1u);
@@ -70,40 +63,14 @@ __device__ inline uint32_t lower_bound_u32(const uint32_t* __restrict__ a, uint3
   return lo;
 }
 
-__device__ inline uint32_t lik_cell_of(const float4 p, const CellGeom& g)
-{
-  int cx = static_cast<int>(floorf((p.x - g.ox) * g.inv));
-  int cy = static_cast<int>(floorf((p.y - g.oy) * g.inv));
-  int cz = static_cast<int>(floorf((p.z - g.oz) * g.inv));
-  cx = min(max(cx, 0), g.nx - 1);
-  cy = min(max(cy, 0), g.ny - 1);
-  cz = min(max(cz, 0), g.nz - 1);
-  return static_cast<uint32_t>((static_cast<size_t>(cz) * g.ny + cy) * g.nx + cx);
-}
-
-// lik_cell_key_kernel for a cloud that may hold non-finite points (a scan, build_transient_cell_grid): those go to cell 0 by
-// decree instead of through a float-to-int conversion of NaN / infinity. Finite points: the same key.
-__global__ void lik_cell_key_any_kernel(const float4* __restrict__ sp, long long n, CellGeom g, uint32_t* __restrict__ key,
-                                        uint32_t* __restrict__ val, uint32_t* __restrict__ count)
-{
-  const long long i = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (i >= n)
-    return;
-  const float4 p = sp[i];
-  const bool finite = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-  const uint32_t k = finite ? lik_cell_of(p, g) : 0u;
-  key[i] = k;
-  val[i] = static_cast<uint32_t>(i);
-  atomicAdd(&count[k], 1u);
-}
-
-__global__ void lik_update_key_kernel(const float4* __restrict__ sp_upd, int n_u, CellGeom g, uint32_t* __restrict__ key,
+__global__ void lik_update_key_kernel(const float4* __restrict__ sp_upd, int n_u, CellGridGeometry g, uint32_t* __restrict__ key,
                                       uint32_t* __restrict__ val)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_u)
     return;
-  key[i] = lik_cell_of(sp_upd[i], g);
+  const float4 p = sp_upd[i];
+  key[i] = cell_index(g, p.x, p.y, p.z);
   val[i] = static_cast<uint32_t>(i);
 }
 
@@ -118,7 +85,7 @@ __global__ void lik_merge_cells_kernel(const uint32_t* __restrict__ base_start, 
 }
 
 __global__ void lik_merge_points_kernel(const float4* __restrict__ base_pts, long long n_base,
-                                        const uint32_t* __restrict__ base_start, CellGeom g,
+                                        const uint32_t* __restrict__ base_start, CellGridGeometry g,
                                         const float4* __restrict__ sp_upd, const uint32_t* __restrict__ ukey,
                                         const uint32_t* __restrict__ uval, uint32_t n_u, float4* __restrict__ out_pts)
 {
@@ -126,7 +93,7 @@ __global__ void lik_merge_points_kernel(const float4* __restrict__ base_pts, lon
   if (t < n_base)
   {
     const float4 p = base_pts[t];
-    out_pts[t + lower_bound_u32(ukey, n_u, lik_cell_of(p, g))] = p;
+    out_pts[t + lower_bound_u32(ukey, n_u, cell_index(g, p.x, p.y, p.z))] = p;
   }
   else if (t < n_base + n_u)
   {
@@ -143,18 +110,8 @@ __global__ void grid_gather_kernel(const float4* __restrict__ src, const uint32_
     dst[k] = src[val[k]];
 }
 
-struct DdaGeom
-{
-  float mnx, mny, mnz;
-  double grid;
-  int nx, ny;
-  unsigned long long total;
-  int bnx, bny;
-};
-
-// RaycastUsingDDA::updatePointCloud / toIndex / getArrayIndex (raycast_using_dda.h:162-190,205-210,225-228): voxel =
-// trunc((p - min) / grid) with a float difference and a double division, x-fastest array index in int arithmetic;
-// setExists -> the voxel's bit in its 4x4x4 brick word
+// voxel of every map point (index_geometry.h: dda_voxel_coord, dda_voxel_index) + the voxels' histogram + setExists -> the
+// voxel's bit in its 4x4x4 brick word (dda_brick_of)
 __global__ void dda_voxel_key_kernel(const float4* __restrict__ map, long long n, DdaGeom g, uint32_t* __restrict__ key,
                                      uint32_t* __restrict__ val, uint32_t* __restrict__ count,
                                      unsigned long long* __restrict__ bricks, int* __restrict__ err)
@@ -163,10 +120,9 @@ __global__ void dda_voxel_key_kernel(const float4* __restrict__ map, long long n
   if (i >= n)
     return;
   const float4 p = map[i];
-  const int c0 = static_cast<int>(static_cast<double>(p.x - g.mnx) / g.grid);
-  const int c1 = static_cast<int>(static_cast<double>(p.y - g.mny) / g.grid);
-  const int c2 = static_cast<int>(static_cast<double>(p.z - g.mnz) / g.grid);
-  const size_t v = static_cast<size_t>(c0 + c1 * g.nx + c2 * (g.nx * g.ny));
+  const int c0 = dda_voxel_coord(p.x, g.mn[0], g.grid), c1 = dda_voxel_coord(p.y, g.mn[1], g.grid),
+            c2 = dda_voxel_coord(p.z, g.mn[2], g.grid);
+  const size_t v = static_cast<size_t>(dda_voxel_index(g, c0, c1, c2));
   val[i] = static_cast<uint32_t>(i);
   if (v >= g.total)
   {
@@ -176,8 +132,10 @@ __global__ void dda_voxel_key_kernel(const float4* __restrict__ map, long long n
   }
   key[i] = static_cast<uint32_t>(v);
   atomicAdd(&count[v], 1u);
-  const size_t brick = (static_cast<size_t>(c2 >> 2) * g.bny + (c1 >> 2)) * g.bnx + (c0 >> 2);
-  atomicOr(&bricks[brick], 1ull << (((c2 & 3) << 4) | ((c1 & 3) << 2) | (c0 & 3)));
+  size_t brick;
+  unsigned long long bit;
+  dda_brick_of(g, c0, c1, c2, brick, bit);
+  atomicOr(&bricks[brick], bit);
 }
 
 // points in voxel order (insertion = map order inside a voxel: the sort is stable) + their original map index
@@ -201,20 +159,9 @@ __global__ void dda_overlay_key_kernel(const float4* __restrict__ upd, int n, Dd
   if (i >= n)
     return;
   const float4 p = upd[i];
-  const int c0 = static_cast<int>(static_cast<double>(p.x - g.mnx) / g.grid);
-  const int c1 = static_cast<int>(static_cast<double>(p.y - g.mny) / g.grid);
-  const int c2 = static_cast<int>(static_cast<double>(p.z - g.mnz) / g.grid);
-  key[i] = static_cast<uint32_t>(c0 + c1 * g.nx + c2 * (g.nx * g.ny));
+  key[i] = static_cast<uint32_t>(dda_voxel_index(g, dda_voxel_coord(p.x, g.mn[0], g.grid), dda_voxel_coord(p.y, g.mn[1], g.grid),
+                                                  dda_voxel_coord(p.z, g.mn[2], g.grid)));
   val[i] = static_cast<uint32_t>(i);
-}
-
-__device__ inline void dda_brick_bit(const DdaGeom& g, uint32_t v, size_t& brick, unsigned long long& bit)
-{
-  const int plane = g.nx * g.ny;
-  const int c2 = static_cast<int>(v) / plane, rem = static_cast<int>(v) - c2 * plane;
-  const int c1 = rem / g.nx, c0 = rem - c1 * g.nx;
-  brick = (static_cast<size_t>(c2 >> 2) * g.bny + (c1 >> 2)) * g.bnx + (c0 >> 2);
-  bit = 1ull << (((c2 & 3) << 4) | ((c1 & 3) << 2) | (c0 & 3));
 }
 
 // the previous overlay goes: a voxel that holds no base point is empty again

@@ -1,5 +1,7 @@
 // host_cloud.h — part of the single translation unit mcl3dl_hip.hip: host-side drivers of cloud_kernels.h shared by the scan
-// upload (api_core.inl) and the scan-preparation / map entry points (api_cloud.inl).
+// upload (api_core.inl), the scan-preparation / map entry points (api_cloud.inl) and the map structures' builders
+// (host_map_compilers.h, host_grid_builders.h): min / max, the stable radix sort and its work arrays, uploads — the map as a
+// device cloud among them.
 #pragma once
 
 namespace
@@ -61,6 +63,17 @@ int cloud_minmax(mcl3dl_hip_ctx* ctx, const float4* pts, long long n, float* hos
 }
 
 // ---- stable radix sort (sort_kernels.h) ---------------------------------------------------------------------------------
+// the sort's work arrays ctx->cl_key[0..1] / cl_val[0..1] for n pairs (+ 1: the scans over them)
+int ensure_sort_pairs(mcl3dl_hip_ctx* ctx, size_t n)
+{
+  for (int k = 0; k < 2; ++k)
+  {
+    TRY(ensure(ctx, ctx->cl_key[k], sizeof(uint32_t) * (n + 1)));
+    TRY(ensure(ctx, ctx->cl_val[k], sizeof(uint32_t) * (n + 1)));
+  }
+  return 0;
+}
+
 int sort_passes(int end_bit)
 {
   return std::max(1, (end_bit + 7) / 8);
@@ -77,12 +90,7 @@ int radix_sort(mcl3dl_hip_ctx* ctx, const RsKeyGen& kg, long long n, int end_bit
     return 0;
   if (n > 0x7fffffffLL)
     return ctx->fail(-3, "too many points to sort");
-  const size_t cap = sizeof(uint32_t) * (static_cast<size_t>(n) + 1);
-  for (int k = 0; k < 2; ++k)
-  {
-    TRY(ensure(ctx, ctx->cl_key[k], cap));
-    TRY(ensure(ctx, ctx->cl_val[k], cap));
-  }
+  TRY(ensure_sort_pairs(ctx, static_cast<size_t>(n)));
   RsKeyGen g = kg;  // (ensure() may have moved the work arrays the caller named before growing them: callers size them first)
   uint32_t* key[2] = { ctx->cl_key[0].as<uint32_t>(), ctx->cl_key[1].as<uint32_t>() };
   uint32_t* val[2] = { ctx->cl_val[0].as<uint32_t>(), ctx->cl_val[1].as<uint32_t>() };
@@ -203,6 +211,18 @@ int upload_cloud(mcl3dl_hip_ctx* ctx, const float* xyz, const uint32_t* label, s
                        nn, out.as<float4>());
   }
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// the map as a device cloud {x, y, z, label bits} in map order; re-uploaded only when the host copy changed
+int ensure_map_dev(mcl3dl_hip_ctx* ctx)
+{
+  const size_t n = ctx->map_xyz.size() / 3;
+  if (ctx->map_dev_valid && ctx->map_dev_n == n)
+    return 0;
+  TRY(upload_cloud(ctx, ctx->map_xyz.data(), ctx->map_label.data(), n, ctx->map_dev));
+  ctx->map_dev_valid = true;
+  ctx->map_dev_n = n;
   return 0;
 }
 
@@ -436,11 +456,7 @@ int device_order_scans(mcl3dl_hip_ctx* ctx, size_t n_s, size_t n_b, const float*
                        int* d_err)
 {
   const size_t n_max = std::max<size_t>(std::max(n_s, n_b), 1);
-  for (int k = 0; k < 2; ++k)
-  {
-    TRY(ensure(ctx, ctx->cl_key[k], sizeof(uint32_t) * (n_max + 1)));
-    TRY(ensure(ctx, ctx->cl_val[k], sizeof(uint32_t) * (n_max + 1)));
-  }
+  TRY(ensure_sort_pairs(ctx, n_max));
   TRY(ensure_scan_block(ctx, n_s, n_b, n_o));
   if (n_s)
   {

@@ -87,7 +87,7 @@ struct mcl3dl_hip_ctx
   // fixed-step march over the cell-sorted map (beam_kd_kernels.h). Read by every call that casts rays, when it casts them.
   int beam_raycast = 0;
   // the cell grid's edge follows match_dist_min — unless no likelihood parameters were ever set and the grid is first wanted by
-  // the kd-tree caster: then it follows that caster's first search radius (lik_cell_edge, host_map_compilers.h).
+  // the kd-tree caster: then it follows that caster's first search radius (lik_cell_edge, host_grid_builders.h).
   // lik_cell_from_beam: the grid in place was built with that edge
   bool lik_params_set = false, lik_cell_from_beam = false;
   // the kd-tree caster's dilated occupancy bitmap of the cell grid in place (beam_kd_kernels.h:kd_occupancy_kernel), and the reach
@@ -102,6 +102,7 @@ struct mcl3dl_hip_ctx
   bool lik_base_dirty = true;
   size_t lik_base_n = 0;
   float lik_base_lo[3] = { 0, 0, 0 }, lik_base_hi[3] = { 0, 0, 0 };  // rescaled bounds the base grid's geometry was laid out for
+  CellGridGeometry lik_base_geom{};  // that geometry: the merged grid's too
   uint64_t lik_grid_merges = 0, lik_grid_rebuilds = 0;
   std::vector<float4> lik_upd_host;  // the update's rescaled points (host staging of the merge)
   LikGrid lg{};
@@ -190,7 +191,7 @@ struct mcl3dl_hip_ctx
   bool dda_overlay_ok = false;
   uint64_t dda_overlay_updates = 0;
   DdaGeom dda_geom{};
-  // the map as a device cloud (host_grid_builders.h); opt.grid_build_host = 1: the cell grid / the DDA grid are built on the
+  // the map as a device cloud (host_cloud.h:ensure_map_dev); opt.grid_build_host = 1: the cell grid / the DDA grid are built on the
   // host instead
   DevBuf map_dev;
   bool map_dev_valid = false;
@@ -846,5 +847,37 @@ int timing_collect(mcl3dl_hip_ctx* ctx)
   ctx->pending.clear();
   return 0;
 }
+
+// The event pair around a build or an update of a map structure (grids, candidate index): start() to stop_ms() on the
+// context's stream, in milliseconds; the events go on every return path.
+struct BuildTimer
+{
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  ~BuildTimer()
+  {
+    if (ev0)
+      (void)hipEventDestroy(ev0);
+    if (ev1)
+      (void)hipEventDestroy(ev1);
+  }
+  int start(mcl3dl_hip_ctx* ctx)
+  {
+    HIP_TRY(hipEventCreate(&ev0));
+    HIP_TRY(hipEventCreate(&ev1));
+    HIP_TRY(hipEventRecord(ev0, ctx->stream));
+    return 0;
+  }
+  // records the end, waits for the stream (staged results are handed over: sync_stream) and reads the time
+  int stop_ms(mcl3dl_hip_ctx* ctx, double* ms)
+  {
+    float f = 0.f;
+    HIP_TRY(hipEventRecord(ev1, ctx->stream));
+    TRY(sync_stream(ctx));
+    HIP_TRY(hipEventSynchronize(ev1));  // (the stream may have been waited for through the polled word: the event is past, the runtime has to look)
+    HIP_TRY(hipEventElapsedTime(&f, ev0, ev1));
+    *ms = f;
+    return 0;
+  }
+};
 
 }  // namespace

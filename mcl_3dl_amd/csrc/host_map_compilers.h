@@ -1,246 +1,10 @@
-// host_map_compilers.h — part of the single translation unit mcl3dl_hip.hip: host drivers of the three map structures
-// (cell-sorted exact-NN grid, DDA occupancy bricks + voxel index, candidate-voxel records; device side in
-// map_compiler.h) and the device prefix scans they share.
+// host_map_compilers.h — part of the single translation unit mcl3dl_hip.hip: the scratch allocator and the device prefix
+// scans every map structure's build shares, and the host driver of the candidate-voxel records (device side in
+// map_compiler.h). The two grids (cell-sorted exact-NN grid, DDA occupancy + voxel index): host_grid_builders.h.
 #pragma once
 
 namespace
 {
-int build_lik_grid(mcl3dl_hip_ctx* ctx);  // host_grid_builders.h
-int build_dda_grid(mcl3dl_hip_ctx* ctx);
-int ensure_map_dev(mcl3dl_hip_ctx* ctx);  // host_grid_builders.h: the map as a device cloud {x, y, z, label}
-int cloud_minmax(mcl3dl_hip_ctx* ctx, const float4* pts, long long n, float* host6, unsigned long long* host_cnt);  // host_cloud.h
-
-// The two search radii of RaycastUsingKDTree (raycast_using_kdtree.h:83, :94): double expressions narrowed to the float
-// parameter of ChunkedKdtree::radiusSearch.
-void kd_ray_radii(const mcl3dl_hip_ctx* ctx, float* grid_min, float* r1, float* r2)
-{
-  const float mn = std::min({ ctx->map_grid[0], ctx->map_grid[1], ctx->map_grid[2] });
-  const float mx = std::max({ ctx->map_grid[0], ctx->map_grid[1], ctx->map_grid[2] });
-  *grid_min = mn;
-  *r1 = static_cast<float>(std::sqrt(2.0) * mx / 2.0);
-  *r2 = static_cast<float>(mn * 2 + std::sqrt(2.0) * mx / 2.0);
-}
-
-// Edge of the cell grid's cubes. A context whose likelihood parameters were never set and that casts with the kd-tree caster
-// lays the grid out for that caster's first radius (one cell each way per step of a ray); everybody else for match_dist_min.
-bool lik_cell_is_beams(const mcl3dl_hip_ctx* ctx)
-{
-  return !ctx->lik_params_set && ctx->beam_raycast == 1;
-}
-
-float lik_cell_edge(const mcl3dl_hip_ctx* ctx)
-{
-  if (lik_cell_is_beams(ctx))
-  {
-    float mn, r1, r2;
-    kd_ray_radii(ctx, &mn, &r1, &r2);
-    return r1 * 1.01f;
-  }
-  return ctx->match_dist_min * 1.01f;
-}
-
-// ---- map compiler: exact-NN grid -----------------------------------------------------------------------
-// Replaces ChunkedKdtree::setInputCloud + pcl::KdTreeFLANN::setInputCloud.  The reference's chunking is a memory
-// device (20 m chunks with duplicated margins, chunked_kdtree.h:124-216) whose query result equals the global
-// nearest neighbour within the radius whenever radius <= max_search_radius; the grid gives that result directly.
-// Host form (option grid_build_host = 1): the sequential counting sort the device builder (host_grid_builders.h) is
-// checked against.
-int build_lik_grid_host(mcl3dl_hip_ctx* ctx)
-{
-  const size_t n = ctx->map_xyz.size() / 3;
-  const float cell = lik_cell_edge(ctx);
-  if (!(cell > 0.f) || !std::isfinite(cell))
-    return ctx->fail(-3, "match_dist_min must be positive and finite");
-  const float inv = 1.0f / cell;
-  std::vector<float> s(3 * n);
-  float mn[3] = { 0, 0, 0 }, mx[3] = { 0, 0, 0 };
-  for (size_t i = 0; i < n; ++i)
-    for (int a = 0; a < 3; ++a)
-    {
-      // PointRepresentation::vectorize: one float product per coordinate
-      const float v = ctx->has_weight ? ctx->map_xyz[3 * i + a] * ctx->weight[a] : ctx->map_xyz[3 * i + a];
-      if (!std::isfinite(v))
-        return ctx->fail(-3, "map point %zu is not finite", i);
-      s[3 * i + a] = v;
-      if (i == 0 || v < mn[a])
-        mn[a] = v;
-      if (i == 0 || v > mx[a])
-        mx[a] = v;
-    }
-  const CellGridGeometry geom = cell_grid_geometry(mn, mx, cell);  // index_geometry.h
-  const float* o = geom.o;
-  const int* dim = geom.dim;
-  double total = 1;
-  for (int a = 0; a < 3; ++a)
-    total *= dim[a];
-  if (total > 3.0e9)
-    return ctx->fail(-4, "likelihood grid would need %.3g cells (map extent too large for the dense index)", total);
-  const size_t ncell = static_cast<size_t>(dim[0]) * dim[1] * dim[2];
-  std::vector<uint32_t> cell_of(n);
-  std::vector<uint32_t> start(ncell + 1, 0);
-  for (size_t i = 0; i < n; ++i)
-  {
-    int c[3];
-    for (int a = 0; a < 3; ++a)
-    {
-      c[a] = static_cast<int>(grid_coord(s[3 * i + a], o[a], inv));  // same expression as the kernel's
-      c[a] = std::min(std::max(c[a], 0), dim[a] - 1);
-    }
-    cell_of[i] = static_cast<uint32_t>((static_cast<size_t>(c[2]) * dim[1] + c[1]) * dim[0] + c[0]);
-    ++start[cell_of[i] + 1];
-  }
-  for (size_t c = 0; c < ncell; ++c)
-    start[c + 1] += start[c];
-  std::vector<uint32_t> fill(start.begin(), start.end() - 1);
-  std::vector<float4> pts(n);
-  for (size_t i = 0; i < n; ++i)
-  {
-    const uint32_t dst = fill[cell_of[i]]++;
-    pts[dst] = make_float4(s[3 * i], s[3 * i + 1], s[3 * i + 2], bits_to_float(static_cast<uint32_t>(i)));
-  }
-  TRY(ensure(ctx, ctx->lik_pts, sizeof(float4) * n));
-  TRY(ensure(ctx, ctx->lik_cells, sizeof(uint32_t) * (ncell + 1)));
-  TRY(h2d(ctx, ctx->lik_pts.p, pts.data(), sizeof(float4) * n));
-  TRY(h2d(ctx, ctx->lik_cells.p, start.data(), sizeof(uint32_t) * (ncell + 1)));
-  TRY(sync_stream(ctx));
-  ctx->lg.cell_start = ctx->lik_cells.as<uint32_t>();
-  ctx->lg.pts = ctx->lik_pts.as<float4>();
-  ctx->lg.ox = o[0];
-  ctx->lg.oy = o[1];
-  ctx->lg.oz = o[2];
-  ctx->lg.inv_cell = inv;
-  ctx->lg.nx = dim[0];
-  ctx->lg.ny = dim[1];
-  ctx->lg.nz = dim[2];
-  ctx->footprint[0] = sizeof(float4) * n;
-  ctx->footprint[1] = sizeof(uint32_t) * (ncell + 1);
-  ctx->lik_dirty = false;
-  ctx->lik_cell_from_beam = lik_cell_is_beams(ctx);
-  ctx->kd_occ_reach = 0;  // (the kd-tree caster's bitmap is of the previous grid)
-  return 0;
-}
-
-// ---- map compiler: DDA occupancy -------------------------------------------------------------------------
-// RaycastUsingDDA::updatePointCloud / setExists, include/mcl_3dl/raycasts/raycast_using_dda.h:162-190,230-235:
-// AABB by getMinMax3D, map_size = (size_t)((max-min)/grid)+1, voxel = trunc((p-min)/grid) (float difference,
-// double division), x-fastest array index; per voxel the points stay in insertion (map) order.
-// the ray-test constants of a DdaGrid (shared by both builders)
-void dda_ray_constants(const mcl3dl_hip_ctx* ctx, DdaGrid& g)
-{
-  g.grid = static_cast<double>(ctx->dda_grid_size);
-  g.ray_angle_half = static_cast<double>(ctx->ray_angle_half);
-  // RaycastUsingDDA ctor, raycast_using_dda.h:59: map_grid_size_y appears twice (reference quirk, kept)
-  const double gx = ctx->map_grid[0], gy = ctx->map_grid[1];
-  g.min_dist_thr_sq = gx * gx + gy * gy + gy * gy;
-  g.hit_tolerance_f = static_cast<float>(static_cast<double>(ctx->hit_range));
-}
-
-// Host form (option grid_build_host = 1); device form in host_grid_builders.h.
-int build_dda_grid_host(mcl3dl_hip_ctx* ctx)
-{
-  const size_t n = ctx->map_xyz.size() / 3;
-  const double grid = static_cast<double>(ctx->dda_grid_size);
-  if (!(grid > 0))
-    return ctx->fail(-3, "dda_grid_size must be positive");
-  float mn[3] = { 3.4e38f, 3.4e38f, 3.4e38f }, mx[3] = { -3.4e38f, -3.4e38f, -3.4e38f };
-  for (size_t i = 0; i < n; ++i)
-    for (int a = 0; a < 3; ++a)
-    {
-      const float v = ctx->map_xyz[3 * i + a];
-      if (v < mn[a])
-        mn[a] = v;
-      if (v > mx[a])
-        mx[a] = v;
-    }
-  int dim[3];
-  double total_d = 1;
-  for (int a = 0; a < 3; ++a)
-  {
-    dim[a] = static_cast<int>(static_cast<size_t>((mx[a] - mn[a]) / grid) + 1);
-    total_d *= dim[a];
-  }
-  if (total_d >= 2147483647.0)  // the reference keeps point_total in an int (raycast_using_dda.h:176)
-    return ctx->fail(-4, "DDA grid would need %.3g voxels (>= 2^31)", total_d);
-  const size_t total = static_cast<size_t>(total_d);
-  std::vector<uint32_t> vox(n);
-  std::vector<uint32_t> start(total + 1, 0);
-  const int bdim[3] = { (dim[0] + 3) / 4, (dim[1] + 3) / 4, (dim[2] + 3) / 4 };
-  std::vector<unsigned long long> bits(static_cast<size_t>(bdim[0]) * bdim[1] * bdim[2], 0ull);
-  for (size_t i = 0; i < n; ++i)
-  {
-    int c[3];
-    for (int a = 0; a < 3; ++a)
-      c[a] = static_cast<int>(static_cast<double>(ctx->map_xyz[3 * i + a] - mn[a]) / grid);
-    const size_t v = static_cast<size_t>(c[0] + c[1] * dim[0] + c[2] * (dim[0] * dim[1]));
-    if (v >= total)
-      return ctx->fail(-3, "map point %zu falls outside its own DDA grid", i);
-    vox[i] = static_cast<uint32_t>(v);
-    ++start[v + 1];
-    const size_t brick = (static_cast<size_t>(c[2] >> 2) * bdim[1] + (c[1] >> 2)) * bdim[0] + (c[0] >> 2);
-    bits[brick] |= 1ull << (((c[2] & 3) << 4) | ((c[1] & 3) << 2) | (c[0] & 3));
-  }
-  for (size_t v = 0; v < total; ++v)
-    start[v + 1] += start[v];
-  std::vector<uint32_t> fill(start.begin(), start.end() - 1);
-  std::vector<float4> pts(n);
-  std::vector<uint32_t> index(n);
-  for (size_t i = 0; i < n; ++i)  // ascending i: insertion order preserved inside a voxel
-  {
-    const uint32_t dst = fill[vox[i]]++;
-    pts[dst] = make_float4(ctx->map_xyz[3 * i], ctx->map_xyz[3 * i + 1], ctx->map_xyz[3 * i + 2],
-                           bits_to_float(ctx->map_label[i]));
-    index[dst] = static_cast<uint32_t>(i);
-  }
-  TRY(ensure(ctx, ctx->dda_bits, sizeof(unsigned long long) * bits.size()));
-  TRY(ensure(ctx, ctx->dda_start, sizeof(uint32_t) * (total + 1)));
-  TRY(ensure(ctx, ctx->dda_pts, sizeof(float4) * n));
-  TRY(ensure(ctx, ctx->dda_index, sizeof(uint32_t) * n));
-  TRY(h2d(ctx, ctx->dda_bits.p, bits.data(), sizeof(unsigned long long) * bits.size()));
-  TRY(h2d(ctx, ctx->dda_start.p, start.data(), sizeof(uint32_t) * (total + 1)));
-  TRY(h2d(ctx, ctx->dda_pts.p, pts.data(), sizeof(float4) * n));
-  TRY(h2d(ctx, ctx->dda_index.p, index.data(), sizeof(uint32_t) * n));
-  TRY(sync_stream(ctx));
-  DdaGrid& g = ctx->dg;
-  g.bricks = ctx->dda_bits.as<unsigned long long>();
-  g.bnx = bdim[0];
-  g.bny = bdim[1];
-  g.bnz = bdim[2];
-  g.mul24_ok = (bdim[0] < (1 << 24) && static_cast<long long>(bdim[1]) * bdim[2] < (1ll << 24)) ? 1 : 0;
-  g.vox_start = ctx->dda_start.as<uint32_t>();
-  g.pts = ctx->dda_pts.as<float4>();
-  g.pt_index = ctx->dda_index.as<uint32_t>();
-  g.min_x = mn[0];
-  g.min_y = mn[1];
-  g.min_z = mn[2];
-  g.max_x = mx[0];
-  g.max_y = mx[1];
-  g.max_z = mx[2];
-  g.nx = dim[0];
-  g.ny = dim[1];
-  g.nz = dim[2];
-  g.ov_n = 0;  // the host builder puts every point into the one array: a map update then rebuilds
-  ctx->dda_overlay_ok = false;
-  dda_ray_constants(ctx, g);
-  ctx->footprint[2] = sizeof(unsigned long long) * bits.size();
-  ctx->footprint[3] = sizeof(uint32_t) * (total + 1);
-  ctx->footprint[4] = sizeof(float4) * n + sizeof(uint32_t) * n;
-  ctx->dda_dirty = false;
-  return 0;
-}
-
-// two events that are destroyed on every return path of the builders below
-struct EventPairRaii
-{
-  hipEvent_t a = nullptr, b = nullptr;
-  ~EventPairRaii()
-  {
-    if (a)
-      (void)hipEventDestroy(a);
-    if (b)
-      (void)hipEventDestroy(b);
-  }
-};
-
 // Scratch memory of the map compilers. Blocks come from — and go back to — a pool in the context (scratch_alloc /
 // scratch_release) instead of hipMalloc / hipFree: a map update used two dozen of each (every hipFree a device
 // synchronisation), a millisecond and more of a 4 ms mapcloud_update (src/mcl_3dl.cpp:141-153). All work is enqueued on the
@@ -582,11 +346,8 @@ int build_cand_grid_at(mcl3dl_hip_ctx* ctx, double voxel_ratio, uint32_t cap = 4
 {
   const unsigned long long rec_bytes = 16ull * cap;  // per voxel
   const size_t n = ctx->map_xyz.size() / 3;
-  EventPairRaii evs;
-  HIP_TRY(hipEventCreate(&evs.a));
-  HIP_TRY(hipEventCreate(&evs.b));
-  const hipEvent_t ev0 = evs.a, ev1 = evs.b;
-  HIP_TRY(hipEventRecord(ev0, ctx->stream));
+  BuildTimer tm;
+  TRY(tm.start(ctx));
   // the rescaled points (PointRepresentation::vectorize; w = map index) and their bounds, on the device from the device copy
   // of the map; they stay there: a map update (update_cand_grid) re-compiles single bricks from them
   TRY(ensure_map_dev(ctx));
@@ -655,11 +416,8 @@ int build_cand_grid_at(mcl3dl_hip_ctx* ctx, double voxel_ratio, uint32_t cap = 4
                            ctx->stream));
     ctx->cand_n_ovf = n_ovf;
     ctx->cand_ovf_leaked = 0;
-    HIP_TRY(hipEventRecord(ev1, ctx->stream));
-    TRY(sync_stream(ctx));
-    float ms2 = 0.f;
-    HIP_TRY(hipEventSynchronize(ev1));
-    HIP_TRY(hipEventElapsedTime(&ms2, ev0, ev1));
+    double ms2 = 0.0;
+    TRY(tm.stop_ms(ctx, &ms2));
     RecGrid& g = ctx->rg;
     g.brick_table = table;
     g.rec = ctx->cand_rec.as<float4>();
@@ -920,11 +678,8 @@ int update_cand_grid(mcl3dl_hip_ctx* ctx, size_t n_base, const std::vector<float
         return 0;
       }
   }
-  EventPairRaii evs;
-  HIP_TRY(hipEventCreate(&evs.a));
-  HIP_TRY(hipEventCreate(&evs.b));
-  const hipEvent_t ev0 = evs.a, ev1 = evs.b;
-  HIP_TRY(hipEventRecord(ev0, ctx->stream));
+  BuildTimer tm;
+  TRY(tm.start(ctx));
   // 1. dirty bricks: within reach of a removed or an added point
   TempBuf d_dirty, d_old, d_newflag, d_dirtyrank, d_sub_table, d_sub_main, d_sub_bxyz, d_relflag, d_rel, d_subrec;
   TRY(scratch_alloc(ctx, d_dirty, sizeof(int) * n_table));
@@ -1045,11 +800,8 @@ int update_cand_grid(mcl3dl_hip_ctx* ctx, size_t n_base, const std::vector<float
   HIP_TRY(hipGetLastError());
   unsigned long long orphaned = 0;
   TRY(d2h(ctx, &orphaned, d_orphan.p, sizeof(orphaned)));
-  HIP_TRY(hipEventRecord(ev1, ctx->stream));
-  TRY(sync_stream(ctx));
-  float ms = 0.f;
-  HIP_TRY(hipEventSynchronize(ev1));
-  HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+  double ms = 0.0;
+  TRY(tm.stop_ms(ctx, &ms));
   ctx->cand_n_bricks = n_bricks;
   ctx->cand_n_ovf = ovf_base + co.n_ovf;
   ctx->cand_ovf_leaked += static_cast<uint32_t>(orphaned);  // reclaimed by compact_overflow (or the next full rebuild)

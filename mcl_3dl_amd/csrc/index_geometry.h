@@ -1,8 +1,9 @@
-// index_geometry.h — the pure arithmetic of the two likelihood indices' geometry, free of HIP so that a plain C++ program can
-// include it (tests/cpp/voxel_slack_check.cpp sweeps it): the candidate-voxel grid (map_compiler.h, host_map_compilers.h) —
-// edges, their float reciprocals, the slack `grow` of V+, reach, origin, voxel and brick counts — the map's cell grid
-// (build_lik_grid_host and its device twin) — origin, edge, dimensions — and the one float expression by which every kernel
-// and every host builder assigns a coordinate its voxel or cell.
+// index_geometry.h — the pure arithmetic of the map structures' geometry, free of HIP so that a plain C++ program can include
+// it (tests/cpp/voxel_slack_check.cpp and tests/cpp/grid_keys_check.cpp run it on the host): the candidate-voxel grid
+// (map_compiler.h, host_map_compilers.h) — edges, their float reciprocals, the slack `grow` of V+, reach, origin, voxel and
+// brick counts — and, stated once for the kernels of grid_kernels.h and the host forms of host_grid_builders.h alike, the
+// map's cell grid (origin, edge, dimensions, cell of a point), the DDA grid (dimensions, voxel of a point, brick word and
+// bit) and the stable counting sort both host forms lay their arrays out with.
 //
 // The slack. A query q gets, per axis, the voxel
 //     v = floor(t),  t = fl(fl(q - o) * inv_e),  inv_e = fl(1 / e)           (float; o, e floats)
@@ -30,7 +31,9 @@
 // r = 0.2 m); the 27-cell scan is refused on a longer grid (radius_search scans a cell more each way and is not).
 #pragma once
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #if defined(__HIPCC__)
 #define MCL3DL_GEOM_HD __host__ __device__
@@ -180,20 +183,119 @@ struct CellGridGeometry
 
 constexpr int LIK_SCAN_MAX_CELLS = 40000;  // per axis: up to here two coordinates within the radius lie in adjacent cells
 
-inline CellGridGeometry cell_grid_geometry(const float mn[3], const float mx[3], float cell)
+// (an axis of 2^31 cells and more counts as INT_MAX cells: every caller refuses such a grid by its cell count)
+MCL3DL_GEOM_HD inline CellGridGeometry cell_grid_geometry(const float mn[3], const float mx[3], float cell)
 {
   CellGridGeometry g;
   g.inv = 1.0f / cell;
   for (int a = 0; a < 3; ++a)
   {
     g.o[a] = mn[a] - 2.0f * cell;
-    g.dim[a] = static_cast<int>(grid_coord(mx[a], g.o[a], g.inv)) + 3;
+    const float c = grid_coord(mx[a], g.o[a], g.inv);
+    g.dim[a] = c < 2147483520.0f ? static_cast<int>(c) + 3 : 2147483647;
   }
   return g;
+}
+
+MCL3DL_GEOM_HD inline int clamp_coord(int c, int n)
+{
+  const int lo = c > 0 ? c : 0;  // max, then min: one instruction each on the device
+  return lo < n - 1 ? lo : n - 1;
+}
+
+// Cell of a rescaled, finite point: grid_coord per axis, clamped into the grid, x-fastest index. Every builder's key — the
+// base, update and merge kernels of grid_kernels.h and the host form — is this function. The queries' cell stays a statement
+// of its own, cell_grid.h:cell_of: the walk needs the three unclamped floats (a query may lie outside the grid), not an index.
+MCL3DL_GEOM_HD inline uint32_t cell_index(const CellGridGeometry& g, float sx, float sy, float sz)
+{
+  const int cx = clamp_coord(static_cast<int>(grid_coord(sx, g.o[0], g.inv)), g.dim[0]);
+  const int cy = clamp_coord(static_cast<int>(grid_coord(sy, g.o[1], g.inv)), g.dim[1]);
+  const int cz = clamp_coord(static_cast<int>(grid_coord(sz, g.o[2], g.inv)), g.dim[2]);
+  return static_cast<uint32_t>((static_cast<size_t>(cz) * g.dim[1] + cy) * g.dim[0] + cx);
+}
+
+// ... of a point that may be non-finite (a scan: a clip keeps NaN): cell 0 by decree instead of a float-to-int conversion of
+// NaN or infinity; no float distance to such a point passes a `<`. Finite points: the same cell.
+MCL3DL_GEOM_HD inline uint32_t cell_index_any(const CellGridGeometry& g, float sx, float sy, float sz)
+{
+  return (std::isfinite(sx) && std::isfinite(sy) && std::isfinite(sz)) ? cell_index(g, sx, sy, sz) : 0u;
 }
 
 inline bool lik_scan_provable(const int dim[3])
 {
   return dim[0] <= LIK_SCAN_MAX_CELLS && dim[1] <= LIK_SCAN_MAX_CELLS && dim[2] <= LIK_SCAN_MAX_CELLS;
+}
+
+// ---- the DDA grid (DdaGrid): RaycastUsingDDA::updatePointCloud / toIndex / getArrayIndex / setExists ------------------------
+// (raycast_using_dda.h:162-190, 205-210, 225-228) with the occupancy kept as one 64-bit word per 4 x 4 x 4 brick of voxels
+struct DdaGeom
+{
+  float mn[3];
+  double grid;
+  int dim[3], bdim[3];       // voxels and bricks per axis
+  unsigned long long total;  // voxels (0 when the grid is refused: 2^31 and more)
+};
+
+// map_size = (size_t)((max - min) / grid) + 1 per axis: float difference, double division. *total_d = the voxel count as a
+// double: the reference keeps point_total in an int (raycast_using_dda.h:176), the caller refuses >= 2^31.
+MCL3DL_GEOM_HD inline DdaGeom dda_grid_geometry(const float mn[3], const float mx[3], double grid, double* total_d)
+{
+  DdaGeom g;
+  g.grid = grid;
+  *total_d = 1;
+  for (int a = 0; a < 3; ++a)
+  {
+    g.mn[a] = mn[a];
+    g.dim[a] = static_cast<int>(static_cast<size_t>((mx[a] - mn[a]) / grid) + 1);
+    g.bdim[a] = (g.dim[a] + 3) / 4;
+    *total_d *= g.dim[a];
+  }
+  g.total = *total_d < 2147483647.0 ? static_cast<unsigned long long>(*total_d) : 0ull;
+  return g;
+}
+
+// toIndex along one axis: float difference, double division, truncation toward zero. The builders' statement; the casting
+// kernels keep the other one, beam_kernels.h:to_index, over the DdaGrid they are handed: that file's bytes are what the
+// committed profiler counters are matched to, and it is not edited for a shared spelling.
+MCL3DL_GEOM_HD inline int dda_voxel_coord(float p, float mn, double grid)
+{
+  return static_cast<int>(static_cast<double>(p - mn) / grid);
+}
+
+// getArrayIndex: x-fastest, in int arithmetic as the reference's
+MCL3DL_GEOM_HD inline int dda_voxel_index(const DdaGeom& g, int c0, int c1, int c2)
+{
+  return c0 + c1 * g.dim[0] + c2 * (g.dim[0] * g.dim[1]);
+}
+
+// setExists: the occupancy word of the voxel's brick and the voxel's bit in it
+MCL3DL_GEOM_HD inline void dda_brick_of(const DdaGeom& g, int c0, int c1, int c2, size_t& brick, unsigned long long& bit)
+{
+  brick = (static_cast<size_t>(c2 >> 2) * g.bdim[1] + (c1 >> 2)) * g.bdim[0] + (c0 >> 2);
+  bit = 1ull << (((c2 & 3) << 4) | ((c1 & 3) << 2) | (c0 & 3));
+}
+
+// the same from a voxel index (dda_voxel_index inverted)
+MCL3DL_GEOM_HD inline void dda_brick_bit(const DdaGeom& g, uint32_t v, size_t& brick, unsigned long long& bit)
+{
+  const int plane = g.dim[0] * g.dim[1];
+  const int c2 = static_cast<int>(v) / plane, rem = static_cast<int>(v) - c2 * plane;
+  const int c1 = rem / g.dim[0];
+  dda_brick_of(g, rem - c1 * g.dim[0], c1, c2, brick, bit);
+}
+
+// ---- the host forms' stable counting sort: key[i] < n_keys -> start (n_keys + 1 run delimiters) and order (the element
+// indices run by run, ascending inside a run — what the device's stable radix sort of (key, index) leaves) ------------------
+inline void counting_sort(const std::vector<uint32_t>& key, size_t n_keys, std::vector<uint32_t>& start, std::vector<uint32_t>& order)
+{
+  start.assign(n_keys + 1, 0);
+  for (const uint32_t k : key)
+    ++start[k + 1];
+  for (size_t k = 0; k < n_keys; ++k)
+    start[k + 1] += start[k];
+  std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+  order.resize(key.size());
+  for (size_t i = 0; i < key.size(); ++i)
+    order[fill[key[i]]++] = static_cast<uint32_t>(i);
 }
 }  // namespace mcl3dl

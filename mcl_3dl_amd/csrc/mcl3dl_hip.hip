@@ -28,14 +28,14 @@ using namespace mcl3dl;
 
 #include "host_options.h"
 #include "host_context.h"
+#include "host_cloud.h"
 #include "host_map_compilers.h"
+#include "host_grid_builders.h"
 #include "host_measure.h"
 #include "host_pf.h"
 #include "host_rng.h"
-#include "host_cloud.h"
 #include "host_weighted.h"
 #include "host_shuffle.h"
-#include "host_grid_builders.h"
 #include "host_group.h"
 
 // =================================================================================================================
