@@ -188,9 +188,7 @@ int mcl3dl_hip_group_global_localization(mcl3dl_hip_group* g, double grid, int d
   // ---- steps 1-3 on every rank (the map is replicated; deterministic, so no collective): nothing resident is touched yet
   std::vector<size_t> pts(N, 0);
   TRY(group_run(g, [&](int r) -> int { return mcl3dl_hip_global_localization_points(g->ctx[r], grid, nullptr, 0, &pts[r], nullptr); }));
-  for (int r = 1; r < N; ++r)
-    if (pts[r] != pts[0])
-      return g->fail(-4, "the ranks disagree on the standable points (%zu and %zu): are their maps the same?", pts[0], pts[r]);
+  TRY(group_agree(g, "the standable points: are their maps the same?", pts.data(), 1));
   if (n_points)
     *n_points = pts[0];
   const size_t n_p = pts[0] * static_cast<size_t>(div_yaw);
@@ -202,33 +200,21 @@ int mcl3dl_hip_group_global_localization(mcl3dl_hip_group* g, double grid, int d
     return g->fail(-3, "%zu points x %d = %zu particles needed, more than resident particles can be (%u)", pts[0], div_yaw, n_p,
                    0x7fffffffu / 16);
   // ---- step 4: every rank seeds its own shard; the group is left as mcl3dl_hip_group_upload_state leaves it
-  g->n_resident = 0;
-  g->rs_begun = g->rs_planned = false;
-  g->noise_on = false;  // fresh State6DOF: no odometry noise
-  TRY(group_run_shards(
-      g, n_p,
-      [&](const Shard& s) -> int
-      {
-        mcl3dl_hip_ctx* ctx = s.ctx;
-        const size_t lo = s.lo, n = s.n;
-        HIP_TRY(hipSetDevice(ctx->device));
-        ctx->gs_n = 0;
-        ctx->gs_cur = 0;
-        if (n == 0)
-          return 0;
-        const size_t cap_count = (n_p + N - 1) / N;  // room for the largest shard (the resampling step's all-gather)
-        TRY(ensure(ctx, ctx->gs_state[0], sizeof(float) * 13 * cap_count));
-        TRY(ensure(ctx, ctx->gs_weight, sizeof(float) * cap_count));
-        ctx->poses_set(0);
-        TRY(ensure(ctx, ctx->pose, sizeof(float) * 7 * n));
-        TRY(mcl3dl_hip_global_localization_seed_device(ctx, div_yaw, imu_quat4, lo, n, ctx->gs_state[0].as<float>(),
-                                                       ctx->pose.as<float>(), ctx->gs_weight.as<float>()));
-        ctx->poses_set(n);
-        ctx->pose_resident = true;
-        ctx->gs_n = n;
-        return 0;
-      }));
-  g->n_resident = n_p;
-  g->n_pose_uploaded = n_p;
+  generation_begin(g);
+  TRY(group_run_shards(g, n_p,
+                       [&](const Shard& s) -> int
+                       {
+                         mcl3dl_hip_ctx* ctx = s.ctx;
+                         TRY(generation_rank_begin(ctx, n_p, N));
+                         if (s.n == 0)
+                           return 0;
+                         ctx->poses_set(0);
+                         TRY(ensure(ctx, ctx->pose, sizeof(float) * 7 * s.n));
+                         TRY(mcl3dl_hip_global_localization_seed_device(ctx, div_yaw, imu_quat4, s.lo, s.n,
+                                                                        ctx->gs_state[0].as<float>(), ctx->pose.as<float>(),
+                                                                        ctx->gs_weight.as<float>()));
+                         return generation_rank_installed(ctx, s.n, true);  // (the seeding launch wrote the poses)
+                       }));
+  generation_installed(g, n_p);
   return 0;
 }

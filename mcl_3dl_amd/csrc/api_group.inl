@@ -93,13 +93,8 @@ int mcl3dl_hip_group_set_likelihood_params(mcl3dl_hip_group* g, float match_dist
 {
   if (!g)
     return -1;
-  for (int r = 0; r < g->n(); ++r)
-  {
-    const int rc = mcl3dl_hip_set_likelihood_params(g->ctx[r], match_dist_min, match_dist_flat, match_weight);
-    if (rc)
-      return g->fail_rank(rc, r);
-  }
-  return 0;
+  return group_forward(g, [&](mcl3dl_hip_ctx* ctx, int)
+                       { return mcl3dl_hip_set_likelihood_params(ctx, match_dist_min, match_dist_flat, match_weight); });
 }
 
 int mcl3dl_hip_group_set_beam_params(mcl3dl_hip_group* g, float map_grid_x, float map_grid_y, float map_grid_z,
@@ -109,28 +104,20 @@ int mcl3dl_hip_group_set_beam_params(mcl3dl_hip_group* g, float map_grid_x, floa
 {
   if (!g)
     return -1;
-  for (int r = 0; r < g->n(); ++r)
-  {
-    const int rc = mcl3dl_hip_set_beam_params(g->ctx[r], map_grid_x, map_grid_y, map_grid_z, dda_grid_size, ray_angle_half,
-                                              hit_range, beam_likelihood_min, num_points, ang_total_ref, filter_label_max,
-                                              add_penalty_short_only_mode);
-    if (rc)
-      return g->fail_rank(rc, r);
-  }
-  return 0;
+  return group_forward(g,
+                       [&](mcl3dl_hip_ctx* ctx, int)
+                       {
+                         return mcl3dl_hip_set_beam_params(ctx, map_grid_x, map_grid_y, map_grid_z, dda_grid_size, ray_angle_half,
+                                                           hit_range, beam_likelihood_min, num_points, ang_total_ref,
+                                                           filter_label_max, add_penalty_short_only_mode);
+                       });
 }
 
 int mcl3dl_hip_group_set_beam_raycast(mcl3dl_hip_group* g, int mode)
 {
   if (!g)
     return -1;
-  for (int r = 0; r < g->n(); ++r)
-  {
-    const int rc = mcl3dl_hip_set_beam_raycast(g->ctx[r], mode);
-    if (rc)
-      return g->fail_rank(rc, r);
-  }
-  return 0;
+  return group_forward(g, [&](mcl3dl_hip_ctx* ctx, int) { return mcl3dl_hip_set_beam_raycast(ctx, mode); });
 }
 
 int mcl3dl_hip_group_set_option(mcl3dl_hip_group* g, const char* name, double value)
@@ -158,13 +145,7 @@ int mcl3dl_hip_group_set_option(mcl3dl_hip_group* g, const char* name, double va
     g->inject_failure_rank = static_cast<int>(value);
     return 0;
   }
-  for (int r = 0; r < g->n(); ++r)
-  {
-    const int rc = mcl3dl_hip_set_option(g->ctx[r], name, value);
-    if (rc)
-      return g->fail_rank(rc, r);
-  }
-  return 0;
+  return group_forward(g, [&](mcl3dl_hip_ctx* ctx, int) { return mcl3dl_hip_set_option(ctx, name, value); });
 }
 
 int mcl3dl_hip_group_collective_stats(const mcl3dl_hip_group* g, uint64_t* rccl_all_reduces, uint64_t* host_combines)
@@ -209,12 +190,11 @@ int mcl3dl_hip_group_measure_batch(mcl3dl_hip_group* g, const float* pose, size_
   if (!pose && g->n_pose_uploaded != n_p)
     return g->fail(-3, "null pose array (and mcl3dl_hip_group_upload_poses holds %zu poses, not %zu)", g->n_pose_uploaded,
                    n_p);
-  if (g->n() == 1 && g->direct_single)
-  {
-    const int rc = mcl3dl_hip_measure_batch(g->ctx[0], pose, n_p, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b,
-                                            origins, n_o, out_lik, out_match_ratio, out_beam);
-    return rc ? g->fail_rank(rc, 0) : 0;
-  }
+  if (g->route() == ROUTE_DIRECT)
+    return group_forward(g, [&](mcl3dl_hip_ctx* ctx, int) {
+      return mcl3dl_hip_measure_batch(ctx, pose, n_p, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o,
+                                      out_lik, out_match_ratio, out_beam);
+    });
   const bool device_order = scan_ordered_on_device(g->ctx[0]->opt, n_s, n_b);
   const HostScan scan{ scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o };
   std::string err;
@@ -262,12 +242,12 @@ int mcl3dl_hip_group_measure_batch_begin(mcl3dl_hip_group* g, const float* pose,
   if (!pose && n_p && g->n_pose_uploaded != n_p)
     return g->fail(-3, "null pose array (and mcl3dl_hip_group_upload_poses holds %zu poses, not %zu)", g->n_pose_uploaded,
                    n_p);
-  if (g->n() == 1 && g->direct_single)
+  if (g->route() == ROUTE_DIRECT)
   {
-    const int rc = mcl3dl_hip_measure_batch_begin(g->ctx[0], pose, n_p, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b,
-                                                  origins, n_o, out_lik, out_match_ratio, out_beam, slice_particles);
-    if (rc)
-      return g->fail_rank(rc, 0);
+    TRY(group_forward(g, [&](mcl3dl_hip_ctx* ctx, int) {
+      return mcl3dl_hip_measure_batch_begin(ctx, pose, n_p, scan_lik_xyz, n_s, scan_beam_xyz, scan_beam_origin, n_b, origins, n_o,
+                                            out_lik, out_match_ratio, out_beam, slice_particles);
+    }));
     g->prog_n_p = n_p;
     g->prog_direct = true;
     return 0;
@@ -317,10 +297,7 @@ int mcl3dl_hip_group_measure_batch_wait(mcl3dl_hip_group* g, size_t particle, si
   if (particle >= g->prog_n_p)
     return g->fail(-3, "particle %zu is not part of the batch (%zu particles)", particle, g->prog_n_p);
   if (g->prog_direct)
-  {
-    const int rc = mcl3dl_hip_measure_batch_wait(g->ctx[0], particle, n_ready);
-    return rc ? g->fail_rank(rc, 0) : 0;
-  }
+    return group_forward(g, [&](mcl3dl_hip_ctx* ctx, int) { return mcl3dl_hip_measure_batch_wait(ctx, particle, n_ready); });
   if (!g->prog_sharded)
   {
     if (n_ready)
@@ -455,8 +432,7 @@ int update_phase_a(GroupUpdate& u, const Shard& s)
   const float* extra = u.extra;
   if (resident && n)
   {
-    if (ctx->gs_n != n)
-      return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, n);
+    TRY(rank_holds(ctx, n));
     // ctx->pose is shared with the non-resident calls (uploads, mcl3dl_hip_group_measure_update, moments of explicit
     // states): whoever wrote it last, the poses evaluated here are those of the resident states
     TRY(resident_poses(ctx));
@@ -576,8 +552,8 @@ int update_phase_b(GroupUpdate& u, const Shard& s)
 int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, const float* extra, size_t n_p, const HostScan& scan,
                       const UpdateOutputs& out, bool prepared = false)
 {
-  if (resident && g->n_resident == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  if (resident)
+    TRY(group_resident(g));
   if (n_p == 0)
     return g->fail(-3, "no particles");
   if (!resident && (!pose || !out.weight))
@@ -585,13 +561,12 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
   if (resident && g->n_resident != n_p)
     return g->fail(-5, "%zu particles are resident on the group's devices, not %zu (mcl3dl_hip_group_upload_state first)",
                    g->n_resident, n_p);
-  if (!resident && g->n() == 1 && g->direct_single)
-  {
-    const int rc = mcl3dl_hip_measure_update(g->ctx[0], pose, extra, out.weight, n_p, scan.scan_lik_xyz, scan.n_s, scan.scan_beam_xyz,
-                                             scan.scan_beam_origin, scan.n_b, scan.origins, scan.n_o, out.lik, out.match_ratio,
-                                             out.beam, out.entropy, out.match_ratio_min, out.match_ratio_max, out.restored);
-    return rc ? g->fail_rank(rc, 0) : 0;
-  }
+  if (!resident && g->route() == ROUTE_DIRECT)
+    return group_forward(g, [&](mcl3dl_hip_ctx* ctx, int) {
+      return mcl3dl_hip_measure_update(ctx, pose, extra, out.weight, n_p, scan.scan_lik_xyz, scan.n_s, scan.scan_beam_xyz,
+                                       scan.scan_beam_origin, scan.n_b, scan.origins, scan.n_o, out.lik, out.match_ratio, out.beam,
+                                       out.entropy, out.match_ratio_min, out.match_ratio_max, out.restored);
+    });
   const size_t N = static_cast<size_t>(g->n());
   GroupUpdate u{ g, resident, prepared, pose, extra, n_p, scan, out };
   u.device_order = scan_ordered_on_device(g->ctx[0]->opt, scan.n_s, scan.n_b);
@@ -606,7 +581,8 @@ int group_update_impl(mcl3dl_hip_group* g, bool resident, const float* pose, con
   TRY(group_allreduce_record(
       g, "update", n_p, [&u](const Shard& s) { return update_phase_a(u, s); }, [&u](const Shard& s) { return update_phase_b(u, s); }));
   g->n_pose_uploaded = n_p;
-  unpack_stats4(&u.stats[4 * first_nonempty_rank(n_p)], out.entropy, out.match_ratio_min, out.match_ratio_max, out.restored);
+  // (every rank computed the same scalars from the same record; rank 0 always holds a particle)
+  unpack_stats4(&u.stats[0], out.entropy, out.match_ratio_min, out.match_ratio_max, out.restored);
   return 0;
 }
 }  // namespace

@@ -43,6 +43,12 @@ inline dim3 grid_of(size_t n)
 {
   return dim3(static_cast<unsigned>((n + 255) / 256));
 }
+
+// room for the noise of the LARGEST shard on every rank, an empty one included: the resampling step's all-gather sends that many
+int odom_noise_room(mcl3dl_hip_ctx* ctx, size_t n_p, int world)
+{
+  return ensure(ctx, ctx->gs_noise[ctx->gs_cur], sizeof(float) * 4 * shard_capacity(n_p, world));
+}
 }  // namespace
 
 int mcl3dl_hip_group_set_odom_noise(mcl3dl_hip_group* g, const float* noise4, size_t n_p)
@@ -53,15 +59,13 @@ int mcl3dl_hip_group_set_odom_noise(mcl3dl_hip_group* g, const float* noise4, si
     return g->fail(-3, "null noise array");
   if (g->n_resident == 0 || g->n_resident != n_p)
     return g->fail(-5, "%zu particles are resident, %zu noise records given", g->n_resident, n_p);
-  const int N = g->n();
   const int rc = group_run_shards(
       g, n_p,
       [&](const Shard& s) -> int
       {
         mcl3dl_hip_ctx* ctx = s.ctx;
         HIP_TRY(hipSetDevice(ctx->device));
-        // (room for the LARGEST shard on every rank, an empty one included: the resampling step's all-gather sends that many)
-        TRY(ensure(ctx, ctx->gs_noise[ctx->gs_cur], sizeof(float) * 4 * ((n_p + N - 1) / N)));
+        TRY(odom_noise_room(ctx, n_p, g->n()));
         if (s.n == 0)
           return 0;
         TRY(h2d(ctx, ctx->gs_noise[ctx->gs_cur].p, noise4 + 4 * s.lo, sizeof(float) * 4 * s.n));
@@ -116,8 +120,7 @@ int mcl3dl_hip_group_predict(mcl3dl_hip_group* g, const float* odom_prev7, const
                                                noise ? ctx->gs_noise[ctx->gs_cur].as<float>() : static_cast<float*>(nullptr),
                                                static_cast<int>(n), m, ctx->pose.as<float>());
                             HIP_TRY(hipGetLastError());
-                            ctx->poses_set(n);
-                            ctx->pose_resident = true;
+                            pose_mirror_stamp(ctx, n);
                             return sync_stream(ctx);
                           });
 }
@@ -145,8 +148,7 @@ int add_noise_launch(mcl3dl_hip_ctx* ctx, size_t n)
   hipLaunchKernelGGL(add_noise_kernel, grid_of(n), dim3(256), 0, ctx->stream, ctx->gs_state[ctx->gs_cur].as<float>(),
                      ctx->rs_d_noise.as<float>(), static_cast<int>(n), ctx->pose.as<float>());
   HIP_TRY(hipGetLastError());
-  ctx->poses_set(n);
-  ctx->pose_resident = true;
+  pose_mirror_stamp(ctx, n);
   return sync_stream(ctx);
 }
 }  // namespace
@@ -208,32 +210,28 @@ int group_measure_resident(mcl3dl_hip_group* g, const char* what, const ShardMod
       TRY(d2h(ctx, out_lik + s.lo, ctx->lik.p, sizeof(float) * s.n));
     return sync_stream(ctx);
   };
-  if (N == 1 && g->direct_single)
-  {
+  if (g->route() == ROUTE_DIRECT)
     // one device: pf::measure as mcl3dl_hip_group_update_resident's single-GPU form runs it (pf_one_gpu: the fused
     // work-group up to PF_FUSED_MAX_PARTICLES particles, else partial + apply), the likelihood formed inside — one or two launches
-    mcl3dl_hip_ctx* ctx = g->ctx[0];
-    const int rc = [&]() -> int
-    {
-      HIP_TRY(hipSetDevice(ctx->device));
-      const size_t n = ctx->gs_n;
-      if (n != n_p)
-        return ctx->fail(-5, "this device holds %zu resident particles, not %zu", n, n_p);
-      TRY(ensure(ctx, ctx->lik, sizeof(float) * n));
-      TRY(ensure(ctx, ctx->partial4, sizeof(double) * 4));
-      TRY(ensure(ctx, ctx->stats4, sizeof(float) * 4));
-      ImuGravity m{};
-      const float* d_lik = nullptr;
-      TRY(model(ctx, n, &d_lik, &m));
-      // (the first kernel reads the likelihoods only)
-      PfCall c{ ctx, ctx->gs_weight.as<float>(), const_cast<float*>(d_lik), nullptr, nullptr, nullptr, n, ctx->stats4.as<float>() };
-      c.model = &m;
-      TRY(pf_one_gpu(c));
-      return fetch(Shard{ ctx, 0, 0, n });
-    }();
-    if (rc)
-      return g->fail_rank(rc, 0);
-  }
+    TRY(group_forward(
+        g,
+        [&](mcl3dl_hip_ctx* ctx, int) -> int
+        {
+          HIP_TRY(hipSetDevice(ctx->device));
+          TRY(rank_holds(ctx, n_p));
+          TRY(ensure(ctx, ctx->lik, sizeof(float) * n_p));
+          TRY(ensure(ctx, ctx->partial4, sizeof(double) * 4));
+          TRY(ensure(ctx, ctx->stats4, sizeof(float) * 4));
+          ImuGravity m{};
+          const float* d_lik = nullptr;
+          TRY(model(ctx, n_p, &d_lik, &m));
+          // (the first kernel reads the likelihoods only)
+          PfCall c{ ctx, ctx->gs_weight.as<float>(), const_cast<float*>(d_lik), nullptr, nullptr, nullptr, n_p,
+                    ctx->stats4.as<float>() };
+          c.model = &m;
+          TRY(pf_one_gpu(c));
+          return fetch(Shard{ ctx, 0, 0, n_p });
+        }));
   else
     TRY(group_allreduce_record(
         g, what, n_p,
@@ -243,8 +241,7 @@ int group_measure_resident(mcl3dl_hip_group* g, const char* what, const ShardMod
           TRY(ensure(ctx, ctx->stats4, sizeof(float) * 4));
           if (s.n == 0)
             return pf_first_half_empty(ctx, s.r, N, ctx->packed.as<double>());
-          if (ctx->gs_n != s.n)
-            return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, s.n);
+          TRY(rank_holds(ctx, s.n));
           TRY(ensure(ctx, ctx->lik, sizeof(float) * s.n));
           ImuGravity m{};
           const float* d_lik = nullptr;
@@ -263,8 +260,8 @@ int group_measure_resident(mcl3dl_hip_group* g, const char* what, const ShardMod
           TRY(pf_second_half(c, N, s.ctx->packed.as<double>()));
           return fetch(s);
         }));
-  // every rank computed the same scalars from the same record
-  unpack_stats4(&stats[4 * first_nonempty_rank(n_p)], entropy, nullptr, nullptr, restored);
+  // every rank computed the same scalars from the same record; rank 0 always holds a particle
+  unpack_stats4(&stats[0], entropy, nullptr, nullptr, restored);
   return 0;
 }
 }  // namespace
@@ -276,8 +273,7 @@ int mcl3dl_hip_group_measure_imu(mcl3dl_hip_group* g, const float* acc3, float a
     return -1;
   if (!acc3)
     return g->fail(-3, "null acceleration");
-  if (g->n_resident == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  TRY(group_resident(g));
   // ImuMeasurementModelGravity(acc_var) + setAccMeasure(acc) (imu_measurement_model_gravity.h:41-48)
   ImuGravity imu{};
   imu.acc = Vec3f{ acc3[0], acc3[1], acc3[2] };
@@ -383,8 +379,7 @@ int mcl3dl_hip_group_measure_landmark(mcl3dl_hip_group* g, const float* measured
   for (int k = 0; k < 7; ++k)
     if (!std::isfinite(measured7[k]))
       return g->fail(-3, "non-finite landmark pose");
-  if (g->n_resident == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  TRY(group_resident(g));
   LandmarkModel lm{};
   if (!landmark_normal_constants(cov36, &lm.a, lm.sinv))
     return g->fail(-3, "landmark covariance: non-finite, singular or without a positive determinant");

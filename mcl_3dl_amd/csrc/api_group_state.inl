@@ -22,20 +22,11 @@ __global__ void state13_to_pose7_kernel(const float* __restrict__ state13, int n
     pose7[7 * static_cast<size_t>(i) + k] = state13[13 * static_cast<size_t>(i) + k];
 }
 
-// padded all-gather layout [rank][max_count][width] -> flat particle order (shards differ in size by at most one); width 13 for
-// the states, 4 for the odometry noise
-__global__ void unpad_states_kernel(const float* __restrict__ padded, size_t max_count, size_t base, size_t rem, size_t n,
-                                    float* __restrict__ flat, size_t width = 13)
+// ctx->pose holds the poses of this rank's n resident states: the launch that wrote the states wrote it too, or rebuild_pose did
+void pose_mirror_stamp(mcl3dl_hip_ctx* ctx, size_t n)
 {
-  const size_t t = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= width * n)
-    return;
-  const size_t i = t / width, k = t % width;
-  // owner of particle i under shard_bounds: the first `rem` shards hold base + 1 particles
-  const size_t split = rem * (base + 1);
-  const size_t r = i < split ? i / (base + 1) : rem + (base ? (i - split) / base : 0);
-  const size_t lo = r * base + (r < rem ? r : rem);
-  flat[t] = padded[(r * max_count + (i - lo)) * width + k];
+  ctx->poses_set(n);
+  ctx->pose_resident = true;
 }
 
 int rebuild_pose(mcl3dl_hip_ctx* ctx, size_t n)
@@ -48,8 +39,7 @@ int rebuild_pose(mcl3dl_hip_ctx* ctx, size_t n)
   hipLaunchKernelGGL(state13_to_pose7_kernel, dim3((ni + 255) / 256), dim3(256), 0, ctx->stream,
                      ctx->gs_state[ctx->gs_cur].as<float>(), ni, ctx->pose.as<float>());
   HIP_TRY(hipGetLastError());
-  ctx->poses_set(n);
-  ctx->pose_resident = true;
+  pose_mirror_stamp(ctx, n);
   return 0;
 }
 
@@ -61,6 +51,70 @@ int resident_poses(mcl3dl_hip_ctx* ctx)
     return rebuild_pose(ctx, ctx->gs_n);
   return 0;
 }
+
+// every one of the rank's n resident particles weighs `value`
+int uniform_weights(mcl3dl_hip_ctx* ctx, size_t n, float value)
+{
+  hipLaunchKernelGGL(fill_kernel, dim3((static_cast<int>(n) + 255) / 256), dim3(256), 0, ctx->stream, ctx->gs_weight.as<float>(),
+                     value, static_cast<float*>(nullptr), 0.0f, static_cast<int>(n));
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// ---- a new generation of resident particles is installed in four steps: the group forgets the old one (with it the plan made
+// for it and the odometry noise: fresh State6DOFs carry none); every rank does, and makes room; every rank that filled its shard
+// marks it; the group takes the new count.
+void generation_begin(mcl3dl_hip_group* g)
+{
+  g->n_resident = 0;
+  g->rs_begun = g->rs_planned = false;
+  g->noise_on = false;
+}
+
+// (room for the LARGEST shard on every rank, an empty one included: the resampling step's all-gathers send that many from each)
+int generation_rank_begin(mcl3dl_hip_ctx* ctx, size_t n_p, int world)
+{
+  HIP_TRY(hipSetDevice(ctx->device));
+  ctx->gs_n = 0;
+  ctx->gs_cur = 0;
+  const size_t cap = shard_capacity(n_p, world);
+  TRY(ensure(ctx, ctx->gs_state[0], sizeof(float) * 13 * cap));
+  return ensure(ctx, ctx->gs_weight, sizeof(float) * cap);
+}
+
+// gs_state[gs_cur] holds the rank's n new states. pose_written: the launch that filled them wrote the pose mirror as well.
+int generation_rank_installed(mcl3dl_hip_ctx* ctx, size_t n, bool pose_written)
+{
+  if (pose_written)
+    pose_mirror_stamp(ctx, n);
+  else
+    TRY(rebuild_pose(ctx, n));
+  ctx->gs_n = n;
+  return 0;
+}
+
+void generation_installed(mcl3dl_hip_group* g, size_t n_p)
+{
+  g->n_resident = n_p;
+  g->n_pose_uploaded = n_p;
+}
+
+// what the three gathers of the resampling steps bring into particle order (host_group_gather.h)
+ShardedArray resident_states(mcl3dl_hip_group* g, mcl3dl_hip_ctx* ctx)
+{
+  return { 13, &ctx->gs_state[ctx->gs_cur], &ctx->gs_pad, &ctx->gs_all, &g->h_state, "shard", "ncclAllGather" };
+}
+
+ShardedArray resident_noise(mcl3dl_hip_group* g, mcl3dl_hip_ctx* ctx)
+{
+  return { 4,       &ctx->gs_noise[ctx->gs_cur],     &ctx->gs_noise_pad, &ctx->gs_noise_all, &g->h_noise,
+           "noise", "ncclAllGather (odometry noise)" };
+}
+
+ShardedArray resident_weights(mcl3dl_hip_group* g, mcl3dl_hip_ctx* ctx)
+{
+  return { 1, &ctx->gs_weight, &ctx->rs_d_wpad, &ctx->rs_d_w, &g->h_weight, "weight", "ncclAllGather (weights)" };
+}
 }  // namespace
 
 int mcl3dl_hip_group_upload_state(mcl3dl_hip_group* g, const float* state13, const float* weight, size_t n_p)
@@ -69,38 +123,23 @@ int mcl3dl_hip_group_upload_state(mcl3dl_hip_group* g, const float* state13, con
     return -1;
   if (!state13 || n_p == 0 || n_p > 0x7fffffffu / 16)
     return g->fail(-3, "bad state array");
-  g->n_resident = 0;
-  g->rs_begun = g->rs_planned = false;
-  g->noise_on = false;  // State6DOF's constructors: no odometry noise until set_odom_noise
-  const int N = g->n();
-  TRY(group_run_shards(
-      g, n_p,
-      [&](const Shard& s) -> int
-      {
-        mcl3dl_hip_ctx* ctx = s.ctx;
-        const size_t lo = s.lo, n = s.n;
-        HIP_TRY(hipSetDevice(ctx->device));
-        ctx->gs_n = 0;
-        ctx->gs_cur = 0;
-        if (n == 0)
-          return 0;
-        // (room for the LARGEST shard on every rank: the all-gather of the resampling step sends that many states)
-        const size_t cap_count = (n_p + N - 1) / N;
-        TRY(ensure(ctx, ctx->gs_state[0], sizeof(float) * 13 * cap_count));
-        TRY(ensure(ctx, ctx->gs_weight, sizeof(float) * cap_count));
-        TRY(h2d(ctx, ctx->gs_state[0].p, state13 + 13 * lo, sizeof(float) * 13 * n));
-        if (weight)
-          TRY(h2d(ctx, ctx->gs_weight.p, weight + lo, sizeof(float) * n));
-        else
-          hipLaunchKernelGGL(fill_kernel, dim3((static_cast<int>(n) + 255) / 256), dim3(256), 0, ctx->stream,
-                             ctx->gs_weight.as<float>(), 1.0f / static_cast<float>(n_p), static_cast<float*>(nullptr), 0.0f,
-                             static_cast<int>(n));
-        TRY(rebuild_pose(ctx, n));
-        ctx->gs_n = n;
-        return sync_stream(ctx);
-      }));
-  g->n_resident = n_p;
-  g->n_pose_uploaded = n_p;
+  generation_begin(g);
+  TRY(group_run_shards(g, n_p,
+                       [&](const Shard& s) -> int
+                       {
+                         mcl3dl_hip_ctx* ctx = s.ctx;
+                         TRY(generation_rank_begin(ctx, n_p, g->n()));
+                         if (s.n == 0)
+                           return 0;
+                         TRY(h2d(ctx, ctx->gs_state[0].p, state13 + 13 * s.lo, sizeof(float) * 13 * s.n));
+                         if (weight)
+                           TRY(h2d(ctx, ctx->gs_weight.p, weight + s.lo, sizeof(float) * s.n));
+                         else
+                           TRY(uniform_weights(ctx, s.n, 1.0f / static_cast<float>(n_p)));
+                         TRY(generation_rank_installed(ctx, s.n, false));
+                         return sync_stream(ctx);
+                       }));
+  generation_installed(g, n_p);
   return 0;
 }
 
@@ -110,21 +149,15 @@ int mcl3dl_hip_group_download_state(mcl3dl_hip_group* g, float* state13, float* 
     return -1;
   if (g->n_resident == 0 || g->n_resident != n_p)
     return g->fail(-5, "%zu particles are resident, %zu asked for", g->n_resident, n_p);
-  return group_run_shards(
-      g, n_p,
-      [&](const Shard& s) -> int
-      {
-        mcl3dl_hip_ctx* ctx = s.ctx;
-        const size_t lo = s.lo, n = s.n;
-        if (n == 0)
-          return 0;
-        HIP_TRY(hipSetDevice(ctx->device));
-        if (state13)
-          TRY(d2h(ctx, state13 + 13 * lo, ctx->gs_state[ctx->gs_cur].p, sizeof(float) * 13 * n));
-        if (weight)
-          TRY(d2h(ctx, weight + lo, ctx->gs_weight.p, sizeof(float) * n));
-        return sync_stream(ctx);
-      });
+  return group_each_shard(g,
+                          [&](mcl3dl_hip_ctx* ctx, int, size_t lo, size_t n) -> int
+                          {
+                            if (state13)
+                              TRY(d2h(ctx, state13 + 13 * lo, ctx->gs_state[ctx->gs_cur].p, sizeof(float) * 13 * n));
+                            if (weight)
+                              TRY(d2h(ctx, weight + lo, ctx->gs_weight.p, sizeof(float) * n));
+                            return sync_stream(ctx);
+                          });
 }
 
 size_t mcl3dl_hip_group_resident(const mcl3dl_hip_group* g)
@@ -153,25 +186,41 @@ namespace
 // f(ctx, rank) on every rank; a group of one device that may call its context directly makes the plain call
 int group_scan_each(mcl3dl_hip_group* g, const std::function<int(mcl3dl_hip_ctx*, int)>& f)
 {
-  if (g->n() == 1 && g->direct_single)
-  {
-    const int rc = f(g->ctx[0], 0);
-    return rc ? g->fail_rank(rc, 0) : 0;
-  }
-  return group_run(g, [&](int r) -> int { return f(g->ctx[r], r); });
+  return g->route() == ROUTE_DIRECT ? group_forward(g, f) : group_run(g, [&](int r) -> int { return f(g->ctx[r], r); });
 }
 
-// three sizes per rank -> the caller's, when all ranks agree (rng_hand_back's rule for the engine state)
-int group_scan_sizes(mcl3dl_hip_group* g, const std::vector<size_t>& got, const char* what, size_t* a, size_t* b, size_t* c)
+// f(ctx, the rank's three sizes) on every rank -> the caller's a, b, c, when all ranks agree on `what`
+int group_scan_sizes(mcl3dl_hip_group* g, const char* what, const std::function<int(mcl3dl_hip_ctx*, size_t*)>& f, size_t* a,
+                     size_t* b, size_t* c)
 {
-  for (int r = 1; r < g->n(); ++r)
-    for (int k = 0; k < 3; ++k)
-      if (got[3 * r + k] != got[k])
-        return g->fail(-4, "the ranks disagree on %s (%zu on rank 0, %zu on rank %d)", what, got[k], got[3 * r + k], r);
+  std::vector<size_t> got(3 * static_cast<size_t>(g->n()), 0);
+  TRY(group_scan_each(g, [&](mcl3dl_hip_ctx* ctx, int r) -> int { return f(ctx, &got[3 * r]); }));
+  TRY(group_agree(g, what, got.data(), 3));
   size_t* out[3] = { a, b, c };
   for (int k = 0; k < 3; ++k)
     if (out[k])
       *out[k] = got[k];
+  return 0;
+}
+
+// ... for the samplers that draw: f(ctx, engine state, n_s installed, n_b installed), every rank from the same engine state
+int group_scan_drawn(mcl3dl_hip_group* g, uint32_t* engine_state, size_t* out_n_s, size_t* out_n_b,
+                     const std::function<int(mcl3dl_hip_ctx*, uint32_t*, size_t*, size_t*)>& f)
+{
+  if (!engine_state)
+    return g->fail(-3, "null engine_state");
+  size_t state = 0;
+  TRY(group_scan_sizes(
+      g, "the drawn scans or the engine state behind them",
+      [&](mcl3dl_hip_ctx* ctx, size_t* got) -> int
+      {
+        uint32_t st = *engine_state;
+        TRY(f(ctx, &st, &got[0], &got[1]));
+        got[2] = st;
+        return 0;
+      },
+      out_n_s, out_n_b, &state));
+  *engine_state = static_cast<uint32_t>(state);
   return 0;
 }
 }  // namespace
@@ -183,13 +232,10 @@ int mcl3dl_hip_group_scan_begin(mcl3dl_hip_group* g, const float* xyz, const uin
 {
   if (!g)
     return -1;
-  std::vector<size_t> got(3 * static_cast<size_t>(g->n()), 0);
-  TRY(group_scan_each(g,
-                      [&](mcl3dl_hip_ctx* ctx, int r) -> int {
-                        return mcl3dl_hip_scan_begin(ctx, xyz, label, n, leaf3, clip_lik4, clip_beam4, &got[3 * r], &got[3 * r + 1],
-                                                     &got[3 * r + 2]);
-                      }));
-  return group_scan_sizes(g, got, "the sizes of the prepared clouds", n_full, n_lik_clipped, n_beam_clipped);
+  return group_scan_sizes(
+      g, "the sizes of the prepared clouds", [&](mcl3dl_hip_ctx* ctx, size_t* got) -> int
+      { return mcl3dl_hip_scan_begin(ctx, xyz, label, n, leaf3, clip_lik4, clip_beam4, &got[0], &got[1], &got[2]); },
+      n_full, n_lik_clipped, n_beam_clipped);
 }
 
 int mcl3dl_hip_group_scan_begin_pointcloud2(mcl3dl_hip_group* g, const uint8_t* data, size_t n_points, uint32_t point_step,
@@ -199,15 +245,14 @@ int mcl3dl_hip_group_scan_begin_pointcloud2(mcl3dl_hip_group* g, const uint8_t* 
 {
   if (!g)
     return -1;
-  std::vector<size_t> got(3 * static_cast<size_t>(g->n()), 0);
-  TRY(group_scan_each(g,
-                      [&](mcl3dl_hip_ctx* ctx, int r) -> int
-                      {
-                        return mcl3dl_hip_scan_begin_pointcloud2(ctx, data, n_points, point_step, off_x, off_y, off_z, off_label,
-                                                                 label_override, leaf3, clip_lik4, clip_beam4, &got[3 * r],
-                                                                 &got[3 * r + 1], &got[3 * r + 2]);
-                      }));
-  return group_scan_sizes(g, got, "the sizes of the prepared clouds", n_full, n_lik_clipped, n_beam_clipped);
+  return group_scan_sizes(
+      g, "the sizes of the prepared clouds",
+      [&](mcl3dl_hip_ctx* ctx, size_t* got) -> int
+      {
+        return mcl3dl_hip_scan_begin_pointcloud2(ctx, data, n_points, point_step, off_x, off_y, off_z, off_label, label_override,
+                                                 leaf3, clip_lik4, clip_beam4, &got[0], &got[1], &got[2]);
+      },
+      n_full, n_lik_clipped, n_beam_clipped);
 }
 
 // ---- the accumulation of clouds on a group: every rank holds its replica (accumClear / accumCloud, src/mcl_3dl.cpp:267-302).
@@ -224,10 +269,9 @@ int mcl3dl_hip_group_scan_accum_push(mcl3dl_hip_group* g, const float* xyz, size
 {
   if (!g)
     return -1;
-  std::vector<size_t> got(3 * static_cast<size_t>(g->n()), 0);  // {cloud index, total points, -}
-  TRY(group_scan_each(g, [&](mcl3dl_hip_ctx* ctx, int r) -> int
-                      { return mcl3dl_hip_scan_accum_push(ctx, xyz, n, affine12, &got[3 * r], &got[3 * r + 1]); }));
-  return group_scan_sizes(g, got, "the accumulated clouds", out_cloud_index, out_total_points, nullptr);
+  return group_scan_sizes(  // {cloud index, total points, -}
+      g, "the accumulated clouds", [&](mcl3dl_hip_ctx* ctx, size_t* got) -> int
+      { return mcl3dl_hip_scan_accum_push(ctx, xyz, n, affine12, &got[0], &got[1]); }, out_cloud_index, out_total_points, nullptr);
 }
 
 int mcl3dl_hip_group_scan_accum_push_pointcloud2(mcl3dl_hip_group* g, const uint8_t* data, size_t n_points, uint32_t point_step,
@@ -236,24 +280,23 @@ int mcl3dl_hip_group_scan_accum_push_pointcloud2(mcl3dl_hip_group* g, const uint
 {
   if (!g)
     return -1;
-  std::vector<size_t> got(3 * static_cast<size_t>(g->n()), 0);
-  TRY(group_scan_each(g,
-                      [&](mcl3dl_hip_ctx* ctx, int r) -> int
-                      {
-                        return mcl3dl_hip_scan_accum_push_pointcloud2(ctx, data, n_points, point_step, off_x, off_y, off_z, affine12,
-                                                                      &got[3 * r], &got[3 * r + 1]);
-                      }));
-  return group_scan_sizes(g, got, "the accumulated clouds", out_cloud_index, out_total_points, nullptr);
+  return group_scan_sizes(
+      g, "the accumulated clouds",
+      [&](mcl3dl_hip_ctx* ctx, size_t* got) -> int
+      {
+        return mcl3dl_hip_scan_accum_push_pointcloud2(ctx, data, n_points, point_step, off_x, off_y, off_z, affine12, &got[0],
+                                                      &got[1]);
+      },
+      out_cloud_index, out_total_points, nullptr);
 }
 
 int mcl3dl_hip_group_scan_accum_size(mcl3dl_hip_group* g, size_t* n_clouds, size_t* n_points)
 {
   if (!g)
     return -1;
-  std::vector<size_t> got(3 * static_cast<size_t>(g->n()), 0);
-  TRY(group_scan_each(g, [&](mcl3dl_hip_ctx* ctx, int r) -> int
-                      { return mcl3dl_hip_scan_accum_size(ctx, &got[3 * r], &got[3 * r + 1]); }));
-  return group_scan_sizes(g, got, "the accumulated clouds", n_clouds, n_points, nullptr);
+  return group_scan_sizes(
+      g, "the accumulated clouds", [&](mcl3dl_hip_ctx* ctx, size_t* got) -> int
+      { return mcl3dl_hip_scan_accum_size(ctx, &got[0], &got[1]); }, n_clouds, n_points, nullptr);
 }
 
 // Replaces: what mcl3dl_hip_scan_begin_accumulated replaces, for the measurement of a device group
@@ -262,14 +305,10 @@ int mcl3dl_hip_group_scan_begin_accumulated(mcl3dl_hip_group* g, const float* af
 {
   if (!g)
     return -1;
-  std::vector<size_t> got(3 * static_cast<size_t>(g->n()), 0);
-  TRY(group_scan_each(g,
-                      [&](mcl3dl_hip_ctx* ctx, int r) -> int
-                      {
-                        return mcl3dl_hip_scan_begin_accumulated(ctx, affine12, leaf3, clip_lik4, clip_beam4, &got[3 * r],
-                                                                 &got[3 * r + 1], &got[3 * r + 2]);
-                      }));
-  return group_scan_sizes(g, got, "the sizes of the prepared clouds", n_full, n_lik_clipped, n_beam_clipped);
+  return group_scan_sizes(
+      g, "the sizes of the prepared clouds", [&](mcl3dl_hip_ctx* ctx, size_t* got) -> int
+      { return mcl3dl_hip_scan_begin_accumulated(ctx, affine12, leaf3, clip_lik4, clip_beam4, &got[0], &got[1], &got[2]); },
+      n_full, n_lik_clipped, n_beam_clipped);
 }
 
 // Replaces: what mcl3dl_hip_scan_finish replaces, on every rank: the sampler's push_back loop (point_cloud_uniform_sampler.h:
@@ -290,22 +329,9 @@ int mcl3dl_hip_group_scan_finish_drawn(mcl3dl_hip_group* g, size_t n_s, size_t n
 {
   if (!g)
     return -1;
-  if (!engine_state)
-    return g->fail(-3, "null engine_state");
-  const int N = g->n();
-  std::vector<size_t> got(3 * static_cast<size_t>(N), 0);  // {n_s installed, n_b installed, engine state}
-  TRY(group_scan_each(g,
-                      [&](mcl3dl_hip_ctx* ctx, int r) -> int
-                      {
-                        uint32_t state = *engine_state;
-                        TRY(mcl3dl_hip_scan_finish_drawn(ctx, n_s, n_b, origins, n_o, &state, &got[3 * r], &got[3 * r + 1]));
-                        got[3 * r + 2] = state;
-                        return 0;
-                      }));
-  size_t state = 0;
-  TRY(group_scan_sizes(g, got, "the drawn scans or the engine state behind them", out_n_s, out_n_b, &state));
-  *engine_state = static_cast<uint32_t>(state);
-  return 0;
+  return group_scan_drawn(g, engine_state, out_n_s, out_n_b,
+                          [&](mcl3dl_hip_ctx* ctx, uint32_t* state, size_t* got_s, size_t* got_b) -> int
+                          { return mcl3dl_hip_scan_finish_drawn(ctx, n_s, n_b, origins, n_o, state, got_s, got_b); });
 }
 
 // Replaces: PointCloudSamplerWithNormal::sample for both models (point_cloud_sampler_with_normal.h:91-185; beam first) on
@@ -316,23 +342,12 @@ int mcl3dl_hip_group_scan_finish_drawn_normal(mcl3dl_hip_group* g, size_t n_s, s
 {
   if (!g)
     return -1;
-  if (!engine_state)
-    return g->fail(-3, "null engine_state");
-  const int N = g->n();
-  std::vector<size_t> got(3 * static_cast<size_t>(N), 0);  // {n_s installed, n_b installed, engine state}
-  TRY(group_scan_each(g,
-                      [&](mcl3dl_hip_ctx* ctx, int r) -> int
-                      {
-                        uint32_t state = *engine_state;
-                        TRY(mcl3dl_hip_scan_finish_drawn_normal(ctx, n_s, n_b, origins, n_o, normal_search_range, fpc_local3,
-                                                                max_weight, &state, &got[3 * r], &got[3 * r + 1]));
-                        got[3 * r + 2] = state;
-                        return 0;
-                      }));
-  size_t state = 0;
-  TRY(group_scan_sizes(g, got, "the drawn scans or the engine state behind them", out_n_s, out_n_b, &state));
-  *engine_state = static_cast<uint32_t>(state);
-  return 0;
+  return group_scan_drawn(g, engine_state, out_n_s, out_n_b,
+                          [&](mcl3dl_hip_ctx* ctx, uint32_t* state, size_t* got_s, size_t* got_b) -> int
+                          {
+                            return mcl3dl_hip_scan_finish_drawn_normal(ctx, n_s, n_b, origins, n_o, normal_search_range, fpc_local3,
+                                                                       max_weight, state, got_s, got_b);
+                          });
 }
 
 // Replaces: what mcl3dl_hip_group_update_resident replaces (measure(), src/mcl_3dl.cpp:377-470), on the scans the group's
@@ -343,8 +358,7 @@ int mcl3dl_hip_group_update_resident_prepared(mcl3dl_hip_group* g, const float* 
 {
   if (!g)
     return -1;
-  if (g->n_resident == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  TRY(group_resident(g));
   for (int r = 0; r < g->n(); ++r)
   {
     const mcl3dl_hip_ctx* c = g->ctx[r];
@@ -370,8 +384,7 @@ int group_expectation_impl(mcl3dl_hip_group* g, const float* bias, const JumpBia
                            float* out_total, int64_t* out_max_index, int64_t* out_max_biased_index)
 {
   const size_t n_p = g->n_resident;
-  if (n_p == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  TRY(group_resident(g));
   const int N = g->n();
   g->h_parts.assign(16 * static_cast<size_t>(N), 0.0);
   std::vector<uint64_t> offsets(N, 0);
@@ -402,8 +415,7 @@ int group_expectation_impl(mcl3dl_hip_group* g, const float* bias, const JumpBia
         JumpBias jb{};
         if (jump)
         {
-          if (ctx->gs_n != n)
-            return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, n);
+          TRY(rank_holds(ctx, n));
           jb = *jump;
           if (out_bias)
           {
@@ -461,67 +473,65 @@ int mcl3dl_hip_group_download_particle(mcl3dl_hip_group* g, int64_t index, float
   if (!g)
     return -1;
   const size_t n_p = g->n_resident;
-  if (n_p == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  TRY(group_resident(g));
   if (index < 0 || static_cast<uint64_t>(index) >= n_p)
     return g->fail(-3, "particle %lld of %zu asked for", static_cast<long long>(index), n_p);
-  const int N = g->n();
-  const size_t i = static_cast<size_t>(index);
-  for (int r = 0; r < N; ++r)
+  // the one rank that holds it, 52 + 4 bytes, no collective: on the calling thread
+  const ShardSlot at = shard_slot(shard_layout(n_p, g->n()), static_cast<size_t>(index));
+  const Shard s = shard_of(g, n_p, static_cast<int>(at.rank));
+  mcl3dl_hip_ctx* ctx = s.ctx;
+  const int rc = [&]() -> int
   {
-    const Shard s = shard_of(g, n_p, r);
-    const size_t lo = s.lo, hi = s.lo + s.n;
-    if (i < lo || i >= hi)
-      continue;
-    // one rank, 52 + 4 bytes, no collective: on the calling thread
-    mcl3dl_hip_ctx* ctx = s.ctx;
-    const int rc = [&]() -> int
-    {
-      HIP_TRY(hipSetDevice(ctx->device));
-      if (ctx->gs_n != hi - lo)
-        return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, hi - lo);
-      if (out_state13)
-        TRY(d2h(ctx, out_state13, ctx->gs_state[ctx->gs_cur].as<float>() + 13 * (i - lo), sizeof(float) * 13));
-      if (out_weight)
-        TRY(d2h(ctx, out_weight, ctx->gs_weight.as<float>() + (i - lo), sizeof(float)));
-      return sync_stream(ctx);
-    }();
-    return rc ? g->fail_rank(rc, r) : 0;
-  }
-  return g->fail(-4, "internal: no shard holds particle %zu", i);
+    HIP_TRY(hipSetDevice(ctx->device));
+    TRY(rank_holds(ctx, s.n));
+    if (out_state13)
+      TRY(d2h(ctx, out_state13, ctx->gs_state[ctx->gs_cur].as<float>() + 13 * at.offset, sizeof(float) * 13));
+    if (out_weight)
+      TRY(d2h(ctx, out_weight, ctx->gs_weight.as<float>() + at.offset, sizeof(float)));
+    return sync_stream(ctx);
+  }();
+  return rc ? g->fail_rank(rc, s.r) : 0;
 }
+
+namespace
+{
+// pf::covariance over the shards: `partial` leaves a rank's 22 sums in ctx->gs_rec (the pose mirror is current), the records
+// are summed in rank order and finished on the host
+int group_covariance_with(mcl3dl_hip_group* g, float* out_cov36,
+                          const std::function<int(mcl3dl_hip_ctx*, int, size_t, size_t)>& partial)
+{
+  g->h_parts.assign(22 * static_cast<size_t>(g->n()), 0.0);
+  TRY(group_each_shard(g,
+                       [&](mcl3dl_hip_ctx* ctx, int r, size_t lo, size_t n) -> int
+                       {
+                         TRY(ensure(ctx, ctx->gs_rec, sizeof(double) * 32));
+                         TRY(resident_poses(ctx));
+                         TRY(partial(ctx, r, lo, n));
+                         TRY(d2h(ctx, &g->h_parts[22 * static_cast<size_t>(r)], ctx->gs_rec.p, sizeof(double) * 22));
+                         return sync_stream(ctx);
+                       }));
+  double total[22] = { 0 };
+  for (int r = 0; r < g->n(); ++r)  // rank order: deterministic
+    for (int k = 0; k < 22; ++k)
+      total[k] += g->h_parts[22 * static_cast<size_t>(r) + k];
+  return mcl3dl_hip_covariance_finish(total, out_cov36);
+}
+}  // namespace
 
 int mcl3dl_hip_group_covariance(mcl3dl_hip_group* g, const float* mean7, float* out_cov36)
 {
   if (!g)
     return -1;
-  const size_t n_p = g->n_resident;
-  if (n_p == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  TRY(group_resident(g));
   if (!mean7 || !out_cov36)
     return g->fail(-3, "null mean / covariance array");
-  const int N = g->n();
-  g->h_parts.assign(22 * static_cast<size_t>(N), 0.0);
-  TRY(group_run_shards(
-      g, n_p,
-      [&](const Shard& s) -> int
-      {
-        mcl3dl_hip_ctx* ctx = s.ctx;
-        if (s.n == 0)
-          return 0;
-        HIP_TRY(hipSetDevice(ctx->device));
-        TRY(ensure(ctx, ctx->gs_rec, sizeof(double) * 32));
-        TRY(resident_poses(ctx));
-        TRY(mcl3dl_hip_covariance_partial_device(ctx, ctx->pose.as<float>(), ctx->gs_weight.as<float>(), s.n, nullptr, 0, mean7,
-                                                 ctx->gs_rec.as<double>()));
-        TRY(d2h(ctx, &g->h_parts[22 * static_cast<size_t>(s.r)], ctx->gs_rec.p, sizeof(double) * 22));
-        return sync_stream(ctx);
-      }));
-  double total[22] = { 0 };
-  for (int r = 0; r < N; ++r)  // rank order: deterministic
-    for (int k = 0; k < 22; ++k)
-      total[k] += g->h_parts[22 * static_cast<size_t>(r) + k];
-  return mcl3dl_hip_covariance_finish(total, out_cov36);
+  return group_covariance_with(g, out_cov36,
+                               [&](mcl3dl_hip_ctx* ctx, int, size_t, size_t n) -> int
+                               {
+                                 return mcl3dl_hip_covariance_partial_device(ctx, ctx->pose.as<float>(),
+                                                                             ctx->gs_weight.as<float>(), n, nullptr, 0, mean7,
+                                                                             ctx->gs_rec.as<double>());
+                               });
 }
 
 int mcl3dl_hip_group_resample_begin(mcl3dl_hip_group* g, size_t n_out, float* out_pstep)
@@ -529,8 +539,7 @@ int mcl3dl_hip_group_resample_begin(mcl3dl_hip_group* g, size_t n_out, float* ou
   if (!g)
     return -1;
   const size_t n_p = g->n_resident;
-  if (n_p == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  TRY(group_resident(g));
   if (n_out == 0)
     n_out = n_p;
   g->rs_begun = g->rs_planned = false;
@@ -554,17 +563,14 @@ int mcl3dl_hip_group_resample_plan(mcl3dl_hip_group* g, int mode, float initial_
     return -1;
   if (!g->rs_begun)
     return g->fail(-5, "group_resample_plan before group_resample_begin");
-  const int N = g->n();
-  std::vector<size_t> n_dup(N, 0);
+  std::vector<size_t> n_dup(g->n(), 0);
   TRY(group_run(g,
                 [&](int r) -> int
                 {
                   return mcl3dl_hip_resample_plan(g->ctx[r], mode, initial_p, r == 0 ? out_source : nullptr,
                                                   r == 0 ? out_duplicate : nullptr, &n_dup[r]);
                 }));
-  for (int r = 1; r < N; ++r)
-    if (n_dup[r] != n_dup[0])
-      return g->fail(-4, "the ranks disagree on the resampling plan (%zu and %zu duplicated particles)", n_dup[0], n_dup[r]);
+  TRY(group_agree(g, "the resampling plan's duplicated particles", n_dup.data(), 1));
   g->rs_n_dup = n_dup[0];
   g->rs_planned = true;
   if (out_n_duplicates)
@@ -582,57 +588,30 @@ int group_resample_apply_impl(mcl3dl_hip_group* g, const float* noise13, size_t 
 {
   const size_t n_p = g->n_resident, n_out = g->rs_n_out;
   const int N = g->n();
-  const bool single = N == 1 && g->direct_single;
-  const bool host_gather = g->collective == 1 && !single;
-  if (!single && !host_gather)
+  const GroupRoute route = g->route();
+  if (route == ROUTE_RCCL)
     TRY(group_comms(g));
   // the odometry noise travels with the states once it has been installed (api_group_motion.inl); without it this call issues
   // the same collectives and launches as it always did
   const bool with_noise = g->noise_on;
-  if (host_gather)
-  {
-    g->h_state.resize(13 * n_p);
-    TRY(mcl3dl_hip_group_download_state(g, g->h_state.data(), nullptr, n_p));
-    if (with_noise)
-    {
-      g->h_noise.resize(4 * n_p);
-      TRY(mcl3dl_hip_group_download_odom_noise(g, g->h_noise.data(), n_p));
-    }
-  }
-  const size_t base = n_p / N, rem = n_p % N, max_count = base + (rem ? 1 : 0);
-  const bool over_rccl = !single && !host_gather;
+  TRY(gather_to_host(g, resident_states));
+  if (with_noise)
+    TRY(gather_to_host(g, resident_noise));
   // everything ahead of the collective; the all-gather is entered by all ranks or by none (group_voted_call)
   const auto prepare = [&](const Shard& s) -> int
   {
     mcl3dl_hip_ctx* ctx = s.ctx;
     const int other = ctx->gs_cur ^ 1;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t cap_new = std::max<size_t>((n_out + N - 1) / N, 1);
+    const size_t cap_new = shard_capacity(n_out, N);
     TRY(ensure(ctx, ctx->gs_state[other], sizeof(float) * 13 * cap_new));
     TRY(ensure(ctx, ctx->gs_weight, sizeof(float) * cap_new));
     if (with_noise)
+    {
       TRY(ensure(ctx, ctx->gs_noise[other], sizeof(float) * 4 * cap_new));
-    if (single)
-      return 0;
-    TRY(ensure(ctx, ctx->gs_all, sizeof(float) * 13 * n_p));
-    if (with_noise)
-      TRY(ensure(ctx, ctx->gs_noise_all, sizeof(float) * 4 * n_p));
-    if (host_gather)
-    {
-      if (with_noise)
-        TRY(h2d(ctx, ctx->gs_noise_all.p, g->h_noise.data(), sizeof(float) * 4 * n_p));
-      return h2d(ctx, ctx->gs_all.p, g->h_state.data(), sizeof(float) * 13 * n_p);
+      TRY(gather_ahead(g, s, n_p, resident_noise(g, ctx)));
     }
-    TRY(ensure(ctx, ctx->gs_pad, sizeof(float) * 13 * max_count * static_cast<size_t>(N)));
-    if (ctx->gs_state[ctx->gs_cur].cap < sizeof(float) * 13 * max_count)  // (every shard buffer holds the largest shard)
-      return ctx->fail(-4, "internal: shard buffer smaller than the all-gather's send count");
-    if (with_noise)
-    {
-      TRY(ensure(ctx, ctx->gs_noise_pad, sizeof(float) * 4 * max_count * static_cast<size_t>(N)));
-      if (ctx->gs_noise[ctx->gs_cur].cap < sizeof(float) * 4 * max_count)
-        return ctx->fail(-4, "internal: noise buffer smaller than the all-gather's send count");
-    }
-    return 0;
+    return gather_ahead(g, s, n_p, resident_states(g, ctx));
   };
   // the all-gather(s), then the rank's slice of the new generation
   const auto apply = [&](const Shard& s, const VotedRank& voted) -> int
@@ -642,42 +621,10 @@ int group_resample_apply_impl(mcl3dl_hip_group* g, const float* noise13, size_t 
     size_t olo, ohi;
     shard_bounds(n_out, N, r, &olo, &ohi);
     const size_t n_new = ohi - olo;
-    const float* d_all = nullptr;
-    const float* d_noise_all = nullptr;
-    if (single)
-    {
-      d_all = ctx->gs_state[ctx->gs_cur].as<float>();
-      d_noise_all = ctx->gs_noise[ctx->gs_cur].as<float>();
-    }
-    else if (host_gather)
-    {
-      d_all = ctx->gs_all.as<float>();
-      d_noise_all = ctx->gs_noise_all.as<float>();
-    }
-    else
-    {
-      // 13 floats x max_count per rank over xGMI into the padded layout, then into particle order
-      TRY(voted.enqueued(g->rccl.AllGather(ctx->gs_state[ctx->gs_cur].p, ctx->gs_pad.p, 13 * max_count, ncclFloat, g->comms[r],
-                                           ctx->stream),
-                         "ncclAllGather"));
-      const size_t total = 13 * n_p;
-      hipLaunchKernelGGL(unpad_states_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, ctx->stream,
-                         ctx->gs_pad.as<float>(), max_count, base, rem, n_p, ctx->gs_all.as<float>());
-      HIP_TRY(hipGetLastError());
-      d_all = ctx->gs_all.as<float>();
-      if (with_noise)
-      {
-        // the four noise floats of every particle the same way: a second all-gather, only while noise is installed
-        TRY(voted.enqueued(g->rccl.AllGather(ctx->gs_noise[ctx->gs_cur].p, ctx->gs_noise_pad.p, 4 * max_count, ncclFloat,
-                                             g->comms[r], ctx->stream),
-                           "ncclAllGather (odometry noise)"));
-        hipLaunchKernelGGL(unpad_states_kernel, dim3(static_cast<unsigned>((4 * n_p + 255) / 256)), dim3(256), 0, ctx->stream,
-                           ctx->gs_noise_pad.as<float>(), max_count, base, rem, n_p, ctx->gs_noise_all.as<float>(),
-                           static_cast<size_t>(4));
-        HIP_TRY(hipGetLastError());
-        d_noise_all = ctx->gs_noise_all.as<float>();
-      }
-    }
+    const float *d_all = nullptr, *d_noise_all = nullptr;
+    TRY(gather_behind(g, s, voted, n_p, resident_states(g, ctx), &d_all));
+    if (with_noise)  // the four noise floats of every particle the same way: a second all-gather, only while noise is installed
+      TRY(gather_behind(g, s, voted, n_p, resident_noise(g, ctx), &d_noise_all));
     if (n_new)
     {
       if (drawn)
@@ -696,26 +643,21 @@ int group_resample_apply_impl(mcl3dl_hip_group* g, const float* noise13, size_t 
         HIP_TRY(hipGetLastError());
       }
       // pf.h:207 / 417: every particle of the new generation weighs 1 / n
-      hipLaunchKernelGGL(fill_kernel, dim3((static_cast<int>(n_new) + 255) / 256), dim3(256), 0, ctx->stream,
-                         ctx->gs_weight.as<float>(), 1.0f / static_cast<float>(n_out), static_cast<float*>(nullptr), 0.0f,
-                         static_cast<int>(n_new));
-      HIP_TRY(hipGetLastError());
+      TRY(uniform_weights(ctx, n_new, 1.0f / static_cast<float>(n_out)));
     }
     ctx->gs_cur = other;
-    ctx->gs_n = n_new;
-    TRY(rebuild_pose(ctx, n_new));
+    TRY(generation_rank_installed(ctx, n_new, false));
     return sync_stream(ctx);
   };
-  const int rc = group_voted_call(VotedCall{ g, "resampling", "all-gather" }, n_p, over_rccl, !single, prepare, apply);
+  const int rc = group_voted_call(VotedCall{ g, "resampling", "all-gather" }, n_p, route == ROUTE_RCCL, route != ROUTE_DIRECT,
+                                  prepare, apply);
   g->rs_begun = g->rs_planned = false;
   if (rc)
   {
-    g->n_resident = 0;  // the shards may be half way into the new generation
-    g->noise_on = false;
+    generation_begin(g);  // the shards may be half way into the new generation
     return rc;
   }
-  g->n_resident = n_out;
-  g->n_pose_uploaded = n_out;
+  generation_installed(g, n_out);
   return 0;
 }
 }  // namespace
@@ -744,63 +686,41 @@ struct GroupPlan
 
 // begin + [uniform draw] + plan over the resident particles in one pass over the ranks: every rank needs ALL weights in
 // particle order (the prefix recurrence is not associative) — its own buffer on a group of one, else gathered through the host
-// ("collective" 1: as the states) or by one ncclAllGather of the padded weight shards + unpad_states_kernel with width 1 —
-// and runs mcl3dl_hip_resample_plan_device over them. Leaves the group where group_resample_plan does.
+// ("collective" 1) or by one ncclAllGather of the padded weight shards, the way the states are (host_group_gather.h) — and runs
+// mcl3dl_hip_resample_plan_device over them. Leaves the group where group_resample_plan does.
 int group_plan_device(mcl3dl_hip_group* g, size_t n_out, int mode, uint32_t state_in, GroupPlan* out)
 {
   const size_t n_p = g->n_resident;
   const int N = g->n();
-  const bool single = N == 1 && g->direct_single;
-  const bool host_gather = g->collective == 1 && !single;
-  const bool over_rccl = !single && !host_gather;
+  const GroupRoute route = g->route();
   g->rs_begun = g->rs_planned = false;
-  if (over_rccl)
+  if (route == ROUTE_RCCL)
     TRY(group_comms(g));
-  if (host_gather)
-  {
-    g->h_weight.resize(n_p);
-    TRY(mcl3dl_hip_group_download_state(g, nullptr, g->h_weight.data(), n_p));
-  }
-  const size_t base = n_p / N, rem = n_p % N, max_count = base + (rem ? 1 : 0);
+  TRY(gather_to_host(g, resident_weights));
   std::vector<GroupPlan> plan(N);
   const auto prepare = [&](const Shard& s) -> int
   {
     mcl3dl_hip_ctx* ctx = s.ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->gs_n != s.n)
-      return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, s.n);
-    if (single)
-      return 0;
-    TRY(ensure(ctx, ctx->rs_d_w, sizeof(float) * n_p));
-    if (host_gather)
-      return h2d(ctx, ctx->rs_d_w.p, g->h_weight.data(), sizeof(float) * n_p);
-    TRY(ensure(ctx, ctx->rs_d_wpad, sizeof(float) * max_count * static_cast<size_t>(N)));
-    if (ctx->gs_weight.cap < sizeof(float) * max_count)  // (every shard buffer holds the largest shard)
-      return ctx->fail(-4, "internal: weight buffer smaller than the all-gather's send count");
-    return 0;
+    TRY(rank_holds(ctx, s.n));
+    return gather_ahead(g, s, n_p, resident_weights(g, ctx));
   };
   const auto behind = [&](const Shard& s, const VotedRank& voted) -> int
   {
     mcl3dl_hip_ctx* ctx = s.ctx;
-    const float* d_w = single ? ctx->gs_weight.as<float>() : ctx->rs_d_w.as<float>();
-    if (over_rccl)
-    {
-      TRY(voted.enqueued(g->rccl.AllGather(ctx->gs_weight.p, ctx->rs_d_wpad.p, max_count, ncclFloat, g->comms[s.r], ctx->stream),
-                         "ncclAllGather (weights)"));
-      hipLaunchKernelGGL(unpad_states_kernel, dim3(static_cast<unsigned>((n_p + 255) / 256)), dim3(256), 0, ctx->stream,
-                         ctx->rs_d_wpad.as<float>(), max_count, base, rem, n_p, ctx->rs_d_w.as<float>(), static_cast<size_t>(1));
-      HIP_TRY(hipGetLastError());
-    }
+    const float* d_w = nullptr;
+    TRY(gather_behind(g, s, voted, n_p, resident_weights(g, ctx), &d_w));
     GroupPlan& p = plan[s.r];
     p.state = state_in;
     return mcl3dl_hip_resample_plan_device(ctx, d_w, n_p, n_out, mode, mode == 0 ? &p.state : nullptr, &p.pstep, &p.initial_p,
                                            &p.n_dup, &p.route);
   };
-  TRY(group_voted_call(VotedCall{ g, "resampling", "all-gather of the weights" }, n_p, over_rccl, !single, prepare, behind));
-  for (int r = 1; r < N; ++r)
-    if (plan[r].n_dup != plan[0].n_dup || plan[r].state != plan[0].state || plan[r].route != plan[0].route)
-      return g->fail(-4, "the ranks disagree on the resampling plan (%zu and %zu duplicated particles, engine states %u and %u)",
-                     plan[0].n_dup, plan[r].n_dup, plan[0].state, plan[r].state);
+  TRY(group_voted_call(VotedCall{ g, "resampling", "all-gather of the weights" }, n_p, route == ROUTE_RCCL, route != ROUTE_DIRECT,
+                       prepare, behind));
+  std::vector<size_t> got;  // {duplicated particles, engine state, route} of every rank
+  for (const GroupPlan& p : plan)
+    got.insert(got.end(), { p.n_dup, static_cast<size_t>(p.state), static_cast<size_t>(p.route) });
+  TRY(group_agree(g, "the resampling plan (duplicated particles, engine state, route)", got.data(), 3));
   g->rs_n_out = n_out;
   g->rs_n_dup = plan[0].n_dup;
   g->rs_begun = g->rs_planned = true;
@@ -815,8 +735,7 @@ int mcl3dl_hip_group_resize_resident(mcl3dl_hip_group* g, size_t n_out, int* out
 {
   if (!g)
     return -1;
-  if (g->n_resident == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  TRY(group_resident(g));
   if (n_out == 0 || n_out > 0x7fffffffu / 16)
     return g->fail(-3, "group_resize_resident: n_out = %zu is outside [1, %u]", n_out, 0x7fffffffu / 16);
   GroupPlan plan;

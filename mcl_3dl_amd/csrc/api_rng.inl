@@ -11,8 +11,8 @@
 //   mcl3dl_hip_group_resample_apply_drawn       pf::resample's generateNoise per duplicated slot, in slot order (pf.h:216)
 namespace
 {
-// DiagonalNoiseGenerator(mean, sigma) for State6DOF; mean6 == null: State6DOF()
-int rng_generator(mcl3dl_hip_group* g, const float* mean6, const float* sigma6, rng::NoiseGen6* gen)
+// DiagonalNoiseGenerator(mean, sigma) for State6DOF; mean6 == null: State6DOF(). The engine state it will draw from is checked too.
+int rng_generator(mcl3dl_hip_group* g, const float* mean6, const float* sigma6, const uint32_t* engine_state, rng::NoiseGen6* gen)
 {
   if (!sigma6)
     return g->fail(-3, "null sigma6");
@@ -25,16 +25,14 @@ int rng_generator(mcl3dl_hip_group* g, const float* mean6, const float* sigma6, 
     gen->mean[k] = mean6 ? mean6[k] : 0.0f;
     gen->dims += sigma6[k] != 0.f ? 1 : 0;
   }
-  return 0;
+  return rng_check_state(g, engine_state);
 }
 
-// every rank ran the same count pass over the same stream: one engine state
+// every rank that drew ran the same count pass over the same stream: one engine state
 int rng_hand_back(mcl3dl_hip_group* g, const std::vector<uint32_t>& states, const std::vector<char>& drew,
                   uint32_t* engine_state)
 {
-  for (size_t r = 1; r < states.size(); ++r)
-    if (drew[r] && drew[0] && states[r] != states[0])
-      return g->fail(-4, "the ranks disagree on the engine state behind the draw (%u and %u)", states[0], states[r]);
+  TRY(group_agree(g, "the engine state behind the draw", states.data(), 1, drew.data()));
   if (drew[0])
     *engine_state = states[0];
   return 0;
@@ -58,8 +56,7 @@ int mcl3dl_hip_group_add_noise_drawn(mcl3dl_hip_group* g, const float* sigma6, u
   if (!g)
     return -1;
   rng::NoiseGen6 gen;
-  TRY(rng_generator(g, nullptr, sigma6, &gen));
-  TRY(rng_check_state(g, engine_state));
+  TRY(rng_generator(g, nullptr, sigma6, engine_state, &gen));
   const size_t n_p = g->n_resident;
   std::vector<uint32_t> states(g->n(), 0u);
   std::vector<char> drew(g->n(), 0);
@@ -98,8 +95,7 @@ int mcl3dl_hip_group_draw_odom_noise(mcl3dl_hip_group* g, const float* odom_err4
       g,
       [&](mcl3dl_hip_ctx* ctx, int r, size_t lo, size_t n) -> int
       {
-        // (room for the largest shard, as set_odom_noise: the resampling step's all-gather sends that many)
-        TRY(ensure(ctx, ctx->gs_noise[ctx->gs_cur], sizeof(float) * 4 * ((n_p + N - 1) / N)));
+        TRY(odom_noise_room(ctx, n_p, N));
         // one shared normal_distribution: accepted attempt k yields values 2k and 2k + 1, four values per particle
         TRY(rng_draw(ctx, x0, 2 * static_cast<uint64_t>(n_p), true, 2 * static_cast<uint64_t>(lo),
                      2 * static_cast<uint64_t>(lo + n), &states[r]));
@@ -117,21 +113,19 @@ int mcl3dl_hip_group_draw_odom_noise(mcl3dl_hip_group* g, const float* odom_err4
     return rc;
   }
   // an empty shard still needs its buffer for the all-gather
-  for (int r = 0; r < N; ++r)
-    if (!drew[r])
-    {
-      mcl3dl_hip_ctx* ctx = g->ctx[r];
-      const int rc_e = [&]() -> int
-      {
-        HIP_TRY(hipSetDevice(ctx->device));
-        return ensure(ctx, ctx->gs_noise[ctx->gs_cur], sizeof(float) * 4 * ((n_p + N - 1) / N));
-      }();
-      if (rc_e)
-      {
-        g->noise_on = false;
-        return g->fail_rank(rc_e, r);
-      }
-    }
+  const int rc_e = group_forward(g,
+                                 [&](mcl3dl_hip_ctx* ctx, int r) -> int
+                                 {
+                                   if (drew[r])
+                                     return 0;
+                                   HIP_TRY(hipSetDevice(ctx->device));
+                                   return odom_noise_room(ctx, n_p, N);
+                                 });
+  if (rc_e)
+  {
+    g->noise_on = false;
+    return rc_e;
+  }
   TRY(rng_hand_back(g, states, drew, engine_state));
   g->noise_on = true;
   return 0;
@@ -149,46 +143,31 @@ int mcl3dl_hip_group_init_drawn(mcl3dl_hip_group* g, const float* mean7, const f
   float mean6[6];
   rng_mean6(mean7, mean6);
   rng::NoiseGen6 gen;
-  TRY(rng_generator(g, mean6, sigma6, &gen));
-  TRY(rng_check_state(g, engine_state));
+  TRY(rng_generator(g, mean6, sigma6, engine_state, &gen));
   if (n_p == 0 || n_p > 0x7fffffffu / 16)
     return g->fail(-3, "init_drawn: %zu particles asked for", n_p);
-  g->n_resident = 0;
-  g->rs_begun = g->rs_planned = false;
-  g->noise_on = false;
+  generation_begin(g);
   const int N = g->n();
   std::vector<uint32_t> states(N, 0u);
   std::vector<char> drew(N, 0);
   const uint32_t x0 = *engine_state;
   const float weight = static_cast<float>(1.0 / static_cast<double>(n_p));  // pf.h:179
-  TRY(group_run_shards(
-      g, n_p,
-      [&](const Shard& s) -> int
-      {
-        mcl3dl_hip_ctx* ctx = s.ctx;
-        const int r = s.r;
-        const size_t lo = s.lo, n = s.n;
-        HIP_TRY(hipSetDevice(ctx->device));
-        ctx->gs_n = 0;
-        ctx->gs_cur = 0;
-        if (n == 0)
-          return 0;
-        const size_t cap_count = (n_p + N - 1) / N;  // as upload_state
-        TRY(ensure(ctx, ctx->gs_state[0], sizeof(float) * 13 * cap_count));
-        TRY(ensure(ctx, ctx->gs_weight, sizeof(float) * cap_count));
-        // p.state_ = generateNoise(engine_, generator): the row IS the state
-        TRY(rng_noise_rows(ctx, x0, gen, n_p, lo, n, ctx->gs_state[0].as<float>(), &states[r]));
-        drew[r] = 1;
-        hipLaunchKernelGGL(fill_kernel, grid_of(n), dim3(256), 0, ctx->stream, ctx->gs_weight.as<float>(), weight,
-                           static_cast<float*>(nullptr), 0.0f, static_cast<int>(n));
-        HIP_TRY(hipGetLastError());
-        TRY(rebuild_pose(ctx, n));
-        ctx->gs_n = n;
-        return sync_stream(ctx);
-      }));
+  TRY(group_run_shards(g, n_p,
+                       [&](const Shard& s) -> int
+                       {
+                         mcl3dl_hip_ctx* ctx = s.ctx;
+                         TRY(generation_rank_begin(ctx, n_p, N));
+                         if (s.n == 0)
+                           return 0;
+                         // p.state_ = generateNoise(engine_, generator): the row IS the state
+                         TRY(rng_noise_rows(ctx, x0, gen, n_p, s.lo, s.n, ctx->gs_state[0].as<float>(), &states[s.r]));
+                         drew[s.r] = 1;
+                         TRY(uniform_weights(ctx, s.n, weight));
+                         TRY(generation_rank_installed(ctx, s.n, false));
+                         return sync_stream(ctx);
+                       }));
   TRY(rng_hand_back(g, states, drew, engine_state));
-  g->n_resident = n_p;
-  g->n_pose_uploaded = n_p;
+  generation_installed(g, n_p);
   return 0;
 }
 
@@ -197,10 +176,8 @@ int mcl3dl_hip_group_resample_apply_drawn(mcl3dl_hip_group* g, const float* sigm
   if (!g)
     return -1;
   rng::NoiseGen6 gen;
-  TRY(rng_generator(g, nullptr, sigma6, &gen));
-  TRY(rng_check_state(g, engine_state));
-  if (g->n_resident == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  TRY(rng_generator(g, nullptr, sigma6, engine_state, &gen));
+  TRY(group_resident(g));
   if (!g->rs_planned)
     return g->fail(-5, "group_resample_apply_drawn before group_resample_plan");
   const size_t n_dup = g->rs_n_dup, n_out = g->rs_n_out;
@@ -239,10 +216,8 @@ int mcl3dl_hip_group_resample_drawn(mcl3dl_hip_group* g, const float* sigma6, ui
   if (!g)
     return -1;
   rng::NoiseGen6 gen;
-  TRY(rng_generator(g, nullptr, sigma6, &gen));
-  TRY(rng_check_state(g, engine_state));
-  if (g->n_resident == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  TRY(rng_generator(g, nullptr, sigma6, engine_state, &gen));
+  TRY(group_resident(g));
   GroupPlan plan;
   TRY(group_plan_device(g, g->n_resident, 0, *engine_state, &plan));
   uint32_t state = plan.state;  // behind initial_p's engine call

@@ -18,15 +18,11 @@ namespace
 int group_covariance_over(mcl3dl_hip_group* g, const float* mean7, const uint32_t* host_list, size_t m,
                           const std::function<int(mcl3dl_hip_ctx*, int, const uint32_t**)>* make, float* out_cov36)
 {
-  const int N = g->n();
-  g->h_parts.assign(22 * static_cast<size_t>(N), 0.0);
   // (an empty shard holds no entry of the list; rank 0 is never empty: the state behind a draw comes from it)
-  TRY(group_each_shard(
-      g,
+  return group_covariance_with(
+      g, out_cov36,
       [&](mcl3dl_hip_ctx* ctx, int r, size_t lo, size_t n) -> int
       {
-        TRY(ensure(ctx, ctx->gs_rec, sizeof(double) * 32));
-        TRY(resident_poses(ctx));
         const uint32_t* d_list = nullptr;
         if (host_list)
         {
@@ -36,16 +32,9 @@ int group_covariance_over(mcl3dl_hip_group* g, const float* mean7, const uint32_
         }
         else
           TRY((*make)(ctx, r, &d_list));
-        TRY(mcl3dl_hip_covariance_window_partial_device(ctx, ctx->pose.as<float>(), ctx->gs_weight.as<float>(), n, d_list, m, lo,
-                                                        mean7, ctx->gs_rec.as<double>()));
-        TRY(d2h(ctx, &g->h_parts[22 * static_cast<size_t>(r)], ctx->gs_rec.p, sizeof(double) * 22));
-        return sync_stream(ctx);
-      }));
-  double total[22] = { 0 };
-  for (int r = 0; r < N; ++r)  // rank order: deterministic
-    for (int k = 0; k < 22; ++k)
-      total[k] += g->h_parts[22 * static_cast<size_t>(r) + k];
-  return mcl3dl_hip_covariance_finish(total, out_cov36);
+        return mcl3dl_hip_covariance_window_partial_device(ctx, ctx->pose.as<float>(), ctx->gs_weight.as<float>(), n, d_list, m, lo,
+                                                           mean7, ctx->gs_rec.as<double>());
+      });
 }
 }  // namespace
 
@@ -112,8 +101,7 @@ int mcl3dl_hip_group_covariance_sampled(mcl3dl_hip_group* g, const float* mean7,
   if (!g)
     return -1;
   const size_t n_p = g->n_resident;
-  if (n_p == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  TRY(group_resident(g));
   if (!mean7 || !out_cov36)
     return g->fail(-3, "null mean / covariance array");
   if (!subset || n_subset == 0 || n_subset > 0x7fffffffu)
@@ -130,8 +118,7 @@ int mcl3dl_hip_group_covariance_drawn(mcl3dl_hip_group* g, const float* mean7, f
   if (!g)
     return -1;
   const size_t n_p = g->n_resident;
-  if (n_p == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  TRY(group_resident(g));
   if (!mean7 || !out_cov36)
     return g->fail(-3, "null mean / covariance array");
   if (std::isnan(random_sample_ratio) || random_sample_ratio < 0.f)

@@ -13,6 +13,7 @@
 #include <rccl/rccl.h>  // types and enum values only: every RCCL call goes through the dlopen'ed pointers below
 
 #include "host_group_sync.h"  // WorkerPool, VoteBarrier, run_round
+#include "shard_layout.h"     // shard_bounds, shard_capacity, the inverse map
 
 namespace
 {
@@ -58,6 +59,10 @@ struct RcclApi
 };
 
 }  // namespace
+
+// how a sharded call combines its ranks: not at all (a group of one device that may call its context directly: it never loads
+// RCCL), through the host ("collective" 1), or over RCCL
+enum GroupRoute { ROUTE_DIRECT, ROUTE_HOST, ROUTE_RCCL };
 
 struct mcl3dl_hip_group
 {
@@ -121,6 +126,10 @@ struct mcl3dl_hip_group
   {
     return static_cast<int>(ctx.size());
   }
+  GroupRoute route() const
+  {
+    return n() == 1 && direct_single ? ROUTE_DIRECT : collective == 1 ? ROUTE_HOST : ROUTE_RCCL;
+  }
   int fail(int code, const char* fmt, ...)
   {
     char buf[640];
@@ -139,15 +148,6 @@ struct mcl3dl_hip_group
 
 namespace
 {
-// contiguous shard [lo, hi) of rank r when n particles are split over `world` ranks (sizes differ by at most one):
-// the same rule as mcl_3dl_amd/distributed.py:shard_bounds
-inline void shard_bounds(size_t n, int world, int r, size_t* lo, size_t* hi)
-{
-  const size_t base = n / world, rem = n % world;
-  *lo = r * base + std::min<size_t>(r, rem);
-  *hi = *lo + base + (static_cast<size_t>(r) < rem ? 1 : 0);
-}
-
 // rank r's view of n_p sharded particles: its context and its shard [lo, lo + n)
 struct Shard
 {
@@ -161,13 +161,6 @@ inline Shard shard_of(const mcl3dl_hip_group* g, size_t n_p, int r)
   size_t lo, hi;
   shard_bounds(n_p, g->n(), r, &lo, &hi);
   return Shard{ g->ctx[r], r, lo, hi - lo };
-}
-
-// Every rank computes the same scalars from the same combined record; they are taken from the first shard that holds a
-// particle. shard_bounds hands rank 0 a particle before any other rank, so that is rank 0 whenever there is a particle at all.
-inline int first_nonempty_rank(size_t)
-{
-  return 0;
 }
 
 // f(rank) on every rank's worker, the failing rank's error reported; no collective, nothing waits for another rank
@@ -186,12 +179,37 @@ int group_run_shards(mcl3dl_hip_group* g, size_t n_p, const F& f)
   return group_run(g, [&](int r) -> int { return f(shard_of(g, n_p, r)); });
 }
 
+// f(ctx, rank) on every rank in turn ON THE CALLING THREAD (the setters, and a group of one device that calls its context
+// directly), the first failing rank's error reported
+template <typename F>
+int group_forward(mcl3dl_hip_group* g, const F& f)
+{
+  for (int r = 0; r < g->n(); ++r)
+  {
+    const int rc = f(g->ctx[r], r);
+    if (rc)
+      return g->fail_rank(rc, r);
+  }
+  return 0;
+}
+
+// the guard of every call on the resident particles
+inline int group_resident(mcl3dl_hip_group* g)
+{
+  return g->n_resident ? 0 : g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+}
+
+// ... and of a rank: it holds the n particles of its shard
+inline int rank_holds(mcl3dl_hip_ctx* ctx, size_t n)
+{
+  return ctx->gs_n == n ? 0 : ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, n);
+}
+
 // the shard-local calls on the resident particles: f(ctx, rank, lo, n) on every rank whose shard holds particles
 template <typename F>
 int group_each_shard(mcl3dl_hip_group* g, const F& f)
 {
-  if (g->n_resident == 0)
-    return g->fail(-5, "no resident particles (mcl3dl_hip_group_upload_state first)");
+  TRY(group_resident(g));
   return group_run_shards(g, g->n_resident,
                           [&](const Shard& s) -> int
                           {
@@ -199,10 +217,22 @@ int group_each_shard(mcl3dl_hip_group* g, const F& f)
                             if (s.n == 0)
                               return 0;
                             HIP_TRY(hipSetDevice(ctx->device));
-                            if (ctx->gs_n != s.n)
-                              return ctx->fail(-5, "this device holds %zu resident particles, its shard has %zu", ctx->gs_n, s.n);
+                            TRY(rank_holds(ctx, s.n));
                             return f(ctx, s.r, s.lo, s.n);
                           });
+}
+
+// Every rank computed the same `width` words (words[width * r + k]) for itself — deterministic replicas, no collective: rank r is
+// held against rank 0 unless either sat the call out (took_part, null: all did). -4 names what differs, the values and the rank.
+template <typename W>
+int group_agree(mcl3dl_hip_group* g, const char* what, const W* words, size_t width, const char* took_part = nullptr)
+{
+  for (int r = 1; r < g->n(); ++r)
+    for (size_t k = 0; k < width && (!took_part || (took_part[0] && took_part[r])); ++k)
+      if (words[width * r + k] != words[k])
+        return g->fail(-4, "the ranks disagree on %s (%llu on rank 0, %llu on rank %d)", what,
+                       static_cast<unsigned long long>(words[k]), static_cast<unsigned long long>(words[width * r + k]), r);
+  return 0;
 }
 
 int group_comms(mcl3dl_hip_group* g)
@@ -301,10 +331,8 @@ template <typename PhaseA, typename PhaseB>
 int group_allreduce_record(mcl3dl_hip_group* g, const char* what, size_t n_p, const PhaseA& phase_a, const PhaseB& phase_b)
 {
   const int N = g->n();
-  const bool no_collective = N == 1 && g->direct_single;
-  const bool host_combine = g->collective == 1 && !no_collective;
-  const bool over_rccl = !no_collective && !host_combine;
-  if (!no_collective)
+  const bool host_combine = g->route() == ROUTE_HOST, over_rccl = g->route() == ROUTE_RCCL;
+  if (over_rccl)
     TRY(group_comms(g));
   const size_t n_pack = 2 + 2 * static_cast<size_t>(N);
   TRY(group_voted_call(

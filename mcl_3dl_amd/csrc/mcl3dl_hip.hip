@@ -37,6 +37,7 @@ using namespace mcl3dl;
 #include "host_weighted.h"
 #include "host_shuffle.h"
 #include "host_group.h"
+#include "host_group_gather.h"
 
 // =================================================================================================================
 // C ABI

@@ -3,7 +3,9 @@ _group_resize_resident (float_prefix.h, resample_prefix_kernels.h) — beside th
 group: group_resample_begin + rng_uniform + _plan + _apply_drawn, and group_resample_begin(n_out) + _plan(1) + _apply. One GPU;
 64, 4096, 65 536 and 262 144 particles with tie-free weights (route 0), 4096 and 262 144 with 10 % dead particles (route 1: the
 tie groups are ordered on the host either way), resizeParticle to three quarters at 262 144. Ten calls each after two warm-up
-calls: min / median / max. The particles are uploaded again in front of every call, outside the timed part.
+calls: min / median / max. The particles are uploaded again in front of every call, outside the timed part. Then the same loop
+where every rank gathers weights, states and odometry noise (host_group_gather.h): one rank through the sharded path over RCCL
+and three contexts combined through the host, 4096 and 70 001 particles (profiles/group_gather_once_ab.txt).
   --profile : three calls each of the one-call forms only (the run rocprofv3 --kernel-trace --stats wraps)
   --write   : runs itself both ways and writes profiles/resample_resident.txt (the CPU replay's step counts appended) and
               profiles/resample_resident_kernel_stats.csv"""
@@ -75,6 +77,41 @@ def main():
                 print("  begin(%d) + plan(1) + apply                 : " % n_out + times(lambda: g.upload_state(st, w),
                                                                                          resize_three))
     g.close()
+    if not profile_only:
+        gathered()
+
+
+def gathered():
+    """The same loop where every rank gathers the weights, the states and the odometry noise: one rank through the sharded path
+    (RCCL all-gathers with one rank) and three contexts on the one GPU combined through the host."""
+    from mcl_3dl_amd import capi
+    for label, devices, collective in (("one rank, direct_single 0 (RCCL)", [0], None), ("three contexts, host gather", [0, 0, 0], "host")):
+        g = capi.Group(devices, collective=collective)
+        g.set_option("direct_single", 0)
+
+        def three_calls():
+            pstep = g.resample_begin()
+            ip, st = capi.rng_uniform(SEED, 0.0, pstep)
+            g.resample_plan(0, ip)
+            g.resample_apply_drawn(SIGMA6, st)
+
+        for n in (4096, 70001):
+            rng = np.random.default_rng(n)
+            st = rng.normal(0, 1, (n, 13)).astype(np.float32)
+            st[:, 3:7] /= np.linalg.norm(st[:, 3:7], axis=1, keepdims=True)
+            w = rng.uniform(0.5, 1.5, n)
+            w = (w / w.sum()).astype(np.float32)
+            noise = rng.normal(0, 0.1, (n, 4)).astype(np.float32)
+
+            def setup():
+                g.upload_state(st, w)
+                g.set_odom_noise(noise)
+
+            print("%s, %d particles, tie-free, odometry noise installed" % (label, n))
+            print("  resample_drawn (one call)                       : " + times(setup, lambda: g.resample_drawn(SIGMA6, SEED)))
+            print("  begin + rng_uniform + plan + apply_drawn         : " + times(setup, three_calls))
+            print("  resize_resident to %d (one call)              : " % (3 * n // 4) + times(setup, lambda: g.resize_resident(3 * n // 4)))
+        g.close()
 
 
 def write():

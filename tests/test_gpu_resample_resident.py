@@ -51,6 +51,15 @@ def g3():
 
 
 @pytest.fixture(scope="module")
+def g1r():
+    """One rank through the sharded path: RCCL runs ncclAllGather with one rank for the weights, the states and the noise."""
+    g = capi.Group([0])
+    g.set_option("direct_single", 0)
+    yield g
+    g.close()
+
+
+@pytest.fixture(scope="module")
 def eng():
     e = capi.Engine(0)
     yield e
@@ -311,6 +320,74 @@ def test_shards_match_a_group_of_one(g1, g3, dead):
         assert res[0][0] == res[1][0]
         np.testing.assert_array_equal(res[0][1], res[1][1])
         np.testing.assert_array_equal(res[0][2], res[1][2])
+
+
+def odom_noise(n):
+    return np.random.default_rng(n + 17).normal(0, 0.1, (n, 4)).astype(F)
+
+
+@pytest.mark.parametrize("with_noise", [False, True])
+@pytest.mark.parametrize("n,n_out", [(1, 3), (65, 64), (1000, 1500)])
+def test_one_rank_over_rccl_equals_the_three_calls(g1r, g1b, n, n_out, with_noise):
+    """The gather of the weights, the states and the odometry noise with one rank over RCCL (padded ncclAllGather + unpad): the
+    one-call forms on the sharded group against the three-call sequences on a direct group of one."""
+    s, w = states(n, seed=n + 1), tie_free(n)
+    st0 = capi.rng_seed(n + 3)
+
+    def start():
+        for g in (g1r, g1b):
+            g.upload_state(s, w)
+            if with_noise:
+                g.set_odom_noise(odom_noise(n))
+
+    start()
+    before = g1r.collective_stats()
+    one, three = one_call(g1r, rc.SIGMA6, st0), three_call(g1b, rc.SIGMA6, st0)
+    # the weights' all-gather, and the states' (the noise rides in the states' round)
+    assert g1r.collective_stats() == dict(rccl=before["rccl"] + 2, host=before["host"])
+    assert one["route"] == int(has_ties(w))
+    assert_same(one, three)
+    assert one["odom"].any() == (with_noise and bool(np.any(three["dup"] == 0)))
+    start()
+    route = g1r.resize_resident(n_out)
+    g1b.resample_begin(n_out)
+    src, dup, nd = g1b.resample_plan(1)
+    g1b.resample_apply()
+    assert route == int(has_ties(w)) and nd == 0
+    assert g1r.resident() == g1b.resident() == n_out
+    got, want = g1r.download_state(), g1b.download_state()
+    np.testing.assert_array_equal(got[0], want[0])
+    np.testing.assert_array_equal(got[0], s[src])
+    np.testing.assert_array_equal(got[1], want[1])
+    np.testing.assert_array_equal(g1r.download_odom_noise(), g1b.download_odom_noise())
+    if with_noise:
+        np.testing.assert_array_equal(g1r.download_odom_noise(), odom_noise(n)[src])
+
+
+def test_more_ranks_than_particles_through_the_host(g1):
+    """Five contexts, three particles: two shards are empty (and every shard is, or is one short of, the largest). Each step
+    against a group of one given the same calls."""
+    s, w = states(3, seed=8), tie_free(3)
+    g5 = capi.Group([0] * 5, collective="host")
+    try:
+        # (g1 is the module's shared direct group: whatever it held, the first step below is an upload_state, which replaces it)
+        def both(call):
+            out = [call(g) for g in (g5, g1)]
+            assert out[0] == out[1]  # what the call returns: resize's route; resample_drawn's engine state, pstep, initial_p, n_dup
+            assert g5.resident() == g1.resident()
+            for a, b in zip(g5.download_state() + (g5.download_odom_noise(),), g1.download_state() + (g1.download_odom_noise(),)):
+                np.testing.assert_array_equal(a, b)
+
+        both(lambda g: g.upload_state(s, w))
+        both(lambda g: g.set_odom_noise(odom_noise(3)))
+        assert g5.download_odom_noise().any()
+        both(lambda g: g.resize_resident(7))
+        assert g5.resident() == 7
+        both(lambda g: g.resize_resident(2))
+        assert g5.resident() == 2
+        both(lambda g: g.resample_drawn(rc.SIGMA6, capi.rng_seed(5)))
+    finally:
+        g5.close()
 
 
 # ---- further cases ---------------------------------------------------------------------------------------------------------
