@@ -572,10 +572,34 @@ int mcl3dl_hip_group_set_odom_error_sigma(mcl3dl_hip_group* g, float sigma);
  *                         {lin_lin, lin_ang, ang_ang, ang_lin}.
  *   resample_apply_drawn  resample_apply with generateNoise per duplicated slot in slot order (pf.h:216); duplicated particles
  *                         get zero odometry noise, as there.
+ *   noise_transform6      MultivariateNoiseGenerator::setCovariance (multivariate_noise_generator.h:63-77) for the `initialpose`
+ *                         covariance: transform36 = V diag(sqrt(lambda)), row-major 6x6. Host only. A definition of this
+ *                         library's own: the 36 doubles cast to float, the lower triangle read, a cyclic Jacobi in double (30
+ *                         sweeps at the most), eigenvalues ascending, each eigenvector's largest component positive (lowest index
+ *                         on a tie), T[i][k] = (float)(V[i][k] sqrt(lambda_k)). No Eigen release's eigenvectors are reproduced
+ *                         (within a repeated eigenvalue any orthonormal basis is valid): particles drawn with it have the
+ *                         reference's distribution, not its bits. An eigenvalue in [-2^-23 |C|_F, 0) — what rounding a positive
+ *                         semi-definite matrix to float can produce — is set to 0; -3 for a more negative one (the reference
+ *                         would fill the particles with NaN; the message on stderr names the eigenvalue), for NULL cov36 /
+ *                         transform36 and for a non-finite entry. eigenvalues6 may be NULL.
+ *   init_drawn_multivariate  cbPosition (src/mcl_3dl.cpp:186-195): pf_->initUsingNoiseGenerator(MultivariateNoiseGenerator<float>(
+ *                         mean, cov)) and, with reset_odom_integ = 1, the integ_reset_func pass behind it. Per particle ONE
+ *                         normal_distribution<float>(0, 1) is called six times (multivariate_noise_generator.h:80-91): 3 n_p
+ *                         accepted attempts of one shared stream, then org = mean6 + transform36 * values in float, the six
+ *                         products summed left to right without fused multiply-add (Eigen's association is not pinned), and
+ *                         generateNoise as for init_drawn; weights 1 / n_p, odometry noise 0. It takes the transform, not the
+ *                         covariance: noise_transform6's, or Eigen's own eigenvectors() * eigenvalues().cwiseSqrt().asDiagonal()
+ *                         for the reference's particles value for value. Zero entries, even an all-zero transform, draw like any
+ *                         other: the engine always advances by the calls of 3 n_p accepted attempts. -3: NULL or non-finite
+ *                         mean7 / transform36, n_p == 0 or > 0x7fffffff / 16, reset_odom_integ not 0 or 1, engine_state as
+ *                         below; nothing is touched then, the resident particles stay.
  * On N devices every rank evaluates the accept decisions of the whole stream (deterministic replicas, no collective) and forms
  * the values of its own shard only. -3: NULL or non-finite sigma6 / mean7 / odom_err4, a negative sigma, engine_state NULL or
  * outside [1, 2^31 - 2]. -5: no resident particles; resample_apply_drawn without a plan. All six sigmas zero is legal: nothing
  * is drawn, engine_state is unchanged and the noise states are the means. */
+int mcl3dl_hip_noise_transform6(const double* cov36, float* transform36, float* eigenvalues6 /*or NULL*/);
+int mcl3dl_hip_group_init_drawn_multivariate(mcl3dl_hip_group* g, const float* mean7, const float* transform36, size_t n_p,
+                                             int reset_odom_integ, uint32_t* engine_state);
 uint32_t mcl3dl_hip_rng_seed(uint32_t seed);
 float mcl3dl_hip_rng_uniform(uint32_t* state, float a, float b);
 int mcl3dl_hip_group_add_noise_drawn(mcl3dl_hip_group* g, const float* sigma6, uint32_t* engine_state);

@@ -134,6 +134,8 @@ SIGNATURES = {
     "mcl3dl_hip_rng_uniform": (_f, [C.POINTER(_u32), _f, _f]),
     "mcl3dl_hip_group_add_noise_drawn": (_i, [_p, _p, C.POINTER(_u32)]),
     "mcl3dl_hip_group_init_drawn": (_i, [_p, _p, _p, _sz, C.POINTER(_u32)]),
+    "mcl3dl_hip_noise_transform6": (_i, [_p, _p, _p]),
+    "mcl3dl_hip_group_init_drawn_multivariate": (_i, [_p, _p, _p, _sz, _i, C.POINTER(_u32)]),
     "mcl3dl_hip_group_draw_odom_noise": (_i, [_p, _p, C.POINTER(_u32)]),
     "mcl3dl_hip_group_resample_apply_drawn": (_i, [_p, _p, C.POINTER(_u32)]),
     "mcl3dl_hip_rng_draw_indices": (_i, [_p, _u64, _sz, C.POINTER(_u32), _p]),
@@ -656,6 +658,19 @@ class Group:
         st = _u32(int(engine_state))
         self._check(self.lib.mcl3dl_hip_group_init_drawn(self.h, _ptr(_np_f32(mean7)), _ptr(_np_f32(sigma6)), int(n_p),
                                                          C.byref(st)))
+        return int(st.value)
+
+    def init_drawn_multivariate(self, mean7, transform36, n_p, engine_state, reset_odom_integ=False):
+        """cbPosition: pf_->initUsingNoiseGenerator(MultivariateNoiseGenerator(mean, cov)) with transform36 = the generator's
+        norm_transform_ (row-major 6x6: noise_transform6(cov)[0], or the caller's own), and with reset_odom_integ the
+        integ_reset_func pass behind it. n_p resident particles, weights 1 / n_p."""
+        st = _u32(int(engine_state))
+        t = _np_f32(transform36).reshape(-1)
+        if t.size != 36:
+            raise ValueError("init_drawn_multivariate: transform36 must hold 36 floats")
+        reset = reset_odom_integ if isinstance(reset_odom_integ, (int, np.integer)) else int(bool(reset_odom_integ))
+        self._check(self.lib.mcl3dl_hip_group_init_drawn_multivariate(self.h, _ptr(_np_f32(mean7)), _ptr(t), int(n_p),
+                                                                      int(reset), C.byref(st)))
         return int(st.value)
 
     def draw_odom_noise(self, odom_err4, engine_state):
@@ -1448,6 +1463,21 @@ def rng_uniform(engine_state, a, b):
     st = _u32(int(engine_state))
     v = load_library().mcl3dl_hip_rng_uniform(C.byref(st), float(a), float(b))
     return float(v), int(st.value)
+
+
+def noise_transform6(cov36):
+    """MultivariateNoiseGenerator::setCovariance for the `initialpose` covariance (36 doubles, row-major), by this library's own
+    definition (no GPU needed): (T float32[6, 6] = V diag(sqrt(lambda)), eigenvalues float32[6] ascending, behind the clamp of
+    rounding-sized negative ones). Raises ValueError for a non-finite entry or a covariance that is not positive semi-definite."""
+    c = np.ascontiguousarray(cov36, dtype=np.float64).reshape(-1)
+    if c.size != 36:
+        raise ValueError("noise_transform6: cov36 must hold 36 values")
+    t, ev = np.zeros((6, 6), np.float32), np.zeros(6, np.float32)
+    rc = load_library().mcl3dl_hip_noise_transform6(_ptr(c), _ptr(t), _ptr(ev))
+    if rc != 0:
+        raise ValueError("noise_transform6: error %d: the covariance holds a non-finite entry or has an eigenvalue below "
+                         "-2^-23 |C|_F (the library names it on stderr)" % rc)
+    return t, ev
 
 
 def rng_draw_indices(engine, range_, count, engine_state):

@@ -7,6 +7,8 @@
 //   mcl3dl_hip_rng_seed / _rng_uniform          engine(seed) / uniform_real_distribution<float>(a, b)(engine): host arithmetic
 //   mcl3dl_hip_group_add_noise_drawn            pf::noise (pf.h:226-237)
 //   mcl3dl_hip_group_init_drawn                 pf::init (pf.h:169-181)
+//   mcl3dl_hip_noise_transform6                 MultivariateNoiseGenerator::setCovariance (noise_transform.h), on the host
+//   mcl3dl_hip_group_init_drawn_multivariate    cbPosition's initUsingNoiseGenerator + integ_reset_func (src/mcl_3dl.cpp:186-195)
 //   mcl3dl_hip_group_draw_odom_noise            update_noise_func (src/mcl_3dl.cpp:817-825)
 //   mcl3dl_hip_group_resample_apply_drawn       pf::resample's generateNoise per duplicated slot, in slot order (pf.h:216)
 namespace
@@ -161,6 +163,65 @@ int mcl3dl_hip_group_init_drawn(mcl3dl_hip_group* g, const float* mean7, const f
                            return 0;
                          // p.state_ = generateNoise(engine_, generator): the row IS the state
                          TRY(rng_noise_rows(ctx, x0, gen, n_p, s.lo, s.n, ctx->gs_state[0].as<float>(), &states[s.r]));
+                         drew[s.r] = 1;
+                         TRY(uniform_weights(ctx, s.n, weight));
+                         TRY(generation_rank_installed(ctx, s.n, false));
+                         return sync_stream(ctx);
+                       }));
+  TRY(rng_hand_back(g, states, drew, engine_state));
+  generation_installed(g, n_p);
+  return 0;
+}
+
+int mcl3dl_hip_noise_transform6(const double* cov36, float* transform36, float* eigenvalues6)
+{
+  char msg[192] = "";
+  const int rc = noise_transform6(cov36, transform36, eigenvalues6, nullptr, msg, sizeof(msg));
+  if (rc)
+    fprintf(stderr, "mcl3dl_hip_noise_transform6: %s\n", msg);  // no handle to keep the message in
+  return rc;
+}
+
+int mcl3dl_hip_group_init_drawn_multivariate(mcl3dl_hip_group* g, const float* mean7, const float* transform36, size_t n_p,
+                                             int reset_odom_integ, uint32_t* engine_state)
+{
+  if (!g)
+    return -1;
+  if (!mean7)
+    return g->fail(-3, "null mean7");
+  for (int k = 0; k < 7; ++k)
+    if (!std::isfinite(mean7[k]))
+      return g->fail(-3, "mean7[%d] is not finite", k);
+  if (!transform36)
+    return g->fail(-3, "null transform36");
+  rng::NoiseGenFull6 gen;
+  for (int k = 0; k < 36; ++k)
+  {
+    if (!std::isfinite(transform36[k]))
+      return g->fail(-3, "transform36[%d] is not finite", k);
+    gen.t[k] = transform36[k];
+  }
+  rng_mean6(mean7, gen.mean);
+  TRY(rng_check_state(g, engine_state));
+  if (n_p == 0 || n_p > 0x7fffffffu / 16)
+    return g->fail(-3, "init_drawn_multivariate: %zu particles asked for", n_p);
+  if (reset_odom_integ != 0 && reset_odom_integ != 1)
+    return g->fail(-3, "reset_odom_integ must be 0 or 1, not %d", reset_odom_integ);
+  gen.reset_odom_integ = reset_odom_integ;
+  generation_begin(g);
+  const int N = g->n();
+  std::vector<uint32_t> states(N, 0u);
+  std::vector<char> drew(N, 0);
+  const uint32_t x0 = *engine_state;
+  const float weight = static_cast<float>(1.0 / static_cast<double>(n_p));  // pf.h:179
+  TRY(group_run_shards(g, n_p,
+                       [&](const Shard& s) -> int
+                       {
+                         mcl3dl_hip_ctx* ctx = s.ctx;
+                         TRY(generation_rank_begin(ctx, n_p, N));
+                         if (s.n == 0)
+                           return 0;
+                         TRY(rng_multivariate_rows(ctx, x0, gen, n_p, s.lo, s.n, ctx->gs_state[0].as<float>(), &states[s.r]));
                          drew[s.r] = 1;
                          TRY(uniform_weights(ctx, s.n, weight));
                          TRY(generation_rank_installed(ctx, s.n, false));

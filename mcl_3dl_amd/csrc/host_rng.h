@@ -182,6 +182,22 @@ int rng_noise_rows(mcl3dl_hip_ctx* ctx, uint32_t state_in, const rng::NoiseGen6&
   return 0;
 }
 
+// n_rows rows of State6DOF::generateNoise behind MultivariateNoiseGenerator(gen), rows [row_begin, row_begin + n_rows) of the
+// n_total the call draws in row order, into d_rows13 (device). One normal_distribution per particle called six times: the saved
+// second value of every accepted attempt is used inside the particle, so the stream is that of one shared distribution, 3 n_total
+// accepted attempts, attempt k giving values 2k and 2k + 1. Zero entries of the transform draw like any other.
+int rng_multivariate_rows(mcl3dl_hip_ctx* ctx, uint32_t state_in, const rng::NoiseGenFull6& gen, uint64_t n_total,
+                          uint64_t row_begin, size_t n_rows, float* d_rows13, uint32_t* state_out)
+{
+  TRY(rng_draw(ctx, state_in, 3 * n_total, true, 3 * row_begin, 3 * (row_begin + n_rows), state_out));
+  if (n_rows == 0)
+    return 0;
+  hipLaunchKernelGGL(rng::rng_multivariate_state_kernel, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0,
+                     ctx->stream, ctx->rng_values.as<float>(), gen, static_cast<int>(n_rows), d_rows13);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // Quat::getRPY (quat.h:191-201) of the mean's rotation, once on the host: float storage, double intermediates, atan2 / asin in
 // double rounded to float (the rule of the landmark update)
 inline void rng_mean6(const float* mean7, float* mean6)

@@ -34,6 +34,7 @@ using namespace mcl3dl;
 #include "host_measure.h"
 #include "host_pf.h"
 #include "host_rng.h"
+#include "noise_transform.h"
 #include "host_weighted.h"
 #include "host_shuffle.h"
 #include "host_group.h"

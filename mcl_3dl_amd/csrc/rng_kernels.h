@@ -5,6 +5,8 @@
 //                            caller's window
 //   rng_noise_state_kernel   one lane per particle: DiagonalNoiseGenerator::operator() (value sigma + mean, zero sigmas skipped)
 //                            and State6DOF::generateNoise into the 13-float rows add_noise_kernel / resample_apply_kernel read
+//   rng_multivariate_state_kernel  one lane per particle: MultivariateNoiseGenerator::operator() (mean + T values, six values of one
+//                            shared distribution) and generateNoise into the same rows
 //   rng_odom_noise_kernel    update_noise_func's four values per particle, scaled, in set_odom_noise's storage order
 #pragma once
 #include <hip/hip_runtime.h>
@@ -62,6 +64,52 @@ __global__ void rng_noise_state_kernel(const float* __restrict__ values, NoiseGe
       v[k] = z[d++] * gen.sigma[k] + gen.mean[k];  // normal_distribution: ret * stddev + mean
   }
   noise6_to_state13(v, gen.mean, row);
+  float* o = out13 + 13 * static_cast<size_t>(i);
+#pragma unroll
+  for (int k = 0; k < 13; ++k)
+    o[k] = row[k];
+}
+
+// MultivariateNoiseGenerator (multivariate_noise_generator.h) for State6DOF: the mean's six values and norm_transform_, row-major
+struct NoiseGenFull6
+{
+  float mean[6], t[36];
+  int reset_odom_integ;  // 1: integ_reset_func behind the draw (src/mcl_3dl.cpp:190-195), columns 7-12 are 0
+};
+
+// one lane per particle: operator() (:80-91) and State6DOF::generateNoise behind ONE normal_distribution<float>(0, 1) called six
+// times, so row i takes values[6 i ...] of the pairs stream (the window starts at the first row's first value; 24 bytes per lane,
+// 8-byte aligned). sample_noise = mean_vec_ + norm_transform_ * random, in float without fused multiply-add, term by term:
+//   s_i   = ((((T[i][0] r0 + T[i][1] r1) + T[i][2] r2) + T[i][3] r3) + T[i][4] r4) + T[i][5] r5
+//   org_i = mean[i] + s_i
+// Eigen's own association of the six-term product is not pinned by the reference (it depends on Eigen's version and vector width:
+// DESIGN.md 3.10.1 says the same of the cloud transforms); this left-to-right sum is the definition here.
+__global__ void rng_multivariate_state_kernel(const float* __restrict__ values, NoiseGenFull6 gen, int n, float* __restrict__ out13)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n)
+    return;
+  const float2* z = reinterpret_cast<const float2*>(values) + 3 * static_cast<size_t>(i);
+  const float2 z01 = z[0], z23 = z[1], z45 = z[2];
+  const float raw[6] = { z01.x, z01.y, z23.x, z23.y, z45.x, z45.y };
+  float r[6], org[6], row[13];
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+    r[k] = raw[k] * 1.0f + 0.0f;  // normal_distribution(0, 1): ret * stddev + mean
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+  {
+    const float* t = gen.t + 6 * k;
+    const float s = ((((t[0] * r[0] + t[1] * r[1]) + t[2] * r[2]) + t[3] * r[3]) + t[4] * r[4]) + t[5] * r[5];
+    org[k] = gen.mean[k] + s;
+  }
+  noise6_to_state13(org, gen.mean, row);
+  if (gen.reset_odom_integ)
+  {
+#pragma unroll
+    for (int k = 7; k < 13; ++k)
+      row[k] = 0.0f;
+  }
   float* o = out13 + 13 * static_cast<size_t>(i);
 #pragma unroll
   for (int k = 0; k < 13; ++k)
