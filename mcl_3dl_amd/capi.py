@@ -2,6 +2,9 @@
 
 There is no CPU fallback: if the shared library is missing, or no gfx950 device is usable, loading / creating an
 engine raises.  The product never imports anything from oracle/.
+
+A call that exists for both a context and a group (mcl3dl_hip_X and mcl3dl_hip_group_X) is added in two places: one method
+on _Calls, which Engine and Group inherit and which reaches its symbol through self._fn("X"), and the name X in MIRRORED.
 """
 import ctypes as C
 import os
@@ -85,23 +88,9 @@ SIGNATURES = {
     "mcl3dl_hip_map_download": (_i, [_p, _p, _p, _sz, C.POINTER(_sz)]),
     "mcl3dl_hip_match_split": (_i, [_p, _p, _p, _sz, _f, _d, _p, _sz, C.POINTER(_sz), _p, _sz, C.POINTER(_sz)]),
     "mcl3dl_hip_group_create": (_i, [C.POINTER(_p), C.POINTER(_i), _i]),
-    "mcl3dl_hip_group_destroy": (None, [_p]),
-    "mcl3dl_hip_group_last_error": (C.c_char_p, [_p]),
     "mcl3dl_hip_group_size": (_i, [_p]),
     "mcl3dl_hip_group_context": (_p, [_p, _i]),
     "mcl3dl_hip_group_shard": (_i, [_sz, _i, _i, C.POINTER(_sz), C.POINTER(_sz)]),
-    "mcl3dl_hip_group_set_map": (_i, [_p, _p, _p, _sz, _u64, _p]),
-    "mcl3dl_hip_group_set_likelihood_params": (_i, [_p, _f, _f, _f]),
-    "mcl3dl_hip_group_set_beam_params": (_i, [_p, _f, _f, _f, _f, _f, _f, _f, _u32, _f, _u32, _i]),
-    "mcl3dl_hip_group_set_beam_raycast": (_i, [_p, _i]),
-    "mcl3dl_hip_group_set_option": (_i, [_p, C.c_char_p, _d]),
-    "mcl3dl_hip_group_upload_poses": (_i, [_p, _p, _sz]),
-    "mcl3dl_hip_group_measure_batch": (_i, [_p, _p, _sz, _p, _sz, _p, _p, _sz, _p, _sz, _p, _p, _p]),
-    "mcl3dl_hip_group_measure_batch_begin": (_i, [_p, _p, _sz, _p, _sz, _p, _p, _sz, _p, _sz, _p, _p, _p, _sz]),
-    "mcl3dl_hip_group_measure_batch_wait": (_i, [_p, _sz, _p]),
-    "mcl3dl_hip_group_measure_batch_end": (_i, [_p]),
-    "mcl3dl_hip_group_measure_update": (_i, [_p, _p, _p, _p, _sz, _p, _sz, _p, _p, _sz, _p, _sz, _p, _p, _p, _p, _p, _p,
-                                            _p]),
     "mcl3dl_hip_group_collective_stats": (_i, [_p, C.POINTER(_u64), C.POINTER(_u64)]),
     "mcl3dl_hip_group_upload_state": (_i, [_p, _p, _p, _sz]),
     "mcl3dl_hip_group_download_state": (_i, [_p, _p, _p, _sz]),
@@ -110,7 +99,6 @@ SIGNATURES = {
     "mcl3dl_hip_group_expectation": (_i, [_p, _p, _p, _p, _p, _p]),
     "mcl3dl_hip_group_covariance": (_i, [_p, _p, _p]),
     "mcl3dl_hip_group_resample_begin": (_i, [_p, _sz, _p]),
-    "mcl3dl_hip_group_resample_plan": (_i, [_p, _i, _f, _p, _p, _p]),
     "mcl3dl_hip_group_resample_apply": (_i, [_p, _p, _sz]),
     "mcl3dl_hip_group_set_odom_noise": (_i, [_p, _p, _sz]),
     "mcl3dl_hip_group_download_odom_noise": (_i, [_p, _p, _sz]),
@@ -146,11 +134,6 @@ SIGNATURES = {
                                              C.POINTER(_i)]),
     "mcl3dl_hip_group_resize_resident": (_i, [_p, _sz, C.POINTER(_i)]),
     "mcl3dl_hip_scan_finish_drawn": (_i, [_p, _sz, _sz, _p, _sz, C.POINTER(_u32), C.POINTER(_sz), C.POINTER(_sz)]),
-    "mcl3dl_hip_group_scan_begin": (_i, [_p, _p, _p, _sz, _p, _p, _p, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
-    "mcl3dl_hip_group_scan_begin_pointcloud2": (_i, [_p, _p, _sz, _u32, _i, _i, _i, _i, _u32, _p, _p, _p, C.POINTER(_sz),
-                                                    C.POINTER(_sz), C.POINTER(_sz)]),
-    "mcl3dl_hip_group_scan_finish": (_i, [_p, _p, _sz, _p, _sz, _p, _sz]),
-    "mcl3dl_hip_group_scan_finish_drawn": (_i, [_p, _sz, _sz, _p, _sz, C.POINTER(_u32), C.POINTER(_sz), C.POINTER(_sz)]),
     "mcl3dl_hip_group_update_resident_prepared": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "mcl3dl_hip_scan_accum_clear": (_i, [_p]),
     "mcl3dl_hip_scan_accum_push": (_i, [_p, _p, _sz, _p, C.POINTER(_sz), C.POINTER(_sz)]),
@@ -158,21 +141,25 @@ SIGNATURES = {
     "mcl3dl_hip_scan_accum_size": (_i, [_p, C.POINTER(_sz), C.POINTER(_sz)]),
     "mcl3dl_hip_scan_accum_download": (_i, [_p, _p, _p, _sz, C.POINTER(_sz)]),
     "mcl3dl_hip_scan_begin_accumulated": (_i, [_p, _p, _p, _p, _p, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
-    "mcl3dl_hip_group_scan_accum_clear": (_i, [_p]),
-    "mcl3dl_hip_group_scan_accum_push": (_i, [_p, _p, _sz, _p, C.POINTER(_sz), C.POINTER(_sz)]),
-    "mcl3dl_hip_group_scan_accum_push_pointcloud2": (_i, [_p, _p, _sz, _u32, _i, _i, _i, _p, C.POINTER(_sz), C.POINTER(_sz)]),
-    "mcl3dl_hip_group_scan_accum_size": (_i, [_p, C.POINTER(_sz), C.POINTER(_sz)]),
-    "mcl3dl_hip_group_scan_begin_accumulated": (_i, [_p, _p, _p, _p, _p, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz)]),
     "mcl3dl_hip_rng_draw_weighted": (_i, [_p, _p, _sz, _sz, C.POINTER(_u32), _p, _p, C.POINTER(_u64)]),
     "mcl3dl_hip_scan_finish_drawn_normal": (_i, [_p, _sz, _sz, _p, _sz, _d, _p, _d, C.POINTER(_u32), C.POINTER(_sz),
                                                 C.POINTER(_sz)]),
-    "mcl3dl_hip_group_scan_finish_drawn_normal": (_i, [_p, _sz, _sz, _p, _sz, _d, _p, _d, C.POINTER(_u32), C.POINTER(_sz),
-                                                      C.POINTER(_sz)]),
     "mcl3dl_hip_rng_shuffle_prefix": (_i, [_p, _sz, _sz, C.POINTER(_u32), _p]),
     "mcl3dl_hip_covariance_window_partial_device": (_i, [_p, _p, _p, _sz, _p, _sz, _sz, _p, _p]),
     "mcl3dl_hip_group_covariance_sampled": (_i, [_p, _p, _p, _sz, _p]),
     "mcl3dl_hip_group_covariance_drawn": (_i, [_p, _p, _f, C.POINTER(_u32), C.POINTER(_sz), _p]),
 }
+
+# the calls that exist for a context and for a group alike: behind the handle the header declares the two identically, so
+# mcl3dl_hip_group_<name> takes the context's entry itself (tests/test_capi_calls_cpu.py holds the header to that)
+MIRRORED = (
+    "destroy", "last_error", "set_map", "set_likelihood_params", "set_beam_params", "set_beam_raycast", "set_option",
+    "upload_poses", "measure_batch", "measure_batch_begin", "measure_batch_wait", "measure_batch_end", "measure_update",
+    "resample_plan", "scan_begin", "scan_begin_pointcloud2", "scan_accum_clear", "scan_accum_push",
+    "scan_accum_push_pointcloud2", "scan_accum_size", "scan_begin_accumulated", "scan_finish", "scan_finish_drawn",
+    "scan_finish_drawn_normal")
+for _name in MIRRORED:
+    SIGNATURES["mcl3dl_hip_group_" + _name] = SIGNATURES["mcl3dl_hip_" + _name]
 
 _lib = None
 
@@ -248,6 +235,43 @@ def _affine12(affine):
     return a
 
 
+def _f3(a):
+    return None if a is None else _np_f32(a)
+
+
+def _scans(scan_lik, scan_beam, scan_beam_origin, origins):
+    sl = _np_f32(scan_lik if scan_lik is not None else np.zeros((0, 3)), 3)
+    sb = _np_f32(scan_beam if scan_beam is not None else np.zeros((0, 3)), 3)
+    so = (np.zeros(len(sb), np.uint32) if scan_beam_origin is None
+          else np.ascontiguousarray(scan_beam_origin, dtype=np.uint32))
+    og = _np_f32(origins if origins is not None else np.zeros((1, 3)), 3)
+    return sl, sb, so, og
+
+
+def _state(engine_state):
+    """The word of the reference's engine a call draws from: handed over by reference, the state behind the draws comes back."""
+    return _u32(int(engine_state))
+
+
+def _sizes(n):
+    """n size_t words for the library to write."""
+    return tuple(C.c_size_t(0) for _ in range(n))
+
+
+def _ints(*words):
+    """Words the library wrote (sizes, an engine state), as a tuple of int."""
+    return tuple(int(w.value) for w in words)
+
+
+def _update_result(ent, rest, rmin=None, rmax=None, **arrays):
+    """What an update returns: its arrays, then the scalars the library wrote (the match ratios where the call has them)."""
+    arrays["entropy"] = float(ent.value)
+    if rmin is not None:
+        arrays["match_ratio_min"], arrays["match_ratio_max"] = float(rmin.value), float(rmax.value)
+    arrays["restored"] = bool(rest.value)
+    return arrays
+
+
 def scan_order_host(scan_lik):
     """mcl3dl_hip_scan_order_host: the engine's order of a likelihood scan, computed on the host (no GPU needed)."""
     lib = load_library()
@@ -261,10 +285,10 @@ def scan_order_host(scan_lik):
 def group_shard(n_p, n_devices, rank):
     """[begin, begin + count) of `rank` — the library's own shard rule (no GPU needed)."""
     lib = load_library()
-    b, c = C.c_size_t(0), C.c_size_t(0)
+    b, c = _sizes(2)
     if lib.mcl3dl_hip_group_shard(n_p, n_devices, rank, C.byref(b), C.byref(c)) != 0:
         raise EngineError("group_shard: bad arguments")
-    return int(b.value), int(c.value)
+    return _ints(b, c)
 
 
 def global_localization_rotations(div_yaw, imu_quat=None):
@@ -294,8 +318,212 @@ def sampler_normal_direction(mean, cov, perform_weighting_ratio=2.0, max_weight_
     return fpc, float(mw.value), float(ratio.value)
 
 
-class Group:
+class _Calls:
+    """The calls a context and a device group share, written once: Engine and Group inherit them, and self._fn(name) is
+    mcl3dl_hip_<name> on the one and mcl3dl_hip_group_<name> on the other (the names in MIRRORED). Where a docstring speaks of
+    "the device", a group does the same on every rank, each on its replica."""
+
+    # _prefix, _error: the symbol prefix of the handle self.h and the text of its EngineError
+
+    def _fn(self, name):
+        return getattr(self.lib, self._prefix + name)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc != 0:
+            raise EngineError(self._error % (rc, self._fn("last_error")(self.h).decode()))
+
+    # ---- configuration -----------------------------------------------------------------------------------------
+    def set_map(self, xyz, label=None, stamp=1, dist_weight=(1.0, 1.0, 1.0)):
+        xyz = _np_f32(xyz, 3)
+        lab = None if label is None else np.ascontiguousarray(label, dtype=np.uint32)
+        dw = None if dist_weight is None else _np_f32(dist_weight)
+        self._check(self._fn("set_map")(self.h, _ptr(xyz), _ptr(lab), len(xyz), int(stamp), _ptr(dw)))
+
+    def set_likelihood_params(self, match_dist_min=0.2, match_dist_flat=0.05, match_weight=5.0):
+        self._check(self._fn("set_likelihood_params")(self.h, match_dist_min, match_dist_flat, match_weight))
+
+    def set_beam_params(self, map_grid=(0.1, 0.1, 0.1), dda_grid_size=0.2, ray_angle_half=0.25 * np.pi / 180.0,
+                        hit_range=0.3, beam_likelihood_min=0.2, num_points=3, ang_total_ref=np.pi / 6.0,
+                        filter_label_max=0xFFFFFFFF, add_penalty_short_only_mode=True):
+        self._check(self._fn("set_beam_params")(
+            self.h, map_grid[0], map_grid[1], map_grid[2], dda_grid_size, ray_angle_half, hit_range,
+            beam_likelihood_min, int(num_points), ang_total_ref, int(filter_label_max),
+            int(bool(add_penalty_short_only_mode))))
+
+    def set_beam_raycast(self, mode):
+        """0 = RaycastUsingDDA (default, the fast path), 1 = RaycastUsingKDTree (the reference's default caster); a group
+        sets it on every rank."""
+        self._check(self._fn("set_beam_raycast")(self.h, int(mode)))
+
+    def set_option(self, name, value):
+        self._check(self._fn("set_option")(self.h, name.encode(), float(value)))
+
+    # ---- host entry points -------------------------------------------------------------------------------------
+    def upload_poses(self, poses):
+        poses = _np_f32(poses, 7)
+        self._check(self._fn("upload_poses")(self.h, _ptr(poses), len(poses)))
+        self._n_uploaded = len(poses)
+
+    def measure_batch(self, poses, scan_lik, scan_beam=None, scan_beam_origin=None, origins=None):
+        """poses=None: the set sent by upload_poses()."""
+        sl, sb, so, og = _scans(scan_lik, scan_beam, scan_beam_origin, origins)
+        if poses is None:
+            n_p = self._n_uploaded
+        else:
+            poses = _np_f32(poses, 7)
+            n_p = len(poses)
+        lik, ratio, beam = (np.zeros(n_p, np.float32) for _ in range(3))
+        self._check(self._fn("measure_batch")(self.h, _ptr(poses), n_p, _ptr(sl), len(sl), _ptr(sb), _ptr(so), len(sb),
+                                              _ptr(og), len(og), _ptr(lik), _ptr(ratio), _ptr(beam)))
+        return lik, ratio, beam
+
+    def measure_batch_begin(self, poses, scan_lik, scan_beam=None, scan_beam_origin=None, origins=None, slice_particles=0,
+                            out=None):
+        """mcl3dl_hip_measure_batch_begin: returns the (lik, ratio, beam) arrays the batch fills in particle order
+        (`out` = three caller-owned float32 arrays, e.g. host_array()s); measure_batch_wait(i) says how far they are valid."""
+        sl, sb, so, og = _scans(scan_lik, scan_beam, scan_beam_origin, origins)
+        if poses is None:
+            n_p = self._n_uploaded
+        else:
+            poses = _np_f32(poses, 7)
+            n_p = len(poses)
+        lik, ratio, beam = out if out is not None else (np.zeros(n_p, np.float32) for _ in range(3))
+        # (a batch still open is ended by this very call and delivers into ITS arrays: they stay alive until it returns)
+        previous = getattr(self, "_batch_keep", None)
+        self._batch_keep = (poses, sl, sb, so, og, lik, ratio, beam, previous)
+        self._check(self._fn("measure_batch_begin")(self.h, _ptr(poses), n_p, _ptr(sl), len(sl), _ptr(sb), _ptr(so), len(sb),
+                                                    _ptr(og), len(og), _ptr(lik), _ptr(ratio), _ptr(beam),
+                                                    int(slice_particles)))
+        self._batch_keep = self._batch_keep[:8]
+        return lik, ratio, beam
+
+    def measure_batch_wait(self, particle):
+        n = C.c_size_t(0)
+        self._check(self._fn("measure_batch_wait")(self.h, int(particle), C.byref(n)))
+        return n.value
+
+    def measure_batch_end(self):
+        self._check(self._fn("measure_batch_end")(self.h))
+        self._batch_keep = None
+
+    def measure_update(self, poses, weights, scan_lik, scan_beam=None, scan_beam_origin=None, origins=None, extra=None):
+        poses = _np_f32(poses, 7)
+        n_p = len(poses)
+        w = _np_f32(weights).copy()
+        ex = None if extra is None else _np_f32(extra)
+        sl, sb, so, og = _scans(scan_lik, scan_beam, scan_beam_origin, origins)
+        lik, ratio, beam = (np.zeros(n_p, np.float32) for _ in range(3))
+        ent, rmin, rmax, rest = C.c_float(0), C.c_float(0), C.c_float(0), C.c_int(0)
+        self._check(self._fn("measure_update")(
+            self.h, _ptr(poses), _ptr(ex), _ptr(w), n_p, _ptr(sl), len(sl), _ptr(sb), _ptr(so), len(sb), _ptr(og),
+            len(og), _ptr(lik), _ptr(ratio), _ptr(beam), C.byref(ent), C.byref(rmin), C.byref(rmax), C.byref(rest)))
+        return _update_result(ent, rest, rmin, rmax, weights=w, lik=lik, quality=ratio, beam=beam)
+
+    # ---- scan preparation on the device (SURVEY.md 8f-2) ----------------------------------------------------------
+    def scan_begin(self, xyz, label=None, leaf=None, clip_lik=(0.5, 10.0, -2.0, 2.0), clip_beam=(0.5, 4.0, -2.0, 2.0)):
+        """VoxelGrid + both clip filters on the device; returns (n_full, n_lik_clipped, n_beam_clipped)."""
+        pts = _np_f32(xyz, 3)
+        lab = None if label is None else np.ascontiguousarray(label, dtype=np.uint32)
+        lf, cl, cb = _f3(leaf), _f3(clip_lik), _f3(clip_beam)
+        a, b, c = _sizes(3)
+        self._check(self._fn("scan_begin")(self.h, _ptr(pts), _ptr(lab), len(pts), _ptr(lf), _ptr(cl), _ptr(cb), C.byref(a),
+                                           C.byref(b), C.byref(c)))
+        return _ints(a, b, c)
+
+    def scan_begin_pointcloud2(self, data, n_points, point_step, off_x, off_y, off_z, off_label=-1, label_override=0,
+                               leaf=None, clip_lik=(0.5, 10.0, -2.0, 2.0), clip_beam=(0.5, 4.0, -2.0, 2.0)):
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        lf, cl, cb = _f3(leaf), _f3(clip_lik), _f3(clip_beam)
+        a, b, c = _sizes(3)
+        self._check(self._fn("scan_begin_pointcloud2")(self.h, _ptr(buf), n_points, point_step, off_x, off_y, off_z, off_label,
+                                                       label_override, _ptr(lf), _ptr(cl), _ptr(cb), C.byref(a), C.byref(b),
+                                                       C.byref(c)))
+        return _ints(a, b, c)
+
+    # ---- clouds accumulated on the device (accumClear / accumCloud and the head of measure(), src/mcl_3dl.cpp:267-336) ----------
+    def scan_accum_clear(self):
+        """accumClear: the accumulation is empty, the next push gets index 0."""
+        self._check(self._fn("scan_accum_clear")(self.h))
+
+    def scan_accum_push(self, xyz, affine=None):
+        """accumCloud for one message: the points (sensor frame) are transformed by `affine` (odom <- sensor; None: taken as they
+        are), labelled with the cloud's index and appended. Returns (cloud index, points held)."""
+        pts = _np_f32(xyz, 3)
+        a = _affine12(affine)
+        idx, tot = _sizes(2)
+        self._check(self._fn("scan_accum_push")(self.h, _ptr(pts), len(pts), _ptr(a), C.byref(idx), C.byref(tot)))
+        return _ints(idx, tot)
+
+    def scan_accum_push_pointcloud2(self, data, n_points, point_step, off_x, off_y, off_z, affine=None):
+        """scan_accum_push from PointCloud2 bytes (the message's label field, if any, is not read)."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        a = _affine12(affine)
+        idx, tot = _sizes(2)
+        self._check(self._fn("scan_accum_push_pointcloud2")(self.h, _ptr(buf), n_points, point_step, off_x, off_y, off_z,
+                                                            _ptr(a), C.byref(idx), C.byref(tot)))
+        return _ints(idx, tot)
+
+    def scan_accum_size(self):
+        """(clouds pushed since the last clear, points held)."""
+        c, n = _sizes(2)
+        self._check(self._fn("scan_accum_size")(self.h, C.byref(c), C.byref(n)))
+        return _ints(c, n)
+
+    def scan_begin_accumulated(self, affine=None, leaf=None, clip_lik=(0.5, 10.0, -2.0, 2.0), clip_beam=(0.5, 4.0, -2.0, 2.0)):
+        """scan_begin on the accumulation, transformed by `affine` (base_link <- odom; None: as it is) on the device; the
+        accumulation stays. Returns (n_full, n_lik_clipped, n_beam_clipped)."""
+        a, lf, cl, cb = _affine12(affine), _f3(leaf), _f3(clip_lik), _f3(clip_beam)
+        x, y, z = _sizes(3)
+        self._check(self._fn("scan_begin_accumulated")(self.h, _ptr(a), _ptr(lf), _ptr(cl), _ptr(cb), C.byref(x), C.byref(y),
+                                                       C.byref(z)))
+        return _ints(x, y, z)
+
+    def scan_finish(self, idx_lik, idx_beam=None, origins=None):
+        il = np.ascontiguousarray(idx_lik if idx_lik is not None else [], dtype=np.uint32)
+        ib = np.ascontiguousarray(idx_beam if idx_beam is not None else [], dtype=np.uint32)
+        og = _np_f32(origins if origins is not None else np.zeros((1, 3)), 3)
+        self._check(self._fn("scan_finish")(self.h, _ptr(il), len(il), _ptr(ib), len(ib), _ptr(og), len(og)))
+
+    def scan_finish_drawn(self, n_s, n_b, origins, engine_state):
+        """scan_finish with the uniform sampler drawn on the device from the reference's engine: beam's n_b draws first, then
+        the likelihood's n_s. Returns (n_s installed, n_b installed, engine state behind the draws)."""
+        og = None if origins is None else _np_f32(origins, 3)
+        st = _state(engine_state)
+        a, b = _sizes(2)
+        self._check(self._fn("scan_finish_drawn")(self.h, int(n_s), int(n_b), _ptr(og), 0 if og is None else len(og),
+                                                  C.byref(st), C.byref(a), C.byref(b)))
+        return _ints(a, b, st)
+
+    def scan_finish_drawn_normal(self, n_s, n_b, origins, normal_search_range, fpc_local, max_weight, engine_state):
+        """scan_finish with PointCloudSamplerWithNormal::sample run on the device for both models from the reference's engine
+        (beam first, then the likelihood): returns (n_s installed, n_b installed, engine state behind the draws)."""
+        og = None if origins is None else _np_f32(origins, 3)
+        f = _np_f32(fpc_local).reshape(-1)
+        if f.size != 3:
+            raise ValueError("scan_finish_drawn_normal: fpc_local must hold 3 floats")
+        st = _state(engine_state)
+        a, b = _sizes(2)
+        self._check(self._fn("scan_finish_drawn_normal")(
+            self.h, int(n_s), int(n_b), _ptr(og), 0 if og is None else len(og), float(normal_search_range), _ptr(f),
+            float(max_weight), C.byref(st), C.byref(a), C.byref(b)))
+        return _ints(a, b, st)
+
+
+class Group(_Calls):
     """N GPUs behind one handle in ONE process (include/mcl3dl_hip.h, "device groups"): host arrays in, host arrays out."""
+
+    _prefix, _error = "mcl3dl_hip_group_", "mcl3dl_hip group error %d: %s"
 
     def __init__(self, device_ids=(0,), collective=None):
         self.lib = load_library()
@@ -309,42 +537,6 @@ class Group:
         if collective is not None:
             self.set_option("collective", {"rccl": 0, "host": 1}[collective])
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.mcl3dl_hip_group_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != 0:
-            raise EngineError("mcl3dl_hip group error %d: %s" % (rc, self.lib.mcl3dl_hip_group_last_error(self.h).decode()))
-
-    def set_map(self, xyz, label=None, stamp=1, dist_weight=(1.0, 1.0, 1.0)):
-        xyz = _np_f32(xyz, 3)
-        lab = None if label is None else np.ascontiguousarray(label, dtype=np.uint32)
-        dw = None if dist_weight is None else _np_f32(dist_weight)
-        self._check(self.lib.mcl3dl_hip_group_set_map(self.h, _ptr(xyz), _ptr(lab), len(xyz), int(stamp), _ptr(dw)))
-
-    def set_likelihood_params(self, match_dist_min=0.2, match_dist_flat=0.05, match_weight=5.0):
-        self._check(self.lib.mcl3dl_hip_group_set_likelihood_params(self.h, match_dist_min, match_dist_flat, match_weight))
-
-    def set_beam_params(self, map_grid=(0.1, 0.1, 0.1), dda_grid_size=0.2, ray_angle_half=0.25 * np.pi / 180.0,
-                        hit_range=0.3, beam_likelihood_min=0.2, num_points=3, ang_total_ref=np.pi / 6.0,
-                        filter_label_max=0xFFFFFFFF, add_penalty_short_only_mode=True):
-        self._check(self.lib.mcl3dl_hip_group_set_beam_params(
-            self.h, map_grid[0], map_grid[1], map_grid[2], dda_grid_size, ray_angle_half, hit_range,
-            beam_likelihood_min, int(num_points), ang_total_ref, int(filter_label_max),
-            int(bool(add_penalty_short_only_mode))))
-
-    def set_beam_raycast(self, mode):
-        """0 = RaycastUsingDDA (default), 1 = RaycastUsingKDTree (the reference's default), on every rank."""
-        self._check(self.lib.mcl3dl_hip_group_set_beam_raycast(self.h, int(mode)))
-
     def get_beam_raycast(self):
         """The caster of rank 0 (set_beam_raycast gives every rank the same)."""
         mode = C.c_int(-1)
@@ -352,68 +544,6 @@ class Group:
         if self.lib.mcl3dl_hip_get_beam_raycast(ctx, C.byref(mode)) != 0:
             raise EngineError("mcl3dl_hip_get_beam_raycast failed on the group's rank 0")
         return int(mode.value)
-
-    def set_option(self, name, value):
-        self._check(self.lib.mcl3dl_hip_group_set_option(self.h, name.encode(), float(value)))
-
-    def upload_poses(self, poses):
-        poses = _np_f32(poses, 7)
-        self._check(self.lib.mcl3dl_hip_group_upload_poses(self.h, _ptr(poses), len(poses)))
-        self._n_uploaded = len(poses)
-
-    def measure_batch_begin(self, poses, scan_lik, scan_beam=None, scan_beam_origin=None, origins=None, slice_particles=0,
-                            out=None):
-        """mcl3dl_hip_measure_batch_begin: returns the (lik, ratio, beam) arrays the batch fills in particle order
-        (`out` = three caller-owned float32 arrays, e.g. host_array()s); measure_batch_wait(i) says how far they are valid."""
-        sl, sb, so, og = Engine._scans(scan_lik, scan_beam, scan_beam_origin, origins)
-        if poses is None:
-            n_p = self._n_uploaded
-        else:
-            poses = _np_f32(poses, 7)
-            n_p = len(poses)
-        lik, ratio, beam = out if out is not None else (np.zeros(n_p, np.float32) for _ in range(3))
-        # (a batch still open is ended by this very call and delivers into ITS arrays: they stay alive until it returns)
-        previous = getattr(self, "_batch_keep", None)
-        self._batch_keep = (poses, sl, sb, so, og, lik, ratio, beam, previous)
-        self._check(self.lib.mcl3dl_hip_group_measure_batch_begin(self.h, _ptr(poses), n_p, _ptr(sl), len(sl), _ptr(sb), _ptr(so),
-                    len(sb), _ptr(og), len(og), _ptr(lik), _ptr(ratio), _ptr(beam), int(slice_particles)))
-        self._batch_keep = self._batch_keep[:8]
-        return lik, ratio, beam
-
-    def measure_batch_wait(self, particle):
-        n = C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_group_measure_batch_wait(self.h, int(particle), C.byref(n)))
-        return n.value
-
-    def measure_batch_end(self):
-        self._check(self.lib.mcl3dl_hip_group_measure_batch_end(self.h))
-        self._batch_keep = None
-
-    def measure_batch(self, poses, scan_lik, scan_beam=None, scan_beam_origin=None, origins=None):
-        sl, sb, so, og = Engine._scans(scan_lik, scan_beam, scan_beam_origin, origins)
-        if poses is None:
-            n_p = self._n_uploaded
-        else:
-            poses = _np_f32(poses, 7)
-            n_p = len(poses)
-        lik, ratio, beam = (np.zeros(n_p, np.float32) for _ in range(3))
-        self._check(self.lib.mcl3dl_hip_group_measure_batch(self.h, _ptr(poses), n_p, _ptr(sl), len(sl), _ptr(sb), _ptr(so),
-                                                            len(sb), _ptr(og), len(og), _ptr(lik), _ptr(ratio), _ptr(beam)))
-        return lik, ratio, beam
-
-    def measure_update(self, poses, weights, scan_lik, scan_beam=None, scan_beam_origin=None, origins=None, extra=None):
-        poses = _np_f32(poses, 7)
-        n_p = len(poses)
-        w = _np_f32(weights).copy()
-        ex = None if extra is None else _np_f32(extra)
-        sl, sb, so, og = Engine._scans(scan_lik, scan_beam, scan_beam_origin, origins)
-        lik, ratio, beam = (np.zeros(n_p, np.float32) for _ in range(3))
-        ent, rmin, rmax, rest = C.c_float(0), C.c_float(0), C.c_float(0), C.c_int(0)
-        self._check(self.lib.mcl3dl_hip_group_measure_update(
-            self.h, _ptr(poses), _ptr(ex), _ptr(w), n_p, _ptr(sl), len(sl), _ptr(sb), _ptr(so), len(sb), _ptr(og),
-            len(og), _ptr(lik), _ptr(ratio), _ptr(beam), C.byref(ent), C.byref(rmin), C.byref(rmax), C.byref(rest)))
-        return dict(weights=w, lik=lik, quality=ratio, beam=beam, entropy=float(ent.value),
-                    match_ratio_min=float(rmin.value), match_ratio_max=float(rmax.value), restored=bool(rest.value))
 
     def collective_stats(self):
         a, b = C.c_uint64(0), C.c_uint64(0)
@@ -438,16 +568,15 @@ class Group:
     def update_resident(self, scan_lik, scan_beam=None, scan_beam_origin=None, origins=None, extra=None, fetch=True):
         n_p = self.resident()
         ex = None if extra is None else _np_f32(extra)
-        sl, sb, so, og = Engine._scans(scan_lik, scan_beam, scan_beam_origin, origins)
+        sl, sb, so, og = _scans(scan_lik, scan_beam, scan_beam_origin, origins)
         w, lik, ratio, beam = ((np.zeros(n_p, np.float32) for _ in range(4)) if fetch else (None, None, None, None))
         ent, rmin, rmax, rest = C.c_float(0), C.c_float(0), C.c_float(0), C.c_int(0)
         self._check(self.lib.mcl3dl_hip_group_update_resident(
             self.h, _ptr(ex), _ptr(sl), len(sl), _ptr(sb), _ptr(so), len(sb), _ptr(og), len(og), _ptr(w), _ptr(lik), _ptr(ratio),
             _ptr(beam), C.byref(ent), C.byref(rmin), C.byref(rmax), C.byref(rest)))
-        return dict(weights=w, lik=lik, quality=ratio, beam=beam, entropy=float(ent.value),
-                    match_ratio_min=float(rmin.value), match_ratio_max=float(rmax.value), restored=bool(rest.value))
+        return _update_result(ent, rest, rmin, rmax, weights=w, lik=lik, quality=ratio, beam=beam)
 
-    # ---- scan preparation on the group, and the update that reads the scans where it left them ------------------------------
+    # ---- one rank's context, and the update that reads the scans where the group's scan preparation left them ----------------
     def context(self, rank=0):
         """The context of one rank as an Engine that does not own it (mcl3dl_hip_group_context): scan_download,
         scan_normal_weights and the other calls on one context, behind the group's own."""
@@ -455,88 +584,6 @@ class Group:
         if not h:
             raise EngineError("mcl3dl_hip_group_context: no rank %d" % rank)
         return Engine._borrowed(h)
-
-    def scan_begin(self, xyz, label=None, leaf=None, clip_lik=(0.5, 10.0, -2.0, 2.0), clip_beam=(0.5, 4.0, -2.0, 2.0)):
-        """Engine.scan_begin on every rank; returns (n_full, n_lik_clipped, n_beam_clipped)."""
-        pts = _np_f32(xyz, 3)
-        lab = None if label is None else np.ascontiguousarray(label, dtype=np.uint32)
-        lf, cl, cb = Engine._f3(leaf), Engine._f3(clip_lik), Engine._f3(clip_beam)
-        a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_group_scan_begin(self.h, _ptr(pts), _ptr(lab), len(pts), _ptr(lf), _ptr(cl), _ptr(cb),
-                                                         C.byref(a), C.byref(b), C.byref(c)))
-        return int(a.value), int(b.value), int(c.value)
-
-    def scan_begin_pointcloud2(self, data, n_points, point_step, off_x, off_y, off_z, off_label=-1, label_override=0,
-                               leaf=None, clip_lik=(0.5, 10.0, -2.0, 2.0), clip_beam=(0.5, 4.0, -2.0, 2.0)):
-        buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        lf, cl, cb = Engine._f3(leaf), Engine._f3(clip_lik), Engine._f3(clip_beam)
-        a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_group_scan_begin_pointcloud2(self.h, _ptr(buf), n_points, point_step, off_x, off_y, off_z,
-                                                                     off_label, label_override, _ptr(lf), _ptr(cl), _ptr(cb),
-                                                                     C.byref(a), C.byref(b), C.byref(c)))
-        return int(a.value), int(b.value), int(c.value)
-
-    # ---- clouds accumulated on the devices, every rank its replica (accumClear / accumCloud and the head of measure()) ----------
-    def scan_accum_clear(self):
-        """accumClear on every rank: the accumulation is empty, the next push gets index 0."""
-        self._check(self.lib.mcl3dl_hip_group_scan_accum_clear(self.h))
-
-    def scan_accum_push(self, xyz, affine=None):
-        """Engine.scan_accum_push on every rank; returns (cloud index, points held)."""
-        pts = _np_f32(xyz, 3)
-        a, idx, tot = _affine12(affine), C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_group_scan_accum_push(self.h, _ptr(pts), len(pts), _ptr(a), C.byref(idx), C.byref(tot)))
-        return int(idx.value), int(tot.value)
-
-    def scan_accum_push_pointcloud2(self, data, n_points, point_step, off_x, off_y, off_z, affine=None):
-        """scan_accum_push from PointCloud2 bytes (the message's label field, if any, is not read)."""
-        buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        a, idx, tot = _affine12(affine), C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_group_scan_accum_push_pointcloud2(self.h, _ptr(buf), n_points, point_step, off_x, off_y,
-                                                                          off_z, _ptr(a), C.byref(idx), C.byref(tot)))
-        return int(idx.value), int(tot.value)
-
-    def scan_accum_size(self):
-        """(clouds pushed since the last clear, points held)."""
-        c, n = C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_group_scan_accum_size(self.h, C.byref(c), C.byref(n)))
-        return int(c.value), int(n.value)
-
-    def scan_begin_accumulated(self, affine=None, leaf=None, clip_lik=(0.5, 10.0, -2.0, 2.0), clip_beam=(0.5, 4.0, -2.0, 2.0)):
-        """Engine.scan_begin_accumulated on every rank; returns (n_full, n_lik_clipped, n_beam_clipped)."""
-        a, lf, cl, cb = _affine12(affine), Engine._f3(leaf), Engine._f3(clip_lik), Engine._f3(clip_beam)
-        x, y, z = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_group_scan_begin_accumulated(self.h, _ptr(a), _ptr(lf), _ptr(cl), _ptr(cb), C.byref(x),
-                                                                     C.byref(y), C.byref(z)))
-        return int(x.value), int(y.value), int(z.value)
-
-    def scan_finish(self, idx_lik, idx_beam=None, origins=None):
-        il = np.ascontiguousarray(idx_lik if idx_lik is not None else [], dtype=np.uint32)
-        ib = np.ascontiguousarray(idx_beam if idx_beam is not None else [], dtype=np.uint32)
-        og = _np_f32(origins if origins is not None else np.zeros((1, 3)), 3)
-        self._check(self.lib.mcl3dl_hip_group_scan_finish(self.h, _ptr(il), len(il), _ptr(ib), len(ib), _ptr(og), len(og)))
-
-    def scan_finish_drawn(self, n_s, n_b, origins, engine_state):
-        """scan_finish with the uniform sampler drawn on the devices (beam's n_b draws first, then the likelihood's n_s).
-        Returns (n_s installed, n_b installed, engine state behind the draws)."""
-        og = None if origins is None else _np_f32(origins, 3)
-        st, a, b = _u32(int(engine_state)), C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_group_scan_finish_drawn(self.h, int(n_s), int(n_b), _ptr(og), 0 if og is None else len(og),
-                                                                C.byref(st), C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value), int(st.value)
-
-    def scan_finish_drawn_normal(self, n_s, n_b, origins, normal_search_range, fpc_local, max_weight, engine_state):
-        """scan_finish with the normal-weighted sampler run on the devices (beam first, then the likelihood): returns (n_s
-        installed, n_b installed, engine state behind the draws)."""
-        og = None if origins is None else _np_f32(origins, 3)
-        f = _np_f32(fpc_local).reshape(-1)
-        if f.size != 3:
-            raise ValueError("scan_finish_drawn_normal: fpc_local must hold 3 floats")
-        st, a, b = _u32(int(engine_state)), C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_group_scan_finish_drawn_normal(
-            self.h, int(n_s), int(n_b), _ptr(og), 0 if og is None else len(og), float(normal_search_range), _ptr(f),
-            float(max_weight), C.byref(st), C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value), int(st.value)
 
     def update_resident_prepared(self, extra=None, fetch=True):
         """update_resident on the scans the group's scan_finish / scan_finish_drawn installed."""
@@ -547,8 +594,7 @@ class Group:
         self._check(self.lib.mcl3dl_hip_group_update_resident_prepared(
             self.h, _ptr(ex), _ptr(w), _ptr(lik), _ptr(ratio), _ptr(beam), C.byref(ent), C.byref(rmin), C.byref(rmax),
             C.byref(rest)))
-        return dict(weights=w, lik=lik, quality=ratio, beam=beam, entropy=float(ent.value),
-                    match_ratio_min=float(rmin.value), match_ratio_max=float(rmax.value), restored=bool(rest.value))
+        return _update_result(ent, rest, rmin, rmax, weights=w, lik=lik, quality=ratio, beam=beam)
 
     def expectation(self, bias=None):
         b = None if bias is None else _np_f32(bias)
@@ -597,7 +643,7 @@ class Group:
         """pf::covariance(1.0, ratio) with std::shuffle(iota(n), engine_) made from the engine state (on the devices from 46341
         particles on): (covariance, sample_num, engine state behind). ratio >= 1 draws nothing and sums every particle."""
         m = _np_f32(mean7)
-        st, ns = _u32(int(engine_state)), C.c_size_t(0)
+        st, ns = _state(engine_state), C.c_size_t(0)
         cov = np.zeros((6, 6), np.float32)
         self._check(self.lib.mcl3dl_hip_group_covariance_drawn(self.h, _ptr(m), float(ratio), C.byref(st), C.byref(ns), _ptr(cov)))
         return cov, int(ns.value), int(st.value)
@@ -613,8 +659,7 @@ class Group:
         n_out = getattr(self, "_rs_n_out", 0) or self.resident()
         src = np.zeros(n_out, np.uint32)
         dup = np.zeros(n_out, np.uint8)
-        self._check(self.lib.mcl3dl_hip_group_resample_plan(self.h, int(mode), float(initial_p), _ptr(src), _ptr(dup),
-                                                            C.byref(nd)))
+        self._check(self._fn("resample_plan")(self.h, int(mode), float(initial_p), _ptr(src), _ptr(dup), C.byref(nd)))
         return src, dup, int(nd.value)
 
     def resample_apply(self, noise13=None):
@@ -649,13 +694,13 @@ class Group:
     # ---- the same draws made on the devices from the reference's engine; engine_state in, the state behind the call out ----
     def add_noise_drawn(self, sigma6, engine_state):
         """pf::noise with the noise drawn on the devices. Returns the engine state behind the call."""
-        st = _u32(int(engine_state))
+        st = _state(engine_state)
         self._check(self.lib.mcl3dl_hip_group_add_noise_drawn(self.h, _ptr(_np_f32(sigma6)), C.byref(st)))
         return int(st.value)
 
     def init_drawn(self, mean7, sigma6, n_p, engine_state):
         """pf::init(mean, sigma): n_p resident particles about mean7 = {pos 3, rot x, y, z, w}, weights 1 / n_p."""
-        st = _u32(int(engine_state))
+        st = _state(engine_state)
         self._check(self.lib.mcl3dl_hip_group_init_drawn(self.h, _ptr(_np_f32(mean7)), _ptr(_np_f32(sigma6)), int(n_p),
                                                          C.byref(st)))
         return int(st.value)
@@ -664,7 +709,7 @@ class Group:
         """cbPosition: pf_->initUsingNoiseGenerator(MultivariateNoiseGenerator(mean, cov)) with transform36 = the generator's
         norm_transform_ (row-major 6x6: noise_transform6(cov)[0], or the caller's own), and with reset_odom_integ the
         integ_reset_func pass behind it. n_p resident particles, weights 1 / n_p."""
-        st = _u32(int(engine_state))
+        st = _state(engine_state)
         t = _np_f32(transform36).reshape(-1)
         if t.size != 36:
             raise ValueError("init_drawn_multivariate: transform36 must hold 36 floats")
@@ -675,13 +720,13 @@ class Group:
 
     def draw_odom_noise(self, odom_err4, engine_state):
         """update_noise_func: odom_err4 = {lin_lin, lin_ang, ang_ang, ang_lin}, the draw order ll, la, aa, al."""
-        st = _u32(int(engine_state))
+        st = _state(engine_state)
         self._check(self.lib.mcl3dl_hip_group_draw_odom_noise(self.h, _ptr(_np_f32(odom_err4)), C.byref(st)))
         return int(st.value)
 
     def resample_apply_drawn(self, sigma6, engine_state):
         """resample_apply with the duplicated slots' noise drawn on the devices, in slot order."""
-        st = _u32(int(engine_state))
+        st = _state(engine_state)
         self._check(self.lib.mcl3dl_hip_group_resample_apply_drawn(self.h, _ptr(_np_f32(sigma6)), C.byref(st)))
         return int(st.value)
 
@@ -689,7 +734,7 @@ class Group:
         """All of pf::resample(sigma) on the resident particles in one call, prefix sums, pstep and initial_p formed on the
         devices: (pstep, initial_p, duplicated particles, engine state behind the call, route). route 0: nothing proportional to
         the particle count crossed the bus on a group of one; 1: tie groups were ordered by std::sort on the host."""
-        st, pstep, ip, nd, route = _u32(int(engine_state)), C.c_float(0), C.c_float(0), C.c_size_t(0), C.c_int(-1)
+        st, pstep, ip, nd, route = _state(engine_state), C.c_float(0), C.c_float(0), C.c_size_t(0), C.c_int(-1)
         self._check(self.lib.mcl3dl_hip_group_resample_drawn(self.h, _ptr(_np_f32(sigma6)), C.byref(st), C.byref(pstep),
                                                              C.byref(ip), C.byref(nd), C.byref(route)))
         self._rs_n_out = 0   # (no plan is pending: a later resample_plan starts from resample_begin)
@@ -710,7 +755,7 @@ class Group:
         ent, rest = C.c_float(0), C.c_int(0)
         self._check(self.lib.mcl3dl_hip_group_measure_imu(self.h, _ptr(a), float(acc_var), _ptr(w), _ptr(lik), C.byref(ent),
                                                           C.byref(rest)))
-        return dict(weights=w, lik=lik, entropy=float(ent.value), restored=bool(rest.value))
+        return _update_result(ent, rest, weights=w, lik=lik)
 
     def measure_landmark(self, measured7, cov36, fetch=True):
         """cbLandmark's pf_->measure: NormalLikelihoodNd<float, 6> over s - measured; cov36 is the message's covariance array
@@ -722,7 +767,7 @@ class Group:
         ent, rest = C.c_float(0), C.c_int(0)
         self._check(self.lib.mcl3dl_hip_group_measure_landmark(self.h, _ptr(m), _ptr(cov), _ptr(w), _ptr(lik), C.byref(ent),
                                                                C.byref(rest)))
-        return dict(weights=w, lik=lik, entropy=float(ent.value), restored=bool(rest.value))
+        return _update_result(ent, rest, weights=w, lik=lik)
 
     def set_odom_error_sigma(self, sigma):
         """sigma > 0: update_resident without `extra` applies the node's odometry factor formed on the devices."""
@@ -732,14 +777,16 @@ class Group:
         """cbGlobalLocalization on the group: afterwards n_points * div_yaw particles are resident. Returns
         (n_points, n_particles)."""
         q = None if imu_quat is None else _np_f32(imu_quat).reshape(4)
-        a, b = C.c_size_t(0), C.c_size_t(0)
+        a, b = _sizes(2)
         self._check(self.lib.mcl3dl_hip_group_global_localization(self.h, float(grid), int(div_yaw), _ptr(q),
                                                                   int(max_particles), C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value)
+        return _ints(a, b)
 
 
-class Engine:
+class Engine(_Calls):
     """One context = one GPU.  Host methods take numpy arrays; *_device methods take torch CUDA tensors."""
+
+    _prefix, _error = "mcl3dl_hip_", "mcl3dl_hip error %d: %s"
 
     def __init__(self, device_id=0):
         self.lib = load_library()
@@ -762,20 +809,9 @@ class Engine:
         return e
 
     def close(self):
-        if getattr(self, "h", None):
-            if getattr(self, "_owned", True):
-                self.lib.mcl3dl_hip_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc):
-        if rc != 0:
-            raise EngineError("mcl3dl_hip error %d: %s" % (rc, self.lib.mcl3dl_hip_last_error(self.h).decode()))
+        if not getattr(self, "_owned", True):
+            self.h = None   # a borrowed context is left to its owner
+        super().close()
 
     # ---- configuration -----------------------------------------------------------------------------------------
     def set_stream(self, stream_handle):
@@ -788,90 +824,12 @@ class Engine:
     def synchronize(self):
         self._check(self.lib.mcl3dl_hip_synchronize(self.h))
 
-    def set_map(self, xyz, label=None, stamp=1, dist_weight=(1.0, 1.0, 1.0)):
-        xyz = _np_f32(xyz, 3)
-        lab = None if label is None else np.ascontiguousarray(label, dtype=np.uint32)
-        dw = None if dist_weight is None else _np_f32(dist_weight)
-        self._check(self.lib.mcl3dl_hip_set_map(self.h, _ptr(xyz), _ptr(lab), len(xyz), int(stamp), _ptr(dw)))
-
-    def set_likelihood_params(self, match_dist_min=0.2, match_dist_flat=0.05, match_weight=5.0):
-        self._check(self.lib.mcl3dl_hip_set_likelihood_params(self.h, match_dist_min, match_dist_flat, match_weight))
-
-    def set_beam_params(self, map_grid=(0.1, 0.1, 0.1), dda_grid_size=0.2, ray_angle_half=0.25 * np.pi / 180.0,
-                        hit_range=0.3, beam_likelihood_min=0.2, num_points=3, ang_total_ref=np.pi / 6.0,
-                        filter_label_max=0xFFFFFFFF, add_penalty_short_only_mode=True):
-        self._check(self.lib.mcl3dl_hip_set_beam_params(
-            self.h, map_grid[0], map_grid[1], map_grid[2], dda_grid_size, ray_angle_half, hit_range,
-            beam_likelihood_min, int(num_points), ang_total_ref, int(filter_label_max),
-            int(bool(add_penalty_short_only_mode))))
-
-    def set_beam_raycast(self, mode):
-        """0 = RaycastUsingDDA (default, the fast path), 1 = RaycastUsingKDTree (the reference's default caster)."""
-        self._check(self.lib.mcl3dl_hip_set_beam_raycast(self.h, int(mode)))
-
     def get_beam_raycast(self):
         mode = C.c_int(-1)
         self._check(self.lib.mcl3dl_hip_get_beam_raycast(self.h, C.byref(mode)))
         return int(mode.value)
 
     # ---- host entry points -------------------------------------------------------------------------------------
-    @staticmethod
-    def _scans(scan_lik, scan_beam, scan_beam_origin, origins):
-        sl = _np_f32(scan_lik if scan_lik is not None else np.zeros((0, 3)), 3)
-        sb = _np_f32(scan_beam if scan_beam is not None else np.zeros((0, 3)), 3)
-        so = (np.zeros(len(sb), np.uint32) if scan_beam_origin is None
-              else np.ascontiguousarray(scan_beam_origin, dtype=np.uint32))
-        og = _np_f32(origins if origins is not None else np.zeros((1, 3)), 3)
-        return sl, sb, so, og
-
-    def upload_poses(self, poses):
-        poses = _np_f32(poses, 7)
-        self._check(self.lib.mcl3dl_hip_upload_poses(self.h, _ptr(poses), len(poses)))
-        self._n_uploaded = len(poses)
-
-    def measure_batch(self, poses, scan_lik, scan_beam=None, scan_beam_origin=None, origins=None):
-        """poses=None: the set sent by upload_poses()."""
-        sl, sb, so, og = self._scans(scan_lik, scan_beam, scan_beam_origin, origins)
-        if poses is None:
-            n_p = self._n_uploaded
-        else:
-            poses = _np_f32(poses, 7)
-            n_p = len(poses)
-        lik = np.zeros(n_p, np.float32)
-        ratio = np.zeros(n_p, np.float32)
-        beam = np.zeros(n_p, np.float32)
-        self._check(self.lib.mcl3dl_hip_measure_batch(self.h, _ptr(poses), n_p, _ptr(sl), len(sl), _ptr(sb), _ptr(so),
-                                                      len(sb), _ptr(og), len(og), _ptr(lik), _ptr(ratio), _ptr(beam)))
-        return lik, ratio, beam
-
-    def measure_batch_begin(self, poses, scan_lik, scan_beam=None, scan_beam_origin=None, origins=None, slice_particles=0,
-                            out=None):
-        """mcl3dl_hip_measure_batch_begin: returns the (lik, ratio, beam) arrays the batch fills in particle order
-        (`out` = three caller-owned float32 arrays, e.g. host_array()s); measure_batch_wait(i) says how far they are valid."""
-        sl, sb, so, og = self._scans(scan_lik, scan_beam, scan_beam_origin, origins)
-        if poses is None:
-            n_p = self._n_uploaded
-        else:
-            poses = _np_f32(poses, 7)
-            n_p = len(poses)
-        lik, ratio, beam = out if out is not None else (np.zeros(n_p, np.float32) for _ in range(3))
-        # (a batch still open is ended by this very call and delivers into ITS arrays: they stay alive until it returns)
-        previous = getattr(self, "_batch_keep", None)
-        self._batch_keep = (poses, sl, sb, so, og, lik, ratio, beam, previous)
-        self._check(self.lib.mcl3dl_hip_measure_batch_begin(self.h, _ptr(poses), n_p, _ptr(sl), len(sl), _ptr(sb), _ptr(so),
-                    len(sb), _ptr(og), len(og), _ptr(lik), _ptr(ratio), _ptr(beam), int(slice_particles)))
-        self._batch_keep = self._batch_keep[:8]
-        return lik, ratio, beam
-
-    def measure_batch_wait(self, particle):
-        n = C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_measure_batch_wait(self.h, int(particle), C.byref(n)))
-        return n.value
-
-    def measure_batch_end(self):
-        self._check(self.lib.mcl3dl_hip_measure_batch_end(self.h))
-        self._batch_keep = None
-
     def pf_measure(self, weights, lik, beam=None, extra=None, match_ratio=None):
         w = _np_f32(weights).copy()
         lk = _np_f32(lik)
@@ -881,25 +839,7 @@ class Engine:
         ent, rmin, rmax, rest = C.c_float(0), C.c_float(0), C.c_float(0), C.c_int(0)
         self._check(self.lib.mcl3dl_hip_pf_measure(self.h, _ptr(w), _ptr(lk), _ptr(bm), _ptr(ex), _ptr(mr), len(w),
                                                    C.byref(ent), C.byref(rmin), C.byref(rmax), C.byref(rest)))
-        return dict(weights=w, entropy=float(ent.value), match_ratio_min=float(rmin.value),
-                    match_ratio_max=float(rmax.value), restored=bool(rest.value))
-
-    def measure_update(self, poses, weights, scan_lik, scan_beam=None, scan_beam_origin=None, origins=None,
-                       extra=None):
-        poses = _np_f32(poses, 7)
-        n_p = len(poses)
-        w = _np_f32(weights).copy()
-        ex = None if extra is None else _np_f32(extra)
-        sl, sb, so, og = self._scans(scan_lik, scan_beam, scan_beam_origin, origins)
-        lik = np.zeros(n_p, np.float32)
-        ratio = np.zeros(n_p, np.float32)
-        beam = np.zeros(n_p, np.float32)
-        ent, rmin, rmax, rest = C.c_float(0), C.c_float(0), C.c_float(0), C.c_int(0)
-        self._check(self.lib.mcl3dl_hip_measure_update(
-            self.h, _ptr(poses), _ptr(ex), _ptr(w), n_p, _ptr(sl), len(sl), _ptr(sb), _ptr(so), len(sb), _ptr(og),
-            len(og), _ptr(lik), _ptr(ratio), _ptr(beam), C.byref(ent), C.byref(rmin), C.byref(rmax), C.byref(rest)))
-        return dict(weights=w, lik=lik, quality=ratio, beam=beam, entropy=float(ent.value),
-                    match_ratio_min=float(rmin.value), match_ratio_max=float(rmax.value), restored=bool(rest.value))
+        return _update_result(ent, rest, rmin, rmax, weights=w)
 
     def host_array(self, shape, dtype=np.float32):
         """A numpy array in page-locked memory of this context (mcl3dl_hip_host_alloc): measure_update reads / writes such
@@ -1069,7 +1009,7 @@ class Engine:
         """begin_device + the uniform draw + plan with the weights left on the device: (pstep, initial_p, duplicated particles,
         engine state behind the draw or None for mode 1, route)."""
         self._rs_n_out = n if n_out is None else n_out
-        st = _u32(0 if engine_state is None else int(engine_state))
+        st = _state(engine_state or 0)
         pstep, ip, nd, route = C.c_float(0), C.c_float(0), C.c_size_t(0), C.c_int(-1)
         self._check(self.lib.mcl3dl_hip_resample_plan_device(self.h, _ptr(d_weight), int(n), int(self._rs_n_out), int(mode),
                                                              None if engine_state is None else C.byref(st), C.byref(pstep),
@@ -1128,57 +1068,6 @@ class Engine:
         return out[:min(n.value, max_out)].copy(), bool(col.value), int(hit.value), int(n.value)
 
     # ---- scan preparation / map path on the device ----------------------------------------
-    @staticmethod
-    def _f3(a):
-        return None if a is None else _np_f32(a)
-
-    def scan_begin(self, xyz, label=None, leaf=None, clip_lik=(0.5, 10.0, -2.0, 2.0), clip_beam=(0.5, 4.0, -2.0, 2.0)):
-        """VoxelGrid + both clip filters on the device; returns (n_full, n_lik_clipped, n_beam_clipped)."""
-        pts = _np_f32(xyz, 3)
-        lab = None if label is None else np.ascontiguousarray(label, dtype=np.uint32)
-        lf, cl, cb = self._f3(leaf), self._f3(clip_lik), self._f3(clip_beam)
-        a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_scan_begin(self.h, _ptr(pts), _ptr(lab), len(pts), _ptr(lf), _ptr(cl), _ptr(cb),
-                                                   C.byref(a), C.byref(b), C.byref(c)))
-        return int(a.value), int(b.value), int(c.value)
-
-    def scan_begin_pointcloud2(self, data, n_points, point_step, off_x, off_y, off_z, off_label=-1, label_override=0,
-                               leaf=None, clip_lik=(0.5, 10.0, -2.0, 2.0), clip_beam=(0.5, 4.0, -2.0, 2.0)):
-        buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        lf, cl, cb = self._f3(leaf), self._f3(clip_lik), self._f3(clip_beam)
-        a, b, c = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_scan_begin_pointcloud2(self.h, _ptr(buf), n_points, point_step, off_x, off_y, off_z,
-                                                               off_label, label_override, _ptr(lf), _ptr(cl), _ptr(cb),
-                                                               C.byref(a), C.byref(b), C.byref(c)))
-        return int(a.value), int(b.value), int(c.value)
-
-    # ---- clouds accumulated on the device (accumClear / accumCloud and the head of measure(), src/mcl_3dl.cpp:267-336) ----------
-    def scan_accum_clear(self):
-        """accumClear: the accumulation is empty, the next push gets index 0."""
-        self._check(self.lib.mcl3dl_hip_scan_accum_clear(self.h))
-
-    def scan_accum_push(self, xyz, affine=None):
-        """accumCloud for one message: the points (sensor frame) are transformed by `affine` (odom <- sensor; None: taken as they
-        are), labelled with the cloud's index and appended. Returns (cloud index, points held)."""
-        pts = _np_f32(xyz, 3)
-        a, idx, tot = _affine12(affine), C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_scan_accum_push(self.h, _ptr(pts), len(pts), _ptr(a), C.byref(idx), C.byref(tot)))
-        return int(idx.value), int(tot.value)
-
-    def scan_accum_push_pointcloud2(self, data, n_points, point_step, off_x, off_y, off_z, affine=None):
-        """scan_accum_push from PointCloud2 bytes (the message's label field, if any, is not read)."""
-        buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        a, idx, tot = _affine12(affine), C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_scan_accum_push_pointcloud2(self.h, _ptr(buf), n_points, point_step, off_x, off_y, off_z,
-                                                                    _ptr(a), C.byref(idx), C.byref(tot)))
-        return int(idx.value), int(tot.value)
-
-    def scan_accum_size(self):
-        """(clouds pushed since the last clear, points held)."""
-        c, n = C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_scan_accum_size(self.h, C.byref(c), C.byref(n)))
-        return int(c.value), int(n.value)
-
     def scan_accum_download(self):
         """(xyz, label) of the accumulation as held: odom frame, push order, label = cloud index."""
         n = C.c_size_t(0)
@@ -1189,48 +1078,11 @@ class Engine:
             self._check(self.lib.mcl3dl_hip_scan_accum_download(self.h, _ptr(xyz), _ptr(lab), n.value, C.byref(n)))
         return xyz, lab
 
-    def scan_begin_accumulated(self, affine=None, leaf=None, clip_lik=(0.5, 10.0, -2.0, 2.0), clip_beam=(0.5, 4.0, -2.0, 2.0)):
-        """scan_begin on the accumulation, transformed by `affine` (base_link <- odom; None: as it is) on the device; the
-        accumulation stays. Returns (n_full, n_lik_clipped, n_beam_clipped)."""
-        a, lf, cl, cb = _affine12(affine), Engine._f3(leaf), Engine._f3(clip_lik), Engine._f3(clip_beam)
-        x, y, z = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_scan_begin_accumulated(self.h, _ptr(a), _ptr(lf), _ptr(cl), _ptr(cb), C.byref(x),
-                                                               C.byref(y), C.byref(z)))
-        return int(x.value), int(y.value), int(z.value)
-
-    def scan_finish(self, idx_lik, idx_beam=None, origins=None):
-        il = np.ascontiguousarray(idx_lik if idx_lik is not None else [], dtype=np.uint32)
-        ib = np.ascontiguousarray(idx_beam if idx_beam is not None else [], dtype=np.uint32)
-        og = _np_f32(origins if origins is not None else np.zeros((1, 3)), 3)
-        self._check(self.lib.mcl3dl_hip_scan_finish(self.h, _ptr(il), len(il), _ptr(ib), len(ib), _ptr(og), len(og)))
-
-    def scan_finish_drawn(self, n_s, n_b, origins, engine_state):
-        """scan_finish with the uniform sampler drawn on the device from the reference's engine: beam's n_b draws first, then
-        the likelihood's n_s. Returns (n_s installed, n_b installed, engine state behind the draws)."""
-        og = None if origins is None else _np_f32(origins, 3)
-        st, a, b = _u32(int(engine_state)), C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_scan_finish_drawn(self.h, int(n_s), int(n_b), _ptr(og), 0 if og is None else len(og),
-                                                          C.byref(st), C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value), int(st.value)
-
-    def scan_finish_drawn_normal(self, n_s, n_b, origins, normal_search_range, fpc_local, max_weight, engine_state):
-        """scan_finish with PointCloudSamplerWithNormal::sample run on the device for both models from the reference's engine
-        (beam first, then the likelihood): returns (n_s installed, n_b installed, engine state behind the draws)."""
-        og = None if origins is None else _np_f32(origins, 3)
-        f = _np_f32(fpc_local).reshape(-1)
-        if f.size != 3:
-            raise ValueError("scan_finish_drawn_normal: fpc_local must hold 3 floats")
-        st, a, b = _u32(int(engine_state)), C.c_size_t(0), C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_scan_finish_drawn_normal(
-            self.h, int(n_s), int(n_b), _ptr(og), 0 if og is None else len(og), float(normal_search_range), _ptr(f),
-            float(max_weight), C.byref(st), C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value), int(st.value)
-
     def rng_draw_weighted(self, weight, num, engine_state=1):
         """The normal-weighted sampler's draw on weights handed in: (ids uint32[num] in the order of the sampled cloud,
         cumulative float64[n], engine state behind the draws, attempts made). num = 0 forms only the cumulative array."""
         w = np.ascontiguousarray(weight, dtype=np.float64)
-        st, draws = _u32(int(engine_state)), _u64(0)
+        st, draws = _state(engine_state), _u64(0)
         out = np.zeros(int(num), np.uint32)
         cum = np.zeros(len(w), np.float64)
         self._check(self.lib.mcl3dl_hip_rng_draw_weighted(self.h, _ptr(w), len(w), int(num), C.byref(st), _ptr(out), _ptr(cum),
@@ -1240,7 +1092,7 @@ class Engine:
     def rng_draw_indices(self, range_, count, engine_state):
         """count draws of std::uniform_int_distribution<size_t>(0, range_ - 1) from the reference's engine, drawn on the device:
         (indices uint32[count], engine state behind them)."""
-        st = _u32(int(engine_state))
+        st = _state(engine_state)
         out = np.zeros(int(count), np.uint32)
         self._check(self.lib.mcl3dl_hip_rng_draw_indices(self.h, int(range_), int(count), C.byref(st), _ptr(out)))
         return out, int(st.value)
@@ -1248,7 +1100,7 @@ class Engine:
     def rng_shuffle_prefix(self, n, m, engine_state):
         """The first m entries of std::shuffle(iota(n), engine) (libstdc++) and the engine state behind the whole shuffle: made on
         the device from n = 46341 on, by the library's serial loop on the host below."""
-        st = _u32(int(engine_state))
+        st = _state(engine_state)
         out = np.zeros(int(m), np.uint32)
         self._check(self.lib.mcl3dl_hip_rng_shuffle_prefix(self.h, int(n), int(m), C.byref(st), _ptr(out)))
         return out, int(st.value)
@@ -1296,8 +1148,8 @@ class Engine:
         pts = _np_f32(xyz, 3)
         lab = None if label is None else np.ascontiguousarray(label, dtype=np.uint32)
         n = C.c_size_t(0)
-        self._check(self.lib.mcl3dl_hip_set_map_downsampled(self.h, _ptr(pts), _ptr(lab), len(pts), _ptr(self._f3(leaf)),
-                                                            int(stamp), _ptr(self._f3(dist_weight)), C.byref(n)))
+        self._check(self.lib.mcl3dl_hip_set_map_downsampled(self.h, _ptr(pts), _ptr(lab), len(pts), _ptr(_f3(leaf)),
+                                                            int(stamp), _ptr(_f3(dist_weight)), C.byref(n)))
         return int(n.value)
 
     def set_map_pointcloud2(self, data, n_points, point_step, off_x, off_y, off_z, off_label=-1, leaf=(0.1, 0.1, 0.1),
@@ -1305,8 +1157,8 @@ class Engine:
         buf = np.frombuffer(bytes(data), dtype=np.uint8)
         n = C.c_size_t(0)
         self._check(self.lib.mcl3dl_hip_set_map_pointcloud2(self.h, _ptr(buf), n_points, point_step, off_x, off_y, off_z,
-                                                            off_label, _ptr(self._f3(leaf)), int(stamp),
-                                                            _ptr(self._f3(dist_weight)), C.byref(n)))
+                                                            off_label, _ptr(_f3(leaf)), int(stamp),
+                                                            _ptr(_f3(dist_weight)), C.byref(n)))
         return int(n.value)
 
     @staticmethod
@@ -1320,7 +1172,7 @@ class Engine:
         lab = None if label is None else np.ascontiguousarray(label, dtype=np.uint32)
         n = C.c_size_t(0)
         st = np.zeros(6, np.float64)
-        self._check(self.lib.mcl3dl_hip_map_update(self.h, _ptr(pts), _ptr(lab), len(pts), _ptr(self._f3(leaf)), int(stamp),
+        self._check(self.lib.mcl3dl_hip_map_update(self.h, _ptr(pts), _ptr(lab), len(pts), _ptr(_f3(leaf)), int(stamp),
                                                    C.byref(n), _ptr(st)))
         return int(n.value), self._update_stats(st)
 
@@ -1330,7 +1182,7 @@ class Engine:
         n = C.c_size_t(0)
         st = np.zeros(6, np.float64)
         self._check(self.lib.mcl3dl_hip_map_update_pointcloud2(self.h, _ptr(buf), n_points, point_step, off_x, off_y, off_z,
-                                                               off_label, _ptr(self._f3(leaf)), int(stamp), C.byref(n),
+                                                               off_label, _ptr(_f3(leaf)), int(stamp), C.byref(n),
                                                                _ptr(st)))
         return int(n.value), self._update_stats(st)
 
@@ -1374,7 +1226,7 @@ class Engine:
 
     # ---- device entry points (torch CUDA tensors or raw device addresses) ---------------------------------------
     def upload_scan(self, scan_lik, scan_beam=None, scan_beam_origin=None, origins=None):
-        sl, sb, so, og = self._scans(scan_lik, scan_beam, scan_beam_origin, origins)
+        sl, sb, so, og = _scans(scan_lik, scan_beam, scan_beam_origin, origins)
         self._check(self.lib.mcl3dl_hip_upload_scan(self.h, _ptr(sl), len(sl), _ptr(sb), _ptr(so), len(sb), _ptr(og),
                                                     len(og)))
 
@@ -1426,9 +1278,6 @@ class Engine:
         return dict(lik_points=int(b[0]), lik_cells=int(b[1]), dda_bits=int(b[2]), dda_voxels=int(b[3]),
                     dda_points=int(b[4]), cand_table=int(b[5]), cand_start=int(b[6]), cand_points=int(b[7]))
 
-    def set_option(self, name, value):
-        self._check(self.lib.mcl3dl_hip_set_option(self.h, name.encode(), float(value)))
-
     def get_option(self, name):
         v = C.c_double(0)
         self._check(self.lib.mcl3dl_hip_get_option(self.h, name.encode(), C.byref(v)))
@@ -1460,7 +1309,7 @@ def rng_seed(seed):
 
 def rng_uniform(engine_state, a, b):
     """uniform_real_distribution<float>(a, b)(engine) on the host: (value, engine state behind the draw)."""
-    st = _u32(int(engine_state))
+    st = _state(engine_state)
     v = load_library().mcl3dl_hip_rng_uniform(C.byref(st), float(a), float(b))
     return float(v), int(st.value)
 
