@@ -640,6 +640,48 @@ int mcl3dl_hip_group_resize_resident(mcl3dl_hip_group* g, size_t n_out, int* out
 int mcl3dl_hip_group_measure_landmark(mcl3dl_hip_group* g, const float* measured7, const double* cov36,
                                       float* out_weight /*n_p or NULL*/, float* out_lik /*n_p or NULL*/, float* entropy,
                                       int* restored);
+/* ---- occupied bins of the particles: KLD size and modes (NOT the reference's behaviour) ------------------------------------
+ * The reference shrinks the particle set by a fixed factor per scan (src/mcl_3dl.cpp:875-885) and publishes one mean. These
+ * calls give a caller what it needs to size the set by the posterior instead (KLD-sampling, Fox 2003) and to read the
+ * hypotheses themselves: which cells of a pose grid the particles occupy, by how many particles and by how much weight.
+ * Nothing calls them unless the caller does. Definitions (mcl_3dl_amd/csrc/particle_bins.h states them once for host and device):
+ *   position bin  pcl::VoxelGrid's expression with bin_xyz[a] in place of the leaf: inv = 1.0f / bin in float,
+ *                 i_a = (int)(floorf(p_a * inv_a) - (float)min_b_a), min_b / max_b from the min / max over the particles with
+ *                 finite positions; the index reported is the absolute one, i_a + min_b_a.
+ *   yaw sector    t0, t1 as Quat::getRPY forms them (include/mcl_3dl/quat.h:193-195); no atan2: the first j in 0 ... yaw_bins - 1
+ *                 with c_j (double)t1 - s_j (double)t0 >= 0 and c_{j+1} (double)t1 - s_{j+1} (double)t0 < 0 (products and
+ *                 difference in double, unfused, the table wrapping around); 0 when no j qualifies (t0 = t1 = 0, a non-finite
+ *                 quaternion) and always with yaw_bins = 1. yaw_bins is 1 or 3 ... 64.
+ *   key           ((i2 div1 + i1) div0 + i0) yaw_bins + sector, div_a = max_b_a - min_b_a + 1; -3 ("the bins are too small for
+ *                 the particles' extent") when div0 div1 div2 yaw_bins > 0xfffffffe or one div_a > 2^31 - 1. A particle with a
+ *                 non-finite position sits in no bin and is counted in *out_nonfinite.
+ *   per bin       count; mass = the sum of the float weights in fp64; leader = the particle with the largest weight, the lowest
+ *                 index on a tie (the strict `<` of pf::max()).
+ *   totals        *out_occupied = bins with a particle, *out_occupied_alive = bins with mass > 0.
+ *   top K         the top_k (0 ... 16) bins by mass descending, then key ascending: out_top_bin4 = {ix, iy, iz, sector} each,
+ *                 out_top_mass, out_top_count, out_top_leader; *out_top_n = min(top_k, occupied) rows are written.
+ * Two calls on the same data return the same bits. Any out_* pointer may be NULL. -3: n = 0, a bin edge <= 0, a bad yaw_bins /
+ * top_k / row_stride.
+ *   _yaw_sector_table  pure host function, no context: out_cs[2 j], out_cs[2 j + 1] = (cos, sin)(2 pi j / yaw_bins), the
+ *                 multiples of a quarter turn exact — the very table the device calls use. -3 for a bad yaw_bins.
+ *   _kld_bound    pure host function: Fox's bound as AMCL's pf_resample_limit writes it, in double: b = 2 / (9 (k - 1)),
+ *                 x = 1 - b + sqrt(b) z, n = ceil((k - 1) / (2 epsilon) x x x); k <= 1 -> 1 (and never less than 1). -3 for
+ *                 epsilon outside (0, 1], a non-finite z, a bound that does not fit 2^62. Clamping to the node's
+ *                 num_particles_ is the caller's.
+ *   _device       n rows of row_stride floats in device memory (7: pose rows, 13: state rows; position at 0..2, quaternion
+ *                 xyzw at 3..6) and n weights. Synchronises twice: the extent, then one record with the top rows.
+ *   group form    the resident particles, leaders as global particle indices. On more than one rank states and weights are
+ *                 brought into particle order on every rank as the resampling plan's weights are, every rank runs the same
+ *                 pipeline and the results must agree (-4 otherwise). -5: no resident particles. */
+int mcl3dl_hip_yaw_sector_table(int yaw_bins, double* out_cs /*2 * yaw_bins*/);
+int mcl3dl_hip_kld_bound(size_t k, double epsilon, double z, size_t* out_n);
+int mcl3dl_hip_particle_bins_device(mcl3dl_hip_ctx* ctx, const float* d_rows, size_t row_stride, const float* d_weight, size_t n,
+                                    const float* bin_xyz, int yaw_bins, int top_k, size_t* out_occupied,
+                                    size_t* out_occupied_alive, size_t* out_nonfinite, int32_t* out_top_bin4 /*4 * top_k*/,
+                                    double* out_top_mass, uint32_t* out_top_count, uint32_t* out_top_leader, size_t* out_top_n);
+int mcl3dl_hip_group_particle_bins(mcl3dl_hip_group* g, const float* bin_xyz, int yaw_bins, int top_k, size_t* out_occupied,
+                                   size_t* out_occupied_alive, size_t* out_nonfinite, int32_t* out_top_bin4 /*4 * top_k*/,
+                                   double* out_top_mass, uint32_t* out_top_count, uint32_t* out_top_leader, size_t* out_top_n);
 /* ---- global localisation: the particle set seeded from the map, on the devices ---------------------------------------------
  * The reference's `global_localization` service (cbGlobalLocalization, src/mcl_3dl.cpp:1039-1099), step by step:
  *   1. pcl::VoxelGrid(leaf = (float)grid) over pc_map_: the BASE map only, a map update overlay is ignored;

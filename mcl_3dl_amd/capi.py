@@ -148,6 +148,12 @@ SIGNATURES = {
     "mcl3dl_hip_covariance_window_partial_device": (_i, [_p, _p, _p, _sz, _p, _sz, _sz, _p, _p]),
     "mcl3dl_hip_group_covariance_sampled": (_i, [_p, _p, _p, _sz, _p]),
     "mcl3dl_hip_group_covariance_drawn": (_i, [_p, _p, _f, C.POINTER(_u32), C.POINTER(_sz), _p]),
+    "mcl3dl_hip_yaw_sector_table": (_i, [_i, _p]),
+    "mcl3dl_hip_kld_bound": (_i, [_sz, _d, _d, C.POINTER(_sz)]),
+    "mcl3dl_hip_particle_bins_device": (_i, [_p, _p, _sz, _p, _sz, _p, _i, _i, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz),
+                                             _p, _p, _p, _p, C.POINTER(_sz)]),
+    "mcl3dl_hip_group_particle_bins": (_i, [_p, _p, _i, _i, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_sz), _p, _p, _p, _p,
+                                            C.POINTER(_sz)]),
 }
 
 # the calls that exist for a context and for a group alike: behind the handle the header declares the two identically, so
@@ -316,6 +322,45 @@ def sampler_normal_direction(mean, cov, perform_weighting_ratio=2.0, max_weight_
                                                float(max_weight), _ptr(fpc), C.byref(mw), C.byref(ratio)) != 0:
         raise ValueError("sampler_normal_direction: the mean, the covariance and the parameters must be finite")
     return fpc, float(mw.value), float(ratio.value)
+
+
+def yaw_sector_table(yaw_bins):
+    """mcl3dl_hip_yaw_sector_table: (yaw_bins, 2) float64 rows (cos, sin)(2 pi j / yaw_bins) — the very table particle_bins
+    decides its yaw sectors with (no GPU needed). yaw_bins is 1 or 3 ... 64."""
+    lib = load_library()
+    out = np.zeros((max(int(yaw_bins), 0), 2), np.float64)
+    if lib.mcl3dl_hip_yaw_sector_table(int(yaw_bins), _ptr(out)) != 0:
+        raise ValueError("yaw_sector_table: yaw_bins must be 1 or 3 ... 64")
+    return out
+
+
+def kld_bound(k, epsilon, z):
+    """mcl3dl_hip_kld_bound: Fox's KLD bound as AMCL's pf_resample_limit writes it — the particles that keep the K-L distance
+    below epsilon at the upper normal quantile z when k bins are occupied (no GPU needed). Not clamped to any particle count."""
+    lib = load_library()
+    n = C.c_size_t(0)
+    if int(k) < 0 or lib.mcl3dl_hip_kld_bound(int(k), float(epsilon), float(z), C.byref(n)) != 0:
+        raise ValueError("kld_bound: epsilon must lie in (0, 1], z be finite and the bound fit 2^62")
+    return int(n.value)
+
+
+class _BinsOut:
+    """The output words and rows of a particle_bins call, and the dict they come back as."""
+
+    def __init__(self, top_k):
+        self.occupied, self.alive, self.nonfinite, self.top_n = _sizes(4)
+        k = max(int(top_k), 0)
+        self.bin4, self.mass = np.zeros((k, 4), np.int32), np.zeros(k, np.float64)
+        self.count, self.leader = np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+
+    def args(self):
+        return (C.byref(self.occupied), C.byref(self.alive), C.byref(self.nonfinite), _ptr(self.bin4), _ptr(self.mass),
+                _ptr(self.count), _ptr(self.leader), C.byref(self.top_n))
+
+    def result(self):
+        occupied, alive, nonfinite, n = _ints(self.occupied, self.alive, self.nonfinite, self.top_n)
+        return dict(occupied=occupied, occupied_alive=alive, nonfinite=nonfinite, top_bin=self.bin4[:n], top_mass=self.mass[:n],
+                    top_count=self.count[:n], top_leader=self.leader[:n])
 
 
 class _Calls:
@@ -747,6 +792,18 @@ class Group(_Calls):
         self._rs_n_out = 0
         return int(route.value)
 
+    def particle_bins(self, bin_xyz, yaw_bins=1, top_k=0):
+        """The cells of a pose grid (edges bin_xyz, yaw_bins yaw sectors) the resident particles occupy — not the reference's
+        behaviour: occupied, occupied_alive (mass > 0) and nonfinite counts, and the top_k bins by mass as top_bin {ix, iy, iz,
+        sector}, top_mass (fp64 sum of the weights), top_count, top_leader (global index of the heaviest particle: the argument
+        of download_particle). kld_bound(occupied, ...) sizes the set for resize_resident."""
+        b = _np_f32(bin_xyz).reshape(-1)
+        if b.size != 3:
+            raise ValueError("particle_bins: bin_xyz must hold three floats")
+        out = _BinsOut(top_k)
+        self._check(self.lib.mcl3dl_hip_group_particle_bins(self.h, _ptr(b), int(yaw_bins), int(top_k), *out.args()))
+        return out.result()
+
     def measure_imu(self, acc, acc_var, fetch=True):
         """cbImu's pf_->measure with ImuMeasurementModelGravity(acc_var) after setAccMeasure(acc)."""
         n_p = self.resident()
@@ -1016,6 +1073,17 @@ class Engine(_Calls):
                                                              C.byref(ip), C.byref(nd), C.byref(route)))
         return (float(pstep.value), float(ip.value), int(nd.value), None if engine_state is None or mode else int(st.value),
                 int(route.value))
+
+    def particle_bins_device(self, d_rows, d_weight, n, bin_xyz, yaw_bins=1, top_k=0, row_stride=7):
+        """Group.particle_bins over n rows of row_stride floats (7: poses, 13: states) and n weights in device memory; leaders
+        index the rows."""
+        b = _np_f32(bin_xyz).reshape(-1)
+        if b.size != 3:
+            raise ValueError("particle_bins_device: bin_xyz must hold three floats")
+        out = _BinsOut(top_k)
+        self._check(self.lib.mcl3dl_hip_particle_bins_device(self.h, _ptr(d_rows), int(row_stride), _ptr(d_weight), int(n),
+                                                             _ptr(b), int(yaw_bins), int(top_k), *out.args()))
+        return out.result()
 
     def float_prefix(self, term=None, constant=0.0, n=None):
         """The serial float recurrence out[i] = fl(out[i - 1] + term[i]) by one wavefront, every prefix; term None: n terms, all

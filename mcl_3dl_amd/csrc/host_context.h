@@ -287,6 +287,9 @@ struct mcl3dl_hip_ctx
   DevBuf wd_w, wd_cum[2], wd_first[2], wd_att, wd_flag, wd_ws, wd_ins, wd_order[2], wd_head, wd_link, wd_first_of, wd_later,
       wd_size, wd_result, wd_out;
   bool rng_table_set = false;
+  // the occupied-bin statistic (api_particle_bins.inl): the yaw sector table, launch 1's per-work-group partials, one record per
+  // occupied bin, the result record
+  DevBuf pb_table, pb_blocks, pb_bins, pb_out;
 
   std::string index_note;  // why the map compiler fell back to a coarser / plainer index form (diagnostics)
 

@@ -45,6 +45,9 @@
 //   resample_prefix_kernels.h  pf::resample / resizeParticle without the host between weights and plan: the accumulated
 //                         probabilities and `pscan += pstep` as the serial float recurrence by one wavefront, every prefix
 //                         written (float_prefix.h), pstep / initial_p / tie flag in a device record, the search fed from it
+//   particle_bins_kernels.h  the occupied bins of a pose grid over the particles (particle_bins.h: the definitions): keys, and a
+//                         segmented reduction over the sorted pairs whose cost does not depend on how the particles are spread;
+//                         totals and the top K bins by mass
 //   stage_kernels.h       head and tail of a host-buffer update as one launch each: scan ordering + pose / weight take-over
 //                         from page-locked host memory; lik_finalize + pf::measure with the results written back there
 //
@@ -74,3 +77,4 @@
 #include "rng_weighted_kernels.h"
 #include "rng_shuffle_kernels.h"
 #include "resample_prefix_kernels.h"
+#include "particle_bins_kernels.h"

@@ -57,4 +57,5 @@ extern "C"
 #include "api_sampler.inl"
 #include "api_rng.inl"
 #include "api_shuffle.inl"
+#include "api_particle_bins.inl"
 }  // extern "C"
