@@ -3,6 +3,10 @@
 // (score_like += dist * match_weight, src/lidar_measurement_model_likelihood.cpp:120-134). Test infrastructure only:
 // tests/test_float_chain_cpu.py builds and runs it (g++ -O2 -ffp-contract=off; x86-64 SSE floats round to nearest even like
 // the device). Exit code 0 = every case equal; prints the pass statistics.
+// With `--cases FILE` instead of a round count it replays the term vectors tests/float_chain_cases.py wrote there (int32 count,
+// then per vector int32 n and n floats), each as ONE row and as pf_strict_sum_kernel hands it over (rows of 4096 terms, the sum
+// carried into the next row, the serial head restarted per row), and prints per vector and form: equality with the serial loop,
+// the sums' bits, passes / clean passes / passes with trouble, and how often each lane was the first one in trouble.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -23,6 +27,13 @@ static float serial(const std::vector<float>& t, float s0)
 }
 
 static long g_passes = 0, g_serial_quads = 0, g_clean_passes = 0;
+
+// what one replay ran through (the --cases mode)
+struct Stats
+{
+  long passes = 0, clean = 0;
+  long first_lane[64] = {};
+};
 
 // the inclusive scan in the association of wave_scan_add: Hillis-Steele steps 1, 2, 4, 8 inside rows of 16, then the row totals
 static void scan64(float* v)
@@ -83,7 +94,7 @@ static bool classify(const float* t, float M, float small, float hu, float& a)
   return (mx < static_cast<uint32_t>(f2i(small))) & (dm < hu);
 }
 
-static float emul(const std::vector<float>& terms, float s0)
+static float emul(const std::vector<float>& terms, float s0, Stats* st = nullptr)
 {
   const int n = static_cast<int>(terms.size());
   const int n4 = (n + 3) >> 2;
@@ -107,6 +118,8 @@ static float emul(const std::vector<float>& terms, float s0)
     }
     const float top = i2f(sb + (1 << 23));
     ++g_passes;
+    if (st)
+      ++st->passes;
     const float M = i2f(sb | 0x00400000), small = i2f(sb - (1 << 23)), hu = i2f(sb - (24 << 23));
     float a[64];
     bool ok[64];
@@ -143,8 +156,12 @@ static float emul(const std::vector<float>& terms, float s0)
       s = s + a[63];
       q += 128;
       ++g_clean_passes;
+      if (st)
+        ++st->clean;
       continue;
     }
+    if (st)
+      ++st->first_lane[L];
     if (L > 0)
       s = s + a[L - 1];
     int at = q + 2 * L;
@@ -168,8 +185,56 @@ static int check(const std::vector<float>& t, float s0, const char* what, long i
   return 0;
 }
 
+static void report(long id, size_t n, const char* form, float want, float got, const Stats& st)
+{
+  const bool equal = f2i(want) == f2i(got) || (want != want && got != got);
+  printf("case %ld n %zu %s equal %d serial %08x emul %08x passes %ld clean %ld trouble %ld lanes", id, n, form, equal ? 1 : 0,
+         static_cast<unsigned>(f2i(want)), static_cast<unsigned>(f2i(got)), st.passes, st.clean, st.passes - st.clean);
+  for (int l = 0; l < 64; ++l)
+    printf(" %ld", st.first_lane[l]);
+  printf("\n");
+}
+
+static int replay_cases(const char* path)
+{
+  FILE* f = fopen(path, "rb");
+  int32_t count = 0;
+  if (!f || fread(&count, 4, 1, f) != 1 || count < 0)
+  {
+    printf("float_chain_emul: cannot read %s\n", path);
+    return 2;
+  }
+  int bad = 0;
+  for (long id = 0; id < count; ++id)
+  {
+    int32_t n = 0;
+    if (fread(&n, 4, 1, f) != 1 || n < 0)
+      return 2;
+    std::vector<float> t(static_cast<size_t>(n));
+    if (n > 0 && fread(t.data(), 4, t.size(), f) != t.size())
+      return 2;
+    const float want = serial(t, 0.0f);
+    Stats row, chunks;
+    const float one = emul(t, 0.0f, &row);
+    float carried = 0.0f;
+    for (size_t base = 0; base < t.size(); base += 4096)
+    {
+      const size_t m = std::min<size_t>(4096, t.size() - base);
+      carried = emul(std::vector<float>(t.begin() + base, t.begin() + base + m), carried, &chunks);
+    }
+    report(id, t.size(), "row", want, one, row);
+    report(id, t.size(), "chunks", want, carried, chunks);
+    bad += (f2i(want) != f2i(one) && !(want != want && one != one)) || (f2i(want) != f2i(carried) && !(want != want && carried != carried));
+  }
+  fclose(f);
+  printf("float_chain_emul: %s; %d vectors\n", bad ? "FAILED" : "all equal", count);
+  return bad ? 1 : 0;
+}
+
 int main(int argc, char** argv)
 {
+  if (argc > 2 && strcmp(argv[1], "--cases") == 0)
+    return replay_cases(argv[2]);
   const long rounds = argc > 1 ? atol(argv[1]) : 300;
   std::mt19937 rng(12345);
   std::uniform_real_distribution<float> U(0.0f, 1.0f);

@@ -13,6 +13,7 @@ import pytest
 
 import resample_cases as rc
 import rng_ref
+from float_chain_cases import prefix_loop, tie_constant   # the plain float32 loop; 1 / n as a tie on every step of one binade
 from mcl_3dl_amd import capi
 from mcl_3dl_amd.synthetic import make_scene
 from oracle import pyoracle
@@ -79,13 +80,6 @@ def tie_free(n):
     return (w / w.sum()).astype(F)
 
 
-def prefix_loop(terms):
-    """acc = 0; acc += t in float32, every prefix (np.add.accumulate on float32 is this loop, started at +0 as in C: 0 + -0 is
-    +0; NaN and inf propagate)."""
-    with np.errstate(all="ignore"):
-        return np.add.accumulate(np.concatenate([[F(0)], np.asarray(terms, F)]), dtype=F)[1:]
-
-
 def has_ties(w):
     keys = prefix_loop(w)
     return bool(np.any(~(keys[:-1] < keys[1:])))
@@ -112,12 +106,6 @@ def assert_same(one, three):
         assert one[key] == three[key], key
     for key in ("s", "w", "odom"):
         np.testing.assert_array_equal(one[key], three[key], err_msg=key)
-
-
-def tie_constant(n, bits):
-    u = np.array([F(1.0) / F(n)], F).view(np.uint32)
-    u = (u & ~np.uint32((1 << bits) - 1)) | np.uint32(1 << (bits - 1))
-    return u.view(F)[0]
 
 
 # ---- the chain on its own ------------------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 (tests/motion_ref.py, itself checked against the reference's own results in tests/test_motion_cpu.py). Every case runs at N = 1
 direct, at N = 1 through the sharded path with RCCL, and at N = 3 contexts on the one device through the host, on a particle
 count that does not divide evenly."""
+import os
 import time
 
 import numpy as np
@@ -204,6 +205,50 @@ def test_imu_measure(cfg, n_p, oracle_kind):
         assert und["restored"]
         np.testing.assert_array_equal(und["lik"], 0.0)
         np.testing.assert_array_equal(und["weights"], w0)
+    finally:
+        g.close()
+
+
+@pytest.mark.parametrize("cfg", CONFIGS, ids=IDS)
+def test_imu_nan_and_underflow_restore_on_the_device(cfg):
+    """A NaN likelihood is a real event: ImuMeasurementModelGravity returns one when rounding pushes the acosf argument above 1.
+    The reference's own such case (tests/golden/motion.npz, imu2: 30 particles, NaN at particle 0) and its underflow case (imu1:
+    every likelihood 0) through measure_imu: the device forms the same NaN, the float sum is NaN resp. 0, and pf::measure restores
+    (pf.h:274-278) — also with that one state among 600 particles, on every shard layout."""
+    G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "motion.npz"))
+    g = group(cfg)
+    try:
+        for case in (2, 1):
+            acc, st, w = G["imu%d_acc" % case], G["imu%d_state" % case], G["imu%d_w" % case]
+            want_lik = G["imu%d_lik" % case]
+            assert G["imu%d_tail" % case][1] == 1.0
+            g.upload_state(st, w)
+            got = g.measure_imu(acc[:3], float(acc[3]))
+            np.testing.assert_array_equal(np.isnan(got["lik"]), np.isnan(want_lik))
+            ok = ~np.isnan(want_lik)
+            np.testing.assert_allclose(got["lik"][ok], want_lik[ok], rtol=2e-6, atol=0)
+            assert got["restored"] and np.isnan(got["entropy"])
+            np.testing.assert_array_equal(got["weights"], w)
+            np.testing.assert_array_equal(got["weights"], G["imu%d_wout" % case])   # the reference's own weights after the call
+            np.testing.assert_array_equal(g.download_state()[1], w)
+            # 600 particles: one NaN among finite likelihoods (particle 311), resp. every particle underflowing
+            big = states(600, 14, spread=0.15)
+            if case == 2:
+                big[311] = st[int(np.nonzero(np.isnan(want_lik))[0][0])]
+            else:
+                big = np.tile(st, (30, 1))
+            w0 = np.random.default_rng(15).uniform(0.5, 1.5, 600).astype(np.float32)
+            w0 /= w0.sum()
+            g.upload_state(big, w0)
+            got = g.measure_imu(acc[:3], float(acc[3]))
+            if case == 2:
+                assert np.isnan(got["lik"][311]) and np.count_nonzero(np.isnan(got["lik"])) == 1
+                assert np.delete(got["lik"], 311).sum() > 0   # (finite and not all zero: without the NaN the update is alive)
+            else:
+                np.testing.assert_array_equal(got["lik"], 0.0)
+            assert got["restored"] and np.isnan(got["entropy"])
+            np.testing.assert_array_equal(got["weights"], w0)
+            np.testing.assert_array_equal(g.download_state()[1], w0)
     finally:
         g.close()
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import motion_ref as mr
+from pf_measure_ref import pf_measure   # pf::measure (pf.h:252-279): float products, float sequential sum, restore unless sum > 0
 
 G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "motion.npz"))
 
@@ -16,17 +17,6 @@ def steps():
     tc = G["pred_tc"]
     for o in G["pred_steps"]:
         yield mr.motion_step(o[0:7], o[7:14], o[14], tc[0], tc[1])
-
-
-def pf_measure(w, lik):
-    """pf::measure (pf.h:252-279): float products, float sequential sum, restore unless sum > 0."""
-    wn = (w * lik).astype(np.float32)
-    s = np.float32(0)
-    for v in wn:
-        s = np.float32(s + v)
-    if not s > 0.0:
-        return w.copy(), True
-    return (wn / s).astype(np.float32), False
 
 
 def test_one_predict_step_device_form():
